@@ -12,9 +12,15 @@ GPU, L=16 (level_scale 1.26), T=2^19, F=2, 64-wide MLPs with 2 hidden layers, fp
 optimised.  Data: 3 stacks simulated from the 128^3 Shepp-Logan phantom with the slice-acquisition
 kernel (synthetic; no dataset on the box), resident in HBM before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what the headline needs: set-up,
+warm-up, ONE timed region of exactly --steps steps, the line.  Everything else it measures runs with --full only, and
+those fields are null without it:
   roofline     — the dominant native kernel timed with HIP events inside the timed region
-  cpu_baseline — the CPU oracle (a port of the same loop) on a bounded sample, rank 0, N=1 only.
+  cpu_baseline — the CPU oracle (a port of the same loop) on a bounded sample, rank 0, N=1 only
+  strict_fp32_mfma / fp16_operands / strong_scaling / small_batch / roofline_uniform / roofline_fwd_bwd_strict /
+  roofline_mlp / inference — the other precisions, configurations and micro-benchmarks of the same process;
+  --full also repeats a short timed region (5 regions when --steps < 100, the median is reported).
+--dump-outputs DIR writes what two steps of the timed path return from the run's starting state (dump_outputs).
 """
 import argparse
 import json
@@ -174,6 +180,50 @@ def _events_ms(fn, n=10, warm=2):
     return s.elapsed_time(e) / n
 
 
+DUMP_STEPS = 2  # steps of the timed path whose losses --dump-outputs writes
+
+
+def save_state(trainer, ds, perm_gen):
+    """Everything a training step reads or advances: parameters, AdamW moments and step count, PSF-noise counter, the data
+    set's order and position, the RNG states.  Taken before the first step, where every run of the same arguments agrees."""
+    f, direct = trainer.flat, trainer.direct
+    return {"flat": [x.clone() for x in (f.param, f.grad, f.exp_avg, f.exp_avg_sq)], "t": trainer.t,
+            "noise_calls": None if direct is None else direct._noise_calls,
+            "data": (ds.xyz, ds.v, ds.slice_idx, ds.count, ds.epoch), "perm_gen": perm_gen.get_state(),
+            "cuda_rng": torch.cuda.get_rng_state(perm_gen.device)}
+
+
+def restore_state(trainer, ds, perm_gen, st):
+    f, direct = trainer.flat, trainer.direct
+    for dst, src in zip((f.param, f.grad, f.exp_avg, f.exp_avg_sq), st["flat"]):
+        dst.copy_(src)  # (in place: the parameters are views of f.param)
+    trainer.t = st["t"]
+    if direct is not None:
+        direct._noise_calls = st["noise_calls"]
+    ds.xyz, ds.v, ds.slice_idx, ds.count, ds.epoch = st["data"]
+    perm_gen.set_state(st["perm_gen"])
+    torch.cuda.set_rng_state(st["cuda_rng"], perm_gen.device)
+
+
+def dump_outputs(path, step_losses):
+    """--dump-outputs: what the training step returns to its caller - its losses - for DUMP_STEPS steps of the timed path
+    run from the state the run started in (restore_state, from the first batch on): step<k>_loss_<name>.npy, float64
+    scalars.  The first step's losses are the same bit for bit in every run (forward, PSF noise and loss reductions are
+    deterministic); the second's carry the first step's backward and AdamW update, whose floating-point atomics sum in
+    arrival order, and agree to rounding.  Parameters are not written: AdamW's eps of 1e-15 turns the rounding of a
+    near-zero gradient into a visible change of its entry (one in millions after one step), and within a few dozen steps
+    into whole learning-rate steps - which is also why nothing late in a run is reproducible."""
+    import re
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for i, losses in enumerate(step_losses, 1):
+        for k, val in losses.items():
+            name = f"step{i}_loss_" + re.sub(r"[^0-9A-Za-z]+", "_", k).strip("_")
+            np.save(os.path.join(path, name + ".npy"), np.asarray(float(val.detach()), dtype=np.float64))
+
+
 def measure_extras(model, args, device, opt):
     """Side measurements of the same process (rank 0, outside the timed region):
     * achievable HBM rates of this box: a 1 GiB device-to-device copy (read + write) and a 1 GiB fill;
@@ -283,8 +333,21 @@ def main():
     ap.add_argument("--no-strict", action="store_true", help="skip the second pass with the MLP products on fp32 MFMAs (kernel timelines)")
     ap.add_argument("--repeats", type=int, default=0,
                     help="how often the timed region of --steps steps is repeated (the median region is reported; every region is in "
-                         "`timed_regions_ms_per_step`); 0 = automatic: 5 when --steps < 100 - a 20-step region is a 20 ms sample -, else 1")
+                         "`timed_regions_ms_per_step`); 0 = automatic: 1, or with --full 5 when --steps < 100 - a 20-step region is a "
+                         "20 ms sample -, else 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (kernel timing + rooflines, CPU baseline, fp32-MFMA and fp16-operand passes, "
+                         "strong scaling, small batches, micro-benchmarks, inference); without it those legs are skipped and their "
+                         "fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed path for two steps from the run's starting state (first batch on) "
+                         "and write what they return, their losses, as DIR/step<k>_loss_<name>.npy (float64) - the same in every "
+                         "run of the same arguments")
     opt = ap.parse_args()
+    if not opt.full:
+        # the plain run: the headline alone
+        opt.no_cpu_baseline = opt.no_extras = opt.no_strict = opt.no_kernel_timing = True
+        opt.small_batches = ""
     # stdout carries ONE line, the JSON result.  Libraries write there too (RCCL prints a version banner through C stdio, which
     # lands AFTER a flushed Python print when stdout is a pipe or a file): file descriptor 1 is pointed at stderr for the run and
     # the result goes to the saved descriptor.
@@ -336,6 +399,7 @@ def main():
     trainer.defer_table_join = os.environ.get("NESVOR_DEFER_TABLE_JOIN", "1") != "0"
     torch.manual_seed(1234 + rank)  # per-rank PSF noise stream; the permutation below is rank-independent
     perm_gen = torch.Generator(device=device).manual_seed(0)
+    start_state = save_state(trainer, ds, perm_gen) if opt.dump_outputs else None
 
     if opt.scaling == "strong" and opt.batch_size % world:
         raise SystemExit("--scaling strong: --batch-size must be a multiple of the number of GPUs")
@@ -423,11 +487,19 @@ def main():
             pairs.append((s_ev, e_ev))
         torch.cuda.synchronize(device)
         bracket_ms = sorted(a.elapsed_time(b) for a, b in pairs)[len(pairs) // 2]
+    elif not opt.full:
+        # a plain run takes the steps of the kernel-timing leg untimed: its timed region starts from the same state (data
+        # position, parameters, settled queues) as that of a --full run
+        direct = trainer.direct
+        for _ in range(2 + min(opt.steps, 50) + (2 if direct is not None and not parallel and direct.native_ready() else 0)):
+            step()
+        torch.cuda.synchronize(device)
     for _ in range(opt.warmup):
         step()
     # the timed region: EXACTLY --steps steps between barrier + synchronize.  A short region (the driver's 20 steps = 20 ms) is a
-    # noisy sample of a GPU whose clock floats with its power draw: it is repeated and the MEDIAN region is the one reported
-    n_rep = opt.repeats if opt.repeats > 0 else (5 if opt.steps < 100 else 1)
+    # noisy sample of a GPU whose clock floats with its power draw: with --full it is repeated and the MEDIAN region is the one
+    # reported (a plain run times one region: exactly --steps timed steps)
+    n_rep = opt.repeats if opt.repeats > 0 else (5 if opt.full and opt.steps < 100 else 1)
     regions = []
     for _ in range(n_rep):
         e_, losses = timed(opt.steps)
@@ -468,7 +540,7 @@ def main():
 
     # BASELINE config 3 as written (2^20 samples per iteration in total): the same job with the batch split over the ranks
     strong = None
-    if world > 1 and opt.scaling == "weak" and opt.batch_size % world == 0:
+    if opt.full and world > 1 and opt.scaling == "weak" and opt.batch_size % world == 0:
         for _ in range(opt.warmup):
             step(opt.batch_size)
         e3, _ = timed(opt.steps, opt.batch_size)
@@ -514,6 +586,15 @@ def main():
         torch.cuda.synchronize(device)
 
     extras = measure_extras(model, args, device, opt) if (rank == 0 and not opt.no_extras) else None
+    if opt.dump_outputs:
+        # after everything timed: the timed path once more, from the starting state, on the first batch (every rank steps)
+        restore_state(trainer, ds, perm_gen, start_state)
+        dump_losses = []
+        for _ in range(DUMP_STEPS):
+            dump_losses.append(step())
+            sync()
+        if rank == 0:
+            dump_outputs(opt.dump_outputs, dump_losses)
     if extras is None:
         extras = {"copy_peak_GBps": None, "fill_peak_GBps": None, "roofline_uniform": None, "roofline_fwd_bwd_strict": None, "inference": None}
 

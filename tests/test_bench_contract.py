@@ -21,7 +21,7 @@ def test_two_ranks_on_one_gpu_emit_one_contract_line(device):
     env = dict(os.environ, NESVOR_SINGLE_DEVICE="1", NESVOR_DIST_BACKEND="gloo", GPU_MAX_HW_QUEUES="8")  # (8: must be lowered, not obeyed)
     env.pop("RANK", None), env.pop("WORLD_SIZE", None), env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
+           "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full",
            "--no-cpu-baseline", "--no-extras", "--no-strict", "--small-batches", ""]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -37,3 +37,40 @@ def test_two_ranks_on_one_gpu_emit_one_contract_line(device):
     assert s is not None and s["scaling"] == "strong" and s["global_batch_pixels"] == 4096 and s["points_per_gpu_per_iter"] == 1 << 19
     assert d["cpu_baseline"] is None and d["vs_baseline"] is None and d["data"] == "synthetic"
     assert "lowered to 4" in p.stderr  # ddp.cap_hw_queues
+
+
+def test_plain_run_times_exactly_steps_and_dumps_reproducible_outputs(device, tmp_path):
+    """``bench.py --gpus 1 --steps K --warmup W`` without --full: ONE timed region of exactly K steps, the side measurements'
+    fields null, and --dump-outputs writes the losses of two steps of the timed path from the run's starting state as float64
+    .npy files - the same in every run, whatever K and W."""
+    import numpy as np
+
+    lines_of, dirs = [], []
+    for steps, warmup in ((7, 2), (3, 1)):
+        out = tmp_path / f"outputs_{steps}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+               "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        lines_of.append(json.loads(lines[0]))
+        dirs.append(out)
+    d = lines_of[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["timed_regions"] == 1 and len(d["timed_regions_ms_per_step"]) == 1
+    assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "strict_fp32_mfma", "fp16_operands", "strong_scaling", "small_batch", "inference"):
+        assert d[k] is None, k
+    files = sorted(os.listdir(dirs[0]))
+    for i in (1, 2):
+        assert {f"step{i}_loss_{k}.npy" for k in ("MSE", "logVar", "MSE_logVar", "transReg", "imageReg")} <= set(files), files
+    assert files == sorted(os.listdir(dirs[1]))
+    for f in files:
+        a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+        assert a.dtype == np.float64 and a.shape == () and np.isfinite(a), f
+        if f.startswith("step1_"):
+            assert a == b, (f, a, b)  # forward, noise and loss reductions are deterministic
+        else:  # after one backward + AdamW: atomics sum in arrival order
+            np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-9, err_msg=f)

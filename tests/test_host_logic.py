@@ -295,6 +295,23 @@ def test_committed_bench_line_carries_the_contract_fields():
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0
 
 
+def test_bench_dump_outputs_writes_each_steps_losses():
+    """``bench.py --dump-outputs``: one float64 scalar file per step and loss, names made file-safe (host logic only)."""
+    import tempfile
+
+    import bench
+
+    steps = [{"MSE": torch.tensor(0.5), "MSE+logVar": torch.tensor(-0.25, requires_grad=True)},
+             {"MSE": torch.tensor(0.375), "MSE+logVar": torch.tensor(-0.5)}]
+    with tempfile.TemporaryDirectory() as d:
+        bench.dump_outputs(d, steps)
+        assert sorted(os.listdir(d)) == ["step1_loss_MSE.npy", "step1_loss_MSE_logVar.npy", "step2_loss_MSE.npy", "step2_loss_MSE_logVar.npy"]
+        for i, losses in enumerate(steps, 1):
+            for k, f in (("MSE", "MSE"), ("MSE+logVar", "MSE_logVar")):
+                a = np.load(os.path.join(d, f"step{i}_loss_{f}.npy"))
+                assert a.dtype == np.float64 and a.shape == () and float(a) == float(losses[k])
+
+
 def test_queue_capacities_saved_by_one_process_are_loaded_by_the_next(tmp_path, monkeypatch):
     """``save_queue_scales`` / ``NESVOR_HASHGRID_QUEUE=load:<file>`` (encoding.QueueSizer): a sizer made under the load policy
     starts from the capacities written for its key (clamped to [START, 1]), any other key from START; no GPU involved."""

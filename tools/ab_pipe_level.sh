@@ -6,7 +6,7 @@ LEVELS=${@:-"0 12 10 13 0 12 10 13"}
 cd $GRAFT_REPO_ROOT 2>/dev/null || cd "$(dirname "$0")/.."
 mkdir -p $OUT
 for lv in $LEVELS; do
-  NESVOR_STEP_PIPE_LEVEL=$lv python bench.py --steps 200 --no-cpu-baseline --no-extras --no-strict > $OUT/pipe_$lv.json 2> $OUT/pipe_$lv.err
+  NESVOR_STEP_PIPE_LEVEL=$lv python bench.py --full --steps 200 --no-cpu-baseline --no-extras --no-strict > $OUT/pipe_$lv.json 2> $OUT/pipe_$lv.err
   python - "$OUT/pipe_$lv.json" $lv <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

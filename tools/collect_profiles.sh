@@ -8,10 +8,10 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line + kernel stats of the same command
-python $ROOT/bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python $ROOT/bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 # (training-step launches only, and the owner pass on the main stream: a kernel that shares the chip with others shows a
 #  stretched duration in a trace; the bench line itself times the two launches the same way)
-NESVOR_OWNER_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -- python $ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2>/dev/null
+NESVOR_OWNER_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -- python $ROOT/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2>/dev/null
 cp $(ls $OUT/kstats/*/*kernel_stats.csv | head -1) $OUT/bench_n1_kernel_stats.csv
 # 2. hash-grid kernels: HBM traffic (FETCH_SIZE / WRITE_SIZE in separate passes) and SQ counters
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -25,7 +25,7 @@ python $ROOT/tools/pmc_summary.py aggregate $OUT/pmc_sq1 $OUT/pmc_sq2 > $OUT/pmc
 python $ROOT/tools/pmc_summary.py owner $OUT/pmc_sq1 $OUT/pmc_sq2 > $OUT/pmc_sq_hashgrid_owner_summary.txt
 # 3. HBM bytes of a whole training step (all kernels of 10 steps, two passes)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $OUT/step_$c -- python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-extras > /dev/null 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $OUT/step_$c -- python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-extras > /dev/null 2>&1
 done
 python $ROOT/tools/step_traffic.py $OUT/step_FETCH_SIZE $OUT/step_WRITE_SIZE 32 > $OUT/step_traffic.json
 # 4. micro-benchmarks

@@ -10,8 +10,8 @@ cd /tmp && export TMPDIR=/tmp
 # 1. the bench line (driver's invocation) + kernel stats of the same command under rocprofv3.  The native one-call step
 #    issues the launches; NESVOR_OWNER_OVERLAP=0 keeps the owner pass on the main stream (a kernel that shares the chip with
 #    others shows a stretched duration in a trace)
-python $ROOT/bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
-NESVOR_OWNER_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -- python $ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras --no-strict --small-batches "" > $OUT/bench_under_rocprof.json 2>/dev/null
+python $ROOT/bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+NESVOR_OWNER_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -- python $ROOT/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras --no-strict --small-batches "" > $OUT/bench_under_rocprof.json 2>/dev/null
 cp $(ls $OUT/kstats/*/*kernel_stats.csv | head -1) $OUT/bench_n1_kernel_stats.csv
 # 2. kernel timeline of one training step (default streams: owner pass on the side stream) and at 512 pixels (2^17 points)
 rocprofv3 --kernel-trace --output-format csv -d $OUT/tl -- python $ROOT/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-extras --no-strict --no-kernel-timing --small-batches "" > /dev/null 2>&1

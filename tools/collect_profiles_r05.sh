@@ -16,8 +16,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line (driver's invocation: 20 steps) and the 200-step default + kernel stats of the same command under rocprofv3
 python $ROOT/bench.py --steps 20 --warmup 5 > $OUT/bench_n1_driver_invocation.json 2> $OUT/bench_n1.err
-NESVOR_HASHGRID_QUEUE_SAVE=/tmp/nesvor_queue_scales.json python $ROOT/bench.py > $OUT/bench_n1.json 2>> $OUT/bench_n1.err
-NESVOR_HASHGRID_QUEUE=load:/tmp/nesvor_queue_scales.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -- python $ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras --no-strict --small-batches "" > $OUT/bench_under_rocprof.json 2>/dev/null
+NESVOR_HASHGRID_QUEUE_SAVE=$OUT/queue_scales.json python $ROOT/bench.py --full > $OUT/bench_n1.json 2>> $OUT/bench_n1.err
+NESVOR_HASHGRID_QUEUE=load:$OUT/queue_scales.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -- python $ROOT/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras --no-strict --small-batches "" > $OUT/bench_under_rocprof.json 2>/dev/null
 python $ROOT/tools/kernel_stats_settled.py $OUT/kstats > $OUT/bench_n1_kernel_stats.csv
 cp $(ls $OUT/kstats/*/*kernel_stats.csv | head -1) $OUT/bench_n1_kernel_stats_rocprof_avg.csv
 # 2. kernel timeline of one training step (default streams: owner pass on the side stream) and at 512 pixels (2^17 points)

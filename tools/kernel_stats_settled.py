@@ -7,8 +7,8 @@ the middle 80 % / min / max in microseconds - the median does not move with a do
 fraction of the hash-grid launches recomputed from the medians alone (2328 B/point x 2^20 points over forward +
 aggregation + owner pass WITHOUT the table's AdamW step - the launch configuration bench.py's `roofline` block times).
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline ...
-    python tools/kernel_stats_settled.py gpurun_out/kt > profiles/r04_bench_n1_kernel_stats.csv
+    rocprofv3 --kernel-trace --output-format csv -d <trace-dir> -- python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline ...
+    python tools/kernel_stats_settled.py <trace-dir> > profiles/r04_bench_n1_kernel_stats.csv
 """
 import collections, csv, glob, sys
 
