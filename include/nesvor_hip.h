@@ -418,7 +418,9 @@ int nesvor_mlp_forward(const nesvor_mlp_t* net, const float* xa, const float* xb
                        float* const* saved_hidden, int64_t N, void* stream);
 /* 1 if (net, N) is a shape the fused backward takes - dX, dW and db in ONE wave-specialised launch, no dpre scratch (pass NULL
  * entries): N, samples_per_pixel and k_a multiples of 16, at most two hidden layers, at most two 16-row input blocks at two
- * hidden layers.  0: pass dpre_scratch[l] (N_pad16 * 64 floats each) and the backward runs as a dX launch + a dW launch. */
+ * hidden layers.  0: pass dpre_scratch[l] (N_pad16 * 64 floats each) and the backward runs as a dX launch + a dW launch: on fp32
+ * MFMAs for bf16_operands = 0 / 2 / 4 (nesvor_mlp_wide_backward_bounded), on 16-bit operands rounded at the fused kernel's points for
+ * bf16_operands = 1 / 3 (any shape the 16-bit forward takes; dxa per sample, dxa_group_sums = 0). */
 int nesvor_mlp_backward_fused_ok(const nesvor_mlp_t* net, int64_t N);
 int nesvor_mlp_backward(const nesvor_mlp_t* net, const float* xa, const float* xb, const float* dy,
                         float* const* saved_hidden, float* const* dpre_scratch, float* dxa, float* dxb,
@@ -467,7 +469,7 @@ int nesvor_mlp_wide_backward(const nesvor_mlp_wide_t* net, const float* xa, cons
 /* ... additionally raising the device scalar *dxb_absmax to max |dxb| (as nesvor_mlp_backward_bounded does; NULL: not wanted).  At
  * width 64 the saved / dpre buffers have the fragment layout of nesvor_mlp_t's full save: nesvor_mlp_backward_bounded hands the
  * shapes its wave-specialised kernel does not take (ragged N, samples per pixel or pixel features not in multiples of 16, three
- * hidden layers) to this entry point - round 6 retired mlp.hip's own dX / dW launch pair. */
+ * hidden layers) to this entry point in the fp32 modes (0, 2, 4); the 16-bit operand modes (1, 3) run mlp.hip's 16-bit launch pair. */
 int nesvor_mlp_wide_backward_bounded(const nesvor_mlp_wide_t* net, const float* xa, const float* xb, const float* dy,
                                      float* const* saved_hidden, float* const* dpre_scratch, float* dxa, float* dxb,
                                      float* dw_partial, int n_partial, int64_t N, float* dxb_absmax, void* stream);

@@ -1159,7 +1159,225 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
 }
 
 // (backward as a dX launch + a dW launch, for the shapes the wave-specialised kernel below does not take: since round 6 the wide
-//  kernels of csrc/mlp_wide.hip at width 64 - same fragment layouts, one implementation instead of two; nesvor_mlp_backward_bounded)
+//  kernels of csrc/mlp_wide.hip at width 64 - same fragment layouts, one implementation instead of two; nesvor_mlp_backward_bounded.
+//  The 16-bit operand modes have a pair of their own, right below.)
+
+// ------------------------------------------------- backward, 16-bit operands: dX launch + dW launch
+// The shapes of modes 1 / 3 (HT = 1 bf16, HT = 2 fp16) that the wave-specialised kernel below does not take: three hidden layers,
+// three or four input blocks at two hidden layers, ragged N, S or k_a.  Any shape the 16-bit forward takes (width 64, 1-3 hidden
+// layers, k_a + k_b <= 64, out_dim <= 16).  The pair reads what that forward saved - 16-bit fragments ([group][block][lane][4],
+// 8 bytes per lane) - and rounds exactly the operands the 16-bit instantiations of mlp_bwd_ws_kernel round, with the same
+// round-to-nearest-even conversions (pack16 / store16):
+//   dX launch : dY -> 16 bit, times W_out^T (16-bit image);  per hidden layer l, from the top: gate with the saved h_l > 0 (fp32
+//               compare of the widened 16-bit value), store the gated pre-activation gradient dpre_l in fp32, round it to 16 bit,
+//               times W_l^T (16-bit image); the layer-0 product is dX (fp32).
+//   dW launch : dW_out = sum_n rn16(dY) h_{NH-1}^T,  dW_l = sum_n rn16(dpre_l) h_{l-1}^T,  dW_0 = sum_n rn16(dpre_0) rn16(x)^T
+//               (saved h are 16-bit already: exact);  db_out = sum_n dY,  db_l = sum_n dpre_l - fp32, unrounded, as the fused
+//               kernel's chain-wave sums.
+// fp32 accumulation everywhere; master weights and biases are never rounded.  In fp16 an operand beyond 65504 becomes inf and
+// reaches the gradients unclamped (what the loss scaler looks for).  dpre scratch: n_pad * 64 fp32 per hidden layer (the fused
+// kernel's dpre never leaves registers; here it is the hand-over between the two launches, kept in fp32 for the bias sums).
+// Outputs as the wide pair: dxa per sample (N, k_a) (no group sums), dxb (k_b, N), dW_partial (n_partial, total_params) in
+// nn.Linear order W0, b0, W1, b1, ... (bias columns always present, as fill_args counts them).  No atomics but the max of
+// dx_absmax (order-free): two calls give the same bits.
+// dX: all transposed images stay in LDS for the whole launch (16-bit: 26 KB at three hidden layers); the first layer's image is
+// kept four blocks tall (zero rows beyond k_in) so that every product has compile-time shapes - at most 12 MFMAs of padding per
+// group, on a path that is not the headline's.
+constexpr int kBlk16 = 128;  // floats per 16-bit image block (256 elements)
+size_t dx16_lds_bytes(int n_hidden) { return sizeof(float) * (size_t)kBlk16 * (kHB + (n_hidden - 1) * kHB * kHB + kHB * kHB); }
+
+template <int HT>
+__global__ __launch_bounds__(256) void mlp_bwd_dx16_kernel(const MlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int n_hidden = a.n_linear - 1, k_in = a.k_a + a.k_b, KB1 = (k_in + 15) >> 4;
+  float* imgo = lds;                                      // W_out^T: ib = kHB, kb = 1
+  float* imgh = imgo + kHB * kBlk16;                      // W_l^T, l = 1 .. n_hidden - 1: kHB x kHB
+  float* img1 = imgh + (n_hidden - 1) * kHB * kHB * kBlk16;  // W_0^T: kHB x kHB (rows beyond k_in zero)
+  build_image_T<HT>(imgo, a.W[n_hidden], a.out_dim, kWidth, kHB, 1);
+  for (int l = 1; l < n_hidden; ++l) build_image_T<HT>(imgh + (l - 1) * kHB * kHB * kBlk16, a.W[l], kWidth, kWidth, kHB, kHB);
+  build_image_T<HT>(img1, a.W[0], kWidth, k_in, kHB, kHB);
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int j = lane & 15, q = lane >> 4;
+  const int64_t n_groups = (a.N + 15) / 16;
+  const int64_t n_tiles = (n_groups + 4 * kG - 1) / (4 * kG);
+  const bool want_dx = a.dxa != nullptr || a.dxb != nullptr;
+  float dx_mx = 0.f;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t g0 = (tile * 4 + wave) * kG;
+    f32x4 go[kG][1], d[kG][kHB];
+#pragma unroll
+    for (int g = 0; g < kG; ++g) {
+      const int64_t n = (g0 + g) * 16 + j;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) go[g][0][r] = (n < a.N && 4 * q + r < a.out_dim) ? a.y[(size_t)(4 * q + r) * a.N + n] : 0.f;
+#pragma unroll
+      for (int ib = 0; ib < kHB; ++ib) d[g][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    apply_layer<1, kHB, HT>(imgo, go, d, lane);
+    for (int l = n_hidden - 1; l >= 0; --l) {
+      // d: gradient w.r.t. the output of hidden layer l -> gated by the saved activation -> dpre_l
+      const s16x4* H = reinterpret_cast<const s16x4*>(a.H[l]);
+      f32x4* P = reinterpret_cast<f32x4*>(a.dpre[l]);
+#pragma unroll
+      for (int g = 0; g < kG; ++g) {
+        const bool ok = g0 + g < n_groups;
+#pragma unroll
+        for (int ib = 0; ib < kHB; ++ib) {
+          const size_t off = ((size_t)(g0 + g) * kHB + ib) * 64 + lane;
+          f32x4 hv = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (ok) hv = unpack16<HT>(__builtin_bit_cast(f32x2, H[off]));
+#pragma unroll
+          for (int r = 0; r < 4; ++r) d[g][ib][r] = hv[r] > 0.f ? d[g][ib][r] : 0.f;
+          if (ok) P[off] = d[g][ib];
+        }
+      }
+      if (l > 0) {
+        f32x4 d2[kG][kHB];
+#pragma unroll
+        for (int g = 0; g < kG; ++g)
+#pragma unroll
+          for (int ib = 0; ib < kHB; ++ib) d2[g][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+        apply_layer<kHB, kHB, HT>(imgh + (l - 1) * kHB * kHB * kBlk16, d, d2, lane);
+#pragma unroll
+        for (int g = 0; g < kG; ++g)
+#pragma unroll
+          for (int ib = 0; ib < kHB; ++ib) d[g][ib] = d2[g][ib];
+      } else if (want_dx) {
+        f32x4 dx[kG][kHB];
+#pragma unroll
+        for (int g = 0; g < kG; ++g)
+#pragma unroll
+          for (int ib = 0; ib < kHB; ++ib) dx[g][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+        apply_layer<kHB, kHB, HT>(img1, d, dx, lane);
+#pragma unroll
+        for (int g = 0; g < kG; ++g) {
+          const int64_t n = (g0 + g) * 16 + j;
+          if (n >= a.N) continue;
+#pragma unroll
+          for (int kb = 0; kb < kHB; ++kb) {
+            if (kb >= KB1) break;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int kk = 16 * kb + 4 * q + r;
+              if (kk < a.k_a) {
+                if (a.dxa != nullptr) a.dxa[(size_t)n * a.k_a + kk] = dx[g][kb][r];
+              } else if (kk - a.k_a < a.k_b && a.dxb != nullptr) {
+                a.dxb[(size_t)(kk - a.k_a) * a.N + n] = dx[g][kb][r];
+                dx_mx = fmaxf(dx_mx, fabsf(dx[g][kb][r]));
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  if (a.dx_absmax != nullptr && a.dxb != nullptr) publish_absmax(a, dx_mx);
+}
+
+// dW / db: one workgroup (4 waves) per partial row, layer after layer over its share of the sample groups (group gi = 16 samples
+// = the k of one 16x16x16 MFMA):  dW_l[out][in] += A . B,  A lane (out feature i, sample quad q) = rn16(dpre_l or dY) of samples
+// 4q .. 4q+3, B lane (in feature i, q) = the layer's 16-bit input of the same samples; D lane (in i, q) = dW rows 4q .. 4q+3.
+__device__ __forceinline__ float frag_f32(const float* __restrict__ F, int64_t gi, int f, int s) {  // (feature f, sample s) of group gi
+  return F[(((size_t)gi * kHB + (f >> 4)) * 64 + ((f & 15) >> 2) * 16 + s) * 4 + (f & 3)];
+}
+__device__ __forceinline__ unsigned short frag_u16(const unsigned short* __restrict__ F, int64_t gi, int f, int s) {
+  return F[(((size_t)gi * kHB + (f >> 4)) * 64 + ((f & 15) >> 2) * 16 + s) * 4 + (f & 3)];
+}
+template <int HT>
+__global__ __launch_bounds__(256) void mlp_bwd_dw16_kernel(const MlpArgs a) {
+  __shared__ float red[4][kHB * 256];  // the four waves' accumulators of one output block (and, after them, their bias sums)
+  const int n_hidden = a.n_linear - 1, k_in = a.k_a + a.k_b, KB1 = (k_in + 15) >> 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 15, q = lane >> 4;
+  const int64_t n_groups = (a.N + 15) / 16;
+  float* out = a.dW_partial + (size_t)blockIdx.x * a.total_params;
+  int poff = 0;
+  for (int l = 0; l < a.n_linear; ++l) {
+    const bool last = l == n_hidden;
+    const int in_dim = l == 0 ? k_in : kWidth, out_dim = last ? a.out_dim : kWidth;
+    const int IB = l == 0 ? KB1 : kHB, OB = last ? 1 : kHB;
+    const unsigned short* Hin = l > 0 ? reinterpret_cast<const unsigned short*>(a.H[l - 1]) : nullptr;
+    f32x4 acc[kHB][kHB];
+    float db[kHB];
+#pragma unroll
+    for (int ob = 0; ob < kHB; ++ob) {
+      db[ob] = 0.f;
+#pragma unroll
+      for (int ib = 0; ib < kHB; ++ib) acc[ob][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int64_t gi = (int64_t)blockIdx.x * 4 + wave; gi < n_groups; gi += (int64_t)gridDim.x * 4) {
+      s16x4 pa[kHB], pb[kHB];
+#pragma unroll
+      for (int ob = 0; ob < kHB; ++ob) {
+        f32x4 av = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (ob < OB) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int64_t n = gi * 16 + 4 * q + t;
+            if (last) av[t] = (n < a.N && i < a.out_dim) ? a.y[(size_t)i * a.N + n] : 0.f;
+            else av[t] = n < a.N ? frag_f32(a.dpre[l], gi, 16 * ob + i, 4 * q + t) : 0.f;
+          }
+          db[ob] += (av[0] + av[1]) + (av[2] + av[3]);
+        }
+        pa[ob] = pack16<HT>(av);
+      }
+#pragma unroll
+      for (int ib = 0; ib < kHB; ++ib) {
+        if (ib < IB) {
+          if (l == 0) {
+            f32x4 xv;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              const int64_t n = min(gi * 16 + 4 * q + t, a.N - 1);  // (a clamped sample beyond N meets a zero A operand)
+              xv[t] = fetch_input(a, 16 * ib + i, n);
+            }
+            pb[ib] = pack16<HT>(xv);
+          } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) pb[ib][t] = (short)frag_u16(Hin, gi, 16 * ib + i, 4 * q + t);
+          }
+        } else {
+          pb[ib] = s16x4{0, 0, 0, 0};
+        }
+      }
+#pragma unroll
+      for (int ob = 0; ob < kHB; ++ob)
+#pragma unroll
+        for (int ib = 0; ib < kHB; ++ib)
+          if (ob < OB && ib < IB) acc[ob][ib] = mfma16h<HT>(pa[ob], pb[ib], acc[ob][ib]);
+    }
+    // the four waves' partial sums through LDS, one output block at a time -> W (out, in)
+#pragma unroll
+    for (int ob = 0; ob < kHB; ++ob) {
+      if (ob >= OB) break;  // (uniform)
+      __syncthreads();
+#pragma unroll
+      for (int ib = 0; ib < kHB; ++ib) *reinterpret_cast<f32x4*>(&red[wave][(ib * 64 + lane) * 4]) = acc[ob][ib];
+      __syncthreads();
+      for (int e = threadIdx.x; e < IB * 256; e += 256) {
+        const float s = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
+        const int r = e & 3, ln = (e >> 2) & 63, ib = e >> 8;
+        const int o = 16 * ob + 4 * (ln >> 4) + r, in = 16 * ib + (ln & 15);
+        if (o < out_dim && in < in_dim) out[poff + o * in_dim + in] = s;
+      }
+    }
+    // bias gradients: over the sample quads (lanes i, i + 16, i + 32, i + 48) and the waves
+    __syncthreads();
+#pragma unroll
+    for (int ob = 0; ob < kHB; ++ob) red[wave][ob * 64 + lane] = db[ob];
+    __syncthreads();
+    for (int e = threadIdx.x; e < OB * 16; e += 256) {
+      const int ob = e >> 4, ii = e & 15;
+      float s = 0.f;
+      for (int w = 0; w < 4; ++w)
+        for (int qq = 0; qq < 4; ++qq) s += red[w][ob * 64 + qq * 16 + ii];
+      if (e < out_dim) out[poff + out_dim * in_dim + e] = s;
+    }
+    poff += out_dim * in_dim + out_dim;
+  }
+}
 
 // ------------------------------------------------- backward, fused dX + dW + db
 // Staging tiles of the wave-specialised backward (fp32 / bf16-operand modes): 16 x 16 fp32, padded rows.
@@ -2713,7 +2931,25 @@ extern "C" int nesvor_mlp_backward_bounded(const nesvor_mlp_t* net, const float*
     // two-kernel path below.  (Rounds 1-4 carried a single-role fused kernel for these shapes.)
     return (int)hipErrorInvalidValue;
   }
-  if (a.bf16) return (int)hipErrorInvalidValue;
+  if (a.bf16) {
+    // modes 1 / 3: the 16-bit pair (mlp_bwd_dx16_kernel, mlp_bwd_dw16_kernel) on the 16-bit fragments the forward saved
+    if (xb == nullptr || dy == nullptr || (a.k_a > 0 && xa == nullptr)) return (int)hipErrorInvalidValue;
+    for (int l = 0; l < net->n_hidden; ++l)
+      if (saved_hidden[l] == nullptr || dpre_scratch[l] == nullptr) return (int)hipErrorInvalidValue;
+    if (a.k_a == 0) a.dxa = nullptr;
+    const int64_t n_tiles = ((N + 15) / 16 + 4 * kG - 1) / (4 * kG);
+    const dim3 grid((unsigned)(n_tiles < 512 ? n_tiles : 512));
+    const size_t lds = dx16_lds_bytes(net->n_hidden);
+    hipStream_t st = (hipStream_t)stream;
+    if (a.half16) {
+      hipLaunchKernelGGL(mlp_bwd_dx16_kernel<2>, grid, dim3(256), lds, st, a);
+      hipLaunchKernelGGL(mlp_bwd_dw16_kernel<2>, dim3((unsigned)n_partial), dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL(mlp_bwd_dx16_kernel<1>, grid, dim3(256), lds, st, a);
+      hipLaunchKernelGGL(mlp_bwd_dw16_kernel<1>, dim3((unsigned)n_partial), dim3(256), 0, st, a);
+    }
+    return (int)hipGetLastError();
+  }
   // dX launch + dW launch on fp32 MFMAs (always a valid evaluation of the split mode): the wide kernels at width 64
   nesvor_mlp_wide_t w{};
   w.width = kWidth; w.n_hidden = net->n_hidden; w.out_dim = net->out_dim; w.k_a = net->k_a; w.k_b = net->k_b; w.b_row0 = net->b_row0;

@@ -187,8 +187,6 @@ class DirectStep:
             return False
         if self.has_b and self.parallel:
             return False
-        if mlp_mod.operand_mode(self.bf16) in (mlp_mod.BF16, mlp_mod.FP16) and not self._fused_backward_takes_all():
-            return False  # (the dX + dW launch pair that other shapes fall back to has no bf16-operand form; the scaled modes 2 / 4 run it on fp32 MFMAs)
         return True
 
     def set_loss_scale(self, scale: float) -> None:

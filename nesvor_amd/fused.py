@@ -111,9 +111,9 @@ class FusedTrainer:
         # the reference's default numerics, opt-in (round 6): fp16 matrix operands + its GradScaler (train.py:161-164)
         self.scaler = None
         if getattr(args, "fp16_loss_scaling", False):
-            if self.direct is None or not direct.half_precision_model(model) or distributed:
-                raise RuntimeError("args.fp16_loss_scaling: the half-precision model structure (no --single-precision) on the "
-                                   "autograd-free step, single process (the reference's loop, which it restates, has no data parallelism)")
+            if not direct.half_precision_model(model) or distributed:
+                raise RuntimeError("args.fp16_loss_scaling: the half-precision model structure (no --single-precision), single process "
+                                   "(the reference's loop, which it restates, has no data parallelism)")
             from . import mlp as _mlp
 
             _mlp.HALF_OPERANDS[0] = _mlp.FP16  # (the module path of tinycudann.Network: inference between / after training)
@@ -132,9 +132,12 @@ class FusedTrainer:
         dropped) and halves the scale, ``growth_interval`` finite steps in a row double it.  Like ``GradScaler.step`` this reads one
         device flag per iteration (a host synchronisation the fp32 path does not have)."""
         sc = self.scaler
-        self.direct.set_loss_scale(sc.scale)
-        losses = self._forward_backward(xyz, v, slice_idx, noise)
-        self.direct.join_owner()
+        if self.direct is not None:
+            self.direct.set_loss_scale(sc.scale)
+            losses = self._forward_backward(xyz, v, slice_idx, noise)
+            self.direct.join_owner()
+        else:  # (shapes the autograd-free step does not take - three hidden layers, ...: autograd over flat_network, loss times the scale)
+            losses = self._forward_backward(xyz, v, slice_idx, noise, loss_scale=sc.scale)
         finite = bool(torch.isfinite(self.flat.grad).all())
         if finite:
             self.t += 1
@@ -187,7 +190,7 @@ class FusedTrainer:
     def decay_lr(self, gamma: float) -> None:
         self.lr *= gamma
 
-    def _forward_backward(self, xyz, v, slice_idx, noise=None) -> Dict[str, torch.Tensor]:
+    def _forward_backward(self, xyz, v, slice_idx, noise=None, loss_scale=1.0) -> Dict[str, torch.Tensor]:
         if self.direct is not None:
             return self.direct.run(xyz, v, slice_idx, noise, defer_owner_join=self._late_join)  # joined in optimizer_step
         losses = self.model(xyz, v, slice_idx) if noise is None else self.model.forward_with_noise(xyz, v, slice_idx, noise)
@@ -195,7 +198,7 @@ class FusedTrainer:
         for k, val in losses.items():
             if k in self.weights and self.weights[k]:
                 loss = loss + self.weights[k] * val
-        loss.backward()
+        (loss * loss_scale if loss_scale != 1.0 else loss).backward()
         return losses
 
     def step(self, xyz, v, slice_idx, noise=None) -> Dict[str, torch.Tensor]:

@@ -16,7 +16,7 @@ from . import _lib
 
 N_PARTIAL = 1024  # workgroups (= partial sums) of the dW kernel: 4 per CU so loads overlap MFMAs
 N_PARTIAL_FUSED = 256  # fused backward: one persistent 8-wave workgroup per CU (wave-specialised kernel)
-FUSED_BACKWARD = True  # False: separate dX and dW kernels (kept as cross-check and for depth 3)
+FUSED_BACKWARD = True  # False: separate dX and dW kernels (cross-check; shapes the fused kernel refuses always take them)
 
 # How an fp32 matrix product is evaluated (nesvor_mlp_t.bf16_operands):
 #   MFMA_FP32 (0): v_mfma_f32_16x16x4_f32 - an fp32 FMA chain;
@@ -324,9 +324,11 @@ def backward_raw(weights, biases, xa, xb, dy, saved, b_row0, k_b, S, dxb, need_d
     d.compact_save = int(saved[0].numel() == (N + 15) // 16 * 16 * 4)  # (the forward that wrote `saved` decided)
     dev = xb.device
     # the wave-specialised fused kernel (dX + dW + db in one launch) needs no dpre scratch (signalled by NULL entries); shapes it
-    # does not take (ragged N, S or k_a not multiples of 16, three hidden layers ...) run as a dX launch + a dW launch
+    # does not take (ragged N, S or k_a not multiples of 16, three hidden layers ...) run as a dX launch + a dW launch - on fp32
+    # MFMAs in the fp32 modes, on 16-bit operands rounded as the fused kernel rounds them in the BF16 / FP16 modes
     fused = FUSED_BACKWARD and bool(_lib.load().nesvor_mlp_backward_fused_ok(ctypes.byref(d), N))
-    dpre = [] if fused else [torch.empty_like(s) for s in saved]
+    # (dpre scratch in fp32 in every mode: the 16-bit operand modes save 16-bit activations, but their pair hands fp32 dpre over)
+    dpre = [] if fused else [torch.empty(s.numel(), dtype=torch.float32, device=s.device) for s in saved]
     # pixel-feature gradient: one row per 16-sample group (summed in the kernel) when a group lies inside a pixel
     group_sums = fused and N % 16 == 0 and S % 16 == 0 and k_a % 16 == 0
     d.dxa_group_sums = 1 if group_sums else 0
@@ -493,11 +495,13 @@ def apply_net(net, xa, xb, b_row0: int, k_b: int, samples_per_pixel: int):
     * Linear/ReLU stacks up to width 128 / seven hidden layers (``--width`` > 64, ``--depth`` > 3: the reference accepts any,
       cli/main.py:68-73): ``wide_mlp`` - hand-written fp32-MFMA kernels with one layer's weights in LDS at a time (round 6);
     * anything beyond (other activations, width > 128): ``library_mlp`` - correct, but on library GEMMs;
-    * the half-precision structure (``tinycudann.Network``): its row-major module interface."""
+    * the half-precision structure (``tinycudann.Network``): its row-major module interface - ``flat_network`` on the 16-bit
+      operand kernels (1-3 hidden layers of width 64, <= 64 inputs; the backward as one fused launch where the wave-specialised
+      kernel takes the shape, else as the 16-bit dX + dW launch pair), the wide kernels beyond."""
     from .tinycudann import Network
 
     if isinstance(net, Network):
-        x = xb[b_row0 : b_row0 + k_b].t()
+        x = xb[b_row0 : b_row0 + k_b].t().contiguous()  # (the module takes a contiguous (N, k) input, as tinycudann does)
         if xa is not None:
             x = torch.cat([xa.repeat_interleave(samples_per_pixel, dim=0), x], 1)
         return net(x).t()
@@ -518,7 +522,7 @@ def apply_net(net, xa, xb, b_row0: int, k_b: int, samples_per_pixel: int):
 
 class FlatNetworkFunction(Function):
     """``tinycudann.Network`` (one flat bias-free parameter vector) on the fused kernels, 16-bit matrix operands (``HALF_OPERANDS``:
-    bf16 by default, fp16 under ``args.fp16_loss_scaling``):
+    bf16 by default, fp16 under ``args.fp16_loss_scaling``), 1-3 hidden layers, <= 64 inputs:
     x (N, k) row-major -> y (N, n_output_dims).  The kernels read a feature-major input and write a feature-major
     output; the two transposes are the price of tinycudann's row-major module interface (the training step proper
     never pays it: nesvor_amd.direct feeds the kernels feature-major tensors)."""
@@ -527,12 +531,10 @@ class FlatNetworkFunction(Function):
     def forward(ctx, x, params, net):
         p = NetParams(net)
         n = x.shape[0]
-        n_pad = (n + 15) // 16 * 16  # the bf16 backward exists for whole 16-sample groups only: pad with zero rows
+        n_pad = (n + 15) // 16 * 16  # whole 16-sample groups: the fused 16-bit backward takes them (pad with zero rows)
         xb = torch.zeros((x.shape[1], n_pad), dtype=torch.float32, device=x.device)
         xb[:, :n] = x.detach().t()
         need = any(ctx.needs_input_grad)
-        if need and (p.n_hidden() > 2 or (p.n_hidden() == 2 and x.shape[1] > 32)):
-            raise NotImplementedError("half-precision Network backward: built for 1-2 hidden layers (<= 32 inputs with 2)")
         y, saved = forward_raw(p.weights, p.biases, None, xb, 0, xb.shape[0], 16, need, HALF_OPERANDS[0])
         ctx.net, ctx.n, ctx.mode = net, n, HALF_OPERANDS[0]
         ctx.save_for_backward(xb, *saved)
