@@ -346,7 +346,8 @@ typedef struct {
                                     backward scale with the LEADING term of every split alone - operands rounded to fp16 after
                                     scaling (no overflow, no loss scaler), ONE MFMA per product in the pipelined forward and the
                                     compact wave-specialised backward; every other kernel evaluates it as mode 2 or mode 0 (more
-                                    accurate, always valid).  REQUIRES `prep`.  Measured: DESIGN.md section 4. */
+                                    accurate, always valid).  REQUIRES `prep`.  The only mode that takes a bias-free network (NULL
+                                    `bias`, see there: the half-precision model structure).  Measured: DESIGN.md section 4. */
   int32_t compact_save;       /* 1: training keeps, per hidden unit and sample, ONE BIT (h > 0) of every hidden layer and nothing
                                  else: saved_hidden[0] = one uint32 per (16-sample group, lane) - 16 N bytes instead of 256 N
                                  per hidden layer - with bit 16 l + 4 b + r = [pre-activation sign bit clear] (= [h_l > 0] for every
@@ -360,7 +361,14 @@ typedef struct {
                                  Needs what nesvor_mlp_compact_save_ok() checks (split operands, the pipelined forward and
                                  the wave-specialised backward); forward and backward of one step must agree on it. */
   const float* weight[NESVOR_MAX_MLP_LAYERS];
-  const float* bias[NESVOR_MAX_MLP_LAYERS];
+  const float* bias[NESVOR_MAX_MLP_LAYERS];  /* (out), or ALL NULL: a bias-free network (tinycudann's half-precision structure) -
+                                 bf16_operands = 4 only.  It runs the pipelined forward and the compact wave-specialised backward
+                                 in their bias-free forms (no bias loads, no bias-gradient sums) and, for every other case (a full save,
+                                 shapes those kernels refuse), the wide kernels below, which evaluate a NULL bias as zero.  Its
+                                 dw_partial rows have NO b columns: W0 | W1 | ... | W_last (out_dim rows), a prefix of tinycudann's
+                                 flat parameter layout.  A NULL bias in any other mode, or next to non-NULL biases, is refused
+                                 (hipErrorInvalidValue) by every entry point; a descriptor without weight pointers (a shape query)
+                                 counts as biased.  Weight norms take max |b| = 0 for a NULL bias. */
   const float* prep;          /* mode 2: NESVOR_MLP_PREP_FLOATS device floats, valid bounds for THIS launch (a bound may be loose -
                                  it costs resolution below 2^-17 of it - but never too small: fp16 overflows at 65504 s).
                                  Operand bounds are SLOTTED: NESVOR_ABSMAX_FLOATS floats each, the bound is the maximum of every
@@ -413,6 +421,10 @@ int64_t nesvor_mlp_weight_images_bytes(const nesvor_mlp_t* net);
 
 /* 1 if (net, N) can run with compact_save = 1 (the field itself is ignored by this query), else 0. */
 int nesvor_mlp_compact_save_ok(const nesvor_mlp_t* net, int64_t N);
+/* 1 if `net` (weight pointers set, bf16_operands = 4; its bias pointers are ignored) runs forward and backward with NULL biases on
+ * hand-written kernels at N, else 0.  The backward of a bias-free network is fused (nesvor_mlp_backward_fused_ok) exactly when its
+ * training forward saves compactly (nesvor_mlp_compact_save_ok); otherwise it runs the wide dX + dW pair through dpre scratch. */
+int nesvor_mlp_bias_free_ok(const nesvor_mlp_t* net, int64_t N);
 
 int nesvor_mlp_forward(const nesvor_mlp_t* net, const float* xa, const float* xb, float* y,
                        float* const* saved_hidden, int64_t N, void* stream);
@@ -640,7 +652,10 @@ typedef struct {
   float delta, w_T;
   const float *axisangle, *axisangle_init, *psf_sigma, *bounding_box, *logit_coef, *log_var_slice, *slice_embedding, *table;
   float *g_axisangle, *g_logit_coef, *g_log_var_slice, *g_slice_embedding, *g_table, *g_density, *g_sigma, *g_bias_net;
-  int32_t n_density_params, n_sigma_params, n_bias_params;
+  int32_t n_density_params, n_sigma_params, n_bias_params;  /* columns of a network's partial rows, summed into g_*: W0,b0,W1,b1,..
+                                              - or, for a bias-free network (NULL biases, bf16_operands = 4 only), its evaluated weights
+                                              W0 | W1 | .. | W_last (out_dim rows): the prefix of its flat gradient; the padding rows
+                                              of tinycudann's last layer are never written */
   const float* gw;                         /* 4 upstream gradients d total / d {MSE, logVar, imageReg, biasReg} */
   float *flat_param, *flat_grad, *flat_exp_avg, *flat_exp_avg_sq;
   int64_t flat_numel;

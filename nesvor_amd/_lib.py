@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # NESVOR_HIP_LIB: load another build of the same ABI (tools/ablate_hashgrid.py times variants of one kernel this way)
 LIB_PATH = os.environ.get("NESVOR_HIP_LIB") or os.path.join(_HERE, "lib", "libnesvor_hip.so")
 MAX_LEVELS = 32
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 LAYOUT_ROW_MAJOR = 0
 LAYOUT_FEATURE_MAJOR = 1
@@ -152,6 +152,7 @@ _SIGNATURES = {
     "nesvor_psf_transform_backward_rng_slices": ([_P] * 4 + [c_uint64, c_uint64] + [_P] * 5 + [c_int, c_int, _P], c_int),
     "nesvor_psf_noise": ([c_uint64, c_uint64, _P, c_int64, _P], c_int),
     "nesvor_mlp_compact_save_ok": ([POINTER(MlpT), c_int64], c_int),
+    "nesvor_mlp_bias_free_ok": ([POINTER(MlpT), c_int64], c_int),
     "nesvor_mlp_backward_fused_ok": ([POINTER(MlpT), c_int64], c_int),
     "nesvor_mlp_prepare": ([POINTER(MlpT), _P, _P, _P, c_int64, _P, c_int, _P], c_int),
     "nesvor_mlp_prepare_weights": ([_P, _P, c_int, _P, c_int64, _P, _P], c_int),

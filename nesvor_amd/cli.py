@@ -13,7 +13,9 @@ here: ``--registration`` accepts the reference's choices, of which ``none`` (the
 ``svort``) and ``stack`` (stack-to-stack rigid registration, nesvor_amd/registration.py) are implemented; there is
 the ``register`` command offers the same two.  Precision follows the reference's switch
 (``--single-precision`` = the fp32 model with biased Linear layers; the default is the reference's half-precision
-structure - bias-free networks - which the HIP path evaluates with bf16 matrix operands and fp32 accumulation).
+structure - bias-free networks - which the HIP path evaluates with bf16 matrix operands and fp32 accumulation;
+``--mlp-fp16`` without ``--single-precision`` trains that structure with power-of-two-scaled fp16 operands instead, on
+the kernels' bias-free forms, and ``--fp16-loss-scaling`` with fp16 operands under the reference's loss scaler).
 """
 import argparse
 import logging
@@ -48,8 +50,9 @@ def _training_flags(p: argparse.ArgumentParser) -> None:
                         "operands and torch.cuda.amp.GradScaler semantics (init_scale 1, growth 2 every 2000 finite steps, backoff 0.5, "
                         "steps with non-finite gradients skipped) instead of this package's bf16 operands without loss scaling")
     g.add_argument("--mlp-fp16", action="store_true",
-                   help="(not in the reference) with --single-precision: power-of-two-scaled fp16 MLP matrix operands (one MFMA per "
-                        "product, no loss scaler needed), fp32 accumulation / weights")
+                   help="(not in the reference) power-of-two-scaled fp16 MLP matrix operands (one MFMA per product, no loss scaler "
+                        "needed), fp32 accumulation / weights: with --single-precision for the fp32 model, without it for the "
+                        "half-precision model structure (bias-free networks; excludes --fp16-loss-scaling and --mlp-bf16)")
     g.add_argument("--mlp-bf16", action="store_true",
                    help="(not in the reference) with --single-precision: bf16 MLP matrix operands, fp32 accumulation / weights")
     g.add_argument("--mlp-fp32-mfma", action="store_true",
@@ -250,12 +253,13 @@ def reconstruct(args: Namespace) -> None:
     args.dtype = torch.float32 if args.single_precision else torch.float16
     if args.mlp_bf16 and not args.single_precision:
         raise SystemExit("--mlp-bf16 is a variant of the fp32 model: pass --single-precision too")
-    if getattr(args, "mlp_fp16", False) and not args.single_precision:
-        raise SystemExit("--mlp-fp16 is a variant of the fp32 model: pass --single-precision too")
+    if getattr(args, "mlp_fp16", False) and getattr(args, "fp16_loss_scaling", False):
+        raise SystemExit("--mlp-fp16 needs no loss scaler: drop --fp16-loss-scaling")
     if getattr(args, "fp16_loss_scaling", False) and args.single_precision:
         raise SystemExit("--fp16-loss-scaling is the reference's DEFAULT numerics (fp16 operands + GradScaler): drop --single-precision")
     if not args.single_precision:
         logging.info("half-precision model structure (bias-free networks): %s matrix operands, fp32 accumulation",
+                     "power-of-two-scaled fp16 (no loss scaler)" if getattr(args, "mlp_fp16", False) else
                      "fp16 (with the reference's loss scaler: init 1, growth 2 / 2000 steps, backoff 0.5)" if getattr(args, "fp16_loss_scaling", False) else "bf16")
     t0 = time.time()
     if args.input_slices is not None:

@@ -831,9 +831,11 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
 #endif
 // SPLM: 0 fp32 MFMAs, 1 (true) the split mode, 2 the split mode's leading term alone (nesvor_mlp_t.bf16_operands == 4: scaled fp16
 // operands, ONE MFMA per product - same scales, images and save formats, a third of the matrix work and half of the splitting)
-template <int KB1, int NH, int SPLM, bool SAVE, bool COMPACT = false, bool OUT1 = false>
+// NOB (mode 4 only): a bias-free network (NULL nesvor_mlp_t.bias) - the accumulators start at zero, no bias is staged or added.
+template <int KB1, int NH, int SPLM, bool SAVE, bool COMPACT = false, bool OUT1 = false, bool NOB = false>
 __global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? NESVOR_FWD_MINBLOCKS : 1) void mlp_fwd_pf_kernel(const MlpArgs a) {
   constexpr bool SPL = SPLM != 0;
+  static_assert(!NOB || SPLM == 2, "NOB: mode-4 instantiations only");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int k_in = a.k_a + a.k_b;
   constexpr int kBlk = 256;  // floats per image block (split mode: two fp16 planes)
@@ -874,12 +876,14 @@ __global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? NESVOR_FWD_MINBLOCKS
   if constexpr (OUT1) {  // the VALU output layer consumes the last hidden layer in ITS units
     for (int e = threadIdx.x; e < kWidth; e += blockDim.x) wout[e] = a.W[NH][e] * inv_unit[NH - 1];
   }
-  for (int e = threadIdx.x; e < (NH + 1) * kWidth; e += blockDim.x) {
-    const int l = e / kWidth, o = e % kWidth;
-    float us = 1.f;  // biases enter as the accumulators' initial values: in the layer's units (the OUT1 output stays fp32)
+  if constexpr (!NOB) {
+    for (int e = threadIdx.x; e < (NH + 1) * kWidth; e += blockDim.x) {
+      const int l = e / kWidth, o = e % kWidth;
+      float us = 1.f;  // biases enter as the accumulators' initial values: in the layer's units (the OUT1 output stays fp32)
 #pragma unroll
-    for (int t = 0; t <= NH; ++t) us = (t == l && !(OUT1 && t == NH)) ? unit[t] : us;
-    bias[e] = (l < NH || o < a.out_dim) ? a.b[l][o] * us : 0.f;
+      for (int t = 0; t <= NH; ++t) us = (t == l && !(OUT1 && t == NH)) ? unit[t] : us;
+      bias[e] = (l < NH || o < a.out_dim) ? a.b[l][o] * us : 0.f;
+    }
   }
   __syncthreads();
 
@@ -962,7 +966,7 @@ __global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? NESVOR_FWD_MINBLOCKS
     for (int l = 0; l < NH; ++l) {
 #pragma unroll
       for (int ob = 0; ob < kHB; ++ob) {
-        const f32x4 bq = *reinterpret_cast<const f32x4*>(bias + l * kWidth + 16 * ob + 4 * q);
+        const f32x4 bq = NOB ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(bias + l * kWidth + 16 * ob + 4 * q);
 #pragma unroll
         for (int g = 0; g < kG; ++g) h[l][g][ob] = bq;
       }
@@ -1008,10 +1012,10 @@ __global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? NESVOR_FWD_MINBLOCKS
       for (int g = 0; g < kG; ++g) {
         part[g] += __shfl_xor(part[g], 16, 64);
         part[g] += __shfl_xor(part[g], 32, 64);
-        o[g][0] = f32x4{part[g] + bias[NH * kWidth], 0.f, 0.f, 0.f};  // (only lanes q == 0 store it)
+        o[g][0] = f32x4{NOB ? part[g] : part[g] + bias[NH * kWidth], 0.f, 0.f, 0.f};  // (only lanes q == 0 store it)
       }
     } else {
-      const f32x4 bq = *reinterpret_cast<const f32x4*>(bias + NH * kWidth + 4 * q);
+      const f32x4 bq = NOB ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(bias + NH * kWidth + 4 * q);
 #pragma unroll
       for (int g = 0; g < kG; ++g) o[g][0] = bq;
       apply_layer<kHB, 1, false, SPLM>(imgo, h[NH - 1], o, lane, mult[NH]);
@@ -1471,7 +1475,8 @@ __device__ unsigned long long g_mlp_timeline[64][8][4];
 // Wave w and wave w+4 sit on the same SIMD, each issues half of the MFMAs, and whatever one of them waits for
 // is covered by the other.  One workgroup barrier per group; both roles stay under 256 registers.
 // Requires the fast input path (a.fast).
-template <int OB, int IB>
+// NOB: a bias-free layer - no bias sums are staged or written (the partial row has no b columns)
+template <int OB, int IB, bool NOB = false>
 __device__ void flush_dw_ws(float* red /* 4 x OB x IB x 256 + 4 x kWidth floats */, const f32x4 (&acc)[OB][IB], const f32x4 (&dbc)[OB],
                             float* out, int out_dim, int in_dim, int slot /* 0..3: accumulator (dW) wave, -1: none */,
                             int chain /* 0..3: chain wave (owns the bias-gradient sums), -1: none */,
@@ -1491,7 +1496,7 @@ __device__ void flush_dw_ws(float* red /* 4 x OB x IB x 256 + 4 x kWidth floats 
   }
   // bias gradient: the chain waves summed dpre per lane (sample j, features 4q..4q+3 of block ob) over their groups;
   // sum the 16 sample lanes of a row here, the four waves below
-  if (chain >= 0) {
+  if (!NOB && chain >= 0) {
 #pragma unroll
     for (int ob = 0; ob < OB; ++ob) {
       f32x4 t;
@@ -1508,9 +1513,11 @@ __device__ void flush_dw_ws(float* red /* 4 x OB x IB x 256 + 4 x kWidth floats 
     const int o = 16 * ob + 4 * (ln >> 4) + r, in = 16 * ib + (ln & 15);
     if (o < out_dim && in < in_dim) out[o * in_dim + in] = s * w_scale;
   }
-  for (int e = threadIdx.x; e < OB * 16; e += blockDim.x) {
-    const float s = (redb[e] + redb[kWidth + e]) + (redb[2 * kWidth + e] + redb[3 * kWidth + e]);
-    if (e < out_dim) out[out_dim * in_dim + e] = s * b_scale;
+  if constexpr (!NOB) {
+    for (int e = threadIdx.x; e < OB * 16; e += blockDim.x) {
+      const float s = (redb[e] + redb[kWidth + e]) + (redb[2 * kWidth + e] + redb[3 * kWidth + e]);
+      if (e < out_dim) out[out_dim * in_dim + e] = s * b_scale;
+    }
   }
 }
 
@@ -1637,11 +1644,14 @@ __device__ __forceinline__ void accumulate_dw_hi(const float* tiles, const s16x4
 // SPLM: as in mlp_fwd_pf_kernel (2 = HI1: the leading term of the split alone; COMPACT instantiations only - every operand still goes
 // through split2(), stage_planes() and the transposing reads, minus their low planes: one MFMA per block product in the chain and the
 // recomputation, one 16x16x16 MFMA per block product of a weight gradient)
-template <int KB1, int NH, int BF16 = 0, int SPLM = 0, bool COMPACT = false, bool OUT1 = false>
+// NOB (HI1 only): a bias-free network (NULL nesvor_mlp_t.bias) - no bias staging for the recomputation, no bias-gradient sums in
+// the chain waves, and partial rows W0 | W1 | ... | W_out (out_dim rows) without b columns: a prefix of tinycudann's flat layout
+template <int KB1, int NH, int BF16 = 0, int SPLM = 0, bool COMPACT = false, bool OUT1 = false, bool NOB = false>
 __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
   constexpr bool SPL = SPLM != 0;
   constexpr bool HI1 = SPLM == 2;
   static_assert(!HI1 || COMPACT, "HI1: compact-save instantiations only");
+  static_assert(!NOB || HI1, "NOB: mode-4 instantiations only");
   static_assert(!COMPACT || (SPL && !BF16), "compact save: split-operand mode only");
   static_assert(!OUT1 || (SPL && !BF16), "OUT1: split-operand mode only");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1710,11 +1720,13 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
 #pragma unroll
       for (int l = 1; l < NH; ++l) build_image_ct<false, SPL, false, kHB, kHB, 512>(imgf2 + (l - 1) * kHB * kHB * kBlk, a.W[l], kWidth, kWidth, sc.sw[l]);
     }
-    for (int e = threadIdx.x; e < NH * kWidth; e += blockDim.x) {
-      float us = unit_h[0];
+    if constexpr (!NOB) {
+      for (int e = threadIdx.x; e < NH * kWidth; e += blockDim.x) {
+        float us = unit_h[0];
 #pragma unroll
-      for (int l = 1; l < NH; ++l) us = e >= l * kWidth ? unit_h[l] : us;
-      bias0[e] = a.b[e / kWidth][e % kWidth] * us;
+        for (int l = 1; l < NH; ++l) us = e >= l * kWidth ? unit_h[l] : us;
+        bias0[e] = a.b[e / kWidth][e % kWidth] * us;
+      }
     }
   }
   __syncthreads();
@@ -1846,8 +1858,10 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
         float* buf = my_tiles + (it & 1) * kBufFloats;
         if constexpr (PLANES) stage_tile0(buf, go, j, q);
         else stage_tile(buf, go, j, q);
-        dbc_o[0] += go;
-        pin(dbc_o[0]);  // (the sum stays HERE: sunk to the end of the iteration it keeps `go` alive past its in-place split)
+        if constexpr (!NOB) {
+          dbc_o[0] += go;
+          pin(dbc_o[0]);  // (the sum stays HERE: sunk to the end of the iteration it keeps `go` alive past its in-place split)
+        }
         // Split mode, round 6: a power of two PER SAMPLE on top of the launch's scale.  The launch's scale maps the largest |dY| of
         // the whole batch to 2^15; a sample whose upstream gradient lies 2^-20 below that kept 14-16 bits of its input gradient
         // and one 2^-30 below it 4-8 (measured: tests/test_gpu_ops.py::test_fused_mlp_split_dynamic_range) - and AdamW turns the
@@ -1920,7 +1934,8 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
             }
             // (the bias-gradient sums take d BEFORE the split, in the units d arrives in: flush_dw_ws scales them back; split mode:
             //  times the sample's 2^-k_j - an FMA where the other modes add)
-            if constexpr (SPL && !BF16) {
+            if constexpr (NOB) {
+            } else if constexpr (SPL && !BF16) {
               f32x4& acc_b = l > 0 ? dbc_h[l > 0 ? l - 1 : 0][ib] : dbc_1[ib];
 #pragma unroll
               for (int r = 0; r < 4; ++r) acc_b[r] = __builtin_fmaf(d[ib][r], inv_pj, acc_b[r]);
@@ -2088,7 +2103,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
           }
           f32x4 h[kHB];
 #pragma unroll
-          for (int ob = 0; ob < kHB; ++ob) h[ob] = *reinterpret_cast<const f32x4*>(bias0 + 16 * ob + 4 * q);
+          for (int ob = 0; ob < kHB; ++ob) h[ob] = NOB ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(bias0 + 16 * ob + 4 * q);
           apply_layer_g1_s<KB1, kHB, false, HI1>(imgf1, xs, h, lane);
 #pragma unroll
           for (int ob = 0; ob < kHB; ++ob)
@@ -2116,7 +2131,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
               stage_planes<HI1>(my_b + ib * kPlaneTileFloats, hs[ib], j, q);
             }
 #pragma unroll
-            for (int ob = 0; ob < kHB; ++ob) h[ob] = *reinterpret_cast<const f32x4*>(bias0 + l * kWidth + 16 * ob + 4 * q);
+            for (int ob = 0; ob < kHB; ++ob) h[ob] = NOB ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(bias0 + l * kWidth + 16 * ob + 4 * q);
             apply_layer_g1_s<kHB, kHB, false, HI1>(imgf2 + (l - 1) * kHB * kHB * kBlk, hs, h, lane);
 #pragma unroll
             for (int ob = 0; ob < kHB; ++ob)
@@ -2383,19 +2398,19 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
     o[0] = tl_t0; o[1] = __builtin_amdgcn_s_memtime(); o[2] = tl_sync; o[3] = tl_wait;
   }
 #endif
-  // epilogue: per-workgroup partial sums in nn.Linear parameter order W0,b0,W1,b1,... (accumulators live in waves 4-7)
+  // epilogue: per-workgroup partial sums in nn.Linear parameter order W0,b0,W1,b1,... (NOB: W0,W1,...; accumulators live in waves 4-7)
   const int slot = role == 1 ? pair : -1, chain = role == 0 ? pair : -1;
   float* out = a.dW_partial + (size_t)blockIdx.x * a.total_params;
   float* red = tiles;
   int poff = 0;
-  flush_dw_ws<kHB, KB1>(red, acc_1, dbc_1, out + poff, kWidth, k_in, slot, chain, inv_w[0], inv_d[0]);
-  poff += kWidth * k_in + kWidth;
+  flush_dw_ws<kHB, KB1, NOB>(red, acc_1, dbc_1, out + poff, kWidth, k_in, slot, chain, inv_w[0], inv_d[0]);
+  poff += kWidth * k_in + (NOB ? 0 : kWidth);
 #pragma unroll
   for (int l = 1; l < NH; ++l) {
-    flush_dw_ws<kHB, kHB>(red, acc_h[l - 1], dbc_h[l - 1], out + poff, kWidth, kWidth, slot, chain, inv_w[l], inv_d[l]);
-    poff += kWidth * kWidth + kWidth;
+    flush_dw_ws<kHB, kHB, NOB>(red, acc_h[l - 1], dbc_h[l - 1], out + poff, kWidth, kWidth, slot, chain, inv_w[l], inv_d[l]);
+    poff += kWidth * kWidth + (NOB ? 0 : kWidth);
   }
-  flush_dw_ws<1, kHB>(red, acc_o, dbc_o, out + poff, a.out_dim, kWidth, slot, chain,
+  flush_dw_ws<1, kHB, NOB>(red, acc_o, dbc_o, out + poff, a.out_dim, kWidth, slot, chain,
                       OUT1 ? (COMPACT ? pow2_inv(unit_h[NH - 1]) : 1.f) : inv_w[NH], 1.f);  // (OUT1: fp32 sums of dy h; a recomputed h arrives in its layer's units)
 }
 
@@ -2470,7 +2485,7 @@ __global__ __launch_bounds__(256) void weight_norms_kernel(const NormJobs jobs) 
     sr += __shfl_xor(sr, 1, 64); sr += __shfl_xor(sr, 2, 64);
     sc += __shfl_xor(sc, 1, 64); sc += __shfl_xor(sc, 2, 64);
     rown = sr; coln = sc;
-    if (tid < out_dim) bmax = fabsf(jobs.b[l][tid]);
+    if (tid < out_dim && jobs.b[l] != nullptr) bmax = fabsf(jobs.b[l][tid]);  // (NULL: a bias-free layer, max |b| = 0)
   }
   float r4[4] = {wmax, rown, coln, bmax};
 #pragma unroll
@@ -2585,6 +2600,15 @@ int launch_kb(K k1, K k2, K k3, K k4, int kb1, dim3 grid, size_t lds, hipStream_
   return (int)hipGetLastError();
 }
 
+// A bias-free network: weights given, every bias NULL (a descriptor without weight pointers - a shape query - counts as biased).
+// Mode 4 only: fill_args refuses a NULL bias next to non-NULL ones, or in any other mode (nesvor_hip.h, nesvor_mlp_t.bias).
+bool bias_free(const nesvor_mlp_t* d) {
+  if (d->weight[0] == nullptr || d->n_hidden < 1 || d->n_hidden + 1 > kMaxLayers) return false;
+  for (int l = 0; l <= d->n_hidden; ++l)
+    if (d->bias[l] != nullptr) return false;
+  return true;
+}
+
 int fill_args(MlpArgs* a, const nesvor_mlp_t* d, int64_t N) {
   if (d->width != kWidth || d->n_hidden < 1 || d->n_hidden + 1 > kMaxLayers || d->out_dim < 1 || d->out_dim > 16 ||
       d->k_a < 0 || d->k_b < 0 || d->k_a + d->k_b < 1 || d->k_a + d->k_b > 64 || d->samples_per_pixel < 1)
@@ -2592,11 +2616,15 @@ int fill_args(MlpArgs* a, const nesvor_mlp_t* d, int64_t N) {
   a->N = N;
   a->n_linear = d->n_hidden + 1;
   a->k_a = d->k_a; a->k_b = d->k_b; a->b_row0 = d->b_row0; a->out_dim = d->out_dim; a->S = d->samples_per_pixel;
+  const bool nob = bias_free(d);
+  int n_null = 0;
+  for (int l = 0; l < a->n_linear; ++l) n_null += d->bias[l] == nullptr ? 1 : 0;
+  if (d->weight[0] != nullptr && n_null != 0 && !(nob && d->bf16_operands == 4)) return (int)hipErrorInvalidValue;
   int total = 0;
   for (int l = 0; l < a->n_linear; ++l) {
     a->W[l] = d->weight[l]; a->b[l] = d->bias[l];
     const int in = l == 0 ? d->k_a + d->k_b : kWidth, out = l == d->n_hidden ? d->out_dim : kWidth;
-    total += in * out + out;
+    total += in * out + (nob ? 0 : out);
   }
   for (int l = a->n_linear; l < kMaxLayers; ++l) { a->W[l] = nullptr; a->b[l] = nullptr; }
   a->total_params = total;
@@ -2661,7 +2689,21 @@ extern "C" int nesvor_mlp_backward_fused_ok(const nesvor_mlp_t* net, int64_t N) 
   if (net == nullptr || N <= 0) return 0;
   MlpArgs a{};
   if (fill_args(&a, net, N)) return 0;
+  if (bias_free(net)) return compact_ok(a, net, N) ? 1 : 0;  // (bias-free: the compact mode-4 kernel only; every other shape runs the wide pair)
   return ws_ok(a, net) ? 1 : 0;
+}
+
+extern "C" int nesvor_mlp_bias_free_ok(const nesvor_mlp_t* net, int64_t N) {
+  if (net == nullptr || N <= 0 || net->weight[0] == nullptr) return 0;
+  nesvor_mlp_t d = *net;
+  for (int l = 0; l < kMaxLayers; ++l) d.bias[l] = nullptr;
+  MlpArgs a{};
+  if (fill_args(&a, &d, N) || !bias_free(&d)) return 0;
+  for (int l = 0; l <= d.n_hidden; ++l)
+    if (d.weight[l] == nullptr) return 0;
+  // forward: the pipelined kernel or the wide kernels (any shape fill_args takes, k_b >= 1); backward: the compact kernel or the
+  // wide pair - both take every such shape
+  return d.k_b >= 1 ? 1 : 0;
 }
 
 extern "C" int64_t nesvor_mlp_weight_images_bytes(const nesvor_mlp_t* net) {
@@ -2692,7 +2734,7 @@ extern "C" int nesvor_mlp_prepare_weights_images(const nesvor_mlp_t* const* nets
       jobs.img[nj] = img != nullptr ? img + wimg_offset(net->n_hidden, kb1, l) : nullptr;
       jobs.oblk[nj] = l == net->n_hidden ? 1 : kHB;
       jobs.iblk[nj] = l == 0 ? kb1 : kHB;
-      if (jobs.W[nj] == nullptr || jobs.b[nj] == nullptr) return (int)hipErrorInvalidValue;
+      if (jobs.W[nj] == nullptr) return (int)hipErrorInvalidValue;  // (a NULL bias: a bias-free layer, max |b| = 0)
     }
   }
   jobs.n_jobs = nj;
@@ -2759,6 +2801,53 @@ extern "C" int nesvor_mlp_forward(const nesvor_mlp_t* net, const float* xa, cons
   bool save_all = saved_hidden != nullptr, save_none = saved_hidden == nullptr;
   const bool compact = net->compact_save != 0 && save_all;
   if (a.bf16 == 2 && a.prep == nullptr) return (int)hipErrorInvalidValue;  // the split mode needs its operand bounds (nesvor_mlp_prepare)
+  if (bias_free(net)) {
+    // bias-free (mode 4): the pipelined kernel's NOB instantiations for a compact save and for inference; every other case - a full
+    // save, shapes the pipelined kernel does not take - on the wide kernels at width 64 (fp32 MFMAs: a valid evaluation of mode 4,
+    // the saved fragments in the full-save layout the wide backward reads), with one pass over y for the optional bound
+    const size_t lds = fwd_lds_bytes(a.n_linear, kb1);
+    const bool pf = use_pf && a.fast && a.off32 && net->n_hidden <= 2 && kb1 <= 2 && ((N >> 4) % (4 * kG)) == 0;
+    if (compact) {
+      if (!compact_ok(a, net, N)) return (int)hipErrorInvalidValue;
+      a.Hm = reinterpret_cast<uint32_t*>(saved_hidden[0]);
+      a.H[0] = nullptr;
+      if (net->out_dim == 1 && out1_on()) {
+        if (net->n_hidden == 1)
+          return launch_kb(mlp_fwd_pf_kernel<1, 1, 2, true, true, true, true>, mlp_fwd_pf_kernel<2, 1, 2, true, true, true, true>,
+                           mlp_fwd_pf_kernel<2, 1, 2, true, true, true, true>, mlp_fwd_pf_kernel<2, 1, 2, true, true, true, true>, kb1, grid,
+                           lds, (hipStream_t)stream, a, 256, n_tiles);
+        return launch_kb(mlp_fwd_pf_kernel<1, 2, 2, true, true, true, true>, mlp_fwd_pf_kernel<2, 2, 2, true, true, true, true>,
+                         mlp_fwd_pf_kernel<2, 2, 2, true, true, true, true>, mlp_fwd_pf_kernel<2, 2, 2, true, true, true, true>, kb1, grid,
+                         lds, (hipStream_t)stream, a, 256, n_tiles);
+      }
+      if (net->n_hidden == 1)
+        return launch_kb(mlp_fwd_pf_kernel<1, 1, 2, true, true, false, true>, mlp_fwd_pf_kernel<2, 1, 2, true, true, false, true>,
+                         mlp_fwd_pf_kernel<2, 1, 2, true, true, false, true>, mlp_fwd_pf_kernel<2, 1, 2, true, true, false, true>, kb1, grid,
+                         lds, (hipStream_t)stream, a, 256, n_tiles);
+      return launch_kb(mlp_fwd_pf_kernel<1, 2, 2, true, true, false, true>, mlp_fwd_pf_kernel<2, 2, 2, true, true, false, true>,
+                       mlp_fwd_pf_kernel<2, 2, 2, true, true, false, true>, mlp_fwd_pf_kernel<2, 2, 2, true, true, false, true>, kb1, grid,
+                       lds, (hipStream_t)stream, a, 256, n_tiles);
+    }
+    if (pf && save_none) {
+      if (net->n_hidden == 1)
+        return launch_kb(mlp_fwd_pf_kernel<1, 1, 2, false, false, false, true>, mlp_fwd_pf_kernel<2, 1, 2, false, false, false, true>,
+                         mlp_fwd_pf_kernel<2, 1, 2, false, false, false, true>, mlp_fwd_pf_kernel<2, 1, 2, false, false, false, true>, kb1,
+                         grid, lds, (hipStream_t)stream, a, 256, n_tiles);
+      return launch_kb(mlp_fwd_pf_kernel<1, 2, 2, false, false, false, true>, mlp_fwd_pf_kernel<2, 2, 2, false, false, false, true>,
+                       mlp_fwd_pf_kernel<2, 2, 2, false, false, false, true>, mlp_fwd_pf_kernel<2, 2, 2, false, false, false, true>, kb1,
+                       grid, lds, (hipStream_t)stream, a, 256, n_tiles);
+    }
+    nesvor_mlp_wide_t w{};
+    w.width = kWidth; w.n_hidden = net->n_hidden; w.out_dim = net->out_dim; w.k_a = net->k_a; w.k_b = net->k_b; w.b_row0 = net->b_row0;
+    w.samples_per_pixel = net->samples_per_pixel;
+    for (int l = 0; l <= net->n_hidden; ++l) { w.weight[l] = net->weight[l]; w.bias[l] = nullptr; }
+    e = nesvor_mlp_wide_forward(&w, xa, xb, y, save_all ? saved_hidden : nullptr, N, stream);
+    if (e || a.y_absmax == nullptr) return e;
+    const int64_t work = ((int64_t)net->out_dim * N + 1023) / 1024;
+    hipLaunchKernelGGL(absmax_rows_kernel, dim3((unsigned)(work < 2048 ? (work < 1 ? 1 : work) : 2048)), dim3(256), 0, (hipStream_t)stream, y,
+                       net->out_dim, N, N, a.y_absmax);
+    return (int)hipGetLastError();
+  }
   if (compact) {
     if (!compact_ok(a, net, N)) return (int)hipErrorInvalidValue;  // (the caller asks nesvor_mlp_compact_save_ok first)
     a.Hm = reinterpret_cast<uint32_t*>(saved_hidden[0]);
@@ -2853,6 +2942,31 @@ extern "C" int nesvor_mlp_backward_bounded(const nesvor_mlp_t* net, const float*
   }
   const int kb1 = (net->k_a + net->k_b + 15) / 16;
   if (a.dxa_group && !(a.fast && net->n_hidden <= 2 && dpre_scratch[0] == nullptr)) return (int)hipErrorInvalidValue;
+  const bool nob = bias_free(net);
+  if (nob && compact) {  // bias-free (mode 4): the compact kernel's NOB instantiations
+    a.Hm = reinterpret_cast<uint32_t*>(saved_hidden[0]);
+    a.H[0] = nullptr;
+    if (net->out_dim == 1 && out1_on()) {
+      const size_t lds_o = ws_bwd_lds_bytes(net->n_hidden, kb1, true, true) + sizeof(float) * kWidth;
+      if (net->n_hidden == 1)
+        return launch_kb(mlp_bwd_ws_kernel<1, 1, 0, 2, true, true, true>, mlp_bwd_ws_kernel<2, 1, 0, 2, true, true, true>,
+                         mlp_bwd_ws_kernel<2, 1, 0, 2, true, true, true>, mlp_bwd_ws_kernel<2, 1, 0, 2, true, true, true>, kb1,
+                         dim3((unsigned)n_partial), lds_o, (hipStream_t)stream, a, 512);
+      return launch_kb(mlp_bwd_ws_kernel<1, 2, 0, 2, true, true, true>, mlp_bwd_ws_kernel<2, 2, 0, 2, true, true, true>,
+                       mlp_bwd_ws_kernel<2, 2, 0, 2, true, true, true>, mlp_bwd_ws_kernel<2, 2, 0, 2, true, true, true>, kb1,
+                       dim3((unsigned)n_partial), lds_o, (hipStream_t)stream, a, 512);
+    }
+    const size_t lds_c = ws_bwd_lds_bytes(net->n_hidden, kb1, true, true);
+    if (net->n_hidden == 1)
+      return launch_kb(mlp_bwd_ws_kernel<1, 1, 0, 2, true, false, true>, mlp_bwd_ws_kernel<2, 1, 0, 2, true, false, true>,
+                       mlp_bwd_ws_kernel<2, 1, 0, 2, true, false, true>, mlp_bwd_ws_kernel<2, 1, 0, 2, true, false, true>, kb1,
+                       dim3((unsigned)n_partial), lds_c, (hipStream_t)stream, a, 512);
+    return launch_kb(mlp_bwd_ws_kernel<1, 2, 0, 2, true, false, true>, mlp_bwd_ws_kernel<2, 2, 0, 2, true, false, true>,
+                     mlp_bwd_ws_kernel<2, 2, 0, 2, true, false, true>, mlp_bwd_ws_kernel<2, 2, 0, 2, true, false, true>, kb1,
+                     dim3((unsigned)n_partial), lds_c, (hipStream_t)stream, a, 512);
+  }
+  // (bias-free without the compact save: the wide pair below - never the wave-specialised kernels above, which write b columns)
+  if (nob && dpre_scratch[0] == nullptr) return (int)hipErrorInvalidValue;  // (nesvor_mlp_backward_fused_ok said 0: pass dpre scratch)
   if (compact) {
     a.Hm = reinterpret_cast<uint32_t*>(saved_hidden[0]);
     a.H[0] = nullptr;
@@ -2954,7 +3068,7 @@ extern "C" int nesvor_mlp_backward_bounded(const nesvor_mlp_t* net, const float*
   nesvor_mlp_wide_t w{};
   w.width = kWidth; w.n_hidden = net->n_hidden; w.out_dim = net->out_dim; w.k_a = net->k_a; w.k_b = net->k_b; w.b_row0 = net->b_row0;
   w.samples_per_pixel = net->samples_per_pixel;
-  for (int l = 0; l <= net->n_hidden; ++l) { w.weight[l] = net->weight[l]; w.bias[l] = net->bias[l]; }
+  for (int l = 0; l <= net->n_hidden; ++l) { w.weight[l] = net->weight[l]; w.bias[l] = net->bias[l]; }  // (bias-free: all NULL)
   return nesvor_mlp_wide_backward_bounded(&w, xa, xb, dy, saved_hidden, dpre_scratch, dxa, dxb, dw_partial, n_partial, N,
                                           dxb != nullptr ? dxb_absmax : nullptr, stream);
 }

@@ -111,16 +111,26 @@ int mlp_backward_into(const nesvor_mlp_t& net, int group_sums, const float* xa, 
       no_scratch[l] = dpre_scratch[l];
     }
   }
-  // per-workgroup partial sums (columns W0,b0,W1,b1,...); the caller sums them into the network's segment of the flat gradient
+  // per-workgroup partial sums (columns W0,b0,W1,b1,... - bias-free: W0,W1,..., the prefix of its flat gradient); the caller sums them
+  // into the network's segment of the flat gradient
   // (ONE launch for all networks of the step, after the last backward: nesvor_sum_rows_multi)
   (void)grad_segment; (void)n_params;
   return nesvor_mlp_backward_bounded(&d, xa, xb, dy, saved, no_scratch, dxa, dxb, partial, NESVOR_STEP_MLP_PARTIALS, N, dxb_absmax, st);
+}
+
+// a network whose biases are all NULL (bias-free: tinycudann's half-precision structure) runs in mode 4 only (nesvor_mlp_t.bias)
+bool bias_free_refused(const nesvor_mlp_t& n) {
+  bool any_null = false;
+  for (int l = 0; l <= n.n_hidden && l < NESVOR_MAX_MLP_LAYERS; ++l) any_null = any_null || n.bias[l] == nullptr;
+  return any_null && n.bf16_operands != 4;
 }
 
 }  // namespace
 
 extern "C" void* nesvor_step_create(const nesvor_step_t* desc) {
   if (desc == nullptr) return nullptr;
+  if (bias_free_refused(desc->density) || (desc->has_lv && bias_free_refused(desc->sigma)) || (desc->has_b && bias_free_refused(desc->bias_net)))
+    return nullptr;
   StepCtx* c = new (std::nothrow) StepCtx;
   if (c == nullptr) return nullptr;
   c->d = *desc;
@@ -174,6 +184,8 @@ extern "C" int nesvor_step_timing_read(void* handle, float* ms) {
 
 extern "C" int nesvor_step_update(void* handle, const nesvor_step_t* desc) {
   if (handle == nullptr || desc == nullptr) return (int)hipErrorInvalidValue;
+  if (bias_free_refused(desc->density) || (desc->has_lv && bias_free_refused(desc->sigma)) || (desc->has_b && bias_free_refused(desc->bias_net)))
+    return (int)hipErrorInvalidValue;
   static_cast<StepCtx*>(handle)->d = *desc;
   return 0;
 }

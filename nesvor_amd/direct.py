@@ -48,7 +48,12 @@ def supported(model: NeSVoR) -> bool:
         return False
     if not (model.axisangle.is_cuda and mlp_mod.FUSED_BACKWARD):
         return False
-    if half_precision_model(model):
+    if half_precision_model(model) and getattr(a, "mlp_fp16", False):
+        # scaled fp16 with NULL biases: the shapes nesvor_mlp_bias_free_ok admits (ragged samples per pixel and wider inputs: the
+        # wide dX + dW pair)
+        if not all(mlp_mod.supported(n) and _bias_free_ok(model, n) for n in _nets(model)):
+            return False
+    elif half_precision_model(model):
         # the bf16-operand kernels exist for the wave-specialised layout only: a 16-sample group inside one pixel,
         # pixel features in whole 16-blocks, first layer of at most 32 inputs unless there is a single hidden layer
         ks = a.n_features_slice if (not a.no_pixel_variance or a.n_levels_bias) else 0
@@ -59,6 +64,32 @@ def supported(model: NeSVoR) -> bool:
         return False
     # (narrower networks run zero-padded on the module path: mlp.kernel_params)
     return all(mlp_mod.n_hidden_layers(n) <= 2 and mlp_mod.native_width(n) for n in _nets(model))
+
+
+def _net_inputs(model: NeSVoR, net):
+    """(k_a, k_b, b_row0) of one of the model's networks as the step feeds it (density: the encoding; sigma: [slice embedding |
+    z rows 1..]; bias field: [slice embedding | the coarsest levels of pe])."""
+    a = model.args
+    ks = a.n_features_slice if (not a.no_pixel_variance or a.n_levels_bias) else 0
+    if net is model.inr.density_net:
+        return 0, model.inr.encoding.spec.n_output_dims, 0
+    if net is getattr(model, "sigma_net", None):
+        return ks, a.n_features_z, 1
+    return ks, a.n_levels_bias * a.n_features_per_level, 0
+
+
+def _bias_free_desc(model: NeSVoR, p, S: int):
+    """The scaled-fp16 descriptor of a bias-free network (NetParams ``p``) with its real weight pointers and NULL biases: the
+    library's shape queries tell a bias-free network from a biased one by those pointers."""
+    k_a, k_b, b_row0 = _net_inputs(model, p.net)
+    return mlp_mod._desc(p.weights, p.biases, k_a, k_b, b_row0, S, mlp_mod.FP16S)
+
+
+def _bias_free_ok(model: NeSVoR, net) -> bool:
+    """``nesvor_mlp_bias_free_ok`` for one network of the model at a batch of 16 pixels."""
+    S = model.args.n_samples
+    d = _bias_free_desc(model, mlp_mod.NetParams(net, mlp_mod.FP16S), S)
+    return bool(_lib.load().nesvor_mlp_bias_free_ok(ctypes.byref(d), 16 * S))
 
 
 class DirectStep:
@@ -82,10 +113,24 @@ class DirectStep:
         self._gw_base, self._w_T_base, self.loss_scale = self.gw.clone(), self.w_T, 1.0
         self.reg_type = loss_mod.REG_TYPES[a.image_regularization]
         self.delta = float(model.delta)
-        # the parameters were re-homed into `flat` before this point: the views taken here stay valid
-        self.d_net = mlp_mod.NetParams(model.inr.density_net)
-        self.s_net = mlp_mod.NetParams(model.sigma_net) if self.has_lv else None
-        self.b_net = mlp_mod.NetParams(model.b_net) if self.has_b else None
+        # evaluation of the MLP matrix products (mlp.operand_mode): scaled fp16 with NULL biases for the half-precision model
+        # structure under args.mlp_fp16; bf16-rounded operands for that structure otherwise and, opt-in, for the fp32 model
+        # (args.mlp_bf16); otherwise fp32 - the split-fp16 default, or the plain fp32 MFMAs with args.mlp_fp32_mfma
+        if half_precision_model(model) and getattr(a, "mlp_fp16", False):
+            self.bf16 = mlp_mod.FP16S  # the bias-free kernels (nesvor_mlp_t.bias NULL): one MFMA per product, no loss scaler
+        elif half_precision_model(model) and getattr(a, "fp16_loss_scaling", False):
+            self.bf16 = mlp_mod.FP16  # the reference's default arithmetic, under its loss scaler (fused.LossScaler)
+        elif bool(getattr(a, "mlp_bf16", False)) or half_precision_model(model):
+            self.bf16 = True
+        elif bool(getattr(a, "mlp_fp16", False)):
+            self.bf16 = mlp_mod.FP16S  # scaled fp16 operands on the split mode's kernels: one MFMA per product (opt-in)
+        else:
+            self.bf16 = mlp_mod.MFMA_FP32 if getattr(a, "mlp_fp32_mfma", False) else False
+        # the parameters were re-homed into `flat` before this point: the views taken here stay valid (a bias-free network's
+        # gradient segment is its flat params.grad)
+        self.d_net = mlp_mod.NetParams(model.inr.density_net, self.bf16)
+        self.s_net = mlp_mod.NetParams(model.sigma_net, self.bf16) if self.has_lv else None
+        self.b_net = mlp_mod.NetParams(model.b_net, self.bf16) if self.has_b else None
         # side stream: the pose regulariser (a serial chain per slice) at the start of the step; at its end the owner pass of
         # the hash-grid backward (latency-bound, finishes the table gradient only) while the main stream runs the
         # sampler backward and the per-slice bookkeeping
@@ -96,17 +141,6 @@ class DirectStep:
         # the table's AdamW step inside the owner pass (nesvor_hashgrid_backward_adamw) whenever one native call covers
         # gradient and update (no data-parallel exchange in between): the table gradient then never goes through HBM
         self._adamw_in_owner = __import__("os").environ.get("NESVOR_ADAMW_IN_OWNER", "1") != "0"
-        # evaluation of the MLP matrix products (mlp.operand_mode): bf16-rounded operands for the half-precision model
-        # structure and, opt-in, for the fp32 model (args.mlp_bf16); otherwise fp32 - the split-fp16 default, or the
-        # plain fp32 MFMAs with args.mlp_fp32_mfma
-        if half_precision_model(model) and getattr(a, "fp16_loss_scaling", False):
-            self.bf16 = mlp_mod.FP16  # the reference's default arithmetic, under its loss scaler (fused.LossScaler)
-        elif bool(getattr(a, "mlp_bf16", False)) or half_precision_model(model):
-            self.bf16 = True
-        elif bool(getattr(a, "mlp_fp16", False)):
-            self.bf16 = mlp_mod.FP16S  # scaled fp16 operands on the split mode's kernels: one MFMA per product (opt-in)
-        else:
-            self.bf16 = mlp_mod.MFMA_FP32 if getattr(a, "mlp_fp32_mfma", False) else False
         import os
 
         import torch.distributed as dist
@@ -182,8 +216,10 @@ class DirectStep:
         if self.loss_scale != 1.0:
             return False  # (the one-call step's descriptors hold the unscaled pose-regulariser weight)
         nets = [self.d_net] + ([self.s_net] if self.has_lv else []) + ([self.b_net] if self.has_b else [])
-        if not all((not p.flat_params) and p.segment is not None and p.segment.numel() == sum(
-                w.numel() + b.numel() for w, b in zip(p.weights, p.biases)) for p in nets):
+        # a biased network: its gradient one contiguous segment in the partial rows' column order; a bias-free one (FP16S): its
+        # flat gradient, whose prefix the partial rows' columns are
+        if not all(p.segment is not None and ((p.bias_free and p.segment.numel() >= p.n_columns()) or (
+                not p.flat_params and p.segment.numel() == p.n_columns())) for p in nets):
             return False
         if self.has_b and self.parallel:
             return False
@@ -213,10 +249,12 @@ class DirectStep:
         if key not in self._native_shapes_ok:
             E = m.inr.encoding.spec.n_output_dims
             ok = lambda dd: bool(_lib.load().nesvor_mlp_backward_fused_ok(ctypes.byref(dd), N))
+            # (a bias-free network is asked with its own pointers: NULL biases change the answer)
+            desc = lambda p, dims: _bias_free_desc(m, p, S) if p.bias_free else dims
             self._native_shapes_ok[key] = (
-                ok(mlp_mod.dims_desc(len(self.d_net.weights) - 1, 1 + a.n_features_z, 0, E, 0, S, self.bf16)),
-                ok(mlp_mod.dims_desc(len(self.s_net.weights) - 1, 1, self.ks, a.n_features_z, 1, S, self.bf16)) if self.has_lv else None,
-                ok(mlp_mod.dims_desc(len(self.b_net.weights) - 1, 1, self.ks, self.kb_bias, 0, S, self.bf16)) if self.has_b else None)
+                ok(desc(self.d_net, mlp_mod.dims_desc(len(self.d_net.weights) - 1, 1 + a.n_features_z, 0, E, 0, S, self.bf16))),
+                ok(desc(self.s_net, mlp_mod.dims_desc(len(self.s_net.weights) - 1, 1, self.ks, a.n_features_z, 1, S, self.bf16))) if self.has_lv else None,
+                ok(desc(self.b_net, mlp_mod.dims_desc(len(self.b_net.weights) - 1, 1, self.ks, self.kb_bias, 0, S, self.bf16))) if self.has_b else None)
         return self._native_shapes_ok[key]
 
     def _fused_backward_takes_all(self, N=None) -> bool:
@@ -247,7 +285,7 @@ class DirectStep:
         d.grid = enc.spec.c_struct
         mode = self.bf16
         d.density = mlp_mod._desc(self.d_net.weights, self.d_net.biases, 0, E, 0, S, mode)
-        n_par = lambda p: sum(w.numel() + b.numel() for w, b in zip(p.weights, p.biases))
+        n_par = lambda p: p.n_columns()  # (a bias-free network: its evaluated weights, the prefix of its flat gradient)
         d.n_density_params, d.g_density = n_par(self.d_net), self.d_net.segment.data_ptr()
         largest = d.n_density_params
         if self.has_lv:

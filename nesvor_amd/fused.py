@@ -106,7 +106,13 @@ class FusedTrainer:
         self._late_join = os.environ.get("NESVOR_OWNER_JOIN_LATE", "1") != "0"  # 0: join the owner pass before the step's epilogue (A/B)
         # autograd-free evaluation of the iteration when the configuration allows it (nesvor_amd.direct)
         from . import direct
+        from . import mlp as _mlp
 
+        if getattr(args, "mlp_fp16", False) and getattr(args, "fp16_loss_scaling", False):
+            raise RuntimeError("args.mlp_fp16 and args.fp16_loss_scaling exclude each other: scaled fp16 needs no loss scaler")
+        if getattr(args, "mlp_fp16", False) and direct.half_precision_model(model):
+            # the bias-free structure in scaled fp16 (NULL biases, no loss scaler): the mode travels with each network
+            _mlp.set_network_operands(direct._nets(model), _mlp.FP16S)
         self.direct = direct.DirectStep(model, self.flat, self.weights) if direct.supported(model) else None
         # the reference's default numerics, opt-in (round 6): fp16 matrix operands + its GradScaler (train.py:161-164)
         self.scaler = None
@@ -114,11 +120,13 @@ class FusedTrainer:
             if not direct.half_precision_model(model) or distributed:
                 raise RuntimeError("args.fp16_loss_scaling: the half-precision model structure (no --single-precision), single process "
                                    "(the reference's loop, which it restates, has no data parallelism)")
-            from . import mlp as _mlp
-
-            _mlp.HALF_OPERANDS[0] = _mlp.FP16  # (the module path of tinycudann.Network: inference between / after training)
+            # (the module path of tinycudann.Network: inference between / after training) - on the model's own networks; the
+            # process-wide default follows as before, for networks that carry no mode of their own
+            _mlp.set_network_operands(direct._nets(model), _mlp.FP16)
+            _mlp.HALF_OPERANDS[0] = _mlp.FP16
             self.scaler = LossScaler()
-        if (getattr(args, "mlp_bf16", False) or getattr(args, "mlp_fp16", False)) and self.direct is None:
+        if getattr(args, "mlp_bf16", False) and self.direct is None or (
+                getattr(args, "mlp_fp16", False) and self.direct is None and not direct.half_precision_model(model)):
             raise RuntimeError("args.mlp_bf16 / args.mlp_fp16 need the autograd-free step (fused fp32 model, MLPs of at most two hidden layers)")
 
     @property

@@ -32,8 +32,9 @@ FUSED_BACKWARD = True  # False: separate dX and dW kernels (cross-check; shapes 
 #   FP16S (4): "scaled fp16" (round 6) - the SPLIT mode's machinery (power-of-two scales from ``prep``, the same operand images,
 #     the bits-only save, the backward's per-sample scale) with the leading term of every split alone: operands rounded to fp16
 #     AFTER scaling (11 bits, no overflow and no loss scaler), ONE MFMA per product.  What fp16 arithmetic buys on the kernels the
-#     fp32 path runs on; opt-in for the fp32 model structure (``args.mlp_fp16``).  Kernels without that form evaluate the full
-#     split or fp32 MFMAs - more accurate, always valid.
+#     fp32 path runs on; opt-in for either model structure (``args.mlp_fp16``; the half-precision structure's bias-free networks
+#     pass NULL biases and run the kernels' bias-free forms).  Kernels without that form evaluate the full split or fp32 MFMAs -
+#     more accurate, always valid.
 MFMA_FP32, BF16, SPLIT, FP16, FP16S = 0, 1, 2, 3, 4
 SCALED_MODES = (SPLIT, FP16S)  # modes that need ``prep`` (operand bounds + weight norms)
 FP32_OPERANDS = MFMA_FP32 if os.environ.get("NESVOR_MLP_FP32", "split").lower() == "mfma" else SPLIT
@@ -120,17 +121,20 @@ class NetParams:
     * single precision: ``nn.Sequential`` of Linear/ReLU - the layers' own Parameters;
     * half precision: bias-free ``tinycudann.Network`` with one flat parameter vector - per-layer views of it (of the
       padded last layer only the first ``n_output_dims`` rows are evaluated; the padding rows never reach an output and
-      keep a zero gradient, as in tinycudann) and one shared all-zero bias vector.
+      keep a zero gradient, as in tinycudann) and one shared all-zero bias vector - or, in the scaled-fp16 mode (FP16S:
+      ``operands``, else the network's own ``network_operands``), NULL biases (``bias_free``): the kernels' bias-free forms,
+      whose partial rows W0 | W1 | ... are the prefix of the flat gradient ``segment`` (``params.grad``).
 
     ``store_grads`` reduces the backward kernel's per-workgroup partial sums (columns W0,b0,W1,b1,...) into the
     parameters' ``.grad`` - which the fused trainer has re-homed into its flat gradient buffer.
     """
 
-    def __init__(self, net):
+    def __init__(self, net, operands=None):
         from .tinycudann import Network
 
         self.net = net
         self.flat_params = isinstance(net, Network)
+        self.bias_free = False
         if self.flat_params:
             p = net.params.data
             self.weights, self.w_off, off = [], [], 0
@@ -139,9 +143,14 @@ class NetParams:
                 self.weights.append(p[off : off + rows * i].view(rows, i))
                 self.w_off.append(off)
                 off += o * i
-            zero = torch.zeros(64, dtype=torch.float32, device=p.device)
-            self.biases = [zero[: w.shape[0]] for w in self.weights]
-            self.segment = None
+            self.bias_free = operand_mode(network_operands(net) if operands is None else operands) == FP16S
+            if self.bias_free:
+                self.biases = [None] * len(self.weights)
+                self.segment = net.params.grad
+            else:
+                zero = torch.zeros(64, dtype=torch.float32, device=p.device)
+                self.biases = [zero[: w.shape[0]] for w in self.weights]
+                self.segment = None
         else:
             layers = linear_layers(net)
             if not native_width(net):
@@ -163,6 +172,10 @@ class NetParams:
     def n_hidden(self):
         return len(self.weights) - 1
 
+    def n_columns(self):
+        """Columns of the backward's partial rows: every evaluated weight and bias (a bias-free network: the weights only)."""
+        return sum(w.numel() + (0 if b is None else b.numel()) for w, b in zip(self.weights, self.biases))
+
     def _sum_rows(self, src_ptr, dst, rows, cols, ld):
         with torch.cuda.device(dst.device):
             err = _lib.load().nesvor_sum_rows(src_ptr, _lib.ptr(dst), rows, cols, ld, _lib.stream_ptr())
@@ -175,7 +188,7 @@ class NetParams:
             col = 0
             for w, off in zip(self.weights, self.w_off):
                 self._sum_rows(partial.data_ptr() + 4 * col, g[off : off + w.numel()], rows, w.numel(), ld)
-                col += w.numel() + w.shape[0]
+                col += w.numel() + (0 if self.bias_free else w.shape[0])
             return
         if self.segment is not None and self.segment.numel() == ld:
             self._sum_rows(partial.data_ptr(), self.segment, rows, ld, ld)
@@ -199,7 +212,7 @@ def _desc(weights, biases, k_a, k_b, b_row0, S, bf16=False, prep=None):
     d.width, d.n_hidden, d.out_dim = 64, len(weights) - 1, weights[-1].shape[0]
     d.k_a, d.k_b, d.b_row0, d.samples_per_pixel = k_a, k_b, b_row0, S
     for i, (w, b) in enumerate(zip(weights, biases)):
-        d.weight[i], d.bias[i] = w.data_ptr(), b.data_ptr()
+        d.weight[i], d.bias[i] = w.data_ptr(), (None if b is None else b.data_ptr())  # (None: a bias-free network, FP16S only)
     if prep is not None:
         d.prep = prep.data_ptr()
     return d
@@ -276,7 +289,7 @@ def forward_raw(weights, biases, xa, xb, b_row0, k_b, S, need_saved, bf16=False,
     rounded to bf16 with fp32 accumulation (opt-in mixed precision); an int selects a mode constant directly.
     prep: the split mode's bounds (``nesvor_mlp_t.prep``; None: computed here by a pass over the inputs and the weights);
     y_absmax: zero-filled tensor of ABSMAX_FLOATS floats whose maximum is raised to max |y|."""
-    _lib.require_device(xb, *weights, *biases, dtype=torch.float32, name="fused MLP input/params")
+    _lib.require_device(xb, *weights, *(b for b in biases if b is not None), dtype=torch.float32, name="fused MLP input/params")
     N = xb.shape[1]
     k_a = 0 if xa is None else xa.shape[1]
     if xa is not None:
@@ -334,7 +347,7 @@ def backward_raw(weights, biases, xa, xb, dy, saved, b_row0, k_b, S, dxb, need_d
     d.dxa_group_sums = 1 if group_sums else 0
     rows = N // 16 if group_sums else N
     dxa = torch.empty((rows, k_a), dtype=torch.float32, device=dev) if (xa is not None and need_dxa) else None
-    total = sum(w.numel() + b.numel() for w, b in zip(weights, biases))
+    total = sum(w.numel() + (0 if b is None else b.numel()) for w, b in zip(weights, biases))  # (bias-free: no b columns)
     n_partial = N_PARTIAL_FUSED if fused else N_PARTIAL
     partial = torch.empty((n_partial, total), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev), _lib.kernel_timer.span("mlp_bwd"):
@@ -521,8 +534,9 @@ def apply_net(net, xa, xb, b_row0: int, k_b: int, samples_per_pixel: int):
 
 
 class FlatNetworkFunction(Function):
-    """``tinycudann.Network`` (one flat bias-free parameter vector) on the fused kernels, 16-bit matrix operands (``HALF_OPERANDS``:
-    bf16 by default, fp16 under ``args.fp16_loss_scaling``), 1-3 hidden layers, <= 64 inputs:
+    """``tinycudann.Network`` (one flat bias-free parameter vector) on the fused kernels, 16-bit matrix operands (the network's
+    ``network_operands``: bf16 by default, fp16 under ``args.fp16_loss_scaling``, scaled fp16 with NULL biases under
+    ``args.mlp_fp16`` - its bounds by ``prepare``, as the fp32 module path takes them), 1-3 hidden layers, <= 64 inputs:
     x (N, k) row-major -> y (N, n_output_dims).  The kernels read a feature-major input and write a feature-major
     output; the two transposes are the price of tinycudann's row-major module interface (the training step proper
     never pays it: nesvor_amd.direct feeds the kernels feature-major tensors)."""
@@ -535,8 +549,9 @@ class FlatNetworkFunction(Function):
         xb = torch.zeros((x.shape[1], n_pad), dtype=torch.float32, device=x.device)
         xb[:, :n] = x.detach().t()
         need = any(ctx.needs_input_grad)
-        y, saved = forward_raw(p.weights, p.biases, None, xb, 0, xb.shape[0], 16, need, HALF_OPERANDS[0])
-        ctx.net, ctx.n, ctx.mode = net, n, HALF_OPERANDS[0]
+        mode = network_operands(net)
+        y, saved = forward_raw(p.weights, p.biases, None, xb, 0, xb.shape[0], 16, need, mode)
+        ctx.net, ctx.n, ctx.mode = net, n, mode
         ctx.save_for_backward(xb, *saved)
         return y[:, :n].t()
 
@@ -544,7 +559,7 @@ class FlatNetworkFunction(Function):
     def backward(ctx, dy):
         xb, *saved = ctx.saved_tensors
         net, n = ctx.net, ctx.n
-        p = NetParams(net)
+        p = NetParams(net, ctx.mode)
         dyb = torch.zeros((dy.shape[1], xb.shape[1]), dtype=torch.float32, device=xb.device)
         dyb[:, :n] = dy.t()
         dxb = torch.empty_like(xb) if ctx.needs_input_grad[0] else None
@@ -555,11 +570,27 @@ class FlatNetworkFunction(Function):
             col, flat = 0, partial.sum(0)
             for w, off in zip(p.weights, p.w_off):  # padding rows of the last layer keep a zero gradient
                 g[off : off + w.numel()] = flat[col : col + w.numel()]
-                col += w.numel() + w.shape[0]
+                col += w.numel() + (0 if p.bias_free else w.shape[0])
         return (None if dxb is None else dxb[:, :n].t()), g, None
 
 
-HALF_OPERANDS = [True]  # the 16-bit operand mode of the half-precision structure's module path: True (bf16) or FP16 (set by train())
+HALF_OPERANDS = [True]  # the default operand mode of the half-precision structure's module path: bf16 (True)
+
+
+def network_operands(net):
+    """The operand mode a ``tinycudann.Network`` is evaluated in: its own ``operands`` attribute (FP16 under the loss scaler, FP16S
+    for ``args.mlp_fp16`` - set per instance by ``FusedTrainer`` and by the model's constructor), else ``HALF_OPERANDS[0]``."""
+    mode = getattr(net, "operands", None)
+    return HALF_OPERANDS[0] if mode is None else mode
+
+
+def set_network_operands(nets, mode) -> None:
+    """Give every ``tinycudann.Network`` of ``nets`` the operand mode ``mode`` (``network_operands``); other modules are left as they are."""
+    from .tinycudann import Network
+
+    for net in nets:
+        if isinstance(net, Network):
+            net.operands = mode
 
 
 def flat_network(net, x):
@@ -570,13 +601,16 @@ def flat_network(net, x):
 def inference_operands(inr, args):
     """How the density network's products are evaluated at inference (the `bf16` argument of ``forward_raw``) -
     the same choice the training step makes (nesvor_amd.direct): bf16 operands for the half-precision model structure
-    and for ``args.mlp_bf16``, otherwise fp32 (split-fp16 evaluation, or the fp32 MFMAs with ``args.mlp_fp32_mfma``)."""
+    and for ``args.mlp_bf16``, scaled fp16 for ``args.mlp_fp16`` (either structure; bias-free for the half-precision one), otherwise
+    fp32 (split-fp16 evaluation, or the fp32 MFMAs with ``args.mlp_fp32_mfma``)."""
     from .tinycudann import Network
 
     net = inr.density_net
     if not supported(net):
         return None  # library GEMMs (apply_net)
     if isinstance(net, Network):
+        if getattr(args, "mlp_fp16", False):
+            return FP16S  # scaled fp16, NULL biases (the bias-free kernels)
         return FP16 if getattr(args, "fp16_loss_scaling", False) else True
     if getattr(args, "mlp_bf16", False):
         return True

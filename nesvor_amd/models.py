@@ -117,6 +117,8 @@ class INR(nn.Module):
             n_hidden_layers=args.depth,
             dtype=args.dtype,
         )
+        if getattr(args, "mlp_fp16", False):  # the bias-free structure in scaled fp16 (a checkpoint carries the flag in its args)
+            fused_mlp_mod.set_network_operands([self.density_net], fused_mlp_mod.FP16S)
 
     def forward(self, x: torch.Tensor, return_all: bool = True):
         x = (x - self.bounding_box[0]) / (self.bounding_box[1] - self.bounding_box[0])
@@ -124,13 +126,13 @@ class INR(nn.Module):
         enc = self.encoding
         if (not torch.is_grad_enabled() and enc.dtype == torch.float16 and fused_mlp_mod.supported(self.density_net)):
             # half-precision model structure at inference (sample_volume / sample_slices): the same two kernels with
-            # bf16 matrix operands; outputs stay fp32
+            # the network's 16-bit operands (mlp.network_operands); outputs stay fp32
             from .encoding import hashgrid_forward
 
             pe_fm = hashgrid_forward(enc.spec, x.reshape(-1, 3).float().contiguous(), enc.params, _lib.LAYOUT_FEATURE_MAJOR)
             net = fused_mlp_mod.NetParams(self.density_net)
             z_fm, _ = fused_mlp_mod.forward_raw(net.weights, net.biases, None, pe_fm, 0, pe_fm.shape[0], 1, False,
-                                                bf16=fused_mlp_mod.HALF_OPERANDS[0])
+                                                bf16=fused_mlp_mod.network_operands(self.density_net))
         else:
             # feature-major hash grid -> fused MLP; (N,E)/(N,16) views are returned for API parity
             pe_fm = hashgrid_encode(x.reshape(-1, 3).float(), enc.params, enc.spec, _lib.LAYOUT_FEATURE_MAJOR, enc.grad_accum)
@@ -212,6 +214,8 @@ class NeSVoR(nn.Module):
             self.sigma_net = build_network(n_input_dims=a.n_features_slice + a.n_features_z, **head)
         if a.n_levels_bias:
             self.b_net = build_network(n_input_dims=a.n_levels_bias * a.n_features_per_level + a.n_features_slice, **head)
+        if getattr(a, "mlp_fp16", False):
+            fused_mlp_mod.set_network_operands([getattr(self, "sigma_net", None), getattr(self, "b_net", None)], fused_mlp_mod.FP16S)
 
     def forward(self, xyz: torch.Tensor, v: torch.Tensor, slice_idx: torch.Tensor) -> Dict[str, Any]:
         """One batch of slice pixels -> dict of scalar losses (models.py:260-327)."""

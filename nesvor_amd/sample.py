@@ -42,11 +42,12 @@ class PsfAveragedDensity:
         self.operands = mlp_mod.inference_operands(model, args)  # None: a network the kernels do not cover (library GEMMs)
         if self.operands is None:
             return
-        self.net = mlp_mod.NetParams(model.density_net)
+        self.net = mlp_mod.NetParams(model.density_net, self.operands)  # (scaled fp16 on a tinycudann.Network: NULL biases)
         # only output 0 (the density logit) of the density network is used here: its other rows (the features of the
         # variance / bias networks) are neither computed into HBM nor stored
         self.weights = list(self.net.weights[:-1]) + [self.net.weights[-1][:1].contiguous()]
-        self.biases = list(self.net.biases[:-1]) + [self.net.biases[-1][:1].contiguous()]
+        last_b = self.net.biases[-1]
+        self.biases = list(self.net.biases[:-1]) + [None if last_b is None else last_b[:1].contiguous()]
 
     def _noise(self, m: int, s: int):
         """-> (noise tensor | None, rng | None): explicit draws (no PSF: zeros; replay mode: the host generator's), or the

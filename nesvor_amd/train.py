@@ -120,6 +120,8 @@ def train(slices: List[Slice], args: Namespace, on_iteration=None) -> Tuple[INR,
     ``args.host_rng = True`` draws the batch permutation and the PSF noise from the HOST generator in the order a CPU run
     of the reference does (train.py:64, models.py:270) and uploads them: with the same ``torch.manual_seed`` the run then
     replays the reference's trajectory (tests/test_gpu_model.py holds it to the reference's own 20-iteration fixture)."""
+    if getattr(args, "mlp_fp16", False) and getattr(args, "fp16_loss_scaling", False):
+        raise RuntimeError("args.mlp_fp16 and args.fp16_loss_scaling exclude each other: scaled fp16 needs no loss scaler")
     dataset = Dataset(slices, args)
     model = NeSVoR(dataset.transformation, dataset.resolution, dataset.mean, dataset.bounding_box, args)
     from . import direct
