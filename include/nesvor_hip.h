@@ -22,7 +22,7 @@ extern "C" {
 #define NESVOR_MAX_LEVELS 32
 #define NESVOR_MAX_MLP_LAYERS 4
 
-/* ABI version; bumped on any signature change. */
+/* ABI version; bumped on any signature change (37: the device loss scaler). */
 int nesvor_hip_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -538,6 +538,12 @@ int nesvor_step_epilogue(const float* dc, const float* c, float* dlogit, const f
                          const float* dtrans, float w_trans, float* daxisangle, const float* loss_pix,
                          const float* trans_terms, float* losses, int n, int B, float img_scale, float img_offset,
                          void* stream);
+/* The same launch with the pose regulariser's weight multiplied by a DEVICE float: w_trans * (*w_trans_scale) (the loss scale
+ * of nesvor_loss_scaler_t, read by the kernel).  w_trans_scale NULL: exactly nesvor_step_epilogue. */
+int nesvor_step_epilogue_scaled(const float* dc, const float* c, float* dlogit, const float* dmat, const float* axisangle,
+                                const float* dtrans, float w_trans, const float* w_trans_scale, float* daxisangle,
+                                const float* loss_pix, const float* trans_terms, float* losses, int n, int B, float img_scale,
+                                float img_offset, void* stream);
 int nesvor_slice_grads(const int64_t* slice_idx, const float* dc_pix, const float* dlvs_pix, const float* dxa,
                        const float* dpix, float* dc, float* dlvs, float* dse, float* dmat, int B, int S, int ks,
                        void* stream);
@@ -566,6 +572,40 @@ int nesvor_adamw_step(float* param, float* grad, float* exp_avg, float* exp_avg_
 typedef struct {
   float lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, grad_scale;
 } nesvor_adamw_t;
+
+/* ------------------------------------------------------------------------
+ * Loss scaler on the device (csrc/scaler.hip): torch.cuda.amp.GradScaler as the reference configures it
+ * (nesvor/nesvor/train.py:161-164, 190-196) without a host read per iteration.  One struct per trainer, in device
+ * memory, 32 bytes; every field is read and written by the kernels below only (the host writes it before a step or
+ * reads it after one, on the same stream).
+ *   scale:          the loss scale every gradient of the step carries;
+ *   growth_factor, backoff_factor, growth_interval: the GradScaler settings;
+ *   growth_tracker: finite steps in a row since the last growth / backoff;  skipped: overflowing steps so far;
+ *   t:              the optimizer's step count (steps taken; a skipped step does not count);
+ *   found_inf:      non-zero once nesvor_grad_found_inf saw a NaN or an Inf since the last nesvor_loss_scaler_update.
+ * ---------------------------------------------------------------------- */
+typedef struct nesvor_loss_scaler_t {
+  float scale, growth_factor, backoff_factor;
+  int32_t growth_interval, growth_tracker, skipped, t;
+  uint32_t found_inf;
+} nesvor_loss_scaler_t;
+
+/* found_inf |= any(!isfinite(grad[0..n))): NaN, +Inf and -Inf count.  Any 4-byte aligned grad. */
+int nesvor_grad_found_inf(const float* grad, int64_t n, nesvor_loss_scaler_t* s, void* stream);
+/* nesvor_adamw_step predicated on the device state: if s->found_inf is zero, exactly nesvor_adamw_step with
+ * bias_correction{1,2} = 1 - beta{1,2}^(s->t + 1) (evaluated in double, as the host does, then rounded to float) and
+ * grad_scale = 1 / (world_size * s->scale) (likewise); otherwise param / exp_avg / exp_avg_sq are not touched and grad is
+ * zero-filled if zero_grad != 0.  s->t is NOT advanced here (nesvor_loss_scaler_update does).  param, grad, exp_avg and
+ * exp_avg_sq 16-byte aligned. */
+int nesvor_adamw_step_scaled(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1,
+                             double beta2, float eps, float weight_decay, int world_size, int zero_grad,
+                             const nesvor_loss_scaler_t* s, void* stream);
+/* The scaler's update, one lane (GradScaler.update): a finite step advances t and growth_tracker and multiplies the scale by
+ * growth_factor when growth_tracker reaches growth_interval (tracker back to 0); an overflowing step multiplies it by
+ * backoff_factor, resets growth_tracker and counts in skipped.  found_inf is cleared. */
+int nesvor_loss_scaler_update(nesvor_loss_scaler_t* s, void* stream);
+/* out[i] = base[i] * s->scale, i < n: the loss kernel's upstream weights (nesvor_loss_t.gw) under the device scale. */
+int nesvor_loss_scale_weights(const float* base, float* out, int n, const nesvor_loss_scaler_t* s, void* stream);
 
 /* Hash-grid backward whose owner pass also takes the AdamW step on the table: the workgroup that completes a chunk's
  * gradient updates table / exp_avg / exp_avg_sq of that chunk while the gradient is still in LDS, so the table gradient

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # NESVOR_HIP_LIB: load another build of the same ABI (tools/ablate_hashgrid.py times variants of one kernel this way)
 LIB_PATH = os.environ.get("NESVOR_HIP_LIB") or os.path.join(_HERE, "lib", "libnesvor_hip.so")
 MAX_LEVELS = 32
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 LAYOUT_ROW_MAJOR = 0
 LAYOUT_FEATURE_MAJOR = 1
@@ -98,6 +98,13 @@ class AdamwT(Structure):
     """Mirror of nesvor_adamw_t."""
 
     _fields_ = [(n, c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "bias_correction1", "bias_correction2", "grad_scale")]
+
+
+class LossScalerT(Structure):
+    """Mirror of nesvor_loss_scaler_t (the device loss scaler's state, csrc/scaler.hip)."""
+
+    _fields_ = [("scale", c_float), ("growth_factor", c_float), ("backoff_factor", c_float), ("growth_interval", c_int32),
+                ("growth_tracker", c_int32), ("skipped", c_int32), ("t", c_int32), ("found_inf", c_uint32)]
 
 
 _lib = None
@@ -184,6 +191,7 @@ _SIGNATURES = {
     "nesvor_step_prologue": ([_P] * 5 + [c_int, c_int, _P], c_int),
     "nesvor_step_prologue_pose": ([_P] * 5 + [c_int, c_int, _P, _P, _P, _P], c_int),
     "nesvor_step_epilogue": ([_P] * 6 + [c_float, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P], c_int),
+    "nesvor_step_epilogue_scaled": ([_P] * 6 + [c_float, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P], c_int),
     "nesvor_hashgrid_backward_adamw": ([POINTER(GridT), _P, _P, _P, _P, _P, c_int64, c_int, _P, c_int, _P, _P, _P, _P, POINTER(AdamwT), _P], c_int),
     "nesvor_hashgrid_backward_adamw_levels": ([POINTER(GridT), _P, _P, _P, _P, _P, c_int64, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, POINTER(AdamwT), _P], c_int),
     "nesvor_hashgrid_forward_levels": ([POINTER(GridT), _P, _P, _P, c_int64, c_int, _P, c_int, c_int, _P], c_int),
@@ -191,6 +199,10 @@ _SIGNATURES = {
         [_P, _P, _P, _P, c_int64] + [c_float] * 8 + [c_int, _P],
         c_int,
     ),
+    "nesvor_grad_found_inf": ([_P, c_int64, _P, _P], c_int),
+    "nesvor_adamw_step_scaled": ([_P, _P, _P, _P, c_int64, c_float, c_double, c_double, c_float, c_float, c_int, c_int, _P, _P], c_int),
+    "nesvor_loss_scaler_update": ([_P, _P], c_int),
+    "nesvor_loss_scale_weights": ([_P, _P, c_int, _P, _P], c_int),
     "nesvor_sum_rows_multi": ([_P, _P, _P, _P, c_int, c_int, _P], c_int),
     "nesvor_sum_rows": ([_P, _P, c_int, c_int, c_int, _P], c_int),
     "nesvor_step_create": ([POINTER(StepT)], c_void_p),

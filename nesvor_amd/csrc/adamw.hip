@@ -17,24 +17,7 @@ template <bool ZERO>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, const AdamArgs a, int prio) {
   if (prio) __builtin_amdgcn_s_setprio(3);  // small launches on the step's critical tail, next to the owner pass (see step_epilogue_kernel)
-  const int64_t n4 = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 P = reinterpret_cast<float4*>(p)[i], G = reinterpret_cast<float4*>(g)[i];
-    float4 M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i];
-    adam1(P.x, G.x, M.x, V.x, a); adam1(P.y, G.y, M.y, V.y, a);
-    adam1(P.z, G.z, M.z, V.z, a); adam1(P.w, G.w, M.w, V.w, a);
-    reinterpret_cast<float4*>(p)[i] = P;
-    reinterpret_cast<float4*>(m)[i] = M;
-    reinterpret_cast<float4*>(v)[i] = V;
-    if (ZERO) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  // tail (n not a multiple of 4)
-  const int64_t t = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) {
-    adam1(p[t], g[t], m[t], v[t], a);
-    if (ZERO) g[t] = 0.f;
-  }
+  adamw_sweep<ZERO>(p, g, m, v, n, a);
 }
 
 }  // namespace
@@ -146,4 +129,4 @@ extern "C" int nesvor_sum_rows_multi(const float* const* in, float* const* out, 
   return (int)hipGetLastError();
 }
 
-extern "C" int nesvor_hip_abi_version(void) { return 36; }
+extern "C" int nesvor_hip_abi_version(void) { return 37; }

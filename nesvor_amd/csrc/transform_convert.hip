@@ -329,7 +329,8 @@ __global__ __launch_bounds__(kStepBlock) void step_prologue_kernel(const float* 
 __global__ __launch_bounds__(kStepBlock) void step_epilogue_kernel(const float* __restrict__ dc, const float* __restrict__ c,
                                                             float* __restrict__ dlogit, const float* __restrict__ dmat,
                                                             const float* __restrict__ axisangle, const float* __restrict__ dtrans,
-                                                            float w_trans, float* __restrict__ daxisangle,
+                                                            float w_trans, const float* __restrict__ w_trans_scale,
+                                                            float* __restrict__ daxisangle,
                                                             const float* __restrict__ loss_pix, const float* __restrict__ trans_terms,
                                                             float* __restrict__ losses, int n, int B, float inv_B, float img_scale,
                                                             float img_offset) {
@@ -350,6 +351,8 @@ __global__ __launch_bounds__(kStepBlock) void step_epilogue_kernel(const float* 
   } else if (blockIdx.x == 1) {
     float tr = 0.f;
     if (dmat != nullptr) {
+      // (the loss scale of the device scaler, nesvor_loss_scaler_t: the same product the host forms for its own scale)
+      if (w_trans_scale != nullptr) w_trans *= *w_trans_scale;
       for (int i = threadIdx.x; i < n; i += blockDim.x) {
         float g[6];
         ax2mat_bwd_one(dmat + (size_t)i * 12, axisangle + (size_t)i * 6, g);
@@ -396,14 +399,22 @@ extern "C" int nesvor_step_prologue(const float* logit_coef, float* c, const flo
   return nesvor_step_prologue_pose(logit_coef, c, axisangle, mat, zero_buf, n_zero, n, nullptr, nullptr, nullptr, stream);
 }
 
+extern "C" int nesvor_step_epilogue_scaled(const float* dc, const float* c, float* dlogit, const float* dmat, const float* axisangle,
+                                           const float* dtrans, float w_trans, const float* w_trans_scale, float* daxisangle,
+                                           const float* loss_pix, const float* trans_terms, float* losses, int n, int B,
+                                           float img_scale, float img_offset, void* stream) {
+  if (n <= 0 || B <= 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(step_epilogue_kernel, dim3(3), dim3(kStepBlock), 0, (hipStream_t)stream, dc, c, dlogit, dmat, axisangle, dtrans,
+                     w_trans, w_trans_scale, daxisangle, loss_pix, trans_terms, losses, n, B, 1.f / (float)B, img_scale, img_offset);
+  return (int)hipGetLastError();
+}
+
 extern "C" int nesvor_step_epilogue(const float* dc, const float* c, float* dlogit, const float* dmat, const float* axisangle,
                                     const float* dtrans, float w_trans, float* daxisangle, const float* loss_pix,
                                     const float* trans_terms, float* losses, int n, int B, float img_scale, float img_offset,
                                     void* stream) {
-  if (n <= 0 || B <= 0) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(step_epilogue_kernel, dim3(3), dim3(kStepBlock), 0, (hipStream_t)stream, dc, c, dlogit, dmat, axisangle, dtrans,
-                     w_trans, daxisangle, loss_pix, trans_terms, losses, n, B, 1.f / (float)B, img_scale, img_offset);
-  return (int)hipGetLastError();
+  return nesvor_step_epilogue_scaled(dc, c, dlogit, dmat, axisangle, dtrans, w_trans, nullptr, daxisangle, loss_pix, trans_terms,
+                                     losses, n, B, img_scale, img_offset, stream);
 }
 
 extern "C" int nesvor_trans_loss(const float* ax, const float* ax_init, float* loss_per_slice, float* grad_ax, int n,

@@ -111,6 +111,7 @@ class DirectStep:
                                 w.get(B_REG, 0) if self.has_b else 0.0], dtype=torch.float32, device=dev)
         self.w_T = float(w.get(T_REG, 0))
         self._gw_base, self._w_T_base, self.loss_scale = self.gw.clone(), self.w_T, 1.0
+        self._scale_state = None  # the device loss scaler's state (set_device_loss_scale): its scale multiplies gw and w_T
         self.reg_type = loss_mod.REG_TYPES[a.image_regularization]
         self.delta = float(model.delta)
         # evaluation of the MLP matrix products (mlp.operand_mode): scaled fp16 with NULL biases for the half-precision model
@@ -213,7 +214,7 @@ class DirectStep:
             return False
         if (self.bf16 is True or self.bf16 == mlp_mod.FP16) and half_precision_model(self.model):
             return False
-        if self.loss_scale != 1.0:
+        if self.loss_scale != 1.0 or self._scale_state is not None:
             return False  # (the one-call step's descriptors hold the unscaled pose-regulariser weight)
         nets = [self.d_net] + ([self.s_net] if self.has_lv else []) + ([self.b_net] if self.has_b else [])
         # a biased network: its gradient one contiguous segment in the partial rows' column order; a bias-free one (FP16S): its
@@ -233,6 +234,16 @@ class DirectStep:
             self.loss_scale = float(scale)
             self.gw.copy_(self._gw_base * self.loss_scale)
             self.w_T = self._w_T_base * self.loss_scale
+
+    def set_device_loss_scale(self, state: torch.Tensor) -> None:
+        """The loss scale of the device scaler (fused.LossScaler with a device; ``state``: its nesvor_loss_scaler_t, whose first
+        word is the scale): every step multiplies the loss kernel's upstream weights by it on the device (nesvor_loss_scale_weights,
+        at the head of the step) and the epilogue the pose regulariser's (nesvor_step_epilogue_scaled) - the scale is never read
+        by the host.  Same products as ``set_loss_scale`` forms on the host."""
+        self._scale_state = state
+        self.loss_scale = 1.0
+        self.gw.copy_(self._gw_base)
+        self.w_T = self._w_T_base
 
     def _fused_backward_ok(self, N=None):
         """Per network (density, sigma | None, bias | None): does the wave-specialised fused MLP backward take it at N points per
@@ -486,6 +497,12 @@ class DirectStep:
         m, a = self.model, self.model.args
         lib = _lib.load()
         dev = xyz.device
+        scale_ptr = _lib.ptr(self._scale_state)  # NULL without the device loss scaler (its scale is the state's first word)
+        if self._scale_state is not None:
+            with torch.cuda.device(dev):
+                err = lib.nesvor_loss_scale_weights(_lib.ptr(self._gw_base), _lib.ptr(self.gw), self.gw.numel(), scale_ptr,
+                                                    _lib.stream_ptr())
+            _lib.check(err, "loss scale weights")
         B, S = xyz.shape[0], a.n_samples
         N = B * S
         n = m.n_slices
@@ -623,10 +640,10 @@ class DirectStep:
         if self.opt_T:
             main.wait_event(pose_reg_done)  # the pose regulariser from the start of the step; NOT the owner pass behind it
         with torch.cuda.device(dev):
-            err = lib.nesvor_step_epilogue(
+            err = lib.nesvor_step_epilogue_scaled(
                 _lib.ptr(dc if self.has_c else None), _lib.ptr(c), _lib.ptr(m.logit_coef.grad if self.has_c else None),
                 _lib.ptr(dmat if self.opt_T else None), _lib.ptr(m.axisangle), _lib.ptr(g_t if self.opt_T else None), self.w_T,
-                _lib.ptr(m.axisangle.grad if self.opt_T else None), _lib.ptr(loss_pix), _lib.ptr(per if self.opt_T else None),
+                scale_ptr, _lib.ptr(m.axisangle.grad if self.opt_T else None), _lib.ptr(loss_pix), _lib.ptr(per if self.opt_T else None),
                 _lib.ptr(vals), n, B, img_scale, img_off, _lib.stream_ptr())
         _lib.check(err, "step epilogue")
         losses = {D_LOSS: vals[0]}

@@ -54,16 +54,84 @@ class FlatParams:
         return self.grad[off : off + cnt]
 
 
+# the fields of nesvor_loss_scaler_t (include/nesvor_hip.h), one 32-bit word each, in order
+_SCALER_FIELDS = ("scale", "growth_factor", "backoff_factor", "growth_interval", "growth_tracker", "skipped", "t", "found_inf")
+_SCALER_FLOATS = ("scale", "growth_factor", "backoff_factor")
+
+
 class LossScaler:
     """``torch.cuda.amp.GradScaler`` as the reference configures it (nesvor/nesvor/train.py:161-164: ``init_scale=1.0,
-    growth_factor=2.0, backoff_factor=0.5``, PyTorch's default ``growth_interval=2000``), host side: the scale is a Python
-    float, the verdict of an iteration (all gradients finite?) is the one device value read per step."""
+    growth_factor=2.0, backoff_factor=0.5``, PyTorch's default ``growth_interval=2000``).
 
-    def __init__(self, init_scale: float = 1.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000):
+    ``device=None``: the host form, kept as the reference implementation - the scale is a Python float and the verdict of an
+    iteration (all gradients finite?) is a device value the caller reads and passes to ``update``.  With a device: the state
+    lives in GPU memory (nesvor_loss_scaler_t, csrc/scaler.hip) and the kernels decide - ``grad_found_inf`` checks a gradient,
+    ``torch.ops.nesvor.adamw_step_scaled_`` steps or skips on that verdict, ``update`` grows / backs off the scale - with no host
+    read.  The fields
+    below are then properties: reading one copies the state to the host (a synchronisation, on demand only), assigning one
+    writes it on the current stream."""
+
+    def __init__(self, init_scale: float = 1.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000,
+                 device=None):
+        self.state = None  # device mode: int32 (8,) = nesvor_loss_scaler_t
+        self._host = {}
+        if device is not None:
+            self.state = torch.zeros(_ops.LOSS_SCALER_WORDS, dtype=torch.int32, device=device)
         self.scale, self.growth_factor, self.backoff_factor, self.growth_interval = float(init_scale), growth_factor, backoff_factor, growth_interval
-        self.growth_tracker, self.skipped = 0, 0
+        self.growth_tracker, self.skipped, self.t, self.found_inf = 0, 0, 0, 0
 
-    def update(self, found_inf: bool) -> None:
+    @property
+    def on_device(self) -> bool:
+        return self.state is not None
+
+    def _read(self) -> Dict[str, float]:
+        w = self.state.cpu()
+        f = w.view(torch.float32)
+        return {k: float(f[i]) if k in _SCALER_FLOATS else int(w[i]) for i, k in enumerate(_SCALER_FIELDS)}
+
+    def _field(name):  # noqa: N805  (class-body helper: one property per field of the state)
+        i, is_float = _SCALER_FIELDS.index(name), name in _SCALER_FLOATS
+
+        def get(self):
+            if self.state is None:
+                return self._host[name]
+            return self._read()[name]
+
+        def put(self, value):
+            if self.state is None:
+                self._host[name] = value
+            elif is_float:
+                self.state.view(torch.float32)[i].fill_(float(value))
+            else:
+                self.state[i].fill_(int(value))
+
+        return property(get, put)
+
+    scale = _field("scale")
+    growth_factor = _field("growth_factor")
+    backoff_factor = _field("backoff_factor")
+    growth_interval = _field("growth_interval")
+    growth_tracker = _field("growth_tracker")
+    skipped = _field("skipped")
+    t = _field("t")  # device mode: the optimizer's step count (steps taken)
+    found_inf = _field("found_inf")  # device mode: the pending verdict (cleared by update)
+    del _field
+
+    def scale_tensor(self) -> torch.Tensor:
+        """Device mode: the scale as a 0-d float tensor view of the state (what a loss is multiplied by on the device)."""
+        return self.state.view(torch.float32)[0]
+
+    def grad_found_inf(self, grad: torch.Tensor) -> None:
+        """Device mode: record whether ``grad`` holds a NaN or an Inf (OR-ed into the pending verdict)."""
+        torch.ops.nesvor.grad_found_inf_(grad, self.state)
+
+    def update(self, found_inf: Optional[bool] = None) -> None:
+        """GradScaler.update.  Host mode: with this iteration's verdict.  Device mode: on the pending verdict (no argument)."""
+        if self.state is not None:
+            if found_inf is not None:
+                raise TypeError("LossScaler.update: the device scaler takes its verdict from grad_found_inf, not from the host")
+            torch.ops.nesvor.loss_scaler_update_(self.state)
+            return
         if found_inf:
             self.scale *= self.backoff_factor
             self.growth_tracker = 0
@@ -75,6 +143,9 @@ class LossScaler:
                 self.growth_tracker = 0
 
     def state_dict(self):
+        if self.state is not None:
+            d = self._read()
+            return {"scale": d["scale"], "growth_tracker": d["growth_tracker"], "skipped": d["skipped"]}
         return {"scale": self.scale, "growth_tracker": self.growth_tracker, "skipped": self.skipped}
 
 
@@ -94,7 +165,8 @@ class FusedTrainer:
         self.weights = loss_weights(args)
         self.lr = float(args.learning_rate)
         self.betas, self.eps, self.weight_decay = (0.9, 0.99), 1e-15, 1e-2
-        self.t = 0
+        self.scaler = None
+        self._t = 0  # the optimizer's step count (under the device loss scaler: its state's, see the property)
         self.world_size = world_size
         self._reduce_hook = None  # set by ddp: callable(flat_grad) performing the all-reduce(sum)
         # True (set by a training loop that touches nothing but the losses between steps): a single-process native step may
@@ -114,20 +186,44 @@ class FusedTrainer:
             # the bias-free structure in scaled fp16 (NULL biases, no loss scaler): the mode travels with each network
             _mlp.set_network_operands(direct._nets(model), _mlp.FP16S)
         self.direct = direct.DirectStep(model, self.flat, self.weights) if direct.supported(model) else None
-        # the reference's default numerics, opt-in (round 6): fp16 matrix operands + its GradScaler (train.py:161-164)
-        self.scaler = None
+        # the reference's default numerics, opt-in (round 6): fp16 matrix operands + its GradScaler (train.py:161-164), the scaler's
+        # state and verdict on the device (csrc/scaler.hip; NESVOR_LOSS_SCALER=host: the host form, single process, for A/B)
         if getattr(args, "fp16_loss_scaling", False):
-            if not direct.half_precision_model(model) or distributed:
-                raise RuntimeError("args.fp16_loss_scaling: the half-precision model structure (no --single-precision), single process "
-                                   "(the reference's loop, which it restates, has no data parallelism)")
+            on_host = os.environ.get("NESVOR_LOSS_SCALER", "device") == "host"
+            if not direct.half_precision_model(model):
+                raise RuntimeError("args.fp16_loss_scaling: the half-precision model structure (no --single-precision)")
+            if distributed and on_host:
+                raise RuntimeError("args.fp16_loss_scaling with NESVOR_LOSS_SCALER=host: single process only (the data-parallel "
+                                   "step decides on the device)")
+            if self.sharded:
+                raise RuntimeError("args.fp16_loss_scaling and the sharded optimizer (args.ddp_sharded_optimizer / NESVOR_DDP_SHARDED=1) "
+                                   "exclude each other: every rank would see only its shard's gradient, and the verdict of the step "
+                                   "would need an all-reduce(MAX) of the overflow flag; use the plain all-reduce exchange")
             # (the module path of tinycudann.Network: inference between / after training) - on the model's own networks; the
             # process-wide default follows as before, for networks that carry no mode of their own
             _mlp.set_network_operands(direct._nets(model), _mlp.FP16)
             _mlp.HALF_OPERANDS[0] = _mlp.FP16
-            self.scaler = LossScaler()
+            self.scaler = LossScaler(device=None if on_host else self.flat.param.device)
+            if self.direct is not None and self.scaler.on_device:
+                self.direct.set_device_loss_scale(self.scaler.state)
         if getattr(args, "mlp_bf16", False) and self.direct is None or (
                 getattr(args, "mlp_fp16", False) and self.direct is None and not direct.half_precision_model(model)):
             raise RuntimeError("args.mlp_bf16 / args.mlp_fp16 need the autograd-free step (fused fp32 model, MLPs of at most two hidden layers)")
+
+    @property
+    def t(self) -> int:
+        """The optimizer's step count.  Under the device loss scaler it lives in the scaler's state (a skipped step does not
+        count, and only the device knows which steps were skipped): reading it then synchronises, assigning it writes it."""
+        if self.scaler is not None and self.scaler.on_device:
+            return self.scaler.t
+        return self._t
+
+    @t.setter
+    def t(self, value: int) -> None:
+        if self.scaler is not None and self.scaler.on_device:
+            self.scaler.t = value
+        else:
+            self._t = value
 
     @property
     def reduce_hook(self):
@@ -137,30 +233,53 @@ class FusedTrainer:
         """One iteration under the loss scaler (``args.fp16_loss_scaling``): what the reference's loop does around its optimizer
         (train.py:190-196: ``scaler.scale(loss).backward(); scaler.step(optimizer); scaler.update()``) - every gradient carries the
         scale, a step whose gradients are not all finite is SKIPPED (parameters, moments and step count untouched, gradients
-        dropped) and halves the scale, ``growth_interval`` finite steps in a row double it.  Like ``GradScaler.step`` this reads one
-        device flag per iteration (a host synchronisation the fp32 path does not have)."""
+        dropped) and halves the scale, ``growth_interval`` finite steps in a row double it."""
+        losses = self._scaled_backward(xyz, v, slice_idx, noise)
+        self._scaled_update()
+        return losses
+
+    def _scaled_backward(self, xyz, v, slice_idx, noise=None) -> Dict[str, torch.Tensor]:
+        """Forward and backward of the scaled loss: the flat gradient holds scale x the step's gradient."""
         sc = self.scaler
         if self.direct is not None:
-            self.direct.set_loss_scale(sc.scale)
+            if not sc.on_device:
+                self.direct.set_loss_scale(sc.scale)  # (the device scaler's reaches the kernels by itself: set_device_loss_scale)
             losses = self._forward_backward(xyz, v, slice_idx, noise)
             self.direct.join_owner()
-        else:  # (shapes the autograd-free step does not take - three hidden layers, ...: autograd over flat_network, loss times the scale)
-            losses = self._forward_backward(xyz, v, slice_idx, noise, loss_scale=sc.scale)
-        finite = bool(torch.isfinite(self.flat.grad).all())
+            return losses
+        # (shapes the autograd-free step does not take - three hidden layers, ...: autograd over flat_network, loss times the scale)
+        return self._forward_backward(xyz, v, slice_idx, noise, loss_scale=sc.scale_tensor() if sc.on_device else sc.scale)
+
+    def _scaled_update(self) -> None:
+        """Exchange (data parallel), verdict, AdamW or skip, scaler update.  The device scaler: four launches and no host read -
+        after the sum all-reduce every rank holds the same gradient bits, so every rank reaches the same verdict by itself.  The
+        host scaler reads the verdict (one synchronisation per step, like ``GradScaler.step``)."""
+        sc, f = self.scaler, self.flat
+        if sc.on_device:
+            if self.reduce_hook is not None:
+                self.reduce_hook(f.grad)  # ONE all-reduce of the whole buffer: the verdict is taken on the reduced gradient
+            sc.grad_found_inf(f.grad)
+            torch.ops.nesvor.adamw_step_scaled_(f.param, f.grad, f.exp_avg, f.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                self.weight_decay, self.world_size, True, sc.state)
+            sc.update()
+            return
+        finite = bool(torch.isfinite(f.grad).all())
         if finite:
             self.t += 1
-            f = self.flat
             torch.ops.nesvor.adamw_step_(f.param, f.grad, f.exp_avg, f.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
                                          self.weight_decay, self.t, 1.0 / (self.world_size * sc.scale), True)
         else:
-            self.flat.grad.zero_()
+            f.grad.zero_()
         sc.update(found_inf=not finite)
-        return losses
 
     @reduce_hook.setter
     def reduce_hook(self, hook) -> None:
         self._reduce_hook = hook
-        if self.direct is not None:
+        if self.direct is not None and self.scaler is not None:
+            # under the loss scaler no part of the buffer may be updated before the verdict on the WHOLE gradient: no early
+            # exchange, no early AdamW of the fine levels (an update already applied cannot be skipped)
+            self.direct.set_overlap(False)
+        elif self.direct is not None:
             # the fine hash-grid levels' gradient is exchanged early, under the rest of the backward: an all-reduce of that
             # range, or - with optimizer sharding - its reduce-scatter (ddp.ShardedExchange part 1)
             self.direct.set_overlap(hook is not None)
@@ -206,7 +325,8 @@ class FusedTrainer:
         for k, val in losses.items():
             if k in self.weights and self.weights[k]:
                 loss = loss + self.weights[k] * val
-        (loss * loss_scale if loss_scale != 1.0 else loss).backward()
+        # (a device tensor: the device scaler's scale, multiplied on the device)
+        (loss * loss_scale if isinstance(loss_scale, torch.Tensor) or loss_scale != 1.0 else loss).backward()
         return losses
 
     def step(self, xyz, v, slice_idx, noise=None) -> Dict[str, torch.Tensor]:

@@ -602,5 +602,57 @@ _op("adamw_step_(Tensor(a!) param, Tensor(b!) grad, Tensor(c!) exp_avg, Tensor(d
     fake=lambda *a: None)
 
 
+# =====================================================================================================================
+# the loss scaler of the fp16 mode on the device (train.py:161-164, 190-196; csrc/scaler.hip).  ``state``: the 32 bytes of
+# nesvor_loss_scaler_t as an int32 tensor of LOSS_SCALER_WORDS elements (nesvor_amd.fused.LossScaler owns one per trainer)
+# =====================================================================================================================
+LOSS_SCALER_WORDS = ctypes.sizeof(_lib.LossScalerT) // 4
+
+
+def _scaler_state(state):
+    _lib.require_device(state, dtype=torch.int32, name="loss scaler state")
+    if state.numel() != LOSS_SCALER_WORDS:
+        raise RuntimeError(f"loss scaler state: {LOSS_SCALER_WORDS} int32 words (nesvor_loss_scaler_t), got {state.numel()}")
+    return _lib.ptr(state)
+
+
+def _grad_found_inf(grad, state):
+    _lib.require_device(grad, dtype=torch.float32, name="gradient")
+    s = _scaler_state(state)
+    with torch.cuda.device(grad.device):
+        err = _lib.load().nesvor_grad_found_inf(_lib.ptr(grad), grad.numel(), s, _lib.stream_ptr())
+    _lib.check(err, "grad found_inf")
+
+
+_op("grad_found_inf_(Tensor grad, Tensor(a!) state) -> ()", _grad_found_inf, fake=lambda *a: None)
+
+
+def _adamw_step_scaled(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, world_size, zero_grad, state):
+    _lib.require_device(param, grad, exp_avg, exp_avg_sq, dtype=torch.float32, name="adamw buffers")
+    if any(t.data_ptr() % 16 for t in (param, grad, exp_avg, exp_avg_sq)):
+        raise RuntimeError("adamw_step_scaled_: the buffers must be 16-byte aligned")
+    s = _scaler_state(state)
+    with torch.cuda.device(param.device):
+        err = _lib.load().nesvor_adamw_step_scaled(
+            _lib.ptr(param), _lib.ptr(grad), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), param.numel(), lr, beta1, beta2, eps,
+            weight_decay, int(world_size), int(bool(zero_grad)), s, _lib.stream_ptr())
+    _lib.check(err, "adamw step (device loss scaler)")
+
+
+_op("adamw_step_scaled_(Tensor(a!) param, Tensor(b!) grad, Tensor(c!) exp_avg, Tensor(d!) exp_avg_sq, float lr, float beta1, "
+    "float beta2, float eps, float weight_decay, int world_size, bool zero_grad, Tensor state) -> ()", _adamw_step_scaled,
+    fake=lambda *a: None)
+
+
+def _loss_scaler_update(state):
+    s = _scaler_state(state)
+    with torch.cuda.device(state.device):
+        err = _lib.load().nesvor_loss_scaler_update(s, _lib.stream_ptr())
+    _lib.check(err, "loss scaler update")
+
+
+_op("loss_scaler_update_(Tensor(a!) state) -> ()", _loss_scaler_update, fake=lambda *a: None)
+
+
 def op_names() -> List[str]:
     return sorted(SCHEMAS)
