@@ -660,6 +660,8 @@ int nesvor_sum_rows_multi(const float* const* in, float* const* out, const int* 
  * nesvor_step_run(phase = 0): the whole iteration.  Data parallel: phase 1 = everything up to and including the hash-grid
  * backward of levels [split_level, L) (the host then starts the all-reduce of that part of the table gradient), phase 2 =
  * the remaining levels and the rest of the iteration.  adam == NULL: no optimizer step (the caller reduces gradients first).
+ * With has_b, phase 0 or phase 1 can itself stop at the bias field's mean and resume behind its all-reduce: the
+ * NESVOR_STEP_BIAS_SUM_* flags below.
  * The PSF noise is drawn inside the sampler kernels from (seed, offset) as in nesvor_psf_transform_forward_rng.
  * ---------------------------------------------------------------------- */
 #define NESVOR_STEP_MLP_PARTIALS 256
@@ -723,6 +725,31 @@ int nesvor_step_run(void* step, const float* xyz, const float* v, const int64_t*
  * nesvor_step_join.  Everything but the table (losses, the other parameters) is complete on `stream` as always. */
 #define NESVOR_STEP_DEFER_JOIN 8
 int nesvor_step_join(void* step, void* stream);
+/* The bias field under data parallelism.  biasReg = (mean log_bias)^2 (models.py:322-323) is not a mean of per-sample terms: it needs
+ * the mean over ALL ranks' samples, one scalar all-reduce between b_net's forward and the loss kernel.  Two flags, OR-ed into
+ * phase 0 or phase 1 (has_b only; never both in one call), run that phase in two calls around the exchange:
+ *   NESVOR_STEP_BIAS_SUM_STOP   : prologue, weight norms and images, sampler, hash-grid forward, b_net's input bounds and forward - in
+ *                                 FRONT of the density network's, it reads pe and se only - and ONE launch that writes this rank's
+ *                                 share of the global mean, sum(log_bias) / (N ranks), into lb_mean; then the call returns.
+ *                                 The host sum-all-reduces that one float in place, on any stream ordered behind `stream`.
+ *   NESVOR_STEP_BIAS_SUM_RESUME : same arguments.  Density and sigma forwards - they run while the scalar travels - then `stream`
+ *                                 waits for the event of nesvor_step_set_bias_mean_event, then the loss kernel and everything
+ *                                 behind it, as the un-staged call of that phase (`adam`, NESVOR_STEP_DEFER_JOIN and split_level
+ *                                 included).  Weight images, operand bounds, timing spans and the side-stream book-keeping of the
+ *                                 first call stay valid for the second, as they do from phase 1 to phase 2.
+ * losses[5] (biasReg) is written by the call that completes the step (RESUME at phase 0, phase 2 otherwise): the square of the
+ * exchanged mean.  Without the flags a phase-1 / phase-2 pair with has_b uses this rank's own mean (a group of one rank).
+ * nesvor_step_set_bias_mean_ranks: the number of ranks W the staged reduction divides by (<= 0 or never set: 1).
+ * nesvor_step_set_bias_mean_event: a hipEvent_t recorded behind the all-reduce; consumed by the next RESUME call (the wait is
+ * enqueued there, the host never blocks; the event may be destroyed once that call has returned).  NULL, or never set: the
+ * caller has ordered `stream` behind the all-reduce itself.
+ * These two flags and two entry points were added WITHOUT a change of nesvor_hip_abi_version() (37; nothing that existed changed
+ * its layout or meaning): the version number does not tell a caller whether they exist - resolve the symbols
+ * (dlsym(lib, "nesvor_step_set_bias_mean_event")) to find out; a library without them refuses the flags with hipErrorInvalidValue. */
+#define NESVOR_STEP_BIAS_SUM_STOP 16
+#define NESVOR_STEP_BIAS_SUM_RESUME 32
+int nesvor_step_set_bias_mean_ranks(void* step, int ranks);
+int nesvor_step_set_bias_mean_event(void* step, void* event);
 /* Per-launch timing of the product step (the roofline leg of bench.py): nesvor_step_timing(handle, 1) makes every following
  * nesvor_step_run bracket the launches listed above with HIP events on the stream each goes to; nesvor_step_timing_read waits
  * for the last run and returns NESVOR_STEP_TIMED_SPANS durations in ms (-1: the span did not occur in that run). */

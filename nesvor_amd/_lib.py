@@ -19,6 +19,8 @@ ABI_VERSION = 37
 LAYOUT_ROW_MAJOR = 0
 LAYOUT_FEATURE_MAJOR = 1
 STEP_DEFER_JOIN = 8  # nesvor_step_run: OR-ed into `phase` (NESVOR_STEP_DEFER_JOIN)
+STEP_BIAS_SUM_STOP = 16  # ... phase 0 / 1 of a bias-field step up to this rank's share of the global mean of log_bias
+STEP_BIAS_SUM_RESUME = 32  # ... and the rest of that phase, behind the event of nesvor_step_set_bias_mean_event
 LAYOUT_CLUSTERED = 4  # forward hint, OR-ed into the layout: 256 consecutive points are one spatial cluster
 LAYOUT_UNCLUSTERED = 8  # backward hint, OR-ed into the layout: consecutive points are not clustered - order them by cell first
 LAYOUT_DY_SCRATCH = 16  # with LAYOUT_UNCLUSTERED | LAYOUT_FEATURE_MAJOR: the workspace (sized by ..._workspace_bytes_ex) has room for dpe as rows
@@ -209,6 +211,8 @@ _SIGNATURES = {
     "nesvor_step_update": ([_P, POINTER(StepT)], c_int),
     "nesvor_step_destroy": ([_P], None),
     "nesvor_step_join": ([_P, _P], c_int),
+    "nesvor_step_set_bias_mean_ranks": ([_P, c_int], c_int),
+    "nesvor_step_set_bias_mean_event": ([_P, _P], c_int),
     "nesvor_step_timing": ([_P, c_int], c_int),
     "nesvor_step_timing_read": ([_P, _P], c_int),
     "nesvor_step_run": ([_P, _P, _P, _P, c_uint64, c_uint64, _P, c_int, c_int, POINTER(AdamwT), _P], c_int),

@@ -16,6 +16,9 @@ the ``register`` command offers the same two.  Precision follows the reference's
 structure - bias-free networks - which the HIP path evaluates with bf16 matrix operands and fp32 accumulation;
 ``--mlp-fp16`` without ``--single-precision`` trains that structure with power-of-two-scaled fp16 operands instead, on
 the kernels' bias-free forms, and ``--fp16-loss-scaling`` with fp16 operands under the reference's loss scaler).
+
+Not in the reference (it is single-process): ``torchrun --nproc-per-node N -m nesvor_amd.cli reconstruct ...`` trains data-parallel,
+one process per GPU (nesvor_amd/ddp.py); rank 0 samples and writes the outputs.  The other commands stay single-process.
 """
 import argparse
 import logging
@@ -83,7 +86,7 @@ def _output_volume_flags(g) -> None:
 
 def _common_flags(p: argparse.ArgumentParser) -> None:
     g = p.add_argument_group("common")
-    g.add_argument("--device", default=0, type=int, help="HIP device index")
+    g.add_argument("--device", default=None, type=int, help="HIP device index (default 0; under a launcher: the rank's own device)")
     g.add_argument("--verbose", type=int, default=1, choices=[0, 1, 2])
     g.add_argument("--output-log", type=str)
     g.add_argument("--seed", type=int, default=None)
@@ -164,13 +167,41 @@ def stacks_to_slices(stacks) -> List:
 def _setup(args: Namespace) -> None:
     level = {0: logging.WARNING, 1: logging.INFO, 2: logging.DEBUG}[args.verbose]
     handlers = [logging.StreamHandler(sys.stderr)]
-    if args.output_log:
+    launched = _under_launcher() and args.command == "reconstruct"
+    if args.output_log and not (launched and int(os.environ.get("RANK", "0")) > 0):  # (data parallel: ONE writer of the log file, rank 0)
         handlers.append(logging.FileHandler(args.output_log, mode="w"))
     logging.basicConfig(level=level, format="%(asctime)s %(levelname)s %(message)s", handlers=handlers, force=True)
+    args.rank, args.distributed = 0, False
+    if launched:
+        # data parallel, one process per GPU (torchrun's environment, or NESVOR_DDP_FORCE=1: a group of one rank)
+        import torch.distributed as dist
+
+        from . import ddp
+
+        args.distributed = not dist.is_initialized()  # (a group the caller made is the caller's to destroy)
+        args.rank, local_rank, _ = ddp.init_distributed()
+        if args.device is not None:
+            logging.warning("--device %d ignored under a launcher: rank %d runs on its own device", args.device, args.rank)
+        args.device = ddp.local_device(local_rank)
+        torch.cuda.set_device(args.device)
+        # every rank starts from the SAME seed (train() derives the per-rank PSF-noise seed from it): without --seed, rank 0's draw
+        # (torch.seed() is an unsigned 64-bit value: its low 63 bits travel as an int64)
+        seed = args.seed if args.seed is not None else (torch.seed() & (2**63 - 1) if args.rank == 0 else 0)
+        seed = torch.tensor([seed], dtype=torch.int64, device=args.device if dist.get_backend() == "nccl" else "cpu")
+        dist.broadcast(seed, src=0)
+        torch.manual_seed(int(seed.item()))
+        return
     if args.seed is not None:
         torch.manual_seed(args.seed)
-    args.device = torch.device("cuda", args.device)
+    args.device = torch.device("cuda", args.device or 0)
     torch.cuda.set_device(args.device)
+
+
+def _under_launcher() -> bool:
+    """torchrun's environment (WORLD_SIZE > 1), or a forced group of one rank (NESVOR_DDP_FORCE=1)."""
+    from . import ddp
+
+    return int(os.environ.get("WORLD_SIZE", "1")) > 1 or ddp.forced()
 
 
 def _load_model(args: Namespace):
@@ -271,13 +302,21 @@ def reconstruct(args: Namespace) -> None:
     model, output_slices, mask = train(slices, args)
     logging.info("Reconstruction finished in %.1f s", time.time() - t0)
     t0 = time.time()
-    data = {"mask": mask, "output_model": model, "output_slices": output_slices}
-    if args.output_volume:
-        data["output_volume"] = sample_volume(model, mask, args)
-    if args.simulated_slices:
-        data["simulated_slices"] = sample_slices(model, output_slices, mask, args)
-    _outputs(data, args)
-    logging.info("Results saving finished in %.1f s", time.time() - t0)
+    try:
+        if getattr(args, "rank", 0) == 0:  # (data parallel: the replicas are identical; the other ranks wait below)
+            data = {"mask": mask, "output_model": model, "output_slices": output_slices}
+            if args.output_volume:
+                data["output_volume"] = sample_volume(model, mask, args)
+            if args.simulated_slices:
+                data["simulated_slices"] = sample_slices(model, output_slices, mask, args)
+            _outputs(data, args)
+            logging.info("Results saving finished in %.1f s", time.time() - t0)
+    finally:
+        if getattr(args, "distributed", False):  # (set by _setup when it made the group; also when rank 0 failed above: the others must leave)
+            import torch.distributed as dist
+
+            dist.barrier()
+            dist.destroy_process_group()
 
 
 def sample_volume_cmd(args: Namespace) -> None:
@@ -302,6 +341,8 @@ def sample_slices_cmd(args: Namespace) -> None:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
+    if args.command != "reconstruct" and int(os.environ.get("RANK", "0")) > 0:
+        return  # under a launcher only `reconstruct` is data-parallel: one process does the rest
     _setup(args)
     t0 = time.time()
     {"reconstruct": reconstruct, "register": register_cmd, "sample-volume": sample_volume_cmd,

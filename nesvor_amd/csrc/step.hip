@@ -16,6 +16,8 @@
 // The configuration switches are those of the reference's args (no_transformation_optimization, no_pixel_variance,
 // no_slice_scale, no_slice_variance, n_levels_bias).  Data-parallel runs call the step in two phases so that the host
 // can start the all-reduce of the fine levels' gradient in between (nesvor_amd/ddp.py).
+// With a bias field the first of them (or the whole step) is itself staged around the all-reduce of ONE float: biasReg = (mean log_bias)^2
+// needs the mean over all ranks' samples (NESVOR_STEP_BIAS_SUM_STOP / NESVOR_STEP_BIAS_SUM_RESUME).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +41,11 @@ struct StepCtx {
   bool head_on_side = false;  // (NESVOR_STEP_HEAD=side: phase 2 of a split run must join what phase 1 forked)
   bool sums_on_side = false;  // the networks' parameter-gradient sums of the current iteration were left on the side stream
   bool pending_join = false;  // a table update of the previous run is still on the side stream (NESVOR_STEP_DEFER_JOIN)
+  // Staged bias-field step (NESVOR_STEP_BIAS_SUM_STOP / _RESUME): ranks the share of the global mean divides by, the event behind the
+  // host's all-reduce of it (consumed by the next RESUME call), the arrival counter of mean_share_kernel
+  int bias_mean_ranks = 1;
+  hipEvent_t bias_mean_event = nullptr;
+  unsigned* mean_ticket = nullptr;
   // nesvor_step_timing: HIP-event brackets around the PRODUCT launches of a run, each pair on the stream its launch goes to
   bool timing = false, timed_run = false;
   hipEvent_t t0[NESVOR_STEP_TIMED_SPANS], t1[NESVOR_STEP_TIMED_SPANS];
@@ -74,6 +81,49 @@ __global__ __launch_bounds__(256) void mean_final_kernel(const float* __restrict
     __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = red[0] * scale;
+}
+
+// out[0] = scale * sum(x[0..n)) in ONE launch (the staged bias-field step: what stands between b_net's forward and the host's
+// all-reduce).  Up to 256 workgroups: float4 grid-stride partial sums (n4 quads; n4 = 0 for a pointer that is not 16-byte aligned;
+// the tail by single floats), one partial per workgroup, and the workgroup that arrives LAST - an agent-scope counter - sums the
+// partials in index order: the result does not depend on who that is.  Serial fp32 additions on the longest path: 3 per quad
+// iteration (ceil(n4 / (256 gridDim.x)) of them), 1 per tail iteration, 8 + 8 for the two trees, 1 rounding for the scale.
+__global__ __launch_bounds__(256) void mean_share_kernel(const float* __restrict__ x, int64_t n, int64_t n4, float scale, float* partial,
+                                                         unsigned* ticket, float* __restrict__ out) {
+  __shared__ float red[256];
+  __shared__ unsigned arrived;
+  const int t = (int)threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  float s = 0.f;
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n4; i += stride) {
+    const float4 q = x4[i];
+    s += (q.x + q.y) + (q.z + q.w);
+  }
+  for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + t; i < n; i += stride) s += x[i];
+  red[t] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  if (t == 0) {
+    __hip_atomic_store(&partial[blockIdx.x], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    arrived = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);  // (releases the partial, acquires the others')
+  }
+  __syncthreads();
+  if (arrived != gridDim.x - 1) return;
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  red[t] = t < (int)gridDim.x ? __hip_atomic_load(&partial[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  if (t == 0) {
+    out[0] = red[0] * scale;
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the next launch on this stream counts from zero
+  }
 }
 
 __global__ __launch_bounds__(256) void add_inplace_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
@@ -149,6 +199,10 @@ extern "C" void* nesvor_step_create(const nesvor_step_t* desc) {
     c->wimg_stride = ((size_t)need + 255) / 256 * 256;
     if (on && need > 0 && hipMalloc(&c->wimg, 3 * c->wimg_stride) != hipSuccess) { c->wimg = nullptr; (void)hipGetLastError(); }  // (without it: the in-kernel builds)
   }
+  if (desc->has_b) {  // (a staged call without it is refused)
+    if (hipMalloc(reinterpret_cast<void**>(&c->mean_ticket), sizeof(unsigned)) != hipSuccess) { c->mean_ticket = nullptr; (void)hipGetLastError(); }
+    else if (hipMemset(c->mean_ticket, 0, sizeof(unsigned)) != hipSuccess) { (void)hipFree(c->mean_ticket); c->mean_ticket = nullptr; (void)hipGetLastError(); }
+  }
   return c;
 }
 
@@ -190,6 +244,17 @@ extern "C" int nesvor_step_update(void* handle, const nesvor_step_t* desc) {
   return 0;
 }
 
+extern "C" int nesvor_step_set_bias_mean_ranks(void* handle, int ranks) {
+  if (handle == nullptr) return (int)hipErrorInvalidValue;
+  static_cast<StepCtx*>(handle)->bias_mean_ranks = ranks > 0 ? ranks : 1;
+  return 0;
+}
+extern "C" int nesvor_step_set_bias_mean_event(void* handle, void* event) {
+  if (handle == nullptr) return (int)hipErrorInvalidValue;
+  static_cast<StepCtx*>(handle)->bias_mean_event = (hipEvent_t)event;
+  return 0;
+}
+
 extern "C" void nesvor_step_destroy(void* handle) {
   if (handle == nullptr) return;
   StepCtx* c = static_cast<StepCtx*>(handle);
@@ -198,6 +263,7 @@ extern "C" void nesvor_step_destroy(void* handle) {
   (void)hipEventDestroy(c->ev_sg0); (void)hipEventDestroy(c->ev_sg1); (void)hipEventDestroy(c->ev_owner_early);
   if (c->tu0[0] != nullptr) { (void)hipEventDestroy(c->tu0[0]); (void)hipEventDestroy(c->tu0[1]); }
   if (c->wimg != nullptr) (void)hipFree(c->wimg);
+  if (c->mean_ticket != nullptr) (void)hipFree(c->mean_ticket);
   for (int k = 0; k < NESVOR_STEP_TIMED_SPANS; ++k) {
     if (c->t0[k] != nullptr) (void)hipEventDestroy(c->t0[k]);
     if (c->t1[k] != nullptr) (void)hipEventDestroy(c->t1[k]);
@@ -215,9 +281,12 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
   const int B = d.B, S = d.S, n = d.n_slices, L = d.grid.n_levels;
   const int64_t N = (int64_t)B * S;
   const bool defer_join = (phase & NESVOR_STEP_DEFER_JOIN) != 0;
-  phase &= ~NESVOR_STEP_DEFER_JOIN;
+  // the bias field's global mean under data parallelism: the phase in two calls around the host's all-reduce of one float
+  const bool bias_stop = (phase & NESVOR_STEP_BIAS_SUM_STOP) != 0, bias_resume = (phase & NESVOR_STEP_BIAS_SUM_RESUME) != 0;
+  phase &= ~(NESVOR_STEP_DEFER_JOIN | NESVOR_STEP_BIAS_SUM_STOP | NESVOR_STEP_BIAS_SUM_RESUME);
   if (phase < 0 || phase > 2 || (phase != 0) != (split_level > 0 && split_level < L)) return (int)hipErrorInvalidValue;
-  if (d.has_b && phase != 0) return (int)hipErrorInvalidValue;  // the bias field's global mean needs the host's all-reduce: Python path
+  if ((bias_stop || bias_resume) && (!d.has_b || phase == 2 || (bias_stop && bias_resume) || ctx->mean_ticket == nullptr))
+    return (int)hipErrorInvalidValue;
   float* c = d.has_c ? d.small : nullptr;       // slice scale n softmax(logit_coef)
   float* mat = d.small + n;                      // (n,3,4) pose matrices
   float* acc = d.small + 13 * n;                 // [dc (n) | dmat (n,12)], zero-filled by the prologue
@@ -281,8 +350,25 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
   };
   // (the bias field's second consumer of the slice embedding keeps round 4's single launch behind the sampler backward)
   const bool early_sg = overlap_owner && !d.has_b;
-  if (ctx->timing) { for (int k = 0; k < NESVOR_STEP_TIMED_SPANS; ++k) ctx->span_used[k] = false; ctx->timed_run = true; }
+  // (a RESUME call continues the run its STOP call began: that call's spans stay)
+  if (ctx->timing && !bias_resume) { for (int k = 0; k < NESVOR_STEP_TIMED_SPANS; ++k) ctx->span_used[k] = false; ctx->timed_run = true; }
+  // b_net's input bounds and forward; `share` = this rank's share of the GLOBAL mean in one launch (staged), else the local mean
+  auto bias_forward = [&](bool share) -> int {
+    if (split_b) NESVOR_TRY(nesvor_mlp_prepare(&net_b, d.se, d.pe, nullptr, N, prep_b, NESVOR_MLP_WHAT_INPUT, main));
+    NESVOR_TRY(nesvor_mlp_forward(&net_b, d.se, d.pe, d.log_bias, d.saved_b, N, main));
+    if (share) {
+      const int64_t n4 = (reinterpret_cast<uintptr_t>(d.log_bias) % 16 == 0) ? N / 4 : 0;
+      const int64_t blocks = (N + 1023) / 1024;
+      hipLaunchKernelGGL(mean_share_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks))), dim3(256), 0, main, d.log_bias, N, n4,
+                         1.f / ((float)N * (float)ctx->bias_mean_ranks), d.mean_scratch, ctx->mean_ticket, d.lb_mean);
+    } else {
+      hipLaunchKernelGGL(mean_partial_kernel, dim3(256), dim3(256), 0, main, d.log_bias, N, d.mean_scratch);
+      hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(256), 0, main, d.mean_scratch, 256, 1.f / (float)N, d.lb_mean);
+    }
+    return 0;
+  };
   if (phase != 2) {
+   if (!bias_resume) {  // (a RESUME call: its STOP call has enqueued everything down to the hash-grid forward)
     // ---- forward
     // ONE launch: slice scales, pose matrices, zero-fill of the per-slice accumulators and operand bounds, and the pose regulariser
     // with its gradient (a function of the parameters alone).  Behind it, on the SAME stream: the networks' weight norms and the
@@ -350,20 +436,29 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
     }
     }
     if (head_on_side && any_split && hipStreamWaitEvent(main, ctx->ev_norms, 0) != hipSuccess) return (int)hipGetLastError();
+   }
+    if (bias_stop) {
+      // Staged: b_net first - it reads pe and se only - so that the density and sigma forwards of the RESUME call run while the
+      // scalar is exchanged (measured on one GPU against b_net behind the density network: inside the spread,
+      // profiles/ddp_bias_overhead_one_gpu.log)
+      NESVOR_TRY(bias_forward(true));
+      return (int)hipGetLastError();  // the host all-reduces d.lb_mean; the RESUME call completes the phase (and counts the run)
+    }
     {
       Span t(ctx, NESVOR_STEP_SPAN_MLP_FWD_DENSITY, main);
       NESVOR_TRY(nesvor_mlp_forward(&net_d, nullptr, d.pe, d.z, d.saved_d, N, main));
     }
-    if (d.has_b) {
-      // (the bias field is off BASELINE's headline configuration: its input bounds by a pass of their own)
-      if (split_b) NESVOR_TRY(nesvor_mlp_prepare(&net_b, d.se, d.pe, nullptr, N, prep_b, NESVOR_MLP_WHAT_INPUT, main));
-      NESVOR_TRY(nesvor_mlp_forward(&net_b, d.se, d.pe, d.log_bias, d.saved_b, N, main));
-      hipLaunchKernelGGL(mean_partial_kernel, dim3(256), dim3(256), 0, main, d.log_bias, N, d.mean_scratch);
-      hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(256), 0, main, d.mean_scratch, 256, 1.f / (float)N, d.lb_mean);
-    }
+    // (the bias field is off BASELINE's headline configuration: its input bounds by a pass of their own)
+    if (d.has_b && !bias_resume) NESVOR_TRY(bias_forward(false));
     if (d.has_lv) {
       Span t(ctx, NESVOR_STEP_SPAN_MLP_FWD_SIGMA, main);
       NESVOR_TRY(nesvor_mlp_forward(&net_s, d.se, d.z, d.log_var, d.saved_s, N, main));
+    }
+    if (bias_resume) {
+      // the loss kernel is the first reader of the exchanged mean: a stream wait, enqueued here - the host never blocks
+      hipEvent_t exchanged = ctx->bias_mean_event;
+      ctx->bias_mean_event = nullptr;  // consumed: the caller may destroy it once this call has returned
+      if (exchanged != nullptr && hipStreamWaitEvent(main, exchanged, 0) != hipSuccess) return (int)hipGetLastError();
     }
     // ---- losses: values and gradients in one launch
     const int z_rows = 1 + d.n_features_z, written = 1 + (d.has_lv ? d.n_features_z : 0);

@@ -119,6 +119,20 @@ def allreduce_flat_(flat_grad: torch.Tensor, group=None, n_buckets: int = 1):
     return works
 
 
+def allreduce_scalar_(t: torch.Tensor, stream: torch.cuda.Stream, group=None) -> torch.cuda.Event:
+    """Sum-all-reduce a small device tensor in place on ``stream`` - a communication stream of the caller's, not the one the
+    step's kernels run on - and return an event recorded behind it (the staged bias-field step, nesvor_amd.direct: the main
+    stream waits for that event only where the loss kernel reads the value, and runs the density / sigma forwards meanwhile).
+    ``stream`` first waits for the current stream (the producer of ``t``).  With RCCL nothing blocks the host: the collective is
+    asynchronous and ``work.wait()`` makes ``stream`` wait for RCCL's stream; with gloo (the test backend) ``wait()`` blocks."""
+    stream.wait_stream(torch.cuda.current_stream(t.device))
+    with torch.cuda.stream(stream):
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group, async_op=True).wait()
+        done = torch.cuda.Event()
+        done.record(stream)
+    return done
+
+
 def wait_all(works) -> None:
     for w in works:
         w.wait()

@@ -154,6 +154,7 @@ class DirectStep:
         # the END of the flat buffer) first; their all-reduce is started at once and overlaps the coarse levels' launch
         # (NESVOR_DDP_OVERLAP=0: one launch, one all-reduce after the step)
         self._early = None
+        self._comm_stream = None  # the bias field's scalar all-reduce (ddp.allreduce_scalar_): a stream of its own, made on first use
         self._owner_pending = False  # an owner pass of the hash-grid backward is running on the side stream
         self._pending_state = None   # ... left there by this native context (its next run joins it by itself)
         self._kernel_noise = os.environ.get("NESVOR_PSF_NOISE", "kernel") != "tensor"
@@ -208,8 +209,7 @@ class DirectStep:
     # ------------------------------------------------------------------------------------------------ one-call iteration
     def native_ready(self, noise=None) -> bool:
         """The iteration can go through ``nesvor_step_run``: PSF noise drawn in the kernels, no per-kernel event timing, every
-        network's gradient one contiguous segment of the flat buffer (the single-precision model under FusedTrainer), and - for
-        the bias field under data parallelism, whose global mean needs the host's all-reduce mid-step - not that combination."""
+        network's gradient one contiguous segment of the flat buffer (the single-precision model under FusedTrainer)."""
         if not (self._native_on and noise is None and self._kernel_noise and not _lib.kernel_timer.enabled):
             return False
         if (self.bf16 is True or self.bf16 == mlp_mod.FP16) and half_precision_model(self.model):
@@ -221,8 +221,6 @@ class DirectStep:
         # flat gradient, whose prefix the partial rows' columns are
         if not all(p.segment is not None and ((p.bias_free and p.segment.numel() >= p.n_columns()) or (
                 not p.flat_params and p.segment.numel() == p.n_columns())) for p in nets):
-            return False
-        if self.has_b and self.parallel:
             return False
         return True
 
@@ -371,6 +369,9 @@ class DirectStep:
         if not handle:
             raise RuntimeError("nesvor_step_create failed")
         st = self._native[key] = {"desc": d, "handle": ctypes.c_void_p(handle), "buf": buf, "ws": None}
+        if self.has_b and self.parallel:
+            # the staged step's reduction writes this rank's share of the GLOBAL mean of log_bias: sum / (N world)
+            _lib.check(_lib.load().nesvor_step_set_bias_mean_ranks(st["handle"], self.world), "bias mean ranks")
         if self._native_timing:
             _lib.check(_lib.load().nesvor_step_timing(st["handle"], 1), "step timing")
         return st
@@ -431,10 +432,25 @@ class DirectStep:
         stream = _lib.stream_ptr()
         args = (st["handle"], _lib.ptr(xyz), _lib.ptr(v), _lib.ptr(slice_idx), seed, offset, _lib.ptr(vals))
         with torch.cuda.device(dev):
+            if self.has_b and self.parallel:
+                # biasReg = (mean log_bias)^2 needs the mean over ALL ranks' samples: the step stops behind b_net's forward with this
+                # rank's share of it, the one float is sum-all-reduced on a stream of its own, and the rest of the phase - whose
+                # density and sigma forwards run meanwhile - waits for it in front of the loss kernel (a stream wait on the event)
+                from . import ddp
+
+                if self._comm_stream is None:
+                    self._comm_stream = torch.cuda.Stream(device=dev)
+                ph = 1 if self.split_level else 0
+                _lib.check(lib.nesvor_step_run(*args, ph | _lib.STEP_BIAS_SUM_STOP, self.split_level, None, stream), "training step (bias sum)")
+                done = ddp.allreduce_scalar_(st["buf"]["lb_mean"], self._comm_stream)
+                _lib.check(lib.nesvor_step_set_bias_mean_event(st["handle"], ctypes.c_void_p(done.cuda_event)), "bias mean event")
+                resume = _lib.STEP_BIAS_SUM_RESUME
+            else:
+                resume = 0
             if self.split_level:
                 from . import ddp
 
-                _lib.check(lib.nesvor_step_run(*args, 1, self.split_level, None, stream), "training step (fine levels)")
+                _lib.check(lib.nesvor_step_run(*args, 1 | resume, self.split_level, None, stream), "training step (fine levels)")
                 self._early = self._start_early()  # async: RCCL's stream, behind the launches above
                 if self.early_update is not None and self.early_exchange is None and self._early is not None:
                     with torch.cuda.stream(self.side):
@@ -447,7 +463,7 @@ class DirectStep:
                 # inside the owner pass) on the side stream: the next run joins it right before its hash-grid forward, anyone
                 # else through join_owner()
                 defer = bool(defer_table_join) and adam is not None and (d.overlap_owner & 3) == 3
-                _lib.check(lib.nesvor_step_run(*args, 0 | (_lib.STEP_DEFER_JOIN if defer else 0), 0, a_ptr, stream), "training step")
+                _lib.check(lib.nesvor_step_run(*args, resume | (_lib.STEP_DEFER_JOIN if defer else 0), 0, a_ptr, stream), "training step")
                 self._owner_pending = bool(d.overlap_owner & 1) and (adam is None or defer)
         self._pending_state = st if self._owner_pending else None
         self._last_state = st
