@@ -22,7 +22,8 @@ extern "C" {
 #define NESVOR_MAX_LEVELS 32
 #define NESVOR_MAX_MLP_LAYERS 4
 
-/* ABI version; bumped on any signature change (37: the device loss scaler). */
+/* ABI version; bumped on any signature change (38: nesvor_hashgrid_forward_levels, nesvor_hashgrid_backward_adamw_levels and the
+ * timing spans 10 and 11 of nesvor_step_timing_read removed; 37: the device loss scaler). */
 int nesvor_hip_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -391,6 +392,12 @@ typedef struct {
                                  step at 2^17 points, within noise at 2^20).  Bit-identical to the in-kernel builds
                                  (tests/test_gpu_ops.py::test_fused_mlp_prebuilt_weight_images_are_bit_identical). */
 } nesvor_mlp_t;
+/* nesvor_mlp_t.bf16_operands, as documented at the field */
+#define NESVOR_MLP_MODE_FP32 0
+#define NESVOR_MLP_MODE_BF16 1
+#define NESVOR_MLP_MODE_SPLIT 2
+#define NESVOR_MLP_MODE_FP16 3
+#define NESVOR_MLP_MODE_FP16_SCALED 4
 #define NESVOR_ABSMAX_SLOTS 16      /* a slotted bound: this many floats, NESVOR_ABSMAX_STRIDE floats (one 256-byte line) apart - */
 #define NESVOR_ABSMAX_STRIDE 64     /* atomics on one cache line serialise at the memory side, publishers spread by workgroup */
 #define NESVOR_ABSMAX_FLOATS (NESVOR_ABSMAX_SLOTS * NESVOR_ABSMAX_STRIDE)
@@ -430,7 +437,10 @@ int nesvor_mlp_forward(const nesvor_mlp_t* net, const float* xa, const float* xb
                        float* const* saved_hidden, int64_t N, void* stream);
 /* 1 if (net, N) is a shape the fused backward takes - dX, dW and db in ONE wave-specialised launch, no dpre scratch (pass NULL
  * entries): N, samples_per_pixel and k_a multiples of 16, at most two hidden layers, at most two 16-row input blocks at two
- * hidden layers.  0: pass dpre_scratch[l] (N_pad16 * 64 floats each) and the backward runs as a dX launch + a dW launch: on fp32
+ * hidden layers.  GUARANTEE: an answer of 1 implies N % 16 == 0, samples_per_pixel % 16 == 0 and k_a % 16 == 0 - every 16-sample
+ * group lies inside one pixel - so 1 is also the rule for who may ask for per-group pixel-feature gradients (dxa_group_sums);
+ * callers do not repeat the divisibility test.  The converse does not hold (a divisible shape may be refused).
+ * 0: pass dpre_scratch[l] (N_pad16 * 64 floats each) and the backward runs as a dX launch + a dW launch: on fp32
  * MFMAs for bf16_operands = 0 / 2 / 4 (nesvor_mlp_wide_backward_bounded), on 16-bit operands rounded at the fused kernel's points for
  * bf16_operands = 1 / 3 (any shape the 16-bit forward takes; dxa per sample, dxa_group_sums = 0). */
 int nesvor_mlp_backward_fused_ok(const nesvor_mlp_t* net, int64_t N);
@@ -618,18 +628,6 @@ int nesvor_hashgrid_backward_adamw(const nesvor_grid_t* grid, const float* u, fl
                                    float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
                                    const float* queue_scale, const float* dy_bound, float* exp_avg, float* exp_avg_sq,
                                    const nesvor_adamw_t* adam, void* stream);
-/* The owner stage (stages == 2) of that backward for levels [level_begin, level_end) only, and the per-cloud forward for a level
- * range (round 6).  The table's update is what the NEXT iteration's forward waits for; updated range by range - the coarse
- * levels first - the next forward starts on the finished levels while the owner pass still works on the others
- * (csrc/step.hip: 84 us of owner pass + 70 us of forward, both latency-bound, no longer strictly one after the other).
- * nesvor_hashgrid_forward_levels: the NESVOR_LAYOUT_CLUSTERED kernel; rows of pe outside the range are not touched. */
-int nesvor_hashgrid_backward_adamw_levels(const nesvor_grid_t* grid, const float* u, float* table, const float* dpe,
-                                          float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
-                                          int level_begin, int level_end, const float* queue_scale, const float* dy_bound,
-                                          float* exp_avg, float* exp_avg_sq, const nesvor_adamw_t* adam, void* stream);
-int nesvor_hashgrid_forward_levels(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N, int layout,
-                                   float* pe_absmax, int level_begin, int level_end, void* stream);
-
 /* out[c] = sum_r in[r * ld + c], c < cols, for a row-major matrix of row pitch ld >= cols floats: reduces the
  * dw_partial of nesvor_mlp_backward (the `partial.sum(0)` of the host side) straight into a gradient segment; with
  * ld > cols, a column range of it (one layer's weights when the model keeps no biases, tinycudann.Network). */
@@ -653,8 +651,8 @@ int nesvor_sum_rows_multi(const float* const* in, float* const* out, const int* 
  *                floats);  partial: 3 x NESVOR_STEP_MLP_PARTIALS x (largest network's parameter count) floats - one third per
  *                network, summed by one nesvor_sum_rows_multi launch;  losses (run argument): 6 floats {MSE, logVar, MSE+logVar, transReg,
  *                imageReg, biasReg} (models.py:14-19)
- *   queue_scale: HOST array (nesvor_hashgrid_backward);  side_stream: a second stream of the same device (pose regulariser,
- *                owner pass of the hash-grid backward); with overlap_owner the table gradient is complete only behind the
+ *   queue_scale: HOST array (nesvor_hashgrid_backward);  side_stream: a second stream of the same device (early per-slice
+ *                gradients, owner pass of the hash-grid backward); with overlap_owner the table gradient is complete only behind the
  *                side stream - the step joins it itself before its own AdamW, a caller that runs the optimizer makes
  *                its stream wait for side_stream
  * nesvor_step_run(phase = 0): the whole iteration.  Data parallel: phase 1 = everything up to and including the hash-grid
@@ -676,11 +674,7 @@ int nesvor_sum_rows_multi(const float* const* in, float* const* out, const int* 
 #define NESVOR_STEP_SPAN_HASHGRID_BWD_AGGREGATE 7
 #define NESVOR_STEP_SPAN_HASHGRID_BWD_OWNER 8   /* the owner pass; with the fused optimizer: owner pass + the table's AdamW step */
 #define NESVOR_STEP_SPAN_PSF_BWD 9
-#define NESVOR_STEP_SPAN_HASHGRID_FWD_LATE 10   /* pipelined table update (round 6): the forward of the levels the previous step's owner pass
-                                                   finished LAST; NESVOR_STEP_SPAN_HASHGRID_FWD then covers the other levels only */
-#define NESVOR_STEP_SPAN_HASHGRID_UNION 11      /* pipelined table update: from the start of the PREVIOUS step's owner pass to the end of this
-                                                   step's hash-grid forward - the time the device spends on those overlapped launches */
-#define NESVOR_STEP_TIMED_SPANS 12
+#define NESVOR_STEP_TIMED_SPANS 10
 typedef struct {
   nesvor_grid_t grid;
   nesvor_mlp_t density, sigma, bias_net;   /* weights / biases: the model's parameters; bf16_operands: evaluation mode */
@@ -743,7 +737,7 @@ int nesvor_step_join(void* step, void* stream);
  * nesvor_step_set_bias_mean_event: a hipEvent_t recorded behind the all-reduce; consumed by the next RESUME call (the wait is
  * enqueued there, the host never blocks; the event may be destroyed once that call has returned).  NULL, or never set: the
  * caller has ordered `stream` behind the all-reduce itself.
- * These two flags and two entry points were added WITHOUT a change of nesvor_hip_abi_version() (37; nothing that existed changed
+ * These two flags and two entry points were added WITHOUT a change of nesvor_hip_abi_version() (37 then; nothing that existed changed
  * its layout or meaning): the version number does not tell a caller whether they exist - resolve the symbols
  * (dlsym(lib, "nesvor_step_set_bias_mean_event")) to find out; a library without them refuses the flags with hipErrorInvalidValue. */
 #define NESVOR_STEP_BIAS_SUM_STOP 16

@@ -129,4 +129,4 @@ extern "C" int nesvor_sum_rows_multi(const float* const* in, float* const* out, 
   return (int)hipGetLastError();
 }
 
-extern "C" int nesvor_hip_abi_version(void) { return 37; }
+extern "C" int nesvor_hip_abi_version(void) { return 38; }

@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
                                                           const float* __restrict__ table, float* __restrict__ pe, int64_t N,
                                                           float* __restrict__ pe_absmax,  // optional: raised to max |pe| (the density network's input bound)
                                                           const uint32_t* __restrict__ perm = nullptr, float* __restrict__ rows = nullptr,
-                                                          int level_begin = 0, int level_stop = NESVOR_MAX_LEVELS) {  // levels [level_begin, min(level_stop, L)): see nesvor_hashgrid_forward_levels
+                                                          int level_begin = 0, int level_stop = NESVOR_MAX_LEVELS) {  // levels [level_begin, min(level_stop, L))
 #ifndef NESVOR_FWD_CLOUD_SLOTS
 #define NESVOR_FWD_CLOUD_SLOTS 512
 #endif
@@ -2461,25 +2461,6 @@ extern "C" int nesvor_hashgrid_forward(const nesvor_grid_t* grid, const float* u
   return nesvor_hashgrid_forward_bounded(grid, u, table, pe, N, layout, nullptr, stream);
 }
 
-namespace {
-template <int F, int LAYOUT>
-int launch_fwd_levels(const nesvor_grid_t* g, const float* u, const float* table, float* pe, int64_t N, float* pe_absmax, int lb, int le,
-                      hipStream_t st) {
-  hipLaunchKernelGGL((hashgrid_fwd_cloud<F, LAYOUT>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, *g, u, table, pe, N, pe_absmax,
-                     (const uint32_t*)nullptr, (float*)nullptr, lb, le);
-  return (int)hipGetLastError();
-}
-}  // namespace
-
-extern "C" int nesvor_hashgrid_forward_levels(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N,
-                                              int layout, float* pe_absmax, int level_begin, int level_end, void* stream) {
-  if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  if (level_begin < 0 || level_end > grid->n_levels || level_begin >= level_end) return (int)hipErrorInvalidValue;
-  layout &= NESVOR_LAYOUT_MASK;
-  DISPATCH_F_LAYOUT(launch_fwd_levels, grid, u, table, pe, N, pe_absmax, level_begin, level_end, (hipStream_t)stream);
-}
-
 extern "C" int64_t nesvor_hashgrid_forward_workspace_bytes(const nesvor_grid_t* grid, int64_t N, int layout) {
   if (grid == nullptr || N <= 0) return 0;
   if (!(layout & NESVOR_LAYOUT_UNCLUSTERED)) return 0;
@@ -2584,21 +2565,8 @@ extern "C" int nesvor_hashgrid_backward_adamw(const nesvor_grid_t* grid, const f
                                               float* grad_table, float* grad_u, int64_t N, int layout, void* workspace,
                                               int stages, const float* queue_scale, const float* dy_bound, float* exp_avg,
                                               float* exp_avg_sq, const nesvor_adamw_t* adam, void* stream) {
-  return nesvor_hashgrid_backward_adamw_levels(grid, u, table, dpe, grad_table, grad_u, N, layout, workspace, stages, 0, grid->n_levels,
-                                               queue_scale, dy_bound, exp_avg, exp_avg_sq, adam, stream);
-}
-
-extern "C" int nesvor_hashgrid_backward_adamw_levels(const nesvor_grid_t* grid, const float* u, float* table, const float* dpe,
-                                                     float* grad_table, float* grad_u, int64_t N, int layout, void* workspace,
-                                                     int stages, int level_begin, int level_end, const float* queue_scale,
-                                                     const float* dy_bound, float* exp_avg, float* exp_avg_sq, const nesvor_adamw_t* adam,
-                                                     void* stream) {
   if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
   if (N <= 0 || workspace == nullptr || (stages & ~3) != 0 || (stages & 3) == 0) return (int)hipErrorInvalidValue;
-  if (level_begin < 0 || level_end > grid->n_levels || level_begin >= level_end) return (int)hipErrorInvalidValue;
-  // (a level range is for the OWNER stage alone - stages == 2: the table's update level range by level range, so that the next
-  //  forward can start on the levels that are done; the aggregation stage always covers every level)
-  if ((level_begin != 0 || level_end != grid->n_levels) && stages != 2) return (int)hipErrorInvalidValue;
   if (table == nullptr || grad_table == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || adam == nullptr) return (int)hipErrorInvalidValue;
   OwnerAdam oa;
   oa.param = table; oa.exp_avg = exp_avg; oa.exp_avg_sq = exp_avg_sq; oa.done = nullptr;
@@ -2606,6 +2574,6 @@ extern "C" int nesvor_hashgrid_backward_adamw_levels(const nesvor_grid_t* grid, 
                         adam->bias_correction2, adam->grad_scale);
   const int hints = layout & (NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH);
   layout &= NESVOR_LAYOUT_MASK;
-  DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages, level_begin, level_end, queue_scale,
+  DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages, 0, grid->n_levels, queue_scale,
                     dy_bound, &oa, (hipStream_t)stream, hints);
 }

@@ -392,7 +392,7 @@ __device__ __forceinline__ void build_image_ct(float* img, const float* __restri
 // the fp32 weights - a few dependent L2 round trips plus the splitting of every element, per workgroup.  The training step now
 // builds them ONCE per iteration - in the launch that takes the weight norms, which has each layer's matrix in LDS and knows its
 // scale - and a workgroup copies them: 16-byte loads, all of a thread's in flight at once, no arithmetic.  Measured in the step
-// (in-job A/B, NESVOR_STEP_WEIGHT_IMAGES=0/1, profiles/r06_mlp_image_build.log): the four MLP launches -3.4 us of 129 us at 2^17
+// (in-job A/B, profiles/r06_mlp_image_build.log): the four MLP launches -3.4 us of 129 us at 2^17
 // points per iteration, within noise at 2^20 (the builds had been brought down to ~1 us per launch in round 4; an ablation
 // with the builds compiled out, -DNESVOR_MLP_ABLATE=8, had suggested 30 us - it trains on garbage images, the poses turn NaN and
 // every kernel of that step gets faster for reasons that have nothing to do with the builds).  Layout of a network's buffer, in fp16 elements, layer
@@ -2619,7 +2619,7 @@ int fill_args(MlpArgs* a, const nesvor_mlp_t* d, int64_t N) {
   const bool nob = bias_free(d);
   int n_null = 0;
   for (int l = 0; l < a->n_linear; ++l) n_null += d->bias[l] == nullptr ? 1 : 0;
-  if (d->weight[0] != nullptr && n_null != 0 && !(nob && d->bf16_operands == 4)) return (int)hipErrorInvalidValue;
+  if (d->weight[0] != nullptr && n_null != 0 && !(nob && d->bf16_operands == NESVOR_MLP_MODE_FP16_SCALED)) return (int)hipErrorInvalidValue;
   int total = 0;
   for (int l = 0; l < a->n_linear; ++l) {
     a->W[l] = d->weight[l]; a->b[l] = d->bias[l];
@@ -2631,12 +2631,12 @@ int fill_args(MlpArgs* a, const nesvor_mlp_t* d, int64_t N) {
   const int S = d->samples_per_pixel;
   a->fast = (N % 16 == 0 && S % 16 == 0 && d->k_a % 16 == 0) ? 1 : 0;
   a->dxa_group = d->dxa_group_sums ? 1 : 0;
-  a->bf16 = d->bf16_operands;  // 0: fp32 MFMA, 1: bf16-rounded operands, 2: split (fp32-equivalent) operands, 3: fp16-rounded operands, 4: scaled fp16 operands
-  if (a->bf16 < 0 || a->bf16 > 4) return (int)hipErrorInvalidValue;
+  a->bf16 = d->bf16_operands;  // NESVOR_MLP_MODE_*
+  if (a->bf16 < NESVOR_MLP_MODE_FP32 || a->bf16 > NESVOR_MLP_MODE_FP16_SCALED) return (int)hipErrorInvalidValue;
   a->hi1 = 0;
-  if (a->bf16 == 4) { a->bf16 = 2; a->hi1 = 1; }  // (the split mode's scales, images and save formats; its leading term alone where a kernel has that form - every other kernel evaluates the full split or fp32 MFMAs: more accurate, always valid)
-  a->half16 = a->bf16 == 3 ? 1 : 0;
-  if (a->half16) a->bf16 = 1;  // (every host-side decision below is that of the 16-bit operand modes; the launches pick the type)
+  if (a->bf16 == NESVOR_MLP_MODE_FP16_SCALED) { a->bf16 = NESVOR_MLP_MODE_SPLIT; a->hi1 = 1; }  // (the split mode's scales, images and save formats; its leading term alone where a kernel has that form - every other kernel evaluates the full split or fp32 MFMAs: more accurate, always valid)
+  a->half16 = a->bf16 == NESVOR_MLP_MODE_FP16 ? 1 : 0;
+  if (a->half16) a->bf16 = NESVOR_MLP_MODE_BF16;  // (every host-side decision below is that of the 16-bit operand modes; the launches pick the type)
   a->prep = d->prep;
   a->y_absmax = d->y_absmax;
   a->wimg = (a->bf16 == 2) ? static_cast<const _Float16*>(d->weight_images) : nullptr;

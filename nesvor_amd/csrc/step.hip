@@ -7,7 +7,7 @@
 // is small (BASELINE C2: 2^18 points; C3 read literally: 2^17 points per GPU on 8 GPUs need 0.2 ms of GPU time).
 // Here the host enqueues everything in one call, into workspace buffers the caller allocated once:
 //
-//   side stream : pose regulariser (serial chain per slice)           ...            owner pass of the hash-grid backward
+//   side stream :                        ...            early per-slice gradients | owner pass of the hash-grid backward
 //   main stream : prologue | sampler | hash grid | MLPs | loss | MLP backwards | aggregation pass | sampler backward
 //                 | per-slice gradients | epilogue | [AdamW]
 // (overlap_owner bit 1: the table's AdamW step is taken by the owner pass itself, chunk by chunk while a chunk's gradient is
@@ -28,18 +28,11 @@ namespace {
 
 struct StepCtx {
   nesvor_step_t d;
-  hipEvent_t ev_fork, ev_pose, ev_agg, ev_owner, ev_bwd, ev_sums, ev_norms, ev_sg0, ev_sg1, ev_owner_early;
-  // Pipelined table update (round 6): the owner pass of the previous run went out as two launches - levels [0, pipe_level), event
-  // ev_owner_early, then the rest, event ev_owner - and this run's hash-grid forward follows it level range by level range
-  int pending_pipe_level = 0;
-  hipEvent_t tu0[2] = {nullptr, nullptr};  // timing: start of a run's owner pass (double-buffered: read by the NEXT run's union span)
-  unsigned run_no = 0;
+  hipEvent_t ev_agg, ev_owner, ev_sg0, ev_sg1;  // stream ordering: main -> side in front of the owner pass / the early per-slice sums, and back
   // Split operand images of the three networks' weights (nesvor_mlp_t.weight_images), rebuilt once per iteration by the launch that
   // takes the weight norms and copied - not rebuilt - by the workgroups of the four MLP launches.  One allocation, owned here.
   void* wimg = nullptr;
   size_t wimg_stride = 0;
-  bool head_on_side = false;  // (NESVOR_STEP_HEAD=side: phase 2 of a split run must join what phase 1 forked)
-  bool sums_on_side = false;  // the networks' parameter-gradient sums of the current iteration were left on the side stream
   bool pending_join = false;  // a table update of the previous run is still on the side stream (NESVOR_STEP_DEFER_JOIN)
   // Staged bias-field step (NESVOR_STEP_BIAS_SUM_STOP / _RESUME): ranks the share of the global mean divides by, the event behind the
   // host's all-reduce of it (consumed by the next RESUME call), the arrival counter of mean_share_kernel
@@ -148,8 +141,7 @@ __global__ void square_kernel(const float* __restrict__ m, float* __restrict__ o
   } while (0)
 
 int mlp_backward_into(const nesvor_mlp_t& net, int group_sums, const float* xa, const float* xb, const float* dy,
-                      float* const* saved, float* dxa, float* dxb, float* partial, float* grad_segment, int n_params,
-                      int64_t N, hipStream_t st, float* const* dpre_scratch, float* dxb_absmax = nullptr) {
+                      float* const* saved, float* dxa, float* dxb, float* partial, int64_t N, hipStream_t st, float* const* dpre_scratch, float* dxb_absmax = nullptr) {
   nesvor_mlp_t d = net;
   d.dxa_group_sums = group_sums;
   // fused dX + dW + db kernel: no dpre scratch; shapes it refuses (nesvor_mlp_backward_fused_ok) run as a dX launch + a dW launch
@@ -164,7 +156,6 @@ int mlp_backward_into(const nesvor_mlp_t& net, int group_sums, const float* xa, 
   // per-workgroup partial sums (columns W0,b0,W1,b1,... - bias-free: W0,W1,..., the prefix of its flat gradient); the caller sums them
   // into the network's segment of the flat gradient
   // (ONE launch for all networks of the step, after the last backward: nesvor_sum_rows_multi)
-  (void)grad_segment; (void)n_params;
   return nesvor_mlp_backward_bounded(&d, xa, xb, dy, saved, no_scratch, dxa, dxb, partial, NESVOR_STEP_MLP_PARTIALS, N, dxb_absmax, st);
 }
 
@@ -172,32 +163,31 @@ int mlp_backward_into(const nesvor_mlp_t& net, int group_sums, const float* xa, 
 bool bias_free_refused(const nesvor_mlp_t& n) {
   bool any_null = false;
   for (int l = 0; l <= n.n_hidden && l < NESVOR_MAX_MLP_LAYERS; ++l) any_null = any_null || n.bias[l] == nullptr;
-  return any_null && n.bf16_operands != 4;
+  return any_null && n.bf16_operands != NESVOR_MLP_MODE_FP16_SCALED;
+}
+bool bias_free_refused(const nesvor_step_t& d) {  // any network the step runs
+  return bias_free_refused(d.density) || (d.has_lv && bias_free_refused(d.sigma)) || (d.has_b && bias_free_refused(d.bias_net));
 }
 
 }  // namespace
 
 extern "C" void* nesvor_step_create(const nesvor_step_t* desc) {
   if (desc == nullptr) return nullptr;
-  if (bias_free_refused(desc->density) || (desc->has_lv && bias_free_refused(desc->sigma)) || (desc->has_b && bias_free_refused(desc->bias_net)))
-    return nullptr;
+  if (bias_free_refused(*desc)) return nullptr;
   StepCtx* c = new (std::nothrow) StepCtx;
   if (c == nullptr) return nullptr;
   c->d = *desc;
-  hipEvent_t* evs[10] = {&c->ev_fork, &c->ev_pose, &c->ev_agg, &c->ev_owner, &c->ev_bwd, &c->ev_sums, &c->ev_norms, &c->ev_sg0, &c->ev_sg1,
-                         &c->ev_owner_early};
+  hipEvent_t* evs[4] = {&c->ev_agg, &c->ev_owner, &c->ev_sg0, &c->ev_sg1};
   for (hipEvent_t* e : evs) {
     if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { delete c; return nullptr; }
   }
   for (int k = 0; k < NESVOR_STEP_TIMED_SPANS; ++k) { c->t0[k] = nullptr; c->t1[k] = nullptr; c->span_used[k] = false; }
   {
-    // NESVOR_STEP_WEIGHT_IMAGES=0: every MLP launch builds its own images (rounds 2-5; A/B switch)
-    static const bool on = []() { const char* e = getenv("NESVOR_STEP_WEIGHT_IMAGES"); return e == nullptr || atoi(e) != 0; }();
     int64_t need = nesvor_mlp_weight_images_bytes(&desc->density);
     if (desc->has_lv && nesvor_mlp_weight_images_bytes(&desc->sigma) > need) need = nesvor_mlp_weight_images_bytes(&desc->sigma);
     if (desc->has_b && nesvor_mlp_weight_images_bytes(&desc->bias_net) > need) need = nesvor_mlp_weight_images_bytes(&desc->bias_net);
     c->wimg_stride = ((size_t)need + 255) / 256 * 256;
-    if (on && need > 0 && hipMalloc(&c->wimg, 3 * c->wimg_stride) != hipSuccess) { c->wimg = nullptr; (void)hipGetLastError(); }  // (without it: the in-kernel builds)
+    if (need > 0 && hipMalloc(&c->wimg, 3 * c->wimg_stride) != hipSuccess) { c->wimg = nullptr; (void)hipGetLastError(); }  // (without it: the in-kernel builds)
   }
   if (desc->has_b) {  // (a staged call without it is refused)
     if (hipMalloc(reinterpret_cast<void**>(&c->mean_ticket), sizeof(unsigned)) != hipSuccess) { c->mean_ticket = nullptr; (void)hipGetLastError(); }
@@ -216,7 +206,6 @@ extern "C" int nesvor_step_timing(void* handle, int on) {
   if (on && c->t0[0] == nullptr) {
     for (int k = 0; k < NESVOR_STEP_TIMED_SPANS; ++k)
       if (hipEventCreate(&c->t0[k]) != hipSuccess || hipEventCreate(&c->t1[k]) != hipSuccess) return (int)hipGetLastError();
-    if (hipEventCreate(&c->tu0[0]) != hipSuccess || hipEventCreate(&c->tu0[1]) != hipSuccess) return (int)hipGetLastError();
   }
   c->timing = on != 0;
   c->timed_run = false;
@@ -229,17 +218,14 @@ extern "C" int nesvor_step_timing_read(void* handle, float* ms) {
   if (!c->timed_run) return 0;
   for (int k = 0; k < NESVOR_STEP_TIMED_SPANS; ++k) {
     if (!c->span_used[k]) continue;
-    // (the union span starts at the PREVIOUS run's owner pass: its first event is that run's tu0)
-    hipEvent_t e0 = k == NESVOR_STEP_SPAN_HASHGRID_UNION ? c->tu0[(c->run_no - 1u) & 1u] : c->t0[k];
-    if (hipEventSynchronize(c->t1[k]) != hipSuccess || hipEventElapsedTime(&ms[k], e0, c->t1[k]) != hipSuccess) return (int)hipGetLastError();
+    if (hipEventSynchronize(c->t1[k]) != hipSuccess || hipEventElapsedTime(&ms[k], c->t0[k], c->t1[k]) != hipSuccess) return (int)hipGetLastError();
   }
   return 0;
 }
 
 extern "C" int nesvor_step_update(void* handle, const nesvor_step_t* desc) {
   if (handle == nullptr || desc == nullptr) return (int)hipErrorInvalidValue;
-  if (bias_free_refused(desc->density) || (desc->has_lv && bias_free_refused(desc->sigma)) || (desc->has_b && bias_free_refused(desc->bias_net)))
-    return (int)hipErrorInvalidValue;
+  if (bias_free_refused(*desc)) return (int)hipErrorInvalidValue;
   static_cast<StepCtx*>(handle)->d = *desc;
   return 0;
 }
@@ -258,10 +244,7 @@ extern "C" int nesvor_step_set_bias_mean_event(void* handle, void* event) {
 extern "C" void nesvor_step_destroy(void* handle) {
   if (handle == nullptr) return;
   StepCtx* c = static_cast<StepCtx*>(handle);
-  (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_pose); (void)hipEventDestroy(c->ev_agg); (void)hipEventDestroy(c->ev_owner);
-  (void)hipEventDestroy(c->ev_bwd); (void)hipEventDestroy(c->ev_sums); (void)hipEventDestroy(c->ev_norms);
-  (void)hipEventDestroy(c->ev_sg0); (void)hipEventDestroy(c->ev_sg1); (void)hipEventDestroy(c->ev_owner_early);
-  if (c->tu0[0] != nullptr) { (void)hipEventDestroy(c->tu0[0]); (void)hipEventDestroy(c->tu0[1]); }
+  (void)hipEventDestroy(c->ev_agg); (void)hipEventDestroy(c->ev_owner); (void)hipEventDestroy(c->ev_sg0); (void)hipEventDestroy(c->ev_sg1);
   if (c->wimg != nullptr) (void)hipFree(c->wimg);
   if (c->mean_ticket != nullptr) (void)hipFree(c->mean_ticket);
   for (int k = 0; k < NESVOR_STEP_TIMED_SPANS; ++k) {
@@ -298,8 +281,8 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
   // Operand bounds and weight norms of the three networks (nesvor_mlp_t.prep, split-operand mode): 3 x NESVOR_MLP_PREP_FLOATS floats
   // behind the accumulators, zero-filled with them by the prologue.  Nobody passes over an operand to find its bound: the
   // producing kernels publish them - the hash-grid forward max |pe|, the density network max |z|, the loss kernel max |d z_0|,
-  // max |d log_var|, max |d log_bias|, sigma_net's backward max |d z_1..| - and one launch per network takes the weight norms on
-  // the side stream, under the sampler and the hash-grid forward.
+  // max |d log_var|, max |d log_bias|, sigma_net's backward max |d z_1..| - and one launch takes the weight norms of all networks,
+  // right behind the prologue.
   float* prep_d = d.small + 26 * n + 1;
   float* prep_s = prep_d + NESVOR_MLP_PREP_FLOATS;
   float* prep_b = prep_s + NESVOR_MLP_PREP_FLOATS;
@@ -315,7 +298,7 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
   net_s.weight_images = (d.has_lv && nesvor_mlp_weight_images_bytes(&net_s) > 0) ? wimg_s : nullptr;
   net_b.weight_images = (d.has_b && nesvor_mlp_weight_images_bytes(&net_b) > 0) ? wimg_b : nullptr;
   // (modes 2 and 4 - the split and its leading term alone - share scales, bounds and images)
-  auto scaled = [](const nesvor_mlp_t& n_) { return n_.bf16_operands == 2 || n_.bf16_operands == 4; };
+  auto scaled = [](const nesvor_mlp_t& n_) { return n_.bf16_operands == NESVOR_MLP_MODE_SPLIT || n_.bf16_operands == NESVOR_MLP_MODE_FP16_SCALED; };
   const bool split_d = scaled(net_d), split_s = d.has_lv && scaled(net_s), split_b = d.has_b && scaled(net_b);
   const int layout = NESVOR_LAYOUT_FEATURE_MAJOR;
   const bool overlap_owner = (d.overlap_owner & 1) != 0;
@@ -326,12 +309,12 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
                           d.g_table == d.flat_grad + table_off && table_off >= 0 && table_off < d.flat_numel;
 
   // Pixel-feature gradients arrive as one row per 16-sample group (summed in the kernel) only from the wave-specialised fused
-  // backward: per NETWORK, divisibility AND nesvor_mlp_backward_fused_ok (round-5 advisor: a network that kernel refuses - e.g. a
-  // sigma_net with more than 32 inputs at two hidden layers, or N beyond 32-bit row offsets - runs as a dX launch + a dW launch
-  // through dpre_scratch and writes one row per SAMPLE; nesvor_amd/direct.py sizes dxa / dxa_b by the same rule)
-  const int group_div = (N % 16 == 0 && S % 16 == 0 && d.ks % 16 == 0) ? 1 : 0;
-  const int group_sums_s = (group_div && d.has_lv && nesvor_mlp_backward_fused_ok(&net_s, N)) ? 1 : 0;
-  const int group_sums_b = (group_div && d.has_b && nesvor_mlp_backward_fused_ok(&net_b, N)) ? 1 : 0;
+  // backward, per NETWORK: nesvor_mlp_backward_fused_ok is the rule (it implies whole groups inside a pixel).  A network that
+  // kernel refuses - e.g. a sigma_net with more than 32 inputs at two hidden layers, or N beyond 32-bit row offsets - runs as a
+  // dX launch + a dW launch through dpre_scratch and writes one row per SAMPLE; nesvor_amd/direct.py sizes dxa / dxa_b by the
+  // same query
+  const int group_sums_s = (d.has_lv && nesvor_mlp_backward_fused_ok(&net_s, N)) ? 1 : 0;
+  const int group_sums_b = (d.has_b && nesvor_mlp_backward_fused_ok(&net_b, N)) ? 1 : 0;
   const int rows_pp_s = group_sums_s ? S / 16 : S, rows_pp_b = group_sums_b ? S / 16 : S;
   const bool first_is_sigma = d.has_lv && d.ks;
   const float* dxa_first = first_is_sigma ? d.dxa : ((d.has_b && d.ks) ? d.dxa_b : nullptr);
@@ -372,20 +355,12 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
     // ---- forward
     // ONE launch: slice scales, pose matrices, zero-fill of the per-slice accumulators and operand bounds, and the pose regulariser
     // with its gradient (a function of the parameters alone).  Behind it, on the SAME stream: the networks' weight norms and the
-    // slice embedding's bound.  NESVOR_STEP_HEAD=side (A/B switch) restores rounds 4-5's arrangement - both on the side stream,
-    // forked behind the prologue, joined in front of the first network / at the epilogue: the fork's event record and the joins'
-    // waits each hold the main stream for 6-8 us (kernel -> marker -> kernel), more than the launches they hide.
-    static const bool head_on_side = []() { const char* e = getenv("NESVOR_STEP_HEAD"); return e != nullptr && e[0] == 's'; }();
-    const bool pose_in_prologue = d.opt_T && !head_on_side;
+    // slice embedding's bound.  (Both on the side stream, forked behind the prologue - rounds 4-5 - was measured slower and
+    // removed: profiles/r05_ab_step_head.log.)
     NESVOR_TRY(nesvor_step_prologue_pose(d.has_c ? d.logit_coef : nullptr, c, d.axisangle, mat, acc, 13 * n + 1 + 3 * NESVOR_MLP_PREP_FLOATS, n,
-                                         pose_in_prologue ? d.axisangle_init : nullptr, pose_in_prologue ? d.trans_terms : nullptr,
-                                         pose_in_prologue ? d.g_trans : nullptr, main));
+                                         d.opt_T ? d.axisangle_init : nullptr, d.opt_T ? d.trans_terms : nullptr,
+                                         d.opt_T ? d.g_trans : nullptr, main));
     const bool any_split = split_d || split_s || split_b;
-    hipStream_t head = main;
-    if (head_on_side && (d.opt_T || any_split)) {
-      if (hipEventRecord(ctx->ev_fork, main) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_fork, 0) != hipSuccess) return (int)hipGetLastError();
-      head = side;
-    }
     if (any_split) {
       const nesvor_mlp_t* nets[3]; float* preps[3]; void* imgs[3]; int nn = 0;
       if (split_d) { nets[nn] = &net_d; imgs[nn] = const_cast<void*>(net_d.weight_images); preps[nn++] = prep_d; }
@@ -395,36 +370,13 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
       // the table's maximum as their bound
       const bool se_bound = split_s && d.ks > 0;
       NESVOR_TRY(nesvor_mlp_prepare_weights_images(nets, preps, imgs, nn, se_bound ? d.slice_embedding : nullptr, (int64_t)n * d.ks,
-                                                   se_bound ? prep_s + NESVOR_MLP_PREP_XA : nullptr, head));
-      if (head_on_side && hipEventRecord(ctx->ev_norms, side) != hipSuccess) return (int)hipGetLastError();
+                                                   se_bound ? prep_s + NESVOR_MLP_PREP_XA : nullptr, main));
     }
-    if (head_on_side && d.opt_T) {
-      NESVOR_TRY(nesvor_trans_loss(d.axisangle, d.axisangle_init, d.trans_terms, d.g_trans, n, side));
-      if (hipEventRecord(ctx->ev_pose, side) != hipSuccess) return (int)hipGetLastError();
-    }
-    ctx->head_on_side = head_on_side;
     {
       Span t(ctx, NESVOR_STEP_SPAN_PSF_FWD, main);
       NESVOR_TRY(nesvor_psf_transform_forward_rng_gather(mat, slice_idx, xyz, d.psf_sigma, seed, offset, d.bounding_box, d.x, d.u, B, S,
                                                          d.ks > 0 ? d.slice_embedding : nullptr, d.ks > 0 ? d.se : nullptr, d.ks, main));
     }
-    const int pipe = ctx->pending_join ? ctx->pending_pipe_level : 0;
-    if (pipe > 0 && pipe < L && S >= 128) {
-      // the previous run's table update arrives level range by level range: the forward of levels [0, pipe) runs while the owner
-      // pass still updates the finer ones
-      if (hipStreamWaitEvent(main, ctx->ev_owner_early, 0) != hipSuccess) return (int)hipGetLastError();
-      {
-        Span t(ctx, NESVOR_STEP_SPAN_HASHGRID_FWD, main);
-        NESVOR_TRY(nesvor_hashgrid_forward_levels(&d.grid, d.u, d.table, d.pe, N, layout, split_d ? prep_d + NESVOR_MLP_PREP_XB : nullptr, 0, pipe, main));
-      }
-      if (hipStreamWaitEvent(main, ctx->ev_owner, 0) != hipSuccess) return (int)hipGetLastError();
-      {
-        Span t(ctx, NESVOR_STEP_SPAN_HASHGRID_FWD_LATE, main);
-        NESVOR_TRY(nesvor_hashgrid_forward_levels(&d.grid, d.u, d.table, d.pe, N, layout, split_d ? prep_d + NESVOR_MLP_PREP_XB : nullptr, pipe, L, main));
-      }
-      if (ctx->timing) { (void)hipEventRecord(ctx->t1[NESVOR_STEP_SPAN_HASHGRID_UNION], main); ctx->span_used[NESVOR_STEP_SPAN_HASHGRID_UNION] = true; }
-      ctx->pending_join = false;
-    } else {
     if (ctx->pending_join) {  // the previous run left its table update on the side stream
       if (hipStreamWaitEvent(main, ctx->ev_owner, 0) != hipSuccess) return (int)hipGetLastError();
       ctx->pending_join = false;
@@ -434,15 +386,13 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
       NESVOR_TRY(nesvor_hashgrid_forward_bounded(&d.grid, d.u, d.table, d.pe, N, layout | (S >= 128 ? NESVOR_LAYOUT_CLUSTERED : 0),
                                                  split_d ? prep_d + NESVOR_MLP_PREP_XB : nullptr, main));
     }
-    }
-    if (head_on_side && any_split && hipStreamWaitEvent(main, ctx->ev_norms, 0) != hipSuccess) return (int)hipGetLastError();
    }
     if (bias_stop) {
       // Staged: b_net first - it reads pe and se only - so that the density and sigma forwards of the RESUME call run while the
       // scalar is exchanged (measured on one GPU against b_net behind the density network: inside the spread,
       // profiles/ddp_bias_overhead_one_gpu.log)
       NESVOR_TRY(bias_forward(true));
-      return (int)hipGetLastError();  // the host all-reduces d.lb_mean; the RESUME call completes the phase (and counts the run)
+      return (int)hipGetLastError();  // the host all-reduces d.lb_mean; the RESUME call completes the phase
     }
     {
       Span t(ctx, NESVOR_STEP_SPAN_MLP_FWD_DENSITY, main);
@@ -490,8 +440,8 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
     float* part_b = d.partial + 2 * (size_t)NESVOR_STEP_MLP_PARTIALS * widest;
     if (d.has_lv) {  // (its input gradient = rows 1.. of dz: raises the density network's upstream bound next to the loss kernel's row 0)
       Span t(ctx, NESVOR_STEP_SPAN_MLP_BWD_SIGMA, main);
-      NESVOR_TRY(mlp_backward_into(net_s, group_sums_s, d.se, d.z, d.dlv, d.saved_s, d.ks ? d.dxa : nullptr, d.dz + N, part_s,
-                                   d.g_sigma, d.n_sigma_params, N, main, d.dpre_scratch, prep_d + NESVOR_MLP_PREP_DY));  // (a scalar publish: slot 0)
+      NESVOR_TRY(mlp_backward_into(net_s, group_sums_s, d.se, d.z, d.dlv, d.saved_s, d.ks ? d.dxa : nullptr, d.dz + N, part_s, N, main,
+                                   d.dpre_scratch, prep_d + NESVOR_MLP_PREP_DY));  // (a scalar publish: slot 0)
     }
     // Per-slice sums that do not depend on the hash-grid backward - d slice scale, d slice variance and the slice embedding's
     // gradient (sigma_net's input gradient) - go to the side stream NOW, under the density network's backward and the aggregation
@@ -505,12 +455,11 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
     }
     {
       Span t(ctx, NESVOR_STEP_SPAN_MLP_BWD_DENSITY, main);
-      NESVOR_TRY(mlp_backward_into(net_d, 0, nullptr, d.pe, d.dz, d.saved_d, nullptr, d.dpe, part_d, d.g_density,
-                                   d.n_density_params, N, main, d.dpre_scratch, dpe_bound));
+      NESVOR_TRY(mlp_backward_into(net_d, 0, nullptr, d.pe, d.dz, d.saved_d, nullptr, d.dpe, part_d, N, main, d.dpre_scratch, dpe_bound));
     }
     if (d.has_b) {
-      NESVOR_TRY(mlp_backward_into(net_b, group_sums_b, d.se, d.pe, d.dlb, d.saved_b, d.ks ? d.dxa_b : nullptr, d.dpe_b, part_b,
-                                   d.g_bias_net, d.n_bias_params, N, main, d.dpre_scratch));
+      NESVOR_TRY(mlp_backward_into(net_b, group_sums_b, d.se, d.pe, d.dlb, d.saved_b, d.ks ? d.dxa_b : nullptr, d.dpe_b, part_b, N, main,
+                                   d.dpre_scratch));
       const int64_t nb = (int64_t)d.kb_bias * N;
       hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((nb / 4 + 255) / 256 + 1)), dim3(256), 0, main, d.dpe, d.dpe_b, nb);
     }
@@ -519,23 +468,9 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
       in[n_jobs] = part_d; out[n_jobs] = d.g_density; cols[n_jobs++] = d.n_density_params;
       if (d.has_lv) { in[n_jobs] = part_s; out[n_jobs] = d.g_sigma; cols[n_jobs++] = d.n_sigma_params; }
       if (d.has_b) { in[n_jobs] = part_b; out[n_jobs] = d.g_bias_net; cols[n_jobs++] = d.n_bias_params; }
-      // Only the closing AdamW (or the caller's optimizer / gradient exchange, which joins the side stream) reads these sums.
-      // NESVOR_STEP_SUMS_SIDE=1 runs them on the side stream, under the aggregation pass, instead of in front of it (9 us of
-      // the critical path) - measured in one job, alternating (gpurun_out/s2j2): 895 / 900 it/s on the main stream, 893 / 896
-      // on the side stream: the aggregation pass starts later behind the cross-stream hand-over than it gains.  Off.
-      hipStream_t sums_stream = main;
-      ctx->sums_on_side = false;
-      static const bool sums_side = []() { const char* e = getenv("NESVOR_STEP_SUMS_SIDE"); return e != nullptr && strcmp(e, "1") == 0; }();  // A/B switch
-      const bool on_side = overlap_owner && sums_side;
-      if (on_side) {
-        if (hipEventRecord(ctx->ev_bwd, main) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_bwd, 0) != hipSuccess) return (int)hipGetLastError();
-        sums_stream = side;
-      }
-      NESVOR_TRY(nesvor_sum_rows_multi(in, out, cols, cols, n_jobs, NESVOR_STEP_MLP_PARTIALS, sums_stream));
-      if (on_side) {
-        if (hipEventRecord(ctx->ev_sums, side) != hipSuccess) return (int)hipGetLastError();
-        ctx->sums_on_side = true;
-      }
+      // Only the closing AdamW (or the caller's optimizer / gradient exchange) reads these sums.  (On the side stream, under the
+      // aggregation pass: measured, no gain, removed - DESIGN.md, "Prebuilt operand images".)
+      NESVOR_TRY(nesvor_sum_rows_multi(in, out, cols, cols, n_jobs, NESVOR_STEP_MLP_PARTIALS, main));
     }
   }
   // ---- hash-grid backward (+ input gradient when the poses are optimised)
@@ -557,29 +492,11 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
       if (hipEventRecord(ctx->ev_agg, main) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_agg, 0) != hipSuccess) return (int)hipGetLastError();
       owner_stream = side;
     }
-    // Pipelined table update (round 6; NESVOR_STEP_PIPE_LEVEL=<level>, default 0 = OFF): when this run leaves the table's update on the
-    // side stream for the next run to join (NESVOR_STEP_DEFER_JOIN), the owner pass goes out as TWO launches - levels [0, pipe), then
-    // the rest - and the next run's forward starts on the first range while the second is still being updated.  Owner pass (84 us
-    // with the table's AdamW) and forward (70 us) are strictly one after the other on the step's critical path, and both are
-    // latency-bound - yet MEASURED (tools/ab_pipe_level.sh, profiles/r06_ab_pipe_level.log, two alternating rounds): 0.944 ms ->
-    // 0.960-0.970 ms at pipe levels 11 / 12 / 14.  The overlapped owner launch stretches by 24 us for 44 us of forward (the two
-    // kernels contend: ~45 % overlap efficiency), the second forward launch repeats the set-up (44 + 44 us against 72), and the
-    // extra event hand-overs take the rest.  Kept as a switch; off.
-    static const int pipe_level = []() { const char* e = getenv("NESVOR_STEP_PIPE_LEVEL"); return e != nullptr ? atoi(e) : 0; }();
-    const int pipe = (fuse_adamw && overlap_owner && defer_join && S >= 128 && pipe_level > 0 && pipe_level < L) ? pipe_level : 0;
-    ctx->pending_pipe_level = pipe;
-    if (ctx->timing) (void)hipEventRecord(ctx->tu0[ctx->run_no & 1u], owner_stream);
+    // (A pipelined table update - the owner pass level range by level range, the next run's forward following it - was measured
+    //  slower and removed: profiles/r06_ab_pipe_level.log, DESIGN.md "Measured, not kept".)
     {
       Span t(ctx, NESVOR_STEP_SPAN_HASHGRID_BWD_OWNER, owner_stream);  // (with fuse_adamw: the owner pass AND the table's AdamW step)
-      if (pipe > 0) {
-        NESVOR_TRY(nesvor_hashgrid_backward_adamw_levels(&d.grid, d.u, d.flat_param + table_off, d.dpe, d.g_table, du, N, layout, d.hg_workspace,
-                                                         2, 0, pipe, d.queue_scale, dpe_bound, d.flat_exp_avg + table_off,
-                                                         d.flat_exp_avg_sq + table_off, adam, owner_stream));
-        if (hipEventRecord(ctx->ev_owner_early, side) != hipSuccess) return (int)hipGetLastError();
-        NESVOR_TRY(nesvor_hashgrid_backward_adamw_levels(&d.grid, d.u, d.flat_param + table_off, d.dpe, d.g_table, du, N, layout, d.hg_workspace,
-                                                         2, pipe, L, d.queue_scale, dpe_bound, d.flat_exp_avg + table_off,
-                                                         d.flat_exp_avg_sq + table_off, adam, owner_stream));
-      } else if (fuse_adamw)
+      if (fuse_adamw)
         NESVOR_TRY(nesvor_hashgrid_backward_adamw(&d.grid, d.u, d.flat_param + table_off, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 2,
                                                   d.queue_scale, dpe_bound, d.flat_exp_avg + table_off, d.flat_exp_avg_sq + table_off, adam,
                                                   owner_stream));
@@ -621,17 +538,12 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
     if (d.has_lv && d.has_b && d.ks)  // second consumer of the slice embedding
       NESVOR_TRY(slice_grads(nullptr, nullptr, d.dxa_b, rows_pp_b, nullptr, nullptr, nullptr, d.g_slice_embedding, nullptr, main));
   }
-  if (ctx->head_on_side && d.opt_T && hipStreamWaitEvent(main, ctx->ev_pose, 0) != hipSuccess) return (int)hipGetLastError();
   const float img_scale = (d.reg_type == 0 ? d.delta : 1.f) / (float)N, img_off = d.reg_type == 0 ? -d.delta : 0.f;
   NESVOR_TRY(nesvor_step_epilogue(d.has_c ? dc : nullptr, c, d.has_c ? d.g_logit_coef : nullptr, d.opt_T ? dmat : nullptr, d.axisangle,
                                   d.opt_T ? d.g_trans : nullptr, d.w_T, d.opt_T ? d.g_axisangle : nullptr, d.loss_pix,
                                   d.opt_T ? d.trans_terms : nullptr, losses, n, B, img_scale, img_off, main));
   if (d.has_b) hipLaunchKernelGGL(square_kernel, dim3(1), dim3(1), 0, main, d.lb_mean, losses + 5);
   if (adam != nullptr) {
-    if (ctx->sums_on_side) {
-      if (hipStreamWaitEvent(main, ctx->ev_sums, 0) != hipSuccess) return (int)hipGetLastError();
-      ctx->sums_on_side = false;
-    }
     if (fuse_adamw) {
       // everything but the table; the table's update is the owner pass, which the next forward must wait for - here, or
       // (NESVOR_STEP_DEFER_JOIN) in the next run right before its hash-grid forward, so that the next iteration's prologue and
@@ -655,7 +567,6 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
                                    adam->eps, adam->weight_decay, adam->bias_correction1, adam->bias_correction2, adam->grad_scale, 1, main));
     }
   }
-  ++ctx->run_no;
   return (int)hipGetLastError();
 }
 

@@ -18,11 +18,13 @@ tinycudann networks, evaluated with bf16 matrix operands), MLPs of at most two h
 autograd path (FusedTrainer decides through ``supported``).
 """
 import ctypes
+import os
 from typing import Dict
 
 import torch
+import torch.distributed as dist
 
-from . import _lib, loss as loss_mod, mlp as mlp_mod, sampler
+from . import _lib, ddp, loss as loss_mod, mlp as mlp_mod, sampler
 from .encoding import hashgrid_backward, hashgrid_forward
 from .models import B_REG, D_LOSS, DS_LOSS, I_REG, S_LOSS, T_REG, NeSVoR
 from .transform import trans_loss_raw
@@ -78,18 +80,17 @@ def _net_inputs(model: NeSVoR, net):
     return ks, a.n_levels_bias * a.n_features_per_level, 0
 
 
-def _bias_free_desc(model: NeSVoR, p, S: int):
-    """The scaled-fp16 descriptor of a bias-free network (NetParams ``p``) with its real weight pointers and NULL biases: the
-    library's shape queries tell a bias-free network from a biased one by those pointers."""
-    k_a, k_b, b_row0 = _net_inputs(model, p.net)
-    return mlp_mod._desc(p.weights, p.biases, k_a, k_b, b_row0, S, mlp_mod.FP16S)
+def _net_desc(model: NeSVoR, p, mode):
+    """The ``MlpT`` of one of the model's networks (NetParams ``p``) as the step feeds it, with its real parameter pointers -
+    NULL biases for a bias-free network: the library's shape queries tell it from a biased one by those pointers, and answer
+    for a biased one as for a descriptor without pointers."""
+    return mlp_mod._desc(p.weights, p.biases, *_net_inputs(model, p.net), model.args.n_samples, mode)
 
 
 def _bias_free_ok(model: NeSVoR, net) -> bool:
     """``nesvor_mlp_bias_free_ok`` for one network of the model at a batch of 16 pixels."""
-    S = model.args.n_samples
-    d = _bias_free_desc(model, mlp_mod.NetParams(net, mlp_mod.FP16S), S)
-    return bool(_lib.load().nesvor_mlp_bias_free_ok(ctypes.byref(d), 16 * S))
+    d = _net_desc(model, mlp_mod.NetParams(net, mlp_mod.FP16S), mlp_mod.FP16S)
+    return bool(_lib.load().nesvor_mlp_bias_free_ok(ctypes.byref(d), 16 * model.args.n_samples))
 
 
 class DirectStep:
@@ -136,19 +137,13 @@ class DirectStep:
         # the hash-grid backward (latency-bound, finishes the table gradient only) while the main stream runs the
         # sampler backward and the per-slice bookkeeping
         # NESVOR_SIDE_STREAM_PRIORITY (A/B switch): HIP stream priority of the side stream (lower number = higher priority)
-        _prio = __import__("os").environ.get("NESVOR_SIDE_STREAM_PRIORITY")
+        _prio = os.environ.get("NESVOR_SIDE_STREAM_PRIORITY")
         self.side = torch.cuda.Stream(device=dev) if _prio is None else torch.cuda.Stream(device=dev, priority=int(_prio))
-        self._overlap_owner = __import__("os").environ.get("NESVOR_OWNER_OVERLAP", "1") != "0"
+        self._overlap_owner = os.environ.get("NESVOR_OWNER_OVERLAP", "1") != "0"
         # the table's AdamW step inside the owner pass (nesvor_hashgrid_backward_adamw) whenever one native call covers
         # gradient and update (no data-parallel exchange in between): the table gradient then never goes through HBM
-        self._adamw_in_owner = __import__("os").environ.get("NESVOR_ADAMW_IN_OWNER", "1") != "0"
-        import os
-
-        import torch.distributed as dist
-
+        self._adamw_in_owner = os.environ.get("NESVOR_ADAMW_IN_OWNER", "1") != "0"
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-        from . import ddp
-
         self.parallel = ddp.active()
         # Data parallel: the hash-grid backward runs in two launches - the fine levels (about half of the table's bytes,
         # the END of the flat buffer) first; their all-reduce is started at once and overlaps the coarse levels' launch
@@ -194,8 +189,6 @@ class DirectStep:
         return lo, hi
 
     def _start_early(self):
-        from . import ddp
-
         lo, hi = self.early_range()
         if self.early_exchange is not None:
             return self.early_exchange(lo, hi)
@@ -243,27 +236,23 @@ class DirectStep:
         self.gw.copy_(self._gw_base)
         self.w_T = self._w_T_base
 
+    def _desc(self, p):
+        """The ``MlpT`` of one of the step's networks (``_net_desc``) in the step's operand mode."""
+        return _net_desc(self.model, p, self.bf16)
+
     def _fused_backward_ok(self, N=None):
         """Per network (density, sigma | None, bias | None): does the wave-specialised fused MLP backward take it at N points per
         iteration?  (``nesvor_mlp_backward_fused_ok``; the answer depends on the shapes and - through the 32-bit row offsets of
         its scalar-base addressing - on N: asked once per N, with the REAL N of the batch, round-5 advisor.)  A network it refuses
         runs as a dX launch + a dW launch through ``nesvor_step_t.dpre_scratch`` and returns its pixel-feature gradient per
         sample, not per 16-sample group."""
-        m, a = self.model, self.model.args
-        S = a.n_samples
-        N = 16 * S if N is None else int(N)
+        N = 16 * self.model.args.n_samples if N is None else int(N)
         if self._native_shapes_ok is None:
             self._native_shapes_ok = {}
         key = (N, mlp_mod.operand_mode(self.bf16))  # (bench.py switches the evaluation mode of a live trainer)
         if key not in self._native_shapes_ok:
-            E = m.inr.encoding.spec.n_output_dims
-            ok = lambda dd: bool(_lib.load().nesvor_mlp_backward_fused_ok(ctypes.byref(dd), N))
-            # (a bias-free network is asked with its own pointers: NULL biases change the answer)
-            desc = lambda p, dims: _bias_free_desc(m, p, S) if p.bias_free else dims
-            self._native_shapes_ok[key] = (
-                ok(desc(self.d_net, mlp_mod.dims_desc(len(self.d_net.weights) - 1, 1 + a.n_features_z, 0, E, 0, S, self.bf16))),
-                ok(desc(self.s_net, mlp_mod.dims_desc(len(self.s_net.weights) - 1, 1, self.ks, a.n_features_z, 1, S, self.bf16))) if self.has_lv else None,
-                ok(desc(self.b_net, mlp_mod.dims_desc(len(self.b_net.weights) - 1, 1, self.ks, self.kb_bias, 0, S, self.bf16))) if self.has_b else None)
+            ok = lambda p: None if p is None else bool(_lib.load().nesvor_mlp_backward_fused_ok(ctypes.byref(self._desc(p)), N))
+            self._native_shapes_ok[key] = (ok(self.d_net), ok(self.s_net), ok(self.b_net))
         return self._native_shapes_ok[key]
 
     def _fused_backward_takes_all(self, N=None) -> bool:
@@ -292,17 +281,16 @@ class DirectStep:
 
         d = _lib.StepT()
         d.grid = enc.spec.c_struct
-        mode = self.bf16
-        d.density = mlp_mod._desc(self.d_net.weights, self.d_net.biases, 0, E, 0, S, mode)
+        d.density = self._desc(self.d_net)
         n_par = lambda p: p.n_columns()  # (a bias-free network: its evaluated weights, the prefix of its flat gradient)
         d.n_density_params, d.g_density = n_par(self.d_net), self.d_net.segment.data_ptr()
         largest = d.n_density_params
         if self.has_lv:
-            d.sigma = mlp_mod._desc(self.s_net.weights, self.s_net.biases, self.ks, a.n_features_z, 1, S, mode)
+            d.sigma = self._desc(self.s_net)
             d.n_sigma_params, d.g_sigma = n_par(self.s_net), self.s_net.segment.data_ptr()
             largest = max(largest, d.n_sigma_params)
         if self.has_b:
-            d.bias_net = mlp_mod._desc(self.b_net.weights, self.b_net.biases, self.ks, self.kb_bias, 0, S, mode)
+            d.bias_net = self._desc(self.b_net)
             d.n_bias_params, d.g_bias_net = n_par(self.b_net), self.b_net.segment.data_ptr()
             largest = max(largest, d.n_bias_params)
         d.B, d.S, d.n_slices = B, S, n
@@ -345,11 +333,10 @@ class DirectStep:
         if self.ks:
             d.se = new("se", B, self.ks)
         # pixel-feature gradients: one row per 16-sample group from the fused backward, one per sample from the launch pair
-        # (csrc/step.hip decides per network by the same rule: divisibility and nesvor_mlp_backward_fused_ok at this N)
-        group_div = N % 16 == 0 and S % 16 == 0 and self.ks % 16 == 0
+        # (csrc/step.hip asks the same query per network: nesvor_mlp_backward_fused_ok at this N)
         _, fused_s, fused_b = self._fused_backward_ok(N)
-        rows_s = N // 16 if (group_div and fused_s) else N
-        rows_b = N // 16 if (group_div and fused_b) else N
+        rows_s = N // 16 if fused_s else N
+        rows_b = N // 16 if fused_b else N
         if self.has_lv:
             d.log_var, d.dlv = new("log_var", N), new("dlv", N)
             saved_buffers(d.sigma, d.saved_s, "saved_s", len(self.s_net.weights) - 1)
@@ -378,8 +365,7 @@ class DirectStep:
 
     # names of the spans nesvor_step_timing_read returns (NESVOR_STEP_SPAN_*), in order
     TIMED_SPANS = ("psf_transform_fwd", "hashgrid_fwd", "mlp_fwd_density", "mlp_fwd_sigma", "imaging_loss_bwd", "mlp_bwd_sigma",
-                   "mlp_bwd_density", "hashgrid_bwd_aggregate", "hashgrid_bwd_owner", "psf_transform_bwd", "hashgrid_fwd_late",
-                   "hashgrid_owner_fwd_union")
+                   "mlp_bwd_density", "hashgrid_bwd_aggregate", "hashgrid_bwd_owner", "psf_transform_bwd")
 
     def set_native_timing(self, on: bool) -> None:
         """HIP-event brackets around the launches of the one-call step, each on the stream its launch goes to (``nesvor_step_timing``:
@@ -436,8 +422,6 @@ class DirectStep:
                 # biasReg = (mean log_bias)^2 needs the mean over ALL ranks' samples: the step stops behind b_net's forward with this
                 # rank's share of it, the one float is sum-all-reduced on a stream of its own, and the rest of the phase - whose
                 # density and sigma forwards run meanwhile - waits for it in front of the loss kernel (a stream wait on the event)
-                from . import ddp
-
                 if self._comm_stream is None:
                     self._comm_stream = torch.cuda.Stream(device=dev)
                 ph = 1 if self.split_level else 0
@@ -448,8 +432,6 @@ class DirectStep:
             else:
                 resume = 0
             if self.split_level:
-                from . import ddp
-
                 _lib.check(lib.nesvor_step_run(*args, 1 | resume, self.split_level, None, stream), "training step (fine levels)")
                 self._early = self._start_early()  # async: RCCL's stream, behind the launches above
                 if self.early_update is not None and self.early_exchange is None and self._early is not None:
@@ -468,6 +450,10 @@ class DirectStep:
         self._pending_state = st if self._owner_pending else None
         self._last_state = st
         sizer.snapshot(ws)
+        return self._loss_dict(vals, vals[5])
+
+    def _loss_dict(self, vals, b_reg) -> Dict[str, torch.Tensor]:
+        """The loss dict of an iteration from the epilogue's values {MSE, logVar, MSE+logVar, transReg, imageReg} and biasReg."""
         losses = {D_LOSS: vals[0]}
         if self.has_var:
             losses[S_LOSS] = vals[1]
@@ -475,7 +461,7 @@ class DirectStep:
         if self.opt_T:
             losses[T_REG] = vals[3]
         if self.has_b:
-            losses[B_REG] = vals[5]
+            losses[B_REG] = b_reg
         losses[I_REG] = vals[4]
         return losses
 
@@ -620,8 +606,6 @@ class DirectStep:
                 dxa, dxa_b = dxa_b, None
         gt = enc.params.grad.view(-1)
         if self.split_level:
-            from . import ddp
-
             L = enc.spec.n_levels
             _, du = hashgrid_backward(enc.spec, u, enc.params, dpe, gt, self.opt_T, _lib.LAYOUT_FEATURE_MAJOR,
                                       levels=(self.split_level, L), dy_bound=dpe_bound)
@@ -662,15 +646,7 @@ class DirectStep:
                 scale_ptr, _lib.ptr(m.axisangle.grad if self.opt_T else None), _lib.ptr(loss_pix), _lib.ptr(per if self.opt_T else None),
                 _lib.ptr(vals), n, B, img_scale, img_off, _lib.stream_ptr())
         _lib.check(err, "step epilogue")
-        losses = {D_LOSS: vals[0]}
-        if self.has_var:
-            losses[S_LOSS] = vals[1]
-            losses[DS_LOSS] = vals[2]
-        if self.opt_T:
-            losses[T_REG] = vals[3]
-        if self.has_b:
-            losses[B_REG] = lb_mean[0] ** 2
-        losses[I_REG] = vals[4]
+        losses = self._loss_dict(vals, lb_mean[0] ** 2 if self.has_b else None)
         if not defer_owner_join:
             self.join_owner()
         return losses

@@ -14,6 +14,7 @@ import os
 
 import torch
 
+from . import direct, mlp as _mlp
 from . import ops as _ops  # noqa: F401  (registers torch.ops.nesvor)
 from .models import NeSVoR
 from .train import loss_weights
@@ -177,9 +178,6 @@ class FusedTrainer:
         self._early_updated = False
         self._late_join = os.environ.get("NESVOR_OWNER_JOIN_LATE", "1") != "0"  # 0: join the owner pass before the step's epilogue (A/B)
         # autograd-free evaluation of the iteration when the configuration allows it (nesvor_amd.direct)
-        from . import direct
-        from . import mlp as _mlp
-
         if getattr(args, "mlp_fp16", False) and getattr(args, "fp16_loss_scaling", False):
             raise RuntimeError("args.mlp_fp16 and args.fp16_loss_scaling exclude each other: scaled fp16 needs no loss scaler")
         if getattr(args, "mlp_fp16", False) and direct.half_precision_model(model):

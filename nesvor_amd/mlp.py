@@ -342,10 +342,10 @@ def backward_raw(weights, biases, xa, xb, dy, saved, b_row0, k_b, S, dxb, need_d
     fused = FUSED_BACKWARD and bool(_lib.load().nesvor_mlp_backward_fused_ok(ctypes.byref(d), N))
     # (dpre scratch in fp32 in every mode: the 16-bit operand modes save 16-bit activations, but their pair hands fp32 dpre over)
     dpre = [] if fused else [torch.empty(s.numel(), dtype=torch.float32, device=s.device) for s in saved]
-    # pixel-feature gradient: one row per 16-sample group (summed in the kernel) when a group lies inside a pixel
-    group_sums = fused and N % 16 == 0 and S % 16 == 0 and k_a % 16 == 0
-    d.dxa_group_sums = 1 if group_sums else 0
-    rows = N // 16 if group_sums else N
+    # pixel-feature gradient: one row per 16-sample group (summed in the kernel) from the fused kernel - which takes only shapes
+    # whose groups lie inside a pixel (nesvor_mlp_backward_fused_ok: N, S and k_a multiples of 16)
+    d.dxa_group_sums = 1 if fused else 0
+    rows = N // 16 if fused else N
     dxa = torch.empty((rows, k_a), dtype=torch.float32, device=dev) if (xa is not None and need_dxa) else None
     total = sum(w.numel() + (0 if b is None else b.numel()) for w, b in zip(weights, biases))  # (bias-free: no b columns)
     n_partial = N_PARTIAL_FUSED if fused else N_PARTIAL

@@ -147,3 +147,50 @@ def test_backward_workspace_size_queries_follow_the_layout_hints():
     assert fw(0 | U) == 256 + sort_bytes and fw(1 | U) == 256 + sort_bytes + n_pad * 32 * 4
     small = lib.nesvor_hashgrid_backward_workspace_bytes(ctypes.byref(spec.c_struct), 1000, None)
     assert 0 < small < base
+
+
+def test_step_span_table_follows_the_header():
+    """``DirectStep.TIMED_SPANS`` names what ``nesvor_step_timing_read`` returns by position: the NESVOR_STEP_SPAN_* indices of the
+    header are 0 .. NESVOR_STEP_TIMED_SPANS - 1 without gaps, the table has that many names, and the names the GPU suite reads
+    (tests/test_gpu_ddp_bias.py::test_timing_spans_survive_the_split) sit at the index of their define."""
+    from nesvor_amd.direct import DirectStep
+
+    text = open(os.path.join(ROOT, "include", "nesvor_hip.h")).read()
+    spans = {name: int(idx) for name, idx in re.findall(r"^#define NESVOR_STEP_SPAN_(\w+)\s+(\d+)\b", text, flags=re.M)}
+    n = int(re.search(r"^#define NESVOR_STEP_TIMED_SPANS\s+(\d+)\b", text, flags=re.M).group(1))
+    assert sorted(spans.values()) == list(range(n)), spans
+    assert len(DirectStep.TIMED_SPANS) == n
+    expected = {"psf_transform_fwd": "PSF_FWD", "hashgrid_fwd": "HASHGRID_FWD", "mlp_fwd_density": "MLP_FWD_DENSITY",
+                "mlp_fwd_sigma": "MLP_FWD_SIGMA", "imaging_loss_bwd": "LOSS", "mlp_bwd_density": "MLP_BWD_DENSITY",
+                "hashgrid_bwd_aggregate": "HASHGRID_BWD_AGGREGATE", "hashgrid_bwd_owner": "HASHGRID_BWD_OWNER",
+                "psf_transform_bwd": "PSF_BWD"}
+    for name, define in expected.items():
+        assert DirectStep.TIMED_SPANS[spans[define]] == name, (name, define)
+
+
+def test_fused_backward_query_implies_whole_groups():
+    """``nesvor_mlp_backward_fused_ok`` is the rule for per-group pixel-feature gradients (``dxa_group_sums``): an answer of 1
+    implies N, samples per pixel and k_a in multiples of 16, so no caller repeats that test.  Host-side logic of the library."""
+    import ctypes
+    import itertools
+
+    import __graft_entry__ as ge
+    from nesvor_amd import _lib, mlp
+
+    ge.build()
+    lib = _lib.load()
+
+    def ok(N, S, k_a, k_b, n_hidden, mode):
+        return lib.nesvor_mlp_backward_fused_ok(ctypes.byref(mlp.dims_desc(n_hidden, 1, k_a, k_b, 0, S, mode)), N)
+
+    modes = (mlp.MFMA_FP32, mlp.BF16, mlp.SPLIT, mlp.FP16)
+    for N, S, k_a, k_b, n_hidden, mode in itertools.product((256, 250), (16, 8, 32, 24), (0, 16, 8), (8, 32), (1, 2), modes):
+        if ok(N, S, k_a, k_b, n_hidden, mode) == 1:
+            assert N % 16 == 0 and S % 16 == 0 and k_a % 16 == 0, (N, S, k_a, k_b, n_hidden, mode)
+    if os.environ.get("NESVOR_MLP_BWD_WS") == "0":
+        return  # (the wave-specialised kernel is switched off: nothing answers 1, only the implication above is checked)
+    # not vacuous; and the converse does not hold: a divisible shape the kernel refuses (48 inputs at two hidden layers)
+    assert ok(256, 16, 16, 8, 2, mlp.MFMA_FP32) == 1
+    assert ok(256, 8, 16, 8, 2, mlp.MFMA_FP32) == 0
+    for mode in modes:
+        assert ok(256, 16, 16, 32, 2, mode) == 0, mode

@@ -1,4 +1,4 @@
-"""CPU: the device loss scaler's C ABI (csrc/scaler.hip) - ABI 37, the exports and their ctypes signatures, the state struct
+"""CPU: the device loss scaler's C ABI (csrc/scaler.hip) - the ABI version, the exports and their ctypes signatures, the state struct
 mirrored by ``_lib.LossScalerT`` - and the host form of ``fused.LossScaler`` that the device form is held to."""
 import ctypes
 import os
@@ -17,9 +17,9 @@ def _lib_loaded():
     return _lib, _lib.load()
 
 
-def test_abi_version_is_37():
+def test_abi_version_is_38():
     _lib, lib = _lib_loaded()
-    assert _lib.ABI_VERSION == 37 and lib.nesvor_hip_abi_version() == 37
+    assert _lib.ABI_VERSION == 38 and lib.nesvor_hip_abi_version() == 38
 
 
 def test_scaler_exports_resolve_with_their_argtypes():
