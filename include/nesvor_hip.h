@@ -340,6 +340,15 @@ typedef struct {
                                     faster 16-bit matrix pipe.  Pipelined forward and wave-specialised backward (dX chain and dW
                                     products); every other kernel evaluates this mode as mode 0, which is always a valid
                                     evaluation of it.  (Rounds 2-4: three bf16 terms per operand, six MFMAs per product.)
+                                    One quantity is NOT at the fp32 chain's error: the bias gradients of the HIDDEN layers.
+                                    MEASURED: every entry of db comes out too small, at N = 2^18 by -1.2e-6 .. -1.9e-6 of
+                                    max |db| on average, 1.9e-6 .. 5.2e-6 at most, against +-1e-7 .. 2e-7 in mode 0 (2^14:
+                                    8e-7 .. 1.3e-6), while dX and dW are at the fp32 chain's error;
+                                    tests/test_gpu_mlp_steady_state.py prints it per case.  NOT ESTABLISHED: the cause.  A
+                                    one-signed error of each pre-activation gradient (~2^-26 of its size, as from 16-bit-MFMA
+                                    accumulators that are not rounded to nearest) would fit - harmless where signs mix, adding
+                                    up like N in db = sum over the batch of dpre against a sum that grows like sqrt(N) - but
+                                    nothing has isolated it.
                                     REQUIRES `prep`;
                                  3: operands rounded to fp16 (the reference's default arithmetic; overflows beyond 65504: its
                                     GradScaler's job), same kernels as mode 1;

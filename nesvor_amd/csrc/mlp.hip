@@ -2562,16 +2562,19 @@ int launch_kb(K k1, K k2, K k3, K k4, int kb1, dim3 grid, size_t lds, hipStream_
   K k = kb1 == 1 ? k1 : kb1 == 2 ? k2 : kb1 == 3 ? k3 : k4;
   const void* fn = reinterpret_cast<const void*>(k);
   static std::mutex mu;
+  int dev = 0;
+  if ((lds > 48 * 1024 || persistent_tiles > 0) && hipGetDevice(&dev) != hipSuccess) dev = 0;
   if (lds > 48 * 1024) {
-    // raise the dynamic-LDS limit once per kernel and size (not per launch: the call is a host-side
-    // attribute change and must not happen inside a stream capture)
-    static std::map<const void*, size_t> raised;
+    // raise the dynamic-LDS limit once per (device, kernel) and size (not per launch: the call is a host-side
+    // attribute change and must not happen inside a stream capture); the attribute is per function AND device
+    static std::map<std::pair<int, const void*>, size_t> raised;
     std::lock_guard<std::mutex> lock(mu);
-    auto it = raised.find(fn);
+    const auto key = std::make_pair(dev, fn);
+    auto it = raised.find(key);
     if (it == raised.end() || it->second < lds) {
       hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return (int)e;
-      raised[fn] = lds;
+      raised[key] = lds;
     }
   }
   if (persistent_tiles > 0) {
@@ -2581,8 +2584,6 @@ int launch_kb(K k1, K k2, K k3, K k4, int kb1, dim3 grid, size_t lds, hipStream_
     static const int fixed = []() { const char* e = getenv("NESVOR_FWD_GRID"); return e ? atoi(e) : 0; }();  // A/B override (run-time)
     int n_wg = fixed;
     if (n_wg <= 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess) dev = 0;
       std::lock_guard<std::mutex> lock(mu);
       auto it = resident.find(std::make_tuple(dev, fn, lds));
       if (it == resident.end()) {

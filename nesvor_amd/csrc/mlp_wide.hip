@@ -20,7 +20,9 @@
 // ([group][block][lane][4]: coalesced 1 KiB wave transactions).  Backward = a dX launch (writes the pre-activation gradients
 // in the same layout) + a dW launch (per-workgroup partial sums in nn.Linear parameter order W0, b0, W1, b1, ...; no atomics).
 #include <hip/hip_runtime.h>
+#include <map>
 #include <mutex>
+#include <utility>
 #include "common.h"
 #include "../../include/nesvor_hip.h"
 
@@ -411,15 +413,24 @@ int fill(WideArgs* a, const nesvor_mlp_wide_t* net, int64_t N) {
   return 0;
 }
 
+// Raise a kernel's dynamic-LDS limit above 48 KiB once per (device, kernel) and size - not per launch: the call is a host-side
+// attribute change and must not happen inside a stream capture.  Keyed by the function's address, not by its pointer TYPE:
+// wide_fwd_kernel<4|8> and wide_bwd_dx_kernel<4|8> are four functions of one type, and the attribute is per function and device.
 template <typename K>
 int raise_lds(K kernel, size_t bytes) {
   static std::mutex mu;
-  static size_t raised = 0;
+  static std::map<std::pair<int, const void*>, size_t> raised;
+  if (bytes <= 48 * 1024) return 0;
+  const void* fn = reinterpret_cast<const void*>(kernel);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
   std::lock_guard<std::mutex> lock(mu);
-  if (bytes > 48 * 1024 && bytes > raised) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  const auto key = std::make_pair(dev, fn);
+  auto it = raised.find(key);
+  if (it == raised.end() || it->second < bytes) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return (int)e;
-    raised = bytes;
+    raised[key] = bytes;
   }
   return 0;
 }

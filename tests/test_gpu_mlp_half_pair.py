@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import small_args
+from mlp_reference import emulated_backward as _emulated_backward  # (shared with tests/test_gpu_mlp_steady_state.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -107,35 +108,6 @@ def test_pair_matches_fused_kernel(device, ht, depth, k_a, k_b, S, out_dim):
     for li, ((dw_p, db_p), (dw_f, db_f)) in enumerate(zip(g_p, g_f)):
         _close(dw_p, dw_f, 1e-5, f"dW{li}")
         _close(db_p, db_f, 1e-5, f"db{li}")
-
-
-def _saved_rows(s, N):
-    """16-bit saved fragments [group][block][lane = 16 q + j][r] -> (N, 64) fp64 activations (feature 16 block + 4 q + r, sample 16 group + j)"""
-    G = s.numel() // 1024
-    return s.view(G, 4, 4, 16, 4).permute(0, 3, 1, 2, 4).reshape(G * 16, 64)[:N].double()
-
-
-def _emulated_backward(W, B, xa, xb, dy, saved, b_row0, k_b, S, dt):
-    """float64 backward with the kernels' rounding points (csrc/mlp.hip, mlp_bwd_dx16_kernel's header): dY and every dpre rounded
-    to the 16-bit type before a product, weights and the network input rounded, saved activations as the forward wrote them."""
-    N = xb.shape[1]
-    rn = (lambda t: t.to(dt).double()) if dt is not None else (lambda t: t.double())  # dt None: no rounding
-    x = xb[b_row0 : b_row0 + k_b].t().double()
-    if xa is not None:
-        x = torch.cat([xa.double().repeat_interleave(S, 0), x], 1)
-    H = [_saved_rows(s, N) for s in saved]
-    g = dy.t().double()
-    grads = [None] * len(W)
-    a = rn(g)
-    grads[-1] = (a.t() @ H[-1], g.sum(0))
-    dh = a @ rn(W[-1])
-    for l in range(len(W) - 2, -1, -1):
-        dpre = dh * (H[l] > 0)
-        a = rn(dpre)
-        inp = H[l - 1] if l > 0 else rn(x)
-        grads[l] = (a.t() @ inp, dpre.sum(0))
-        dh = a @ rn(W[l])
-    return dh, grads
 
 
 PAIR_ONLY = [  # (depth, k_a, k_b, S, N, out_dim, biased)
