@@ -464,13 +464,18 @@ int nesvor_mlp_backward_bounded(const nesvor_mlp_t* net, const float* xa, const 
                                 float* dw_partial, int n_partial, int64_t N, float* dxb_absmax, void* stream);
 
 /* ------------------------------------------------------------------------
- * The same networks at ANY width up to 128 and up to NESVOR_MLP_WIDE_MAX_LAYERS - 1 hidden layers (round 6; csrc/mlp_wide.hip):
+ * The same networks at ANY width up to 256 and up to NESVOR_MLP_WIDE_MAX_LAYERS - 1 hidden layers (round 6; csrc/mlp_wide.hip):
  * the reference builds its MLPs with any --width / --depth (nesvor/cli/main.py:68-73 -> build_network,
  * nesvor/nesvor/models.py:42-67; bias-free tinycudann.Network in half precision, models.py:28-41), and shapes outside
  * nesvor_mlp_t's (width 64, at most three hidden layers) used to leave the hand-written path for library GEMMs.  fp32 matrix
  * cores (v_mfma_f32_16x16x4_f32: an fp32 FMA chain), activations in registers from input to output, ONE layer's weights in LDS
- * at a time (a 128 x 128 layer is 64 KB: the workgroup swaps the operand image between layers of a 256-sample tile).  Widths
- * that are not multiples of 16 run zero-padded (exactly the same function).  Input composition, layouts and the meaning of
+ * at a time (a 128 x 128 layer is 64 KB: the workgroup swaps the operand image between layers of a 256-sample tile).  Above
+ * width 128 a layer's image (256 KB at width 256) exceeds the CU's 160 KiB of LDS: it streams through LDS as a CHUNKED image,
+ * 32 output rows x all k at a time in two alternating 32 KB buffers (one barrier per chunk, the next chunk's loads in flight
+ * behind this chunk's MFMAs), under 128-sample tiles of one 16-sample group per wave; the saved / dpre fragments have sixteen
+ * blocks per group (nesvor_mlp_wide_saved_floats = N padded to 16, times 256), of which the blocks at or beyond
+ * ceil(width / 16) are padding that no kernel writes or reads.
+ * Widths that are not multiples of 16 run zero-padded (exactly the same function).  Input composition, layouts and the meaning of
  * xa / xb / b_row0 / k_a / k_b / samples_per_pixel as for nesvor_mlp_t; k_a + k_b <= 64, out_dim <= 16.
  *   forward : y (out_dim, N); saved_hidden = n_hidden device buffers of nesvor_mlp_wide_saved_floats(net, N) floats each (the
  *             post-ReLU activations in MFMA fragment layout) or NULL (inference);
@@ -478,10 +483,11 @@ int nesvor_mlp_backward_bounded(const nesvor_mlp_t* net, const float* xa, const 
  *             nesvor_mlp_wide_param_count(net)): per-workgroup partial sums in nn.Linear parameter order W0, b0, W1, b1, ...
  *             (no b columns for a NULL bias), to be summed over the rows by the caller; dpre_scratch = n_hidden buffers of the
  *             saved buffers' size.  Two launches (dX chain, then dW / db), no atomics.
- * Errors: hipErrorInvalidValue for shapes outside the limits or missing buffers. */
+ * Errors: hipErrorInvalidValue for shapes outside the limits (a width beyond 256 included: nesvor_mlp_wide_param_count returns
+ * -1 for them) or missing buffers. */
 #define NESVOR_MLP_WIDE_MAX_LAYERS 8
 typedef struct {
-  int32_t width;              /* hidden width, 1..128 */
+  int32_t width;              /* hidden width, 1..256 */
   int32_t n_hidden;           /* 1..NESVOR_MLP_WIDE_MAX_LAYERS-1 */
   int32_t out_dim;            /* 1..16 */
   int32_t k_a, k_b, b_row0;

@@ -53,7 +53,7 @@ class MlpT(Structure):
 
 
 class MlpWideT(Structure):
-    """Mirror of nesvor_mlp_wide_t (width <= 128, up to seven hidden layers: csrc/mlp_wide.hip)."""
+    """Mirror of nesvor_mlp_wide_t (width <= 256, up to seven hidden layers; above 128 the chunked-image kernels: csrc/mlp_wide.hip)."""
 
     _fields_ = [
         ("width", c_int32), ("n_hidden", c_int32), ("out_dim", c_int32),

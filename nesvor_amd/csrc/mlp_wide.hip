@@ -1,5 +1,5 @@
-// Hand-written MLP kernels for the shapes the 64-wide fused kernels (mlp.hip) do not take: hidden width up to 128 (two
-// 64-column tiles = eight 16-feature blocks) and up to seven hidden layers.
+// Hand-written MLP kernels for the shapes the 64-wide fused kernels (mlp.hip) do not take: hidden width up to 256 (four
+// 64-column tiles = sixteen 16-feature blocks) and up to seven hidden layers.
 //
 // The reference builds these networks with any --width / --depth (nesvor/cli/main.py:68-73 -> build_network,
 // nesvor/nesvor/models.py:42-67: Linear + ReLU stacks with biases in single precision, bias-free in half precision); rounds 3-5
@@ -13,6 +13,8 @@
 // workgroup keeps ONE layer's operand image and swaps it between layers - a tile is 8 waves x 2 groups = 256 samples, the
 // 64 KB image of the next layer arrives from L2 as sixteen 16-byte loads per thread - two barriers per layer and tile, next to
 // 512 MFMAs per wave.  HB = 4 (width <= 64, for the deep networks) or 8 (width <= 128); narrower widths run zero-padded.
+// Width 129 .. 256 (HB = 16): one layer's image no longer fits, so it streams through LDS in 32-row chunks, double-buffered,
+// with one 16-sample group per wave - the "chunked images" section below.
 //
 // Input composition as in mlp.hip: [pixel features xa (P, k_a) broadcast over the S samples of a pixel | rows b_row0 ..
 // b_row0 + k_b of a feature-major matrix xb (rows, N)], k_a + k_b <= 64; output (out_dim <= 16, N) feature-major.
@@ -47,6 +49,7 @@ struct WideArgs {
   float* dx_absmax;       // dX kernel, optional: device scalar raised (atomic max) to max |dxb| (nesvor_mlp_backward_bounded's contract)
   int64_t N;
   int n_linear, width, k_a, k_b, b_row0, out_dim, S, total_params;
+  int dw_parts;           // dW kernel at sixteen blocks: workgroups per partial row (each runs every dw_parts-th pass)
 };
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
@@ -297,97 +300,411 @@ __global__ __launch_bounds__(kWaves * 64) void wide_bwd_dx_kernel(const WideArgs
   }
 }
 
+// ------------------------------------------------------------------------------------------------ width 129 .. 256: chunked images
+// Sixteen 16-feature blocks (HB = 16).  One layer's image is up to 256 KB - more than the CU's 160 KiB of LDS - so a layer
+// streams through LDS in CHUNKS of two row blocks (32 rows x up to 256 k = 32 KB at most; chunk[rb][kb][lane][r], row stride =
+// the layer's k blocks), and the register tile is ONE 16-sample group per wave (a tile is 8 waves x 16 = 128 samples): 64
+// registers of input state, 64 of next-layer state, 8 of one chunk's accumulators, 16 of the next chunk on its way.  (Four row
+// blocks per chunk - 64 KB, 16 + 32 registers - spilled: 212 bytes of scratch in the forward at 256 registers; two do not.)
+//
+// Double-buffered (2 x 32 KB), ONE barrier per chunk - chosen over one buffer with two barriers per chunk because a chunk is
+// only 128 MFMAs per wave (an eighth of what stands next to the HB = 8 path's barrier pair), and at two waves per SIMD of 229
+// registers the workgroup is alone on its CU either way: the second buffer costs no occupancy, and the L2 latency of the next
+// chunk's loads hides behind the MFMAs of this one instead of between two barriers.  Per chunk every thread (1) issues the global loads of the NEXT chunk
+// of the sequence (next row blocks, else the next layer's first chunk, else - a tile further - the first layer's again) into
+// registers, (2) runs the MFMAs of this chunk from buffer `cur`, (3) writes the registers to buffer `cur ^ 1`, (4) barrier.
+// The barrier of chunk s - 1 orders both the stores of chunk s (visible) and the reads of chunk s - 1 (done before buffer
+// `cur ^ 1` is written again in chunk s).  Biases (forward) travel the same way in two 256-float slots, swapped per layer.
+// Blocks at or beyond ceil(width / 16) are zero padding: never computed, saved or read (the k loops and the row blocks stop at
+// the width's blocks), so a 136-wide network costs 9 x 9 blocks per layer, not 16 x 16.
+constexpr int kHBc = 16;                                   // blocks of the chunked path
+constexpr int kCB = 2;                                     // row blocks per chunk
+constexpr int kDwMaxParts = 4;                             // dW workgroups per partial row at most (mlp.py: WIDE_DW_MAX_PARTS)
+constexpr int kChunkFloats = kCB * kHBc * 256;             // 32 KB
+constexpr int kChunkU = kCB * kHBc * 64 / (kWaves * 64);   // 16-byte slots per thread and chunk: 4
+
+// chunk[rb][kb][lane][r] = W[16 (ob0 + rb) + (lane & 15)][16 kb + 4 (lane >> 4) + r], rb < nb  (load_image's element, into registers)
+__device__ __forceinline__ void fetch_chunk(f32x4 (&v)[kChunkU], const float* __restrict__ W, int out_dim, int in_dim, int ob0, int nb, int KB) {
+  const int total = nb * KB * 64;
+  const bool vec = (in_dim & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0;
+#pragma unroll
+  for (int u = 0; u < kChunkU; ++u) {
+    const int e = threadIdx.x + u * (kWaves * 64);
+    v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (e < total) {
+      const int lane = e & 63, blk = e >> 6;
+      const int kb = blk % KB, rb = blk / KB;
+      const int row = 16 * (ob0 + rb) + (lane & 15), col = 16 * kb + 4 * (lane >> 4);
+      if (row < out_dim) {
+        const float* p = W + (size_t)row * in_dim + col;
+        if (vec && col + 3 < in_dim) v[u] = *reinterpret_cast<const f32x4*>(p);
+        else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[u][r] = col + r < in_dim ? p[r] : 0.f;
+        }
+      }
+    }
+  }
+}
+// transposed (backward): chunk[rb][kb][lane][r] = W[16 kb + 4 (lane >> 4) + r][16 (ib0 + rb) + (lane & 15)]
+__device__ __forceinline__ void fetch_chunk_T(f32x4 (&v)[kChunkU], const float* __restrict__ W, int out_dim, int in_dim, int ib0, int nb, int KB) {
+  const int total = nb * KB * 64;
+#pragma unroll
+  for (int u = 0; u < kChunkU; ++u) {
+    const int e = threadIdx.x + u * (kWaves * 64);
+    v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (e < total) {
+      const int lane = e & 63, blk = e >> 6;
+      const int kb = blk % KB, rb = blk / KB;
+      const int in = 16 * (ib0 + rb) + (lane & 15), o0 = 16 * kb + 4 * (lane >> 4);
+      if (in < in_dim) {
+        const int off = o0 * in_dim + in;  // (one uniform base + 32-bit offsets: at most 256 x 256 floats)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[u][r] = o0 + r < out_dim ? W[off + r * in_dim] : 0.f;
+      }
+    }
+  }
+}
+__device__ __forceinline__ void store_chunk(float* chunk, const f32x4 (&v)[kChunkU], int total) {
+#pragma unroll
+  for (int u = 0; u < kChunkU; ++u) {
+    const int e = threadIdx.x + u * (kWaves * 64);
+    if (e < total) *reinterpret_cast<f32x4*>(chunk + (size_t)e * 4) = v[u];
+  }
+}
+// acc[rb] += chunk[rb] . x[kb]  for rb < nb, kb < KB (wave-uniform bounds); k ascending per accumulator, as apply_layer
+__device__ __forceinline__ void apply_chunk(const float* __restrict__ chunk, const f32x4 (&x)[kHBc], f32x4 (&acc)[kCB], int nb, int KB, int lane) {
+#pragma unroll
+  for (int kb = 0; kb < kHBc; ++kb) {
+    if (kb < KB) {
+      f32x4 a4[kCB];
+#pragma unroll
+      for (int rb = 0; rb < kCB; ++rb)
+        a4[rb] = rb < nb ? *reinterpret_cast<const f32x4*>(chunk + (size_t)((rb * KB + kb) * 64 + lane) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int rb = 0; rb < kCB; ++rb)
+          if (rb < nb) acc[rb] = mfma4(a4[rb][r], x[kb][r], acc[rb]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kWaves * 64) void wide_fwd_chunked_kernel(const WideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* bias = lds + 2 * kChunkFloats;  // two slots of 256 floats
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = lane & 15, q = lane >> 4;
+  const int n_hidden = a.n_linear - 1, k_in = a.k_a + a.k_b, KB1 = (k_in + 15) >> 4, WB = (a.width + 15) >> 4;
+  const int64_t n_groups = (a.N + 15) / 16;
+  const int64_t n_tiles = (n_groups + kWaves - 1) / kWaves;
+  int cur = 0, bcur = 0;  // the buffer / bias slot of the chunk / layer about to be evaluated
+  {  // the first chunk of the first layer (the grid never exceeds the tiles: every workgroup has a tile)
+    f32x4 v[kChunkU];
+    const int nb = min(kCB, WB);
+    fetch_chunk(v, a.W[0], a.width, k_in, 0, nb, KB1);
+    store_chunk(lds, v, nb * KB1 * 64);
+    if (threadIdx.x < 256) bias[threadIdx.x] = (a.b[0] != nullptr && (int)threadIdx.x < a.width) ? a.b[0][threadIdx.x] : 0.f;
+    __syncthreads();
+  }
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {  // (workgroup-uniform trip count: barriers inside)
+    const int64_t gi = tile * kWaves + wave;
+    const int64_t n = gi * 16 + j;
+    f32x4 x[kHBc];
+    {
+      const int64_t nn = n < a.N ? n : a.N - 1;
+      const float* pa = a.xa != nullptr ? a.xa + (size_t)(nn / a.S) * a.k_a : nullptr;
+      const float* pb = a.xb + (size_t)a.b_row0 * a.N + nn;
+#pragma unroll
+      for (int kb = 0; kb < kHBc; ++kb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int kk = 16 * kb + 4 * q + r;
+          float v = 0.f;
+          if (kb < 4 && n < a.N && kk < k_in) v = kk < a.k_a ? pa[kk] : pb[(size_t)(kk - a.k_a) * a.N];  // (k_in <= 64)
+          x[kb][r] = v;
+        }
+    }
+    for (int l = 0; l < a.n_linear; ++l) {
+      const bool last = l == n_hidden;
+      const int KB = l == 0 ? KB1 : WB, OB = last ? 1 : WB;
+      const float* bs = bias + bcur * 256;
+      f32x4 xn[kHBc];
+#pragma unroll
+      for (int ob = 0; ob < kHBc; ++ob) xn[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < kHBc / kCB; ++c) {
+        if (kCB * c < OB) {  // (uniform)
+          // (1) the next chunk of the sequence, into registers
+          const bool same = kCB * (c + 1) < OB;                       // more row blocks of this layer
+          const bool have = same || !last || tile + gridDim.x < n_tiles;
+          const int nl = same ? l : (last ? 0 : l + 1), nc = same ? c + 1 : 0;
+          const int n_in = nl == 0 ? k_in : a.width, n_out = nl == n_hidden ? a.out_dim : a.width;
+          const int nKB = nl == 0 ? KB1 : WB, nnb = min(kCB, (nl == n_hidden ? 1 : WB) - kCB * nc);
+          f32x4 v[kChunkU];
+          float nbias = 0.f;
+          if (have) {
+            fetch_chunk(v, a.W[nl], n_out, n_in, kCB * nc, nnb, nKB);
+            if (!same && threadIdx.x < 256 && a.b[nl] != nullptr && (int)threadIdx.x < n_out) nbias = a.b[nl][threadIdx.x];
+          }
+          // (2) this chunk
+          const int nb = min(kCB, OB - kCB * c);
+          f32x4 acc[kCB];
+#pragma unroll
+          for (int rb = 0; rb < kCB; ++rb)
+            acc[rb] = rb < nb ? *reinterpret_cast<const f32x4*>(bs + 16 * (kCB * c + rb) + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+          apply_chunk(lds + cur * kChunkFloats, x, acc, nb, KB, lane);
+          if (!last) {
+#pragma unroll
+            for (int rb = 0; rb < kCB; ++rb) {
+              if (rb < nb) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[rb][r] = relu_f(acc[rb][r]);
+                if (a.H[l] != nullptr && gi < n_groups)
+                  __builtin_nontemporal_store(acc[rb], reinterpret_cast<f32x4*>(a.H[l] + (((size_t)gi * kHBc + kCB * c + rb) * 64 + lane) * 4));
+                xn[kCB * c + rb] = acc[rb];
+              }
+            }
+          } else if (n < a.N) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (4 * q + r < a.out_dim) a.y[(size_t)(4 * q + r) * a.N + n] = acc[0][r];
+          }
+          // (3) the next chunk into the other buffer, (4) one barrier
+          if (have) {
+            store_chunk(lds + (cur ^ 1) * kChunkFloats, v, nnb * nKB * 64);
+            if (!same && threadIdx.x < 256) bias[(bcur ^ 1) * 256 + threadIdx.x] = nbias;
+          }
+          __syncthreads();
+          cur ^= 1;
+        }
+      }
+      bcur ^= 1;
+      if (!last) {
+#pragma unroll
+        for (int ob = 0; ob < kHBc; ++ob) x[ob] = xn[ob];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kWaves * 64) void wide_bwd_dx_chunked_kernel(const WideArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = lane & 15, q = lane >> 4;
+  const int n_hidden = a.n_linear - 1, k_in = a.k_a + a.k_b, KB1 = (k_in + 15) >> 4, WB = (a.width + 15) >> 4;
+  const int64_t n_groups = (a.N + 15) / 16;
+  const int64_t n_tiles = (n_groups + kWaves - 1) / kWaves;
+  const bool want_dx = a.dxa != nullptr || a.dxb != nullptr;
+  const int l_end = want_dx ? 0 : 1;  // the last layer whose transposed image is applied
+  float dx_mx = 0.f;
+  int cur = 0;
+  {  // the first chunk of the output layer's transposed image: rows = its inputs (WB blocks), k = out_dim (one block)
+    f32x4 v[kChunkU];
+    const int nb = min(kCB, WB);
+    fetch_chunk_T(v, a.W[n_hidden], a.out_dim, a.width, 0, nb, 1);
+    store_chunk(lds, v, nb * 64);
+    __syncthreads();
+  }
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t gi = tile * kWaves + wave;
+    const int64_t n = gi * 16 + j;
+    const bool ok = gi < n_groups;
+    f32x4 d[kHBc];  // the chain's state; block 0 first carries dY
+#pragma unroll
+    for (int ib = 0; ib < kHBc; ++ib) d[ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d[0][r] = (n < a.N && 4 * q + r < a.out_dim) ? a.y[(size_t)(4 * q + r) * a.N + n] : 0.f;
+    for (int l = n_hidden; l >= 0; --l) {
+      if (l < n_hidden) {  // gate with the saved activations: d = dpre[l]
+#pragma unroll
+        for (int ib = 0; ib < kHBc; ++ib) {
+          if (ib < WB) {
+            const size_t off = (((size_t)gi * kHBc + ib) * 64 + lane) * 4;
+            f32x4 hv = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (ok) hv = *reinterpret_cast<const f32x4*>(a.H[l] + off);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) d[ib][r] = hv[r] > 0.f ? d[ib][r] : 0.f;
+            if (ok) *reinterpret_cast<f32x4*>(a.dpre[l] + off) = d[ib];
+          }
+        }
+      }
+      if (l < l_end) break;  // (uniform)
+      // through W_l^T: rows = inputs of layer l (IB blocks), k = outputs of layer l (KB blocks)
+      const int IB = l == 0 ? KB1 : WB, KB = l == n_hidden ? 1 : WB;
+      f32x4 d2[kHBc];
+#pragma unroll
+      for (int ib = 0; ib < kHBc; ++ib) d2[ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < kHBc / kCB; ++c) {
+        if (kCB * c < IB) {  // (uniform)
+          const bool same = kCB * (c + 1) < IB;
+          const bool wrap = l == l_end;  // after this layer: the next tile's output layer
+          const bool have = same || !wrap || tile + gridDim.x < n_tiles;
+          const int nl = same ? l : (wrap ? n_hidden : l - 1), nc = same ? c + 1 : 0;
+          const int n_in = nl == 0 ? k_in : a.width, n_out = nl == n_hidden ? a.out_dim : a.width;
+          const int nKB = nl == n_hidden ? 1 : WB, nnb = min(kCB, (nl == 0 ? KB1 : WB) - kCB * nc);
+          f32x4 v[kChunkU];
+          if (have) fetch_chunk_T(v, a.W[nl], n_out, n_in, kCB * nc, nnb, nKB);
+          const int nb = min(kCB, IB - kCB * c);
+          f32x4 acc[kCB];
+#pragma unroll
+          for (int rb = 0; rb < kCB; ++rb) acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
+          apply_chunk(lds + cur * kChunkFloats, d, acc, nb, KB, lane);
+#pragma unroll
+          for (int rb = 0; rb < kCB; ++rb)
+            if (rb < nb) d2[kCB * c + rb] = acc[rb];
+          if (have) store_chunk(lds + (cur ^ 1) * kChunkFloats, v, nnb * nKB * 64);
+          __syncthreads();
+          cur ^= 1;
+        }
+      }
+#pragma unroll
+      for (int ib = 0; ib < kHBc; ++ib) d[ib] = d2[ib];
+    }
+    if (want_dx && n < a.N) {
+      const int64_t dxb_lane = (int64_t)(4 * q - a.k_a) * a.N + n;  // row 4 q - k_a (+ 16 ib + r below), column n
+#pragma unroll
+      for (int ib = 0; ib < 4; ++ib)  // (k_in <= 64: four input blocks at most)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int kk = 16 * ib + 4 * q + r;
+          if (ib >= KB1) continue;
+          if (kk < a.k_a) {
+            if (a.dxa != nullptr) a.dxa[(size_t)n * a.k_a + kk] = d[ib][r];
+          } else if (kk - a.k_a < a.k_b) {
+            // (per-lane part + uniform row part: sixteen hoisted 64-bit lane addresses would not fit the register budget)
+            if (a.dxb != nullptr) { a.dxb[dxb_lane + (int64_t)(16 * ib + r) * a.N] = d[ib][r]; dx_mx = fmaxf(dx_mx, fabsf(d[ib][r])); }
+          }
+        }
+    }
+  }
+  if (a.dx_absmax != nullptr && a.dxb != nullptr) {
+    dx_mx = wave_max(dx_mx);
+    if (lane == 0 && dx_mx > 0.f) atomicMax(reinterpret_cast<unsigned int*>(a.dx_absmax), __float_as_uint(dx_mx));
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ backward: dW, db
 // One workgroup (4 waves) accumulates, layer after layer and - at eight blocks - four output blocks at a time, over its share
 // of the sample groups:   dW_l[out][in] = sum_n d_l[out][n] x_l[in][n]   (MFMA rows = out, columns = in, k = samples).
+// At sixteen blocks (width 129 .. 256) a pass is four output blocks x EIGHT input blocks - acc[4][16] would be 256 registers -
+// so the staging buffer stays 32 KB; the passes of a partial row are dealt round-robin to `dw_parts` workgroups (they write
+// disjoint columns of the row: still no atomics, and every column has one writer summing in one order), because the rows of
+// such a network are large and the caller keeps their number small (nesvor_amd/mlp.py: WIDE_PARTIAL_BYTES).
 template <int HB>
 __device__ __forceinline__ float frag_elem(const float* __restrict__ F, int64_t gi, int f, int s) {
   return F[(((size_t)gi * HB + (f >> 4)) * 64 + ((f & 15) >> 2) * 16 + s) * 4 + (f & 3)];  // (feature f, sample s) of group gi
 }
+// Which partial row a dW workgroup sums into and which passes of that row it runs: every pass of row blockIdx.x up to eight
+// blocks; at sixteen, workgroup w of n_rows * dw_parts runs the passes p with p % dw_parts == w / n_rows of row w % n_rows.
+struct DwShare { unsigned n_rows, row; int parts, part; };
+template <int HB>
+__device__ __forceinline__ DwShare dw_share(const WideArgs& a) {
+  if constexpr (HB > 8) {
+    const unsigned n_rows = gridDim.x / a.dw_parts;
+    return DwShare{n_rows, blockIdx.x % n_rows, a.dw_parts, (int)(blockIdx.x / n_rows)};
+  } else {
+    return DwShare{gridDim.x, blockIdx.x, 1, 0};
+  }
+}
 template <int HB>
 __global__ __launch_bounds__(256) void wide_bwd_dw_kernel(const WideArgs a) {
+  constexpr bool kSplit = HB > 8;            // sixteen blocks: input blocks in two passes, padding blocks skipped, rows shared
   constexpr int OC = 4;                      // output blocks per pass
-  __shared__ float red[4][HB * 256];         // per-wave staging of one accumulator row of blocks
+  constexpr int IC = kSplit ? 8 : HB;        // input blocks per pass
+  __shared__ float red[4][IC * 256];         // per-wave staging of one accumulator row of blocks
   const int n_hidden = a.n_linear - 1, k_in = a.k_a + a.k_b, KB1 = (k_in + 15) >> 4;
+  const int WB = kSplit ? (a.width + 15) >> 4 : HB;  // (the zero-padding blocks of the chunked kernels are neither written nor read)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, q = lane >> 4;
   const int64_t n_groups = (a.N + 15) / 16;
-  float* out = a.dW_partial + (size_t)blockIdx.x * a.total_params;
-  int poff = 0;
+  const DwShare sh = dw_share<HB>(a);
+  const unsigned n_rows = sh.n_rows, row = sh.row;
+  float* out = a.dW_partial + (size_t)row * a.total_params;
+  int poff = 0, pass = 0;
   for (int l = 0; l < a.n_linear; ++l) {
     const int in_dim = l == 0 ? k_in : a.width, out_dim = l == n_hidden ? a.out_dim : a.width;
-    const int IB = l == 0 ? KB1 : HB, OB = l == n_hidden ? 1 : HB;
+    const int IB = l == 0 ? KB1 : WB, OB = l == n_hidden ? 1 : WB;
     for (int ob0 = 0; ob0 < OB; ob0 += OC) {
-      f32x4 acc[OC][HB];
-      float db[OC];
-#pragma unroll
-      for (int oc = 0; oc < OC; ++oc) {
-        db[oc] = 0.f;
-#pragma unroll
-        for (int ib = 0; ib < HB; ++ib) acc[oc][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      for (int64_t gi = (int64_t)blockIdx.x * 4 + wave; gi < n_groups; gi += (int64_t)gridDim.x * 4) {
-        float av[OC][4], bv[HB][4];
+      const int n_ipass = kSplit ? (IB + IC - 1) / IC : 1;  // (up to eight blocks: one pass takes every input block)
+      for (int ip = 0; ip < n_ipass; ++ip, ++pass) {
+        if (pass % sh.parts != sh.part) continue;  // (uniform)
+        const int ib0 = ip * IC;
+        const bool with_db = ip == 0;  // the bias gradient of these output blocks: once, not per input-block pass
+        f32x4 acc[OC][IC];
+        float db[OC];
 #pragma unroll
         for (int oc = 0; oc < OC; ++oc) {
-          if (ob0 + oc < OB) {
+          db[oc] = 0.f;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              const int64_t n = gi * 16 + 4 * q + t;
-              float v;
-              if (l == n_hidden) v = (n < a.N && i < a.out_dim) ? a.y[(size_t)i * a.N + n] : 0.f;
-              else v = n < a.N ? frag_elem<HB>(a.dpre[l], gi, 16 * (ob0 + oc) + i, 4 * q + t) : 0.f;
-              av[oc][t] = v;
-            }
-            db[oc] += (av[oc][0] + av[oc][1]) + (av[oc][2] + av[oc][3]);
-          }
+          for (int ib = 0; ib < IC; ++ib) acc[oc][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
+        for (int64_t gi = (int64_t)row * 4 + wave; gi < n_groups; gi += (int64_t)n_rows * 4) {
+          float av[OC][4], bv[IC][4];
 #pragma unroll
-        for (int ib = 0; ib < HB; ++ib) {
-          if (ib < IB) {
+          for (int oc = 0; oc < OC; ++oc) {
+            if (ob0 + oc < OB) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              const int64_t n = min(gi * 16 + 4 * q + t, a.N - 1);  // (a clamped sample beyond N meets a zero A operand)
-              const int kk = 16 * ib + i;
-              bv[ib][t] = l == 0 ? (kk < k_in ? fetch_input(a, kk, n) : 0.f) : frag_elem<HB>(a.H[l - 1], gi, kk, 4 * q + t);
+              for (int t = 0; t < 4; ++t) {
+                const int64_t n = gi * 16 + 4 * q + t;
+                float v;
+                if (l == n_hidden) v = (n < a.N && i < a.out_dim) ? a.y[(size_t)i * a.N + n] : 0.f;
+                else v = n < a.N ? frag_elem<HB>(a.dpre[l], gi, 16 * (ob0 + oc) + i, 4 * q + t) : 0.f;
+                av[oc][t] = v;
+              }
+              if (with_db) db[oc] += (av[oc][0] + av[oc][1]) + (av[oc][2] + av[oc][3]);
             }
           }
+#pragma unroll
+          for (int ib = 0; ib < IC; ++ib) {
+            if (ib0 + ib < IB) {
+#pragma unroll
+              for (int t = 0; t < 4; ++t) {
+                const int64_t n = min(gi * 16 + 4 * q + t, a.N - 1);  // (a clamped sample beyond N meets a zero A operand)
+                const int kk = 16 * (ib0 + ib) + i;
+                bv[ib][t] = l == 0 ? (kk < k_in ? fetch_input(a, kk, n) : 0.f) : frag_elem<HB>(a.H[l - 1], gi, kk, 4 * q + t);
+              }
+            }
+          }
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int oc = 0; oc < OC; ++oc)
+#pragma unroll
+              for (int ib = 0; ib < IC; ++ib)
+                if (ob0 + oc < OB && ib0 + ib < IB) acc[oc][ib] = mfma4(av[oc][t], bv[ib][t], acc[oc][ib]);
         }
+        // the four waves' partial sums through LDS, one row of blocks at a time -> W (out, in)
+        const int nib = min(IB - ib0, IC);
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+        for (int oc = 0; oc < OC; ++oc) {
+          if (ob0 + oc >= OB) break;  // (uniform)
+          __syncthreads();
 #pragma unroll
-          for (int oc = 0; oc < OC; ++oc)
-#pragma unroll
-            for (int ib = 0; ib < HB; ++ib)
-              if (ob0 + oc < OB && ib < IB) acc[oc][ib] = mfma4(av[oc][t], bv[ib][t], acc[oc][ib]);
-      }
-      // the four waves' partial sums through LDS, one row of blocks at a time -> W (out, in)
-#pragma unroll
-      for (int oc = 0; oc < OC; ++oc) {
-        if (ob0 + oc >= OB) break;  // (uniform)
+          for (int ib = 0; ib < IC; ++ib) *reinterpret_cast<f32x4*>(&red[wave][(ib * 64 + lane) * 4]) = acc[oc][ib];
+          __syncthreads();
+          for (int e = threadIdx.x; e < nib * 256; e += 256) {
+            const float s = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
+            const int r = e & 3, ln = (e >> 2) & 63, ib = e >> 8;
+            const int o = 16 * (ob0 + oc) + 4 * (ln >> 4) + r, in = 16 * (ib0 + ib) + (ln & 15);
+            if (o < out_dim && in < in_dim) out[poff + o * in_dim + in] = s;
+          }
+        }
+        // bias gradients: sum over the sample quads (lanes i, i + 16, i + 32, i + 48) and over the waves
+        if (!with_db) continue;  // (uniform)
         __syncthreads();
 #pragma unroll
-        for (int ib = 0; ib < HB; ++ib) *reinterpret_cast<f32x4*>(&red[wave][(ib * 64 + lane) * 4]) = acc[oc][ib];
+        for (int oc = 0; oc < OC; ++oc) red[wave][oc * 64 + lane] = db[oc];
         __syncthreads();
-        for (int e = threadIdx.x; e < IB * 256; e += 256) {
-          const float s = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-          const int r = e & 3, ln = (e >> 2) & 63, ib = e >> 8;
-          const int o = 16 * (ob0 + oc) + 4 * (ln >> 4) + r, in = 16 * ib + (ln & 15);
-          if (o < out_dim && in < in_dim) out[poff + o * in_dim + in] = s;
+        for (int e = threadIdx.x; e < OC * 16; e += 256) {
+          const int oc = e >> 4, ii = e & 15;
+          float s = 0.f;
+          for (int w = 0; w < 4; ++w)
+            for (int qq = 0; qq < 4; ++qq) s += red[w][oc * 64 + qq * 16 + ii];
+          const int o = 16 * (ob0 + oc) + ii;
+          if (ob0 + oc < OB && o < out_dim && a.b[l] != nullptr) out[poff + out_dim * in_dim + o] = s;
         }
-      }
-      // bias gradients: sum over the sample quads (lanes i, i + 16, i + 32, i + 48) and over the waves
-      __syncthreads();
-#pragma unroll
-      for (int oc = 0; oc < OC; ++oc) red[wave][oc * 64 + lane] = db[oc];
-      __syncthreads();
-      for (int e = threadIdx.x; e < OC * 16; e += 256) {
-        const int oc = e >> 4, ii = e & 15;
-        float s = 0.f;
-        for (int w = 0; w < 4; ++w)
-          for (int qq = 0; qq < 4; ++qq) s += red[w][oc * 64 + qq * 16 + ii];
-        const int o = 16 * (ob0 + oc) + ii;
-        if (ob0 + oc < OB && o < out_dim && a.b[l] != nullptr) out[poff + out_dim * in_dim + o] = s;
       }
     }
     poff += out_dim * in_dim + (a.b[l] != nullptr ? out_dim : 0);
@@ -396,7 +713,7 @@ __global__ __launch_bounds__(256) void wide_bwd_dw_kernel(const WideArgs a) {
 
 int fill(WideArgs* a, const nesvor_mlp_wide_t* net, int64_t N) {
   if (net == nullptr) return (int)hipErrorInvalidValue;
-  if (net->width < 1 || net->width > 128 || net->n_hidden < 1 || net->n_hidden > kL - 1 || net->out_dim < 1 || net->out_dim > 16)
+  if (net->width < 1 || net->width > 256 || net->n_hidden < 1 || net->n_hidden > kL - 1 || net->out_dim < 1 || net->out_dim > 16)
     return (int)hipErrorInvalidValue;
   if (net->k_a < 0 || net->k_b < 1 || net->k_a + net->k_b > 64 || net->b_row0 < 0 || net->samples_per_pixel < 1) return (int)hipErrorInvalidValue;
   *a = WideArgs{};
@@ -410,12 +727,17 @@ int fill(WideArgs* a, const nesvor_mlp_wide_t* net, int64_t N) {
     total += out * in + (net->bias[l] != nullptr ? out : 0);
   }
   a->total_params = total;
+  a->dw_parts = 1;
   return 0;
 }
 
+// 16-feature blocks of the kernels' instantiation for a width: 4 (<= 64), 8 (<= 128), 16 (<= 256: the chunked kernels)
+int blocks_of(int width) { return width <= 64 ? 4 : width <= 128 ? 8 : kHBc; }
+
 // Raise a kernel's dynamic-LDS limit above 48 KiB once per (device, kernel) and size - not per launch: the call is a host-side
 // attribute change and must not happen inside a stream capture.  Keyed by the function's address, not by its pointer TYPE:
-// wide_fwd_kernel<4|8> and wide_bwd_dx_kernel<4|8> are four functions of one type, and the attribute is per function and device.
+// wide_fwd_kernel<4|8>, wide_bwd_dx_kernel<4|8> and the two chunked kernels are six functions of one type, and the attribute is
+// per function and device.
 template <typename K>
 int raise_lds(K kernel, size_t bytes) {
   static std::mutex mu;
@@ -448,8 +770,7 @@ int n_cus() {
 
 extern "C" int64_t nesvor_mlp_wide_saved_floats(const nesvor_mlp_wide_t* net, int64_t N) {
   if (net == nullptr || N <= 0) return 0;
-  const int HB = net->width <= 64 ? 4 : 8;
-  return ((N + 15) / 16) * 16 * (int64_t)(16 * HB);
+  return ((N + 15) / 16) * 16 * (int64_t)(16 * blocks_of(net->width));
 }
 
 extern "C" int nesvor_mlp_wide_param_count(const nesvor_mlp_wide_t* net) {
@@ -467,7 +788,15 @@ extern "C" int nesvor_mlp_wide_forward(const nesvor_mlp_wide_t* net, const float
   if (xb == nullptr || y == nullptr || (a.k_a > 0 && xa == nullptr)) return (int)hipErrorInvalidValue;
   a.xa = xa; a.xb = xb; a.y = y;
   for (int l = 0; l < net->n_hidden; ++l) a.H[l] = saved_hidden != nullptr ? saved_hidden[l] : nullptr;
-  const int HB = net->width <= 64 ? 4 : 8;
+  const int HB = blocks_of(net->width);
+  if (HB == kHBc) {  // 128-sample tiles, two chunk buffers + two bias slots; its registers leave the workgroup alone on a CU
+    const size_t lds = sizeof(float) * (size_t)(2 * kChunkFloats + 2 * 256);
+    const int64_t n_tiles = ((N + 15) / 16 + kWaves - 1) / kWaves;
+    const int64_t cap = n_cus();
+    if ((e = raise_lds(wide_fwd_chunked_kernel, lds))) return e;
+    hipLaunchKernelGGL(wide_fwd_chunked_kernel, dim3((unsigned)(n_tiles < cap ? n_tiles : cap)), dim3(kWaves * 64), lds, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+  }
   const size_t lds = sizeof(float) * (size_t)(HB * HB * 256 + 16 * HB);
   const int64_t n_tiles = ((N + 15) / 16 + kWaves * kG - 1) / (kWaves * kG);
   const int64_t cap = (int64_t)n_cus() * 2;
@@ -504,7 +833,20 @@ extern "C" int nesvor_mlp_wide_backward_bounded(const nesvor_mlp_wide_t* net, co
     if (saved_hidden[l] == nullptr || dpre_scratch[l] == nullptr) return (int)hipErrorInvalidValue;
     a.H[l] = saved_hidden[l]; a.dpre[l] = dpre_scratch[l];
   }
-  const int HB = net->width <= 64 ? 4 : 8;
+  const int HB = blocks_of(net->width);
+  if (HB == kHBc) {
+    const size_t lds = sizeof(float) * (size_t)(2 * kChunkFloats);
+    const int64_t n_tiles = ((N + 15) / 16 + kWaves - 1) / kWaves;
+    const int64_t cap = n_cus();
+    // dW: two workgroups per CU (what its registers let a CU hold) where the caller's rows allow it, as column parts of the rows -
+    // at most kDwMaxParts per row, so a caller who wants the chip full passes at least 2 x CUs / that many rows
+    const int want = (2 * n_cus() + n_partial - 1) / n_partial;
+    a.dw_parts = want < 1 ? 1 : want > kDwMaxParts ? kDwMaxParts : want;
+    if ((e = raise_lds(wide_bwd_dx_chunked_kernel, lds))) return e;
+    hipLaunchKernelGGL(wide_bwd_dx_chunked_kernel, dim3((unsigned)(n_tiles < cap ? n_tiles : cap)), dim3(kWaves * 64), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(wide_bwd_dw_kernel<16>, dim3((unsigned)n_partial * a.dw_parts), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+  }
   const size_t lds = sizeof(float) * (size_t)(HB * HB * 256);
   const int64_t n_tiles = ((N + 15) / 16 + kWaves * kG - 1) / (kWaves * kG);
   const int64_t cap = (int64_t)n_cus() * 2;

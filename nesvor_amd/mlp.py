@@ -359,13 +359,31 @@ def backward_raw(weights, biases, xa, xb, dy, saved, b_row0, k_b, S, dxb, need_d
 
 
 # ------------------------------------------------------------------------------------------------ wider / deeper networks
-WIDE_MAX_WIDTH, WIDE_MAX_HIDDEN = 128, 7  # nesvor_mlp_wide_t (csrc/mlp_wide.hip)
+WIDE_MAX_WIDTH, WIDE_MAX_HIDDEN = 256, 7  # nesvor_mlp_wide_t (csrc/mlp_wide.hip)
 N_PARTIAL_WIDE = 1024
+# Partial rows of the wide dW kernel.  Width <= 128 keeps N_PARTIAL_WIDE rows (0.4 GB at 128 x 7 hidden; results depend on the
+# row count, so it stays).  A row grows with width^2 - 1024 rows of a 256 x 7 network would be 1.7 GB - so above 128 the count is
+# the largest that keeps the buffer at or under WIDE_PARTIAL_BYTES, at most N_PARTIAL_WIDE.  The dW kernel fills the chip with two
+# workgroups per CU (what its registers let a CU hold: the launcher's target), and at these widths the library runs up to
+# WIDE_DW_MAX_PARTS workgroups per row (each takes every parts-th pass of the row's columns, csrc/mlp_wide.hip), so the count never
+# drops below 2 x CUs / WIDE_DW_MAX_PARTS: 128 on 256 CUs, where the largest shape the kernels take (256 x 7, 64 inputs, 16
+# outputs, biased: 1.66 MB per row) still gets 161 rows.
+WIDE_PARTIAL_BYTES = 256 << 20
+WIDE_DW_MAX_PARTS = 4  # kDwMaxParts (csrc/mlp_wide.hip)
+
+
+def wide_partial_rows(width: int, n_params: int, device) -> int:
+    """Rows of ``wide_backward_raw``'s partial buffer (= rows the caller sums): the rule next to ``WIDE_PARTIAL_BYTES``."""
+    if width <= 128:
+        return N_PARTIAL_WIDE
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    floor = -(-2 * cus // WIDE_DW_MAX_PARTS)
+    return max(floor, min(N_PARTIAL_WIDE, WIDE_PARTIAL_BYTES // (4 * n_params)))
 
 
 def wide_supported(seq) -> bool:
     """Linear/ReLU stacks (with or without biases) outside the 64-wide fused kernels but inside the hand-written wide kernels
-    (round 6): one hidden width <= 128, 1-7 hidden layers, <= 64 inputs, <= 16 outputs; and the bias-free ``tinycudann.Network``
+    (round 6; above 128 the chunked-image kernels): one hidden width <= 256, 1-7 hidden layers, <= 64 inputs, <= 16 outputs; and the bias-free ``tinycudann.Network``
     of such shapes."""
     from .tinycudann import Network
 
@@ -432,7 +450,7 @@ def wide_forward_raw(weights, biases, xa, xb, b_row0, k_b, S, need_saved):
 
 
 def wide_backward_raw(weights, biases, xa, xb, dy, saved, b_row0, k_b, S, dxb, need_dxa):
-    """-> (dxa (N, k_a) per sample | None, partial (N_PARTIAL_WIDE, n_params): sum over dim 0 = W0, b0, W1, b1, ... gradients)."""
+    """-> (dxa (N, k_a) per sample | None, partial (``wide_partial_rows``, n_params): sum over dim 0 = W0, b0, W1, b1, ... gradients)."""
     N = xb.shape[1]
     k_a = 0 if xa is None else xa.shape[1]
     d = _wide_desc(weights, biases, k_a, k_b, b_row0, S)
@@ -440,10 +458,11 @@ def wide_backward_raw(weights, biases, xa, xb, dy, saved, b_row0, k_b, S, dxb, n
     dpre = [torch.empty_like(s) for s in saved]
     dxa = torch.empty((N, k_a), dtype=torch.float32, device=xb.device) if (xa is not None and need_dxa) else None
     total = lib.nesvor_mlp_wide_param_count(ctypes.byref(d))
-    partial = torch.empty((N_PARTIAL_WIDE, total), dtype=torch.float32, device=xb.device)
+    n_partial = wide_partial_rows(d.width, total, xb.device)
+    partial = torch.empty((n_partial, total), dtype=torch.float32, device=xb.device)
     with torch.cuda.device(xb.device), _lib.kernel_timer.span("mlp_bwd"):
         err = lib.nesvor_mlp_wide_backward(ctypes.byref(d), _lib.ptr(xa), _lib.ptr(xb), _lib.ptr(dy), _ptr_array8(saved), _ptr_array8(dpre),
-                                           _lib.ptr(dxa), _lib.ptr(dxb), _lib.ptr(partial), N_PARTIAL_WIDE, N, _lib.stream_ptr())
+                                           _lib.ptr(dxa), _lib.ptr(dxb), _lib.ptr(partial), n_partial, N, _lib.stream_ptr())
     _lib.check(err, "wide mlp backward")
     return dxa, partial
 
@@ -505,9 +524,10 @@ def apply_net(net, xa, xb, b_row0: int, k_b: int, samples_per_pixel: int):
     feature-major xb] -> (out_dim, N) feature-major, differentiable.  Picks the evaluation:
 
     * Linear/ReLU stacks inside the fused kernels' shapes: ``fused_mlp`` (the dispatcher op);
-    * Linear/ReLU stacks up to width 128 / seven hidden layers (``--width`` > 64, ``--depth`` > 3: the reference accepts any,
-      cli/main.py:68-73): ``wide_mlp`` - hand-written fp32-MFMA kernels with one layer's weights in LDS at a time (round 6);
-    * anything beyond (other activations, width > 128): ``library_mlp`` - correct, but on library GEMMs;
+    * Linear/ReLU stacks up to width 256 / seven hidden layers (``--width`` > 64, ``--depth`` > 3: the reference accepts any,
+      cli/main.py:68-73): ``wide_mlp`` - hand-written fp32-MFMA kernels with one layer's weights in LDS at a time (round 6),
+      above width 128 one 32-row chunk of a layer at a time;
+    * anything beyond (other activations, width > 256): ``library_mlp`` - correct, but on library GEMMs;
     * the half-precision structure (``tinycudann.Network``): its row-major module interface - ``flat_network`` on the 16-bit
       operand kernels (1-3 hidden layers of width 64, <= 64 inputs; the backward as one fused launch where the wave-specialised
       kernel takes the shape, else as the 16-bit dX + dW launch pair), the wide kernels beyond."""
@@ -520,14 +540,14 @@ def apply_net(net, xa, xb, b_row0: int, k_b: int, samples_per_pixel: int):
         return net(x).t()
     if supported(net):
         return fused_mlp(net, xa, xb, b_row0, k_b, samples_per_pixel)
-    if wide_supported(net):  # width <= 128, up to seven hidden layers: the hand-written wide kernels (csrc/mlp_wide.hip)
+    if wide_supported(net):  # width <= 256, up to seven hidden layers: the hand-written wide kernels (csrc/mlp_wide.hip)
         return wide_mlp(net, xa, xb, b_row0, k_b, samples_per_pixel)
     key = tuple((type(m).__name__, getattr(m, "in_features", 0), getattr(m, "out_features", 0)) for m in net)
     if key not in _warned_library:
         _warned_library.add(key)
         import logging
 
-        logging.warning("MLP %s is outside the hand-written HIP kernels (ReLU; width <= 128, 1-7 hidden layers of one width, <= 64 "
+        logging.warning("MLP %s is outside the hand-written HIP kernels (ReLU; width <= 256, 1-7 hidden layers of one width, <= 64 "
                         "inputs, <= 16 outputs): its products run on library GEMMs - expect a several times slower iteration",
                         [k[1:] for k in key if k[0] == "Linear"])
     return library_mlp(net, xa, xb, b_row0, k_b, samples_per_pixel)

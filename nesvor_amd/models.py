@@ -13,8 +13,9 @@ Two execution paths share the parameters:
 * ``nesvor_amd.fused`` / ``nesvor_amd.direct`` — the autograd-free training step used by ``train()``.
 
 Networks outside the fused kernels' shapes (``--width`` > 64, ``--depth`` > 3, ...; the reference accepts
-any, cli/main.py:68-73) keep every other stage on the HIP kernels and evaluate their matrix products on
-library GEMMs (``nesvor_amd.mlp.apply_net``), with a warning about speed.
+any, cli/main.py:68-73) run on the hand-written wide kernels up to width 256 and seven hidden layers; beyond
+that they keep every other stage on the HIP kernels and evaluate their matrix products on library GEMMs
+(``nesvor_amd.mlp.apply_net``), with a warning about speed.
 """
 from argparse import Namespace
 from math import log2
@@ -67,8 +68,8 @@ def build_network(**config):
     if dtype != torch.float32:
         raise ValueError("unknown dtype")
     # any --width / --depth builds (cli/main.py:68-73): shapes the fused kernels cover (ReLU, width <= 64 - narrower
-    # ones zero-padded, exact -, 1-3 hidden layers, <= 64 inputs, <= 16 outputs) run on them, the rest on library GEMMs
-    # through nesvor_amd.mlp.apply_net, which says so once
+    # ones zero-padded, exact -, 1-3 hidden layers, <= 64 inputs, <= 16 outputs) run on them, wider / deeper ones (width <= 256,
+    # <= 7 hidden layers) on the wide kernels, the rest on library GEMMs through nesvor_amd.mlp.apply_net, which says so once
     act = None if config["activation"] == "None" else getattr(nn, config["activation"])
     out_act = None if config["output_activation"] == "None" else getattr(nn, config["output_activation"])
     dims = [config["n_input_dims"]] + [config["n_neurons"]] * config["n_hidden_layers"] + [config["n_output_dims"]]

@@ -414,7 +414,7 @@ _op("fused_mlp(Tensor? xa, Tensor xb, Tensor[] weights, Tensor[] biases, int b_r
     "bool save) -> (Tensor, Tensor[])", _mlp_forward, fake=_mlp_fake, backward=_mlp_backward_formula, setup_context=_mlp_setup)
 
 
-# ---- the same networks at width <= 128 / up to seven hidden layers (csrc/mlp_wide.hip); `biases` empty = bias-free
+# ---- the same networks at width <= 256 / up to seven hidden layers (csrc/mlp_wide.hip); `biases` empty = bias-free
 def _wide_forward(xa, xb, weights, biases, b_row0, k_b, samples_per_pixel, save):
     return _mlp.wide_forward_raw(list(weights), list(biases), xa, xb, b_row0, k_b, samples_per_pixel, save)
 
@@ -466,7 +466,7 @@ def _wide_backward_formula(ctx, dy, d_saved):
 def _wide_fake(xa, xb, weights, biases, b_row0, k_b, S, save):
     n = xb.shape[1]
     n_pad = (n + 15) // 16 * 16
-    hb = 4 if weights[0].shape[0] <= 64 else 8
+    hb = 4 if weights[0].shape[0] <= 64 else 8 if weights[0].shape[0] <= 128 else 16
     saved = [xb.new_empty(n_pad * 16 * hb) for _ in range(len(weights) - 1)] if save else []
     return xb.new_empty((weights[-1].shape[0], n)), saved
 

@@ -123,7 +123,7 @@ class Network(nn.Module):
             need = torch.is_grad_enabled() and (x.requires_grad or self.params.requires_grad)
             y, _ = torch.ops.nesvor.wide_mlp(None, x.to(torch.float32).t().contiguous(), ws, [], 0, x.shape[1], 1, need)
             return y[: self.n_output_dims].t()
-        # shapes outside both kernel families (other activations, more than 128 neurons): library GEMMs on the same flat
+        # shapes outside both kernel families (other activations, more than 256 neurons): library GEMMs on the same flat
         # parameters, fp32
         if not Network._warned:
             Network._warned = True
