@@ -250,6 +250,29 @@ int nesvor_hashgrid_backward_bounded(const nesvor_grid_t* grid, const float* u, 
                                      float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
                                      int level_begin, int level_end, const float* queue_scale, const float* dy_bound,
                                      void* stream);
+/* Hand-over from the forward to the backward of the SAME points.  The aggregation pass of the backward starts with work that
+ * depends on u alone: the order of every 256-point cloud by the Morton code of its finest-level cells, the cloud's bounding
+ * box, its lattice boxes and window bits per level and the schedule of its box rounds.  nesvor_hashgrid_forward_plan is
+ * nesvor_hashgrid_forward_bounded on clustered points (always the one-workgroup-per-cloud kernel, pe and pe_absmax bit-identical)
+ * that also writes
+ *   order:      nesvor_hashgrid_cloud_order_bytes(N) bytes - exactly the bytes the aggregation pass finds for itself;
+ *   cloud_plan: NULL, or nesvor_hashgrid_cloud_plan_bytes(grid, N) bytes, 16-byte aligned (n_features <= 2; 0 = no plan for this
+ *               grid) - one record per cloud, computed with the chunking of nesvor_hashgrid_backward_*(.., queue_scale).
+ * nesvor_hashgrid_backward_plan is nesvor_hashgrid_backward_bounded that takes them: with `order` (non-NULL) no launch sorts, any
+ * level range; with `cloud_plan` as well (all levels only) the set-up is read from the records.  Both are valid only for the u, N,
+ * grid and queue_scale levels' chunking they were written for; not with NESVOR_LAYOUT_UNCLUSTERED.  order == cloud_plan == NULL:
+ * nesvor_hashgrid_backward_bounded.  nesvor_hashgrid_backward_order_offset: where in `workspace` a backward WITHOUT a hand-over
+ * keeps the order it sorted (tests compare the two).
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.) */
+int64_t nesvor_hashgrid_cloud_order_bytes(int64_t N);
+int64_t nesvor_hashgrid_cloud_plan_bytes(const nesvor_grid_t* grid, int64_t N);
+int64_t nesvor_hashgrid_backward_order_offset(const nesvor_grid_t* grid, int64_t N, const float* queue_scale);
+int nesvor_hashgrid_forward_plan(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N, int layout,
+                                 float* pe_absmax, void* order, void* cloud_plan, const float* queue_scale, void* stream);
+int nesvor_hashgrid_backward_plan(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
+                                  float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
+                                  int level_begin, int level_end, const float* queue_scale, const float* dy_bound,
+                                  const void* order, const void* cloud_plan, void* stream);
 /* Same contract, tcnn-style per-corner global atomics (slow on MI355X: memory-side atomics). */
 int nesvor_hashgrid_backward_atomic(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
                                     float* grad_table, float* grad_u, int64_t N, int layout, void* stream);

@@ -153,6 +153,11 @@ _SIGNATURES = {
     "nesvor_hashgrid_backward_levels": ([POINTER(GridT), _P, _P, _P, _P, _P, c_int64, c_int, _P, c_int, c_int, c_int, _P, _P], c_int),
     "nesvor_hashgrid_backward_bounded": ([POINTER(GridT), _P, _P, _P, _P, _P, c_int64, c_int, _P, c_int, c_int, c_int, _P, _P, _P], c_int),
     "nesvor_hashgrid_backward_atomic": ([POINTER(GridT), _P, _P, _P, _P, _P, c_int64, c_int, _P], c_int),
+    "nesvor_hashgrid_cloud_order_bytes": ([c_int64], c_int64),
+    "nesvor_hashgrid_cloud_plan_bytes": ([POINTER(GridT), c_int64], c_int64),
+    "nesvor_hashgrid_backward_order_offset": ([POINTER(GridT), c_int64, _P], c_int64),
+    "nesvor_hashgrid_forward_plan": ([POINTER(GridT), _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P], c_int),
+    "nesvor_hashgrid_backward_plan": ([POINTER(GridT), _P, _P, _P, _P, _P, c_int64, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P], c_int),
     "nesvor_psf_transform_forward": ([_P] * 8 + [c_int, c_int, _P], c_int),
     "nesvor_psf_transform_backward": ([_P] * 9 + [c_int, c_int, _P], c_int),
     "nesvor_psf_transform_forward_rng_gather": ([_P] * 4 + [c_uint64, c_uint64] + [_P] * 3 + [c_int, c_int, _P, _P, c_int, _P], c_int),

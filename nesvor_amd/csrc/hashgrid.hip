@@ -159,6 +159,102 @@ __device__ __forceinline__ CellPos locate(const LevelParams& p, float ux, float 
   return c;
 }
 
+// Bitonic sort of one 32-bit key per thread over SPAN consecutive threads of a 256-thread workgroup (ascending).  The 26
+// exchanges at distance 1..8 are DPP moves, the 7 at distance 16 / 32 lane swaps (common.h::lane_xor_u32); only the 3
+// exchanges across waves go through LDS.  (Rounds 1-3 used __shfl_xor = ds_bpermute for all 33 in-wave exchanges: one
+// sort cost 0.03 ms of the pass, profiles/r01_ablate_hashgrid.log.)
+template <int K, int J>
+__device__ __forceinline__ void bitonic_merge(uint32_t& sv, int tid, uint32_t* sortbuf) {
+  uint32_t other;
+  if constexpr (J < 64) {
+    other = lane_xor_u32<J>(sv, tid & 63);
+  } else {
+    __syncthreads();
+    sortbuf[tid] = sv;
+    __syncthreads();
+    other = sortbuf[tid ^ J];
+  }
+  const bool keep_min = ((tid & K) == 0) == ((tid & J) == 0);
+  sv = keep_min ? min(sv, other) : max(sv, other);
+  if constexpr (J > 1) bitonic_merge<K, J / 2>(sv, tid, sortbuf);
+}
+template <int K>
+__device__ __forceinline__ void bitonic_sort(uint32_t& sv, int tid, uint32_t* sortbuf) {
+  if constexpr (K > 2) bitonic_sort<K / 2>(sv, tid, sortbuf);
+  bitonic_merge<K, K / 2>(sv, tid, sortbuf);
+}
+
+__device__ __forceinline__ uint32_t spread3(uint32_t x) {  // 8 bits -> every third bit
+  x &= 0xffu;
+  x = (x ^ (x << 8)) & 0x0300f00fu;
+  x = (x ^ (x << 4)) & 0x030c30c3u;
+  x = (x ^ (x << 2)) & 0x09249249u;
+  return x;
+}
+
+// Key of the cloud order: (Morton code of the sample's cell at the finest level << 8) | thread.  Lanes past N sort last.
+__device__ __forceinline__ uint32_t cloud_sort_key(const nesvor_grid_t& g, bool in_range, float ux, float uy, float uz, int tid) {
+  uint32_t code = 0x00ffffffu;
+  if (in_range) {
+    const LevelParams pf = load_level(g, g.n_levels - 1);
+    const CellPos c = locate(pf, ux, uy, uz);
+    code = spread3(c.gx) | (spread3(c.gy) << 1) | (spread3(c.gz) << 2);
+  }
+  return (code << 8) | (uint32_t)tid;
+}
+
+// Lattice box of a cloud at one level, from the cloud's bounding box [ulo, uhi] (locate() is monotone in u): first cell (x, y, z),
+// cells spanned - 1 (x, y, z; they wrap for out-of-range input), vertices of the box (0: it does not fit `max_slots`, or boxes
+// are off), largest slot a sample's first corner may take.  The per-cloud forward and the aggregation pass both call this.
+__device__ __forceinline__ void lattice_box(const LevelParams& p, const float (&ulo)[3], const float (&uhi)[3], bool boxes_on, uint32_t max_slots,
+                                            uint32_t (&b)[8]) {
+  const CellPos blo = locate(p, ulo[0], ulo[1], ulo[2]), bhi = locate(p, uhi[0], uhi[1], uhi[2]);
+  const uint32_t ex = bhi.gx - blo.gx, ey = bhi.gy - blo.gy, ez = bhi.gz - blo.gz;
+  const bool fits = boxes_on && ex < max_slots && ey < max_slots && ez < max_slots &&
+                    (uint64_t)(ex + 2u) * (ey + 2u) * (ez + 2u) <= (uint64_t)max_slots;
+  const uint32_t nx = ex + 2u, nxy = nx * (ey + 2u), vol = fits ? nxy * (ez + 2u) : 0u;
+  b[0] = blo.gx; b[1] = blo.gy; b[2] = blo.gz; b[3] = ex; b[4] = ey; b[5] = ez; b[6] = vol;
+  b[7] = fits ? vol - 2u - nx - nxy : 0u;  // = slot (inside the box) of the first corner of the box's last cell
+}
+// Address bits of the spatially addressed merge table (NESVOR_HG_SPATIAL), a | b << 8 | c << 16 for x, y, z: dealt one at a time
+// to the axis whose box extent per slot is the largest.
+__device__ __forceinline__ uint32_t window_bits(uint32_t ex, uint32_t ey, uint32_t ez, int log2_slots) {
+  const uint32_t vx = min(ex, 1023u) + 2u, vy = min(ey, 1023u) + 2u, vz = min(ez, 1023u) + 2u;
+  uint32_t ba = 0, bb = 0, bc = 0;
+  for (int n = 0; n < log2_slots; ++n) {
+    const uint32_t rx = (vx << 12) >> ba, ry = (vy << 12) >> bb, rz = (vz << 12) >> bc;
+    if (rz >= rx && rz >= ry) ++bc;
+    else if (ry >= rx) ++bb;
+    else ++ba;
+  }
+  return ba | (bb << 8) | (bc << 16);
+}
+
+// ---- what the aggregation pass of the backward (hashgrid_bwd_aggregate below) derives from the sample positions alone, and the
+// per-cloud forward can therefore hand to it
+#ifndef NESVOR_HG_SLOTS
+#define NESVOR_HG_SLOTS 1024      // merge-table slots at F <= 2.  A/B (gpurun_out/s2j2): 2048 slots at two workgroups per CU (66 KB of LDS) let levels
+                                  // 12-13 take the box path, and the pass goes from 0.346 to 0.505 ms: it lives on its four waves per SIMD
+#endif
+constexpr int kMaxChunks = 256;               // table chunks (queues) per level
+constexpr int kAggMaxGroup = 8;               // levels per box round of the aggregation pass
+template <int F> constexpr int agg_slots() { return F <= 2 ? NESVOR_HG_SLOTS : (F == 4 ? 512 : 256); }
+// Cloud plan: one record of plan_words(L) 32-bit words per workgroup (R = plan_rows(L) = L + 1 rounded up to a multiple of 4, so
+// that every array starts on a 16-byte boundary; 1152 bytes at L = 16):
+//   [0, 6)   bounding box of the cloud's samples (float bits: min x, y, z, max x, y, z)
+//   [6]      box_end (levels [0, box_end) address the merge table by box slot)        [7]  0
+//   [8, 8 + 8 R)   lbox[level][8] as lattice_box() returns it with agg_slots<F>() slots and the plan's box_slots switch
+//   then R words each: lwin[], slot_off[], bkt_off[], grp_end[], rnd_slots[], rnd_bkts[] - window_bits() and the
+//   RoundSchedule of levels [0, L) under agg_slots<F>() slots, kMaxChunks buckets, kAggMaxGroup levels per round and the
+//   backward plan's n_chunks[]; rows of levels >= L are zero.
+// Valid for the u, N, grid and chunking it was computed from.
+__host__ __device__ constexpr uint32_t plan_rows(int L) { return (uint32_t)(L + 4) & ~3u; }
+__host__ __device__ constexpr uint32_t plan_words(int L) { return 8u + 14u * plan_rows(L); }
+struct CloudPlanArgs {  // what the forward needs of the backward's BwdPlan to write the records
+  uint32_t n_chunks[NESVOR_MAX_LEVELS];
+  uint32_t box_slots;
+};
+
 template <int F>
 __device__ __forceinline__ void load_feat(const float* __restrict__ p, float (&v)[F]) {
   if constexpr (F == 1) {
@@ -339,7 +435,11 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
                                                           const float* __restrict__ table, float* __restrict__ pe, int64_t N,
                                                           float* __restrict__ pe_absmax,  // optional: raised to max |pe| (the density network's input bound)
                                                           const uint32_t* __restrict__ perm = nullptr, float* __restrict__ rows = nullptr,
-                                                          int level_begin = 0, int level_stop = NESVOR_MAX_LEVELS) {  // levels [level_begin, min(level_stop, L))
+                                                          int level_begin = 0, int level_stop = NESVOR_MAX_LEVELS,  // levels [level_begin, min(level_stop, L))
+                                                          // hand-over to the backward of the same points (both optional; perm == nullptr, F <= 2):
+                                                          uint8_t* __restrict__ order = nullptr,        // the cloud order hashgrid_bwd_aggregate writes with order_mode == 1
+                                                          uint32_t* __restrict__ cloud_plan = nullptr,  // one cloud plan record per workgroup (layout: plan_words())
+                                                          const CloudPlanArgs cpa = CloudPlanArgs{}) {
 #ifndef NESVOR_FWD_CLOUD_SLOTS
 #define NESVOR_FWD_CLOUD_SLOTS 512
 #endif
@@ -352,6 +452,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
   __shared__ uint32_t lpar[NESVOR_MAX_LEVELS + 1][4];   // res, size, offset, hashed
   __shared__ uint32_t slot_off[NESVOR_MAX_LEVELS + 1], grp_end[NESVOR_MAX_LEVELS + 1], rnd_slots[NESVOR_MAX_LEVELS + 1];
   __shared__ int32_t box_end_s;
+  __shared__ uint32_t sortbuf[256];
   const int tid = threadIdx.x, lane = tid & 63;
   const int64_t slot_i = (int64_t)blockIdx.x * 256 + tid;   // position in the processing order
   const bool valid = slot_i < N;
@@ -361,6 +462,13 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
   const int L = g.n_levels, E = L * F;
   const int lb = level_begin, le = min(level_stop, L);  // (uniform kernel arguments)
   const float ux = u[3 * ii], uy = u[3 * ii + 1], uz = u[3 * ii + 2];
+  if (order != nullptr) {  // (kernel argument: uniform)
+    // the backward's sort of the cloud, done here where the SIMDs have issue slots to spare; in a scope of its own, in front of
+    // the level rounds: its registers are dead before they start.  The forward itself keeps processing thread = sample.
+    uint32_t sv = cloud_sort_key(g, valid, ux, uy, uz, tid);
+    bitonic_sort<NESVOR_SORT_SPAN>(sv, tid, sortbuf);
+    order[(int64_t)blockIdx.x * 256 + tid] = (uint8_t)(sv & 255u);
+  }
   {
     float lo[3] = {ux, uy, uz}, hi[3] = {ux, uy, uz};
 #pragma unroll
@@ -383,13 +491,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
       // (per-lane index into the kernel arguments = vector loads from the kernarg segment: measured FASTER here than the uniform
       //  loop of scalar loads + selects that the aggregation pass uses - forward 71.8 -> 75.0 us with it)
       const LevelParams p = load_level(g, tid);
-      const CellPos blo = locate(p, ulo[0], ulo[1], ulo[2]), bhi = locate(p, uhi[0], uhi[1], uhi[2]);
-      const uint32_t ex = bhi.gx - blo.gx, ey = bhi.gy - blo.gy, ez = bhi.gz - blo.gz;
-      const bool fits = ex < (uint32_t)kSlots && ey < (uint32_t)kSlots && ez < (uint32_t)kSlots &&
-                        (uint64_t)(ex + 2u) * (ey + 2u) * (ez + 2u) <= (uint64_t)kSlots;
-      const uint32_t nx = ex + 2u, nxy = nx * (ey + 2u), vol = fits ? nxy * (ez + 2u) : 0u;
-      b[0] = blo.gx; b[1] = blo.gy; b[2] = blo.gz; b[3] = ex; b[4] = ey; b[5] = ez; b[6] = vol;
-      b[7] = fits ? vol - 2u - nx - nxy : 0u;
+      lattice_box(p, ulo, uhi, true, (uint32_t)kSlots, b);
       lpar[tid][0] = p.res; lpar[tid][1] = p.size; lpar[tid][2] = p.offset; lpar[tid][3] = p.hashed;
     }
     if (tid <= L) {
@@ -399,6 +501,42 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
     const RoundSchedule rs = round_schedule(b[6], 0u, lb, le, tid, (uint32_t)kSlots, 0xFFFFFFFFu, kMaxGroup);
     if (tid == 0) box_end_s = rs.box_end;
     if (tid < NESVOR_MAX_LEVELS) { slot_off[tid] = rs.slot_off; grp_end[tid] = rs.grp_end; rnd_slots[tid] = rs.rnd_slots; }
+  } else if (tid < 128 && cloud_plan != nullptr) {
+    // wave 1 (it only waits for wave 0 here): the same for the AGGREGATION pass of the backward - its slot count, its bucket limit,
+    // its chunking - written out as the cloud's plan record, lane = level
+    if constexpr (F <= 2) {
+      const int lv = tid - 64;
+      float ulo[3], uhi[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        ulo[d] = fminf(fminf(ubox[0][d], ubox[1][d]), fminf(ubox[2][d], ubox[3][d]));
+        uhi[d] = fmaxf(fmaxf(ubox[0][3 + d], ubox[1][3 + d]), fmaxf(ubox[2][3 + d], ubox[3][3 + d]));
+      }
+      constexpr uint32_t kAggSlots = (uint32_t)agg_slots<F>();
+      uint32_t b[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+      uint32_t win = 0u, nch = 0u;
+      if (lv < L) {
+        const LevelParams p = load_level(g, lv);
+        lattice_box(p, ulo, uhi, cpa.box_slots != 0u, kAggSlots, b);
+        win = window_bits(b[3], b[4], b[5], __builtin_ctz(kAggSlots));
+        nch = cpa.n_chunks[lv];
+      }
+      const RoundSchedule rs = round_schedule(b[6], nch, 0, L, lv, kAggSlots, (uint32_t)kMaxChunks, kAggMaxGroup);
+      const uint32_t R = plan_rows(L);
+      uint32_t* rec = cloud_plan + (size_t)blockIdx.x * plan_words(L);
+      if (lv == 0) {
+        uint4* h = reinterpret_cast<uint4*>(rec);
+        h[0] = make_uint4(__float_as_uint(ulo[0]), __float_as_uint(ulo[1]), __float_as_uint(ulo[2]), __float_as_uint(uhi[0]));
+        h[1] = make_uint4(__float_as_uint(uhi[1]), __float_as_uint(uhi[2]), (uint32_t)rs.box_end, 0u);
+      }
+      if ((uint32_t)lv < R) {
+        uint4* bx = reinterpret_cast<uint4*>(rec + 8 + 8 * lv);
+        bx[0] = make_uint4(b[0], b[1], b[2], b[3]);
+        bx[1] = make_uint4(b[4], b[5], b[6], b[7]);
+        uint32_t* a = rec + 8 + 8 * R + lv;
+        a[0] = win; a[R] = rs.slot_off; a[2 * R] = rs.bkt_off; a[3 * R] = rs.grp_end; a[4 * R] = rs.rnd_slots; a[5 * R] = rs.rnd_bkts;
+      }
+    }
   }
   __syncthreads();
   const int box_end = __builtin_amdgcn_readfirstlane(box_end_s);
@@ -651,7 +789,6 @@ __global__ __launch_bounds__(256) void hashgrid_bwd(const nesvor_grid_t g, const
 }
 
 // ------------------------------------------- backward, owner-computes version
-constexpr int kMaxChunks = 256;               // table chunks (queues) per level
 constexpr int kSubQueues = 8;                 // every queue is split by the XCC the producing workgroup runs on (see below); plan.n_sub <= 8 are used
 constexpr uint32_t kTailStride = 4096;        // counters per sub-queue set (>= kMaxChunks * NESVOR_MAX_LEVELS)
 constexpr uint32_t kOverflowBase = kTailStride - NESVOR_MAX_LEVELS;  // last words of counter set 0: records per level that found their queue full
@@ -674,39 +811,6 @@ struct BwdPlan {
 // (further per-launch inputs of the aggregation pass travel as separate kernel arguments: growing this struct moved the
 //  compiler's per-level reads of it - plan.shift[level], plan.cap[level] ... - from scalar loads to per-lane global loads,
 //  which cost the uniform-points case a factor of three)
-
-// Bitonic sort of one 32-bit key per thread over SPAN consecutive threads of a 256-thread workgroup (ascending).  The 26
-// exchanges at distance 1..8 are DPP moves, the 7 at distance 16 / 32 lane swaps (common.h::lane_xor_u32); only the 3
-// exchanges across waves go through LDS.  (Rounds 1-3 used __shfl_xor = ds_bpermute for all 33 in-wave exchanges: one
-// sort cost 0.03 ms of the pass, profiles/r01_ablate_hashgrid.log.)
-template <int K, int J>
-__device__ __forceinline__ void bitonic_merge(uint32_t& sv, int tid, uint32_t* sortbuf) {
-  uint32_t other;
-  if constexpr (J < 64) {
-    other = lane_xor_u32<J>(sv, tid & 63);
-  } else {
-    __syncthreads();
-    sortbuf[tid] = sv;
-    __syncthreads();
-    other = sortbuf[tid ^ J];
-  }
-  const bool keep_min = ((tid & K) == 0) == ((tid & J) == 0);
-  sv = keep_min ? min(sv, other) : max(sv, other);
-  if constexpr (J > 1) bitonic_merge<K, J / 2>(sv, tid, sortbuf);
-}
-template <int K>
-__device__ __forceinline__ void bitonic_sort(uint32_t& sv, int tid, uint32_t* sortbuf) {
-  if constexpr (K > 2) bitonic_sort<K / 2>(sv, tid, sortbuf);
-  bitonic_merge<K, K / 2>(sv, tid, sortbuf);
-}
-
-__device__ __forceinline__ uint32_t spread3(uint32_t x) {  // 8 bits -> every third bit
-  x &= 0xffu;
-  x = (x ^ (x << 8)) & 0x0300f00fu;
-  x = (x ^ (x << 4)) & 0x030c30c3u;
-  x = (x ^ (x << 2)) & 0x09249249u;
-  return x;
-}
 
 // Phase 1 of the backward.  One workgroup = 256 consecutive samples (one PSF cloud).
 //  * once per workgroup: bitonic-sort the samples by the Morton code of their finest-level cell, so
@@ -769,10 +873,6 @@ __device__ __forceinline__ float from_fixed(unsigned long long q) {
 // BOUND: max |dy| comes from the caller (`dy_bound`) and the pass over dy that determines it is compiled out.  A template
 // parameter, not a run-time branch: with the branch in place the compiler restructured the pass it guards, and the kernel
 // WITHOUT a bound ran 3x slower on uniform points (4.9 vs 1.6 ms) and 4 % slower on PSF clouds (tools/hg_variants.py).
-#ifndef NESVOR_HG_SLOTS
-#define NESVOR_HG_SLOTS 1024      // merge-table slots at F <= 2.  A/B (gpurun_out/s2j2): 2048 slots at two workgroups per CU (66 KB of LDS) let levels
-                                  // 12-13 take the box path, and the pass goes from 0.346 to 0.505 ms: it lives on its four waves per SIMD
-#endif
 #ifndef NESVOR_HG_MINBLOCKS
 #define NESVOR_HG_MINBLOCKS 4
 #endif
@@ -803,7 +903,10 @@ __device__ unsigned long long g_hg_timeline[kTlWgs][kTlMarks];
 #else
 #define HG_TICK(site) do { } while (0)
 #endif
-template <int F, int LAYOUT, bool INPUT_GRAD, bool MERGE, bool BOUND = false>
+// PLAN: the cloud's order comes from `order` and its bounding box, lattice boxes, window bits and round schedule from its record
+// in `cloud_plan` - both written by hashgrid_fwd_cloud for the same u, N, grid and chunking, all levels in one launch.  A template
+// parameter like BOUND, for the same reason.
+template <int F, int LAYOUT, bool INPUT_GRAD, bool MERGE, bool BOUND = false, bool PLAN = false>
 __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2)) void hashgrid_bwd_aggregate(const nesvor_grid_t g, const BwdPlan plan,
                                                               const float* __restrict__ u,
                                                               const float* __restrict__ table,
@@ -816,7 +919,9 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
                                                               uint8_t* __restrict__ order,         // one byte per sample: the Morton-sorted order of every workgroup's samples
                                                               int order_mode,                      // 1: sort and write `order` (first launch of a backward), 2: read it (later launches of a split backward)
                                                               const uint32_t* __restrict__ perm,   // null, or the points in lattice-cell order (unclustered input: sort_points below): workgroup w takes points perm[256 w ..]
-                                                              int dy_by_slot) {                    // 1: dpe is already in that order (row r = point perm[r]): gather_dy_rows_kernel
+                                                              int dy_by_slot,                      // 1: dpe is already in that order (row r = point perm[r]): gather_dy_rows_kernel
+                                                              const uint32_t* __restrict__ cloud_plan = nullptr) {  // PLAN: the forward's records (plan_words())
+  static_assert(!PLAN || (MERGE && F <= 2), "the cloud plan exists for the merging pass at F <= 2");
   // the queue tails of the NEXT backward (the other of the workspace's two tail regions) are zero-filled here, so that
   // no launch of its own is needed for it
   for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < (uint32_t)kSubQueues * kTailStride; t += gridDim.x * 256u) tails_next[t] = 0u;
@@ -832,10 +937,10 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
   __shared__ uint32_t sortbuf[256];
   // workgroup-wide merge table: slots addressed by position in the lattice box (box rounds; tkeys then holds
   // level << 27 | entry index of every slot) or by open addressing keyed by the level-local entry index
-  constexpr int kSlots = F <= 2 ? NESVOR_HG_SLOTS : (F == 4 ? 512 : 256);
+  constexpr int kSlots = agg_slots<F>();
   constexpr uint32_t kEmpty = 0xFFFFFFFFu;
   constexpr uint32_t kKeyMask = (1u << 27) - 1u;
-  constexpr int kMaxGroup = 8;  // levels per box round
+  constexpr int kMaxGroup = kAggMaxGroup;  // levels per box round
   __shared__ __attribute__((aligned(16))) uint32_t tkeys[kSlots];
   // slot values are 64-bit fixed point: integer LDS atomics are returnless and resolve same-address lanes in
   // hardware (ds_add_f32 retires ~3 cycles per lane on gfx950, a compare-and-swap loop pays a round trip per
@@ -890,18 +995,17 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
 
   // ---- sort the workgroup's samples by Morton code of the finest-level cell
   uint32_t sv;
-  {
+  if constexpr (PLAN) sv = (uint32_t)order[base + tid];
+  else {
     const int64_t s0_ = base + tid;
-    uint32_t code = 0x00ffffffu;
+    float kx = 0.f, ky = 0.f, kz = 0.f;
     if (s0_ < N) {
       const int64_t i0 = perm != nullptr ? (int64_t)perm[s0_] : s0_;
-      const LevelParams pf = load_level(g, g.n_levels - 1);
-      const CellPos c = locate(pf, u[3 * i0], u[3 * i0 + 1], u[3 * i0 + 2]);
-      code = spread3(c.gx) | (spread3(c.gy) << 1) | (spread3(c.gz) << 2);
+      kx = u[3 * i0]; ky = u[3 * i0 + 1]; kz = u[3 * i0 + 2];
     }
-    sv = (code << 8) | (uint32_t)tid;
+    sv = cloud_sort_key(g, s0_ < N, kx, ky, kz, tid);
     // a later launch of a split backward (data parallel: coarse levels after the fine ones) re-uses the order the first
-    // launch found - same samples, same key
+    // launch found - same samples, same key - and so does a backward behind a forward that wrote it
     if (order_mode == 2) sv = (uint32_t)order[base + tid];
     else
 #pragma unroll 1
@@ -936,10 +1040,12 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     // bounding box of the workgroup's samples: locate() is monotone in u, so the lattice box of every level follows
     // from these six numbers
     float lo[3] = {ux, uy, uz}, hi[3] = {ux, uy, uz};
+    if constexpr (!PLAN) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      lo[d] = -wave_max_f32_dpp(-lo[d]);
-      hi[d] = wave_max_f32_dpp(hi[d]);
+      for (int d = 0; d < 3; ++d) {
+        lo[d] = -wave_max_f32_dpp(-lo[d]);
+        hi[d] = wave_max_f32_dpp(hi[d]);
+      }
     }
     // ONE fixed-point scale for the whole launch of this workgroup: max |dy| over its samples and all levels (eight
     // levels' loads in flight at a time).  The adds of one slot sum to at most 256 max|dy| (corner weights of a sample
@@ -980,8 +1086,10 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     }
     m = wave_max_f32_dpp(m);
     if (lane == 0) {
+      if constexpr (!PLAN) {
 #pragma unroll
-      for (int d = 0; d < 3; ++d) { ubox[tid >> 6][d] = lo[d]; ubox[tid >> 6][3 + d] = hi[d]; }
+        for (int d = 0; d < 3; ++d) { ubox[tid >> 6][d] = lo[d]; ubox[tid >> 6][3 + d] = hi[d]; }
+      }
       gmax[tid >> 6] = m;
     }
   }
@@ -990,12 +1098,14 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
   float ulo[3] = {0.f, 0.f, 0.f}, uhi[3] = {0.f, 0.f, 0.f};
   float fscale = 1.f, finv = 1.f;
   if constexpr (MERGE) {
+    if constexpr (!PLAN) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      ulo[d] = fminf(fminf(ubox[0][d], ubox[1][d]), fminf(ubox[2][d], ubox[3][d]));
-      uhi[d] = fmaxf(fmaxf(ubox[0][3 + d], ubox[1][3 + d]), fmaxf(ubox[2][3 + d], ubox[3][3 + d]));
-      ulo[d] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ulo[d])));
-      uhi[d] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, uhi[d])));
+      for (int d = 0; d < 3; ++d) {
+        ulo[d] = fminf(fminf(ubox[0][d], ubox[1][d]), fminf(ubox[2][d], ubox[3][d]));
+        uhi[d] = fmaxf(fmaxf(ubox[0][3 + d], ubox[1][3 + d]), fmaxf(ubox[2][3 + d], ubox[3][3 + d]));
+        ulo[d] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ulo[d])));
+        uhi[d] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, uhi[d])));
+      }
     }
     {
       float mx = 256.f * fmaxf(fmaxf(gmax[0], gmax[1]), fmaxf(gmax[2], gmax[3]));
@@ -1009,47 +1119,57 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     // the lattice boxes of all levels at once (wave 0, lane l: level l) instead of two locate() per level in every
     // thread, and the round schedule from them (uniform loop over the levels, v_readlane picks a level's numbers)
     HG_TICK(6);  // box of the samples, fixed-point scale (all threads)
-    if (tid < 64) {
+    // per level, for code that indexes levels per lane: the grid's and the plan's numbers (lane = level; the queue capacities can
+    // change from launch to launch, so they never come from the forward's record)
+    auto fill_lpar = [&](int lv, const LevelParams& p) __attribute__((always_inline)) {
+      lpar[lv][0] = p.res; lpar[lv][1] = p.size; lpar[lv][2] = p.offset; lpar[lv][3] = p.hashed;
+      lpar[lv][4] = plan.cap[lv]; lpar[lv][5] = plan.bucket_base[lv]; lpar[lv][6] = (uint32_t)plan.rec_off[lv];
+      lpar[lv][7] = plan.shift[lv];
+      if constexpr (kPerLevel) {
+        // a slot sums at most 256 values of at most max |dy| each: mapped below 2^30
+        const float mxl = 256.f * __uint_as_float(lmax_bits[lv]);
+        int se = 29 - ((int)((__float_as_uint(mxl) >> 23) & 0xFFu) - 127);
+        se = se > 100 ? 100 : (se < -100 ? -100 : se);
+        lscale[lv][0] = __uint_as_float((uint32_t)(se + 127) << 23);
+        lscale[lv][1] = __uint_as_float((uint32_t)(127 - se) << 23);
+      }
+    };
+    if constexpr (PLAN) {
+      // the cloud's record, 16 bytes per thread from the last thread down (wave 0 fills lpar meanwhile); every array of the record
+      // starts on a 16-byte boundary and has R >= L + 1 rows
+      const uint32_t R = plan_rows(g.n_levels), nq = plan_words(g.n_levels) / 4u, q = 255u - (uint32_t)tid;
+      if (q < nq) {
+        const uint4 w4 = reinterpret_cast<const uint4*>(cloud_plan)[(size_t)blockIdx.x * nq + q];
+        const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+        if (q < 2u) {
+          if (q == 1u) box_end_s = (int32_t)w[2];
+        } else if (q < 2u + 2u * R) {
+          uint32_t* dst = &lbox[0][0] + (q - 2u) * 4u;
+          if ((q - 2u) * 4u < (uint32_t)(NESVOR_MAX_LEVELS + 1) * 8u) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[k] = w[k];
+          }
+        } else {
+          const uint32_t qa = q - 2u - 2u * R, a = qa / (R / 4u), r0 = (qa - a * (R / 4u)) * 4u;
+          uint32_t* dst = a == 0u ? lwin : (a == 1u ? slot_off : (a == 2u ? bkt_off : (a == 3u ? grp_end : (a == 4u ? rnd_slots : rnd_bkts))));
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (r0 + k <= (uint32_t)NESVOR_MAX_LEVELS) dst[r0 + k] = w[k];
+        }
+      }
+      if (tid < g.n_levels) fill_lpar(tid, load_level(g, tid));
+    } else if (tid < 64) {
       uint32_t b[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
       uint32_t nch = 0u;
       // (lane = level: per-lane reads of the kernel arguments are vector loads from the kernarg segment - measured faster here than a
       //  uniform loop of scalar loads with selects: 26 against 93 timeline units)
-      const LevelParams p = load_level(g, tid < g.n_levels ? tid : 0);
       const int tl_ = tid < g.n_levels ? tid : 0;
-      const uint32_t pl_nch = plan.n_chunks[tl_], pl_cap = plan.cap[tl_], pl_base = plan.bucket_base[tl_], pl_rec = (uint32_t)plan.rec_off[tl_],
-                     pl_shift = plan.shift[tl_];
+      const LevelParams p = load_level(g, tl_);
       if (tid < g.n_levels) {
-        const CellPos blo = locate(p, ulo[0], ulo[1], ulo[2]), bhi = locate(p, uhi[0], uhi[1], uhi[2]);
-        const uint32_t ex = bhi.gx - blo.gx, ey = bhi.gy - blo.gy, ez = bhi.gz - blo.gz;  // cells spanned - 1 (wrap if out of range)
-        const bool fits = plan.box_slots != 0u && ex < (uint32_t)kSlots && ey < (uint32_t)kSlots && ez < (uint32_t)kSlots &&
-                          (uint64_t)(ex + 2u) * (ey + 2u) * (ez + 2u) <= (uint64_t)kSlots;
-        const uint32_t nx = ex + 2u, nxy = nx * (ey + 2u), vol = fits ? nxy * (ez + 2u) : 0u;
-        b[0] = blo.gx; b[1] = blo.gy; b[2] = blo.gz; b[3] = ex; b[4] = ey; b[5] = ez; b[6] = vol;
-        b[7] = fits ? vol - 2u - nx - nxy : 0u;  // = slot (inside the box) of the first corner of the box's last cell
-        {
-          // address bits of the spatially addressed table: one at a time to the axis whose box extent per slot is the largest
-          const uint32_t vx = min(ex, 1023u) + 2u, vy = min(ey, 1023u) + 2u, vz = min(ez, 1023u) + 2u;
-          uint32_t ba = 0, bb = 0, bc = 0;
-          for (int n = 0; n < __builtin_ctz(kSlots); ++n) {
-            const uint32_t rx = (vx << 12) >> ba, ry = (vy << 12) >> bb, rz = (vz << 12) >> bc;
-            if (rz >= rx && rz >= ry) ++bc;
-            else if (ry >= rx) ++bb;
-            else ++ba;
-          }
-          lwin[tid] = ba | (bb << 8) | (bc << 16);
-        }
-        nch = pl_nch;
-        lpar[tid][0] = p.res; lpar[tid][1] = p.size; lpar[tid][2] = p.offset; lpar[tid][3] = p.hashed;
-        lpar[tid][4] = pl_cap; lpar[tid][5] = pl_base; lpar[tid][6] = pl_rec;
-        lpar[tid][7] = pl_shift;
-        if constexpr (kPerLevel) {
-          // a slot sums at most 256 values of at most max |dy| each: mapped below 2^30
-          const float mxl = 256.f * __uint_as_float(lmax_bits[tid]);
-          int se = 29 - ((int)((__float_as_uint(mxl) >> 23) & 0xFFu) - 127);
-          se = se > 100 ? 100 : (se < -100 ? -100 : se);
-          lscale[tid][0] = __uint_as_float((uint32_t)(se + 127) << 23);
-          lscale[tid][1] = __uint_as_float((uint32_t)(127 - se) << 23);
-        }
+        lattice_box(p, ulo, uhi, plan.box_slots != 0u, (uint32_t)kSlots, b);
+        lwin[tid] = window_bits(b[3], b[4], b[5], __builtin_ctz(kSlots));
+        nch = plan.n_chunks[tl_];
+        fill_lpar(tid, p);
       }
       HG_TICK(7);  // per-level boxes, window bits, lpar (lane = level)
       if (tid <= g.n_levels) {
@@ -2262,14 +2382,18 @@ inline int sort_points(const float* u, int64_t N, uint32_t* base, hipStream_t st
 template <int F, int LAYOUT>
 int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table, const float* dpe, float* gt,
                      float* gu, int64_t N, void* workspace, int stages, int level_begin, int level_end, const float* queue_scale,
-                     const float* dy_bound, const OwnerAdam* adam, hipStream_t st, int hints = 0) {
+                     const float* dy_bound, const OwnerAdam* adam, hipStream_t st, int hints = 0,
+                     const uint8_t* fwd_order = nullptr, const uint32_t* cloud_plan = nullptr) {  // the forward's hand-over (nesvor_hashgrid_forward_plan)
   const bool unclustered = (hints & NESVOR_LAYOUT_UNCLUSTERED) != 0;
+  // the forward's order is the order of the points as given; its plan covers all levels at F <= 2
+  if ((fwd_order != nullptr || cloud_plan != nullptr) && unclustered) return (int)hipErrorInvalidValue;
+  if (cloud_plan != nullptr && (fwd_order == nullptr || F > 2 || level_begin != 0 || level_end != g->n_levels)) return (int)hipErrorInvalidValue;
   if constexpr (LAYOUT == NESVOR_LAYOUT_FEATURE_MAJOR) {
     // unclustered feature-major dpe with room for its re-ordered copy (NESVOR_LAYOUT_DY_SCRATCH: the workspace was sized by
     // nesvor_hashgrid_backward_workspace_bytes_ex with the same layout): the aggregation pass runs in its row-major form on the copy
     if (unclustered && (hints & NESVOR_LAYOUT_DY_SCRATCH) && (stages & 1))
       return launch_bwd_owner<F, NESVOR_LAYOUT_ROW_MAJOR>(g, u, table, dpe, gt, gu, N, workspace, stages, level_begin, level_end, queue_scale,
-                                                          dy_bound, adam, st, hints | 0x10000);
+                                                          dy_bound, adam, st, hints | 0x10000, fwd_order, cloud_plan);
   }
   BwdPlan plan;
   uint64_t n_rec;
@@ -2281,17 +2405,18 @@ int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table,
   uint32_t* tails = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + (par ? kTailBytes : 0));
   uint32_t* tails_next = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + (par ? 0 : kTailBytes));
   uint32_t* records = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + kHeadBytes);
-  uint8_t* order = reinterpret_cast<uint8_t*>(records) + n_rec * (1 + F) * sizeof(uint32_t);  // ceil(N / 256) * 256 bytes
-  const int order_mode = (stages & 4) ? 2 : 1;
+  uint8_t* const own_order = reinterpret_cast<uint8_t*>(records) + n_rec * (1 + F) * sizeof(uint32_t);  // ceil(N / 256) * 256 bytes
+  uint8_t* const order = fwd_order != nullptr ? const_cast<uint8_t*>(fwd_order) : own_order;  // (only read in mode 2)
+  const int order_mode = (fwd_order != nullptr || (stages & 4)) ? 2 : 1;
   // unclustered input: the points in cell order (a later launch of a split backward finds the first launch's order in place)
   // (256-byte aligned in absolute terms: the records in front have any multiple of 4 bytes; the size query leaves the slack)
-  uint32_t* const perm_buf = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(order) + (uintptr_t)((N + 255) / 256) * 256 + 255) & ~(uintptr_t)255);
+  uint32_t* const perm_buf = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(own_order) + (uintptr_t)((N + 255) / 256) * 256 + 255) & ~(uintptr_t)255);
   const uint32_t* const perm = unclustered ? perm_buf : nullptr;
   dim3 grid((unsigned)((N + 255) / 256)), block(256);
   hipError_t e;
   int dy_by_slot = 0;
   if (!(stages & 1)) goto owner_stage;
-  if (unclustered && order_mode == 1) {
+  if (unclustered && !(stages & 4)) {
     const int se = sort_points(u, N, perm_buf, st);
     if (se) return se;
   }
@@ -2299,7 +2424,7 @@ int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table,
     const int E = g->n_levels * F;
     float* rows = reinterpret_cast<float*>(reinterpret_cast<char*>(perm_buf) + ((sort_bytes(N) + 255) & ~(uint64_t)255));
     // (a later launch of a split backward finds the first launch's copy in place)
-    if (order_mode == 1) {
+    if (!(stages & 4)) {
       const size_t lds = sizeof(float) * kGatherPts * (E + 1);
       if (lds > 48 * 1024) {
         static std::mutex mu;
@@ -2322,8 +2447,21 @@ int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table,
 #define NESVOR_LAUNCH_AGG(IG, MG, BD)                                                                                     \
     hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, IG, MG, BD>), grid, block, 0, st, *g, plan, u, table, dpe, gt, gu, \
                        tails, tails_next, records, N, dy_bound, order, order_mode, perm, dy_by_slot)
+#define NESVOR_LAUNCH_AGG_PLAN(IG, BD)                                                                                      \
+    hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, IG, true, BD, true>), grid, block, 0, st, *g, plan, u, table, dpe, gt, gu, \
+                       tails, tails_next, records, N, dy_bound, order, order_mode, perm, dy_by_slot, cloud_plan)
     const bool bounded = dy_bound != nullptr && merge;  // (the bound only scales the merge table's fixed-point sums)
-    if (gu != nullptr) { if (bounded) NESVOR_LAUNCH_AGG(true, true, true); else if (merge) NESVOR_LAUNCH_AGG(true, true, false); else NESVOR_LAUNCH_AGG(true, false, false); }
+    bool planned = false;
+    if constexpr (F <= 2) {
+      if (cloud_plan != nullptr && merge) {  // (without merging there are no boxes and no rounds: the order alone is used)
+        planned = true;
+        if (gu != nullptr) { if (bounded) NESVOR_LAUNCH_AGG_PLAN(true, true); else NESVOR_LAUNCH_AGG_PLAN(true, false); }
+        else { if (bounded) NESVOR_LAUNCH_AGG_PLAN(false, true); else NESVOR_LAUNCH_AGG_PLAN(false, false); }
+      }
+    }
+#undef NESVOR_LAUNCH_AGG_PLAN
+    if (planned) { }
+    else if (gu != nullptr) { if (bounded) NESVOR_LAUNCH_AGG(true, true, true); else if (merge) NESVOR_LAUNCH_AGG(true, true, false); else NESVOR_LAUNCH_AGG(true, false, false); }
     else { if (bounded) NESVOR_LAUNCH_AGG(false, true, true); else if (merge) NESVOR_LAUNCH_AGG(false, true, false); else NESVOR_LAUNCH_AGG(false, false, false); }
 #undef NESVOR_LAUNCH_AGG
   }
@@ -2411,6 +2549,24 @@ int launch_fwd(const nesvor_grid_t* g, const float* u, const float* table, float
   }
   dim3 grid((unsigned)((N + 255) / 256), g->n_levels), block(256);
   hipLaunchKernelGGL((hashgrid_fwd<F, LAYOUT>), grid, block, 0, st, *g, u, table, pe, N, mode == 1 ? 1 : 0, pe_absmax);
+  return (int)hipGetLastError();
+}
+
+// The per-cloud forward on the points as given, writing the backward's cloud order and (cloud_plan != nullptr) plan records.
+template <int F, int LAYOUT>
+int launch_fwd_plan(const nesvor_grid_t* g, const float* u, const float* table, float* pe, int64_t N, float* pe_absmax, uint8_t* order,
+                    uint32_t* cloud_plan, const float* queue_scale, hipStream_t st) {
+  CloudPlanArgs cpa{};
+  if (cloud_plan != nullptr) {
+    if (F > 2) return (int)hipErrorInvalidValue;
+    BwdPlan plan;
+    uint64_t n_rec;
+    if (!make_plan(g, N, &plan, &n_rec, queue_scale)) return (int)hipErrorInvalidValue;
+    for (int l = 0; l < NESVOR_MAX_LEVELS; ++l) cpa.n_chunks[l] = plan.n_chunks[l];
+    cpa.box_slots = plan.box_slots;
+  }
+  hipLaunchKernelGGL((hashgrid_fwd_cloud<F, LAYOUT>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, *g, u, table, pe, N, pe_absmax,
+                     (const uint32_t*)nullptr, (float*)nullptr, 0, NESVOR_MAX_LEVELS, order, cloud_plan, cpa);
   return (int)hipGetLastError();
 }
 
@@ -2559,6 +2715,47 @@ extern "C" int nesvor_hashgrid_backward_bounded(const nesvor_grid_t* grid, const
   layout &= NESVOR_LAYOUT_MASK;
   DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages, level_begin, level_end,
                     queue_scale, dy_bound, nullptr, (hipStream_t)stream, hints);
+}
+
+extern "C" int64_t nesvor_hashgrid_cloud_order_bytes(int64_t N) { return N <= 0 ? 0 : (N + 255) / 256 * 256; }
+
+extern "C" int64_t nesvor_hashgrid_cloud_plan_bytes(const nesvor_grid_t* grid, int64_t N) {
+  if (grid == nullptr || N <= 0 || grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS || grid->n_features > 2) return 0;
+  return (N + 255) / 256 * (int64_t)plan_words(grid->n_levels) * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int64_t nesvor_hashgrid_backward_order_offset(const nesvor_grid_t* grid, int64_t N, const float* queue_scale) {
+  BwdPlan plan;
+  uint64_t n_rec;
+  if (grid == nullptr || N <= 0 || grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return -1;
+  if (!make_plan(grid, N, &plan, &n_rec, queue_scale)) return -1;
+  return (int64_t)(kHeadBytes + n_rec * (1 + grid->n_features) * sizeof(uint32_t));
+}
+
+extern "C" int nesvor_hashgrid_forward_plan(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N, int layout,
+                                            float* pe_absmax, void* order, void* cloud_plan, const float* queue_scale, void* stream) {
+  if (N <= 0) return 0;
+  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
+  if (order == nullptr || (reinterpret_cast<uintptr_t>(cloud_plan) & 15u) != 0) return (int)hipErrorInvalidValue;
+  layout &= NESVOR_LAYOUT_MASK;
+  DISPATCH_F_LAYOUT(launch_fwd_plan, grid, u, table, pe, N, pe_absmax, static_cast<uint8_t*>(order), static_cast<uint32_t*>(cloud_plan),
+                    queue_scale, (hipStream_t)stream);
+}
+
+extern "C" int nesvor_hashgrid_backward_plan(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
+                                             float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
+                                             int level_begin, int level_end, const float* queue_scale, const float* dy_bound,
+                                             const void* order, const void* cloud_plan, void* stream) {
+  if (N <= 0) return 0;
+  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
+  if (workspace == nullptr || (stages & 3) == 0) return (int)hipErrorInvalidValue;
+  if (level_begin < 0 || level_end > grid->n_levels || level_begin >= level_end) return (int)hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(cloud_plan) & 15u) != 0) return (int)hipErrorInvalidValue;
+  const int hints = layout & (NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH);
+  layout &= NESVOR_LAYOUT_MASK;
+  DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages, level_begin, level_end,
+                    queue_scale, dy_bound, nullptr, (hipStream_t)stream, hints, static_cast<const uint8_t*>(order),
+                    static_cast<const uint32_t*>(cloud_plan));
 }
 
 extern "C" int nesvor_hashgrid_backward_adamw(const nesvor_grid_t* grid, const float* u, float* table, const float* dpe,

@@ -33,6 +33,11 @@ struct StepCtx {
   // takes the weight norms and copied - not rebuilt - by the workgroups of the four MLP launches.  One allocation, owned here.
   void* wimg = nullptr;
   size_t wimg_stride = 0;
+  // Hand-over from the hash-grid forward to the aggregation pass of the backward of the same run (nesvor_hashgrid_forward_plan):
+  // the order of every cloud's samples and the clouds' plan records, sized for handover_points points.  Owned here.
+  void* hg_order = nullptr;
+  void* hg_plan = nullptr;
+  int64_t handover_points = 0;
   bool pending_join = false;  // a table update of the previous run is still on the side stream (NESVOR_STEP_DEFER_JOIN)
   // Staged bias-field step (NESVOR_STEP_BIAS_SUM_STOP / _RESUME): ranks the share of the global mean divides by, the event behind the
   // host's all-reduce of it (consumed by the next RESUME call), the arrival counter of mean_share_kernel
@@ -169,6 +174,21 @@ bool bias_free_refused(const nesvor_step_t& d) {  // any network the step runs
   return bias_free_refused(d.density) || (d.has_lv && bias_free_refused(d.sigma)) || (d.has_b && bias_free_refused(d.bias_net));
 }
 
+// (Re-)allocates the hand-over buffers for d.B x d.S points.  Without them (no memory, unclustered batches) the backward finds
+// order and plan itself as before.
+void size_handover(StepCtx* c) {
+  const nesvor_step_t& d = c->d;
+  const int64_t N = (int64_t)d.B * d.S;
+  if (d.S < 128 || N <= 0 || N == c->handover_points) return;
+  if (c->hg_order != nullptr) (void)hipFree(c->hg_order);
+  if (c->hg_plan != nullptr) (void)hipFree(c->hg_plan);
+  c->hg_order = nullptr; c->hg_plan = nullptr; c->handover_points = 0;
+  const int64_t ob = nesvor_hashgrid_cloud_order_bytes(N), pb = nesvor_hashgrid_cloud_plan_bytes(&d.grid, N);
+  if (hipMalloc(&c->hg_order, (size_t)ob) != hipSuccess) { c->hg_order = nullptr; (void)hipGetLastError(); return; }
+  if (pb > 0 && hipMalloc(&c->hg_plan, (size_t)pb) != hipSuccess) { c->hg_plan = nullptr; (void)hipGetLastError(); }
+  c->handover_points = N;
+}
+
 }  // namespace
 
 extern "C" void* nesvor_step_create(const nesvor_step_t* desc) {
@@ -189,6 +209,7 @@ extern "C" void* nesvor_step_create(const nesvor_step_t* desc) {
     c->wimg_stride = ((size_t)need + 255) / 256 * 256;
     if (need > 0 && hipMalloc(&c->wimg, 3 * c->wimg_stride) != hipSuccess) { c->wimg = nullptr; (void)hipGetLastError(); }  // (without it: the in-kernel builds)
   }
+  size_handover(c);
   if (desc->has_b) {  // (a staged call without it is refused)
     if (hipMalloc(reinterpret_cast<void**>(&c->mean_ticket), sizeof(unsigned)) != hipSuccess) { c->mean_ticket = nullptr; (void)hipGetLastError(); }
     else if (hipMemset(c->mean_ticket, 0, sizeof(unsigned)) != hipSuccess) { (void)hipFree(c->mean_ticket); c->mean_ticket = nullptr; (void)hipGetLastError(); }
@@ -227,6 +248,7 @@ extern "C" int nesvor_step_update(void* handle, const nesvor_step_t* desc) {
   if (handle == nullptr || desc == nullptr) return (int)hipErrorInvalidValue;
   if (bias_free_refused(*desc)) return (int)hipErrorInvalidValue;
   static_cast<StepCtx*>(handle)->d = *desc;
+  size_handover(static_cast<StepCtx*>(handle));  // (B or S changed: hipFree waits for the launches that read the old buffers)
   return 0;
 }
 
@@ -246,6 +268,8 @@ extern "C" void nesvor_step_destroy(void* handle) {
   StepCtx* c = static_cast<StepCtx*>(handle);
   (void)hipEventDestroy(c->ev_agg); (void)hipEventDestroy(c->ev_owner); (void)hipEventDestroy(c->ev_sg0); (void)hipEventDestroy(c->ev_sg1);
   if (c->wimg != nullptr) (void)hipFree(c->wimg);
+  if (c->hg_order != nullptr) (void)hipFree(c->hg_order);
+  if (c->hg_plan != nullptr) (void)hipFree(c->hg_plan);
   if (c->mean_ticket != nullptr) (void)hipFree(c->mean_ticket);
   for (int k = 0; k < NESVOR_STEP_TIMED_SPANS; ++k) {
     if (c->t0[k] != nullptr) (void)hipEventDestroy(c->t0[k]);
@@ -302,6 +326,12 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
   const bool split_d = scaled(net_d), split_s = d.has_lv && scaled(net_s), split_b = d.has_b && scaled(net_b);
   const int layout = NESVOR_LAYOUT_FEATURE_MAJOR;
   const bool overlap_owner = (d.overlap_owner & 1) != 0;
+  // The hash-grid forward of a clustered batch sorts every cloud and writes its plan for the aggregation pass of the same run, which
+  // then neither sorts nor derives boxes and schedule.  (NESVOR_HASHGRID_FWD forces a forward kernel: no hand-over then.)
+  static const bool fwd_forced = getenv("NESVOR_HASHGRID_FWD") != nullptr;
+  const bool handover = S >= 128 && !fwd_forced && ctx->hg_order != nullptr && ctx->handover_points == N;
+  const void* hg_order = handover ? ctx->hg_order : nullptr;
+  const void* hg_plan = handover ? ctx->hg_plan : nullptr;  // (level-range launches - data-parallel runs - take the order only)
   // AdamW on the table inside the owner pass (single call covers gradient and update, nothing to exchange in between);
   // the table is the LAST segment of the flat buffers
   const int64_t table_off = d.table - d.flat_param;
@@ -383,8 +413,12 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
     }
     {
       Span t(ctx, NESVOR_STEP_SPAN_HASHGRID_FWD, main);
-      NESVOR_TRY(nesvor_hashgrid_forward_bounded(&d.grid, d.u, d.table, d.pe, N, layout | (S >= 128 ? NESVOR_LAYOUT_CLUSTERED : 0),
-                                                 split_d ? prep_d + NESVOR_MLP_PREP_XB : nullptr, main));
+      if (handover)
+        NESVOR_TRY(nesvor_hashgrid_forward_plan(&d.grid, d.u, d.table, d.pe, N, layout, split_d ? prep_d + NESVOR_MLP_PREP_XB : nullptr,
+                                                ctx->hg_order, phase == 0 ? ctx->hg_plan : nullptr, d.queue_scale, main));
+      else
+        NESVOR_TRY(nesvor_hashgrid_forward_bounded(&d.grid, d.u, d.table, d.pe, N, layout | (S >= 128 ? NESVOR_LAYOUT_CLUSTERED : 0),
+                                                   split_d ? prep_d + NESVOR_MLP_PREP_XB : nullptr, main));
     }
    }
     if (bias_stop) {
@@ -482,8 +516,8 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
       //  set-up, 36 + 50 us side by side against 63 us, and the cross-stream hand-overs ate the rest: 0.285 -> 0.294 ms at 2^17
       //  points.  Not kept.)
       Span t(ctx, NESVOR_STEP_SPAN_HASHGRID_BWD_AGGREGATE, main);
-      NESVOR_TRY(nesvor_hashgrid_backward_bounded(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 1, 0, L,
-                                                  d.queue_scale, dpe_bound, main));
+      NESVOR_TRY(nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 1, 0, L,
+                                               d.queue_scale, dpe_bound, hg_order, hg_plan, main));
     }
     // the owner pass only finishes grad_table (or, fused, takes the table's AdamW step): it runs under the sampler backward
     // and the per-slice bookkeeping
@@ -507,13 +541,13 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
     if (overlap_owner && hipEventRecord(ctx->ev_owner, side) != hipSuccess) return (int)hipGetLastError();
   } else if (phase == 1) {
     // fine levels first (the end of the flat gradient): the host starts their all-reduce when this call returns
-    return nesvor_hashgrid_backward_bounded(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 3, split_level, L,
-                                            d.queue_scale, dpe_bound, main);
+    return nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 3, split_level, L,
+                                         d.queue_scale, dpe_bound, hg_order, nullptr, main);
   } else {
     // the coarse levels: aggregation on the main stream, their owner pass again under the rest of the step (the caller joins
     // the side stream before it reduces / applies the rest of the gradient)
-    NESVOR_TRY(nesvor_hashgrid_backward_bounded(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 1 | 4 | 8, 0,
-                                                split_level, d.queue_scale, dpe_bound, main));
+    NESVOR_TRY(nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 1 | 4 | 8, 0,
+                                             split_level, d.queue_scale, dpe_bound, hg_order, nullptr, main));
     hipStream_t owner_stream = main;
     if (overlap_owner) {
       if (hipEventRecord(ctx->ev_agg, main) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_agg, 0) != hipSuccess) return (int)hipGetLastError();

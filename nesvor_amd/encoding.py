@@ -14,7 +14,23 @@ UNCLUSTERED_FWD_MIN_POINTS = 1 << 15  # below this the launches of the ordered f
 _FWD_MODE = __import__("os").environ.get("NESVOR_HASHGRID_FWD", "")  # cloud | level | gather: force one kernel (csrc/hashgrid.hip); sorted: force the ordered forward
 
 
-def hashgrid_forward(spec: HashGridSpec, u: torch.Tensor, table: torch.Tensor, layout=_lib.LAYOUT_ROW_MAJOR, clustered=False):
+class CloudPlan:
+    """What ``hashgrid_forward(..., clustered=True, want_plan=True)`` hands to ``hashgrid_backward(..., plan=...)`` of the SAME
+    points: the Morton order of every 256-point cloud (``order``, one byte per point) and, at one or two features per level, the
+    clouds' plan records (``records``: bounding box, lattice boxes, window bits, round schedule -
+    ``nesvor_hashgrid_forward_plan``).  Valid for the ``u`` tensor object it was computed from (unchanged since), its grid and the
+    backward's chunking; ``hashgrid_backward`` passes NULL for anything else."""
+
+    def __init__(self, spec, u, order, records):
+        self.spec, self.u, self.version = spec, u, u._version
+        self.order, self.records = order, records
+
+    def fits(self, spec, u) -> bool:
+        return u is self.u and u._version == self.version and spec is self.spec
+
+
+def hashgrid_forward(spec: HashGridSpec, u: torch.Tensor, table: torch.Tensor, layout=_lib.LAYOUT_ROW_MAJOR, clustered=False,
+                     want_plan=False):
     """clustered=True: the caller's promise that every 256 consecutive points are spatially clustered (the PSF samples of a
     slice pixel are contiguous; consecutive voxels of a raster-ordered lattice): the one-workgroup-per-256-points kernel on the
     points as given.  clustered=False (the default: any tcnn-style caller, nesvor/nesvor/models.py:25; points in arbitrary
@@ -26,8 +42,14 @@ def hashgrid_forward(spec: HashGridSpec, u: torch.Tensor, table: torch.Tensor, l
         order of a coarse lattice's cells and the per-cloud kernel runs on workgroups of neighbouring points, every thread
         writing its point's whole row (``nesvor_hashgrid_forward_unclustered``; 0.36 against 0.49 ms - the per-level kernel
         writes 8 bytes per (point, level) into rows of 128).
-    A performance hint only: the encoded values are the same."""
+    A performance hint only: the encoded values are the same.
+    want_plan=True (clustered batches only): returns ``(pe, CloudPlan)`` - the per-cloud kernel also does the set-up work of the
+    backward's aggregation pass that depends on ``u`` alone; ``pe`` is bit-identical."""
     _lib.require_device(u, table, dtype=torch.float32, name="hashgrid input/table")
+    if want_plan:
+        if not clustered or u.shape[0] == 0:
+            raise RuntimeError("a cloud plan exists for clustered, non-empty batches only")
+        return _hashgrid_forward_plan(spec, u, table, layout)
     N = u.shape[0]
     E = spec.n_output_dims
     shape = (N, E) if layout == _lib.LAYOUT_ROW_MAJOR else (E, N)
@@ -51,6 +73,23 @@ def hashgrid_forward(spec: HashGridSpec, u: torch.Tensor, table: torch.Tensor, l
             )
     _lib.check(err, "hashgrid forward")
     return pe
+
+
+def _hashgrid_forward_plan(spec, u, table, layout, pe_absmax=None):
+    N = u.shape[0]
+    E = spec.n_output_dims
+    pe = torch.empty((N, E) if layout == _lib.LAYOUT_ROW_MAJOR else (E, N), dtype=torch.float32, device=u.device)
+    lib = _lib.load()
+    g = ctypes.byref(spec.c_struct)
+    order = torch.empty(lib.nesvor_hashgrid_cloud_order_bytes(N), dtype=torch.uint8, device=u.device)
+    nbytes = lib.nesvor_hashgrid_cloud_plan_bytes(g, N)
+    records = torch.empty(nbytes // 4, dtype=torch.int32, device=u.device) if nbytes > 0 else None  # (torch allocations are 512-byte aligned)
+    sizer = queue_sizer(spec, N, u.device)
+    with torch.cuda.device(u.device), _lib.kernel_timer.span("hashgrid_fwd"):
+        err = lib.nesvor_hashgrid_forward_plan(g, _lib.ptr(u), _lib.ptr(table), _lib.ptr(pe), N, layout, _lib.ptr(pe_absmax), _lib.ptr(order),
+                                               _lib.ptr(records), sizer.scale, _lib.stream_ptr())
+    _lib.check(err, "hashgrid forward (with cloud plan)")
+    return pe, CloudPlan(spec, u, order, records)
 
 
 def points_are_ordered(u: torch.Tensor, box_fraction: float = 1.0 / 16) -> bool:
@@ -185,7 +224,7 @@ def _workspace(spec, N, device, sizer=None, layout=0):
 
 
 def hashgrid_backward(spec, u, table, dpe, grad_table=None, need_input_grad=True, layout=_lib.LAYOUT_ROW_MAJOR,
-                      method="owner", levels=None, grad_u=None, first=True, owner_stream=None, dy_bound=None, clustered=True):
+                      method="owner", levels=None, grad_u=None, first=True, owner_stream=None, dy_bound=None, clustered=True, plan=None):
     """Accumulates into grad_table (allocated zero-filled if None); returns (grad_table, grad_u|None).
     method: "owner" (LDS aggregation + per-chunk owners, the MI355X path) or "atomic" (per-corner atomics).
     levels = (begin, end): only these levels ("owner" method) - a data-parallel step splits the backward in two so
@@ -197,7 +236,9 @@ def hashgrid_backward(spec, u, table, dpe, grad_table=None, need_input_grad=True
     (the training step gets the bound from the MLP backward that produced dpe, csrc/step.hip).
     clustered=False: consecutive points are not spatially clustered (uniform points, a shuffled batch) - the "owner" method
     then orders them by coarse lattice cell first (``NESVOR_LAYOUT_UNCLUSTERED``); the default is what the training step
-    produces, the S PSF samples of a pixel next to each other.  The gradients do not depend on the hint."""
+    produces, the S PSF samples of a pixel next to each other.  The gradients do not depend on the hint.
+    plan: the ``CloudPlan`` of the forward of the same ``u`` ("owner" method, clustered): no launch sorts; a backward over all
+    levels also reads its set-up from the plan's records.  A plan of another tensor, grid or an unclustered call is ignored."""
     _lib.require_device(u, table, dpe, dtype=torch.float32, name="hashgrid backward input")
     if not clustered:
         layout = layout | _lib.LAYOUT_UNCLUSTERED | _lib.LAYOUT_DY_SCRATCH
@@ -221,8 +262,12 @@ def hashgrid_backward(spec, u, table, dpe, grad_table=None, need_input_grad=True
                     _lib.ptr(grad_u), N, layout, _lib.ptr(ws))
             l0, l1 = (0, spec.n_levels) if levels is None else levels
             extra = 0 if first else (4 | 8)  # keep the queue tails, add to grad_u
-            call = lambda stage: lib.nesvor_hashgrid_backward_bounded(*args, stage | extra, l0, l1, sizer.scale, _lib.ptr(dy_bound),
-                                                                      _lib.stream_ptr())
+            if plan is not None and not (clustered and plan.fits(spec, u)):
+                plan = None
+            p_order = _lib.ptr(plan.order) if plan is not None else None
+            p_rec = _lib.ptr(plan.records) if plan is not None and (l0, l1) == (0, spec.n_levels) else None
+            call = lambda stage, st=None: lib.nesvor_hashgrid_backward_plan(*args, stage | extra, l0, l1, sizer.scale, _lib.ptr(dy_bound),
+                                                                            p_order, p_rec, st or _lib.stream_ptr())
             if _lib.kernel_timer.enabled:  # bracket each of the two launches with its own events
                 with _lib.kernel_timer.span("hashgrid_bwd_aggregate"):
                     err = call(1)
@@ -233,8 +278,7 @@ def hashgrid_backward(spec, u, table, dpe, grad_table=None, need_input_grad=True
                 err = call(1)
                 if err == 0:
                     owner_stream.wait_stream(torch.cuda.current_stream(u.device))
-                    err = lib.nesvor_hashgrid_backward_bounded(*args, 2 | extra, l0, l1, sizer.scale, _lib.ptr(dy_bound),
-                                                               ctypes.c_void_p(owner_stream.cuda_stream))
+                    err = call(2, ctypes.c_void_p(owner_stream.cuda_stream))
             else:
                 err = call(3)
         else:
