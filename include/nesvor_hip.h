@@ -13,6 +13,7 @@
 #ifndef NESVOR_HIP_H
 #define NESVOR_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -804,6 +805,26 @@ int nesvor_step_timing_read(void* handle, float* ms);
 int nesvor_vvr_similarity(const float* source, int D, int H, int W, const float* points, const float* target,
                           const float* mats, const float* to_unit_xyz, int64_t M, int K, double* sums,
                           double* target_sums, void* stream);
+
+/* ----------------------------------------------------------------------
+ * Similarity sums of the slice-to-volume registration: the acquisition operator A (nesvor_slice_acq_forward with
+ * interp_psf = 0 and no volume mask) applied to every slice under K poses, reduced at once.  vol (D,H,W) fp32,
+ * psf (d_p,h_p,w_p), transforms (n,K,3,4) in A's convention (voxel units), slices (n,h,w) acquired values,
+ * slices_mask (n,h,w) bytes or NULL, res_slice the pixel size in voxels.  A pixel is valid under a pose when its mask byte
+ * is set (or the mask is NULL) and the PSF weight A finds there is > 0.  Over the valid pixels, I = A's value, J = the
+ * acquired value:
+ *   sums[i][k] = { count, sum I, sum I^2, sum I J, sum J, sum J^2 }        fp64, (n,K,6), fully written (no memset needed);
+ * a (slice, pose) without a valid pixel yields six exact zeros.  The sums are reproducible (no atomics: per-workgroup
+ * partials in the workspace, added in workgroup order by a second launch).  workspace: device memory of at least
+ * nesvor_svr_similarity_workspace_bytes(n, K, h, w) bytes (0 for sizes the call treats as a no-op).
+ * K <= 0 or n == 0: no-op, returns 0.  hipErrorInvalidValue: a size below 1, a PSF of more than 1024 elements
+ * (compose the sums from nesvor_slice_acq_forward then), a workspace that is too small.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_svr_similarity(const float* vol, int D, int H, int W, const float* psf, int d_p, int h_p, int w_p,
+                          const float* transforms, const float* slices, const uint8_t* slices_mask, int n, int K, int h,
+                          int w, float res_slice, double* sums, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_svr_similarity_workspace_bytes(int n, int K, int h, int w);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ every op wrapper raises on non-device tensors.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 import torch
 
@@ -220,6 +220,9 @@ _SIGNATURES = {
     "nesvor_step_timing_read": ([_P, _P], c_int),
     "nesvor_step_run": ([_P, _P, _P, _P, c_uint64, c_uint64, _P, c_int, c_int, POINTER(AdamwT), _P], c_int),
     "nesvor_vvr_similarity": ([_P, c_int, c_int, c_int, _P, _P, _P, _P, c_int64, c_int, _P, _P, _P], c_int),
+    "nesvor_svr_similarity": ([_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P,
+                               c_size_t, _P], c_int),
+    "nesvor_svr_similarity_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
 }
 
 

@@ -4,14 +4,15 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
     python -m nesvor_amd.cli reconstruct   --input-stacks a.nii.gz b.nii.gz [--stack-masks ...] [--thicknesses ...]
                                            | --input-slices DIR   --output-volume v.nii.gz [--output-model m.pt]
                                            [--output-slices DIR] [--simulated-slices DIR]  [training flags]
-    python -m nesvor_amd.cli register      --input-stacks a.nii.gz b.nii.gz --output-slices DIR [--registration stack|none]
+    python -m nesvor_amd.cli register      --input-stacks a.nii.gz b.nii.gz --output-slices DIR [--registration stack|svr|none]
     python -m nesvor_amd.cli sample-volume --input-model m.pt --output-volume v.nii.gz [--output-resolution 0.8] ...
     python -m nesvor_amd.cli sample-slices --input-model m.pt --input-slices DIR --simulated-slices DIR
 
 Differences from the reference, all because the SVoRT transformer (pretrained weights, torchvision) is out of scope
 here: ``--registration`` accepts the reference's choices, of which ``none`` (the default; the reference defaults to
-``svort``) and ``stack`` (stack-to-stack rigid registration, nesvor_amd/registration.py) are implemented; there is
-the ``register`` command offers the same two.  Precision follows the reference's switch
+``svort``), ``stack`` (stack-to-stack rigid registration) and ``svr`` (stack registration, then every slice registered
+rigidly to a volume reconstructed from all of them; not a choice of the reference; both in nesvor_amd/registration.py)
+are implemented; the ``register`` command offers the same three.  Precision follows the reference's switch
 (``--single-precision`` = the fp32 model with biased Linear layers; the default is the reference's half-precision
 structure - bias-free networks - which the HIP path evaluates with bf16 matrix operands and fp32 accumulation;
 ``--mlp-fp16`` without ``--single-precision`` trains that structure with power-of-two-scaled fp16 operands instead, on
@@ -111,7 +112,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--output-model", type=str)
     g.add_argument("--mask-threshold", type=float, default=1.0)
     g = p.add_argument_group("registration")
-    g.add_argument("--registration", default="none", type=str, choices=["svort", "svort-stack", "stack", "none"])
+    g.add_argument("--registration", default="none", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _training_flags(p)
     _common_flags(p)
@@ -124,7 +125,7 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_argument_group("output")
     g.add_argument("--output-slices", type=str, required=True)
     g = p.add_argument_group("registration")
-    g.add_argument("--registration", default="stack", type=str, choices=["svort", "svort-stack", "stack", "none"])
+    g.add_argument("--registration", default="stack", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _common_flags(p)
 
@@ -244,17 +245,24 @@ def _load_stacks(args: Namespace) -> List:
 
 def register(args: Namespace, stacks: List) -> List:
     """Stacks -> motion-corrected slices (cli/commands.py:171-176): ``none`` keeps the nominal poses, ``stack``
-    registers every stack to the first one; the SVoRT-based choices need the pretrained transformer (out of scope)."""
-    if args.registration not in ("none", "stack"):
+    registers every stack to the first one, ``svr`` then registers every slice to a volume reconstructed from all of
+    them (``register_slices``); the SVoRT-based choices need the pretrained transformer (out of scope)."""
+    if args.registration not in ("none", "stack", "svr"):
         raise NotImplementedError(f"--registration {args.registration}: the SVoRT transformer is out of scope of this "
                                   "build; register with the reference and pass the result through --input-slices, or use "
-                                  "--registration stack / none")
+                                  "--registration svr / stack / none")
     if args.registration == "stack":
         from .registration import register_stacks
 
         t1 = time.time()
         stacks = register_stacks(stacks)
         logging.info("Stack registration finished in %.1f s", time.time() - t1)
+    elif args.registration == "svr":
+        from .registration import register_slices
+
+        t1 = time.time()
+        stacks = register_slices(stacks)
+        logging.info("Slice-to-volume registration finished in %.1f s", time.time() - t1)
     return stacks_to_slices(stacks)
 
 

@@ -280,6 +280,39 @@ _op("slice_acq_adjoint_forward(Tensor transforms, Tensor psf, Tensor slices, Ten
 
 
 # =====================================================================================================================
+# similarity sums of the slice-to-volume registration (csrc/svr.hip): A under K poses per slice, reduced in one call
+# =====================================================================================================================
+SVR_MAX_PSF_ELEMENTS = 1024  # larger PSFs are refused by the kernel (its LDS tap list); compose from slice_acq_forward
+
+
+def _svr_similarity(vol, psf, transforms, slices, slices_mask, res_slice):
+    _lib.require_device(vol, psf, transforms, slices, dtype=torch.float32, name="svr_similarity vol/psf/transforms/slices")
+    sm = _mask(slices_mask)
+    if vol.ndim < 3 or psf.ndim != 3 or transforms.ndim != 4 or tuple(transforms.shape[2:]) != (3, 4) or slices.ndim < 3:
+        raise RuntimeError("svr_similarity: vol (..., D, H, W), psf (d, h, w), transforms (n, K, 3, 4), slices (n, ..., h, w)")
+    n, K = int(transforms.shape[0]), int(transforms.shape[1])
+    h, w = int(slices.shape[-2]), int(slices.shape[-1])
+    if slices.numel() != n * h * w or (sm is not None and sm.numel() != n * h * w):
+        raise RuntimeError("svr_similarity: slices / slices_mask must hold n x h x w elements")
+    if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
+        raise RuntimeError("svr_similarity: one volume expected")
+    sums = torch.empty((n, K, 6), dtype=torch.float64, device=vol.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_svr_similarity_workspace_bytes(n, K, h, w))
+    workspace = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=vol.device)
+    with torch.cuda.device(vol.device):
+        err = lib.nesvor_svr_similarity(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), _lib.ptr(psf), *(int(s) for s in psf.shape),
+                                        _lib.ptr(transforms), _lib.ptr(slices), _lib.ptr(sm), n, K, h, w, float(res_slice),
+                                        _lib.ptr(sums), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "svr similarity")
+    return sums
+
+
+_op("svr_similarity(Tensor vol, Tensor psf, Tensor transforms, Tensor slices, Tensor? slices_mask, float res_slice) -> Tensor",
+    _svr_similarity, fake=lambda vol, psf, tf, s, sm, r: vol.new_empty((tf.shape[0], tf.shape[1], 6), dtype=torch.float64))
+
+
+# =====================================================================================================================
 # multi-resolution hash-grid encoding (tinycudann.Encoding "HashGrid"; the scalars are its encoding_config)
 # =====================================================================================================================
 _SPECS = {}

@@ -22,10 +22,15 @@ PyTorch ``grid_sample`` + the loss, as the reference does - one objective evalua
 finite-difference gradient needs 13 of them.  Fused (HIP, ``nesvor_vvr_similarity``): when the loss is given by name
 (global NCC or MSE) and the gradient is by finite differences, ONE launch samples the source under all 13 poses and
 returns the moment sums the loss is a function of (fp64); ``stack_registration`` uses it.
+
+Slice-to-volume registration (``SVR``, ``register_slices`` = ``--registration svr``; no counterpart in the reference, whose
+slice-level choices need the pretrained SVoRT transformer): the same descent with one pose per slice, the objective being
+the similarity of the acquired slice and the slice simulated from the volume by the acquisition operator.
 """
 import ctypes
 import logging
 import math
+import os
 import time
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -33,8 +38,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .transform import RigidTransform, mat_transform_points
-from .utils import gaussian_blur, meshgrid, ncc_loss
+from .slice_acquisition import slice_acquisition
+from .transform import RigidTransform, mat_transform_points, mat_update_resolution
+from .utils import gaussian_blur, get_PSF, meshgrid, ncc_loss
 
 
 def resample(x: torch.Tensor, res_xyz_old: Sequence[float], res_xyz_new: Sequence[float]) -> torch.Tensor:
@@ -191,6 +197,14 @@ class VVR:
         return loss, grad
 
     # ---- descent -----------------------------------------------------------------------------------------------
+    # `_round` names the batch entries it evaluates (`idx`, rows of its `theta`); here every entry is a whole problem on the
+    # level's one (source, target) pair and the index is not needed - SVR picks each entry's slice by it
+    def _gradient_at(self, idx: torch.Tensor, cur: torch.Tensor, lv, step: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self._gradient(cur, lv, step)
+
+    def _trial_at(self, idx: torch.Tensor, theta: torch.Tensor, lv) -> torch.Tensor:
+        return self._objective_fused(theta, lv) if self._fused(theta, lv) else self._objective(theta, lv)
+
     def _round(self, theta: torch.Tensor, lv: _Level, step: float, state: Dict) -> Tuple[torch.Tensor, torch.Tensor]:
         """Up to max_iter accepted moves of length `step`; an entry leaves the active set at its first rejected move."""
         active = torch.ones(theta.shape[0], dtype=torch.bool, device=theta.device)
@@ -198,7 +212,7 @@ class VVR:
         for _ in range(self.max_iter):
             idx = torch.nonzero(active).flatten()
             cur = theta[idx]
-            loss, grad = self._gradient(cur, lv, step)
+            loss, grad = self._gradient_at(idx, cur, lv, step)
             loss_all[idx] = loss
             if self.momentum:
                 if "buf" not in state:
@@ -209,7 +223,7 @@ class VVR:
             else:
                 direction = grad
             move = direction / (torch.linalg.norm(direction, dim=-1, keepdim=True) + 1e-6) * (-step)
-            better = (self._objective_fused(cur + move, lv) if self._fused(cur, lv) else self._objective(cur + move, lv)) < loss
+            better = self._trial_at(idx, cur + move, lv) < loss
             active[idx] = better
             if not bool(better.any()):
                 break
@@ -235,6 +249,157 @@ class VVR:
             for _ in range(self.num_steps):
                 cur, loss = self._round(cur, lv, step, state)
                 step /= 2
+        return theta0 + (cur * unit - theta0), loss
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# slice-to-volume registration
+# ---------------------------------------------------------------------------------------------------------------------
+class _SliceLevel:
+    """One pyramid level of ``SVR``: the volume on the level's grid, the slices and their masks at the level's pixel size,
+    the PSF of a slice in the level's voxels."""
+
+    def __init__(self, volume: torch.Tensor, slices: torch.Tensor, mask: torch.Tensor, psf: torch.Tensor, res_slice: float,
+                 voxel: float):
+        self.volume, self.slices, self.mask, self.psf = volume, slices, mask, psf  # (D,H,W), (n,h,w), (n,h,w) bool, (d,h,w)
+        self.res_slice, self.voxel = res_slice, voxel  # pixel size in voxels; voxel size in mm
+        self.index: Optional[torch.Tensor] = None  # batch entry of the descent -> slice (the slices that take part in this level)
+
+
+class SVR(VVR):
+    """``SVR(num_levels, num_steps, step_size, max_iter, optimizer, loss, min_valid=32)`` then
+    ``theta_out, loss = svr(theta, slices, slices_mask, volume, params, trans_first)``: every slice registered rigidly to
+    the volume by simulating it through the acquisition operator A (``slice_acquisition`` forward: PSF-weighted sampling at
+    the slice's pose) and descending on the similarity of simulated and acquired slice - ``VVR``'s descent, one pose per slice.
+
+    theta (n,6) axis-angle [rad | mm], slices / slices_mask (n,1,h,w), volume (1,1,D,H,W) at ``params["res_r"]``,
+    ``params = {"res_s": pixel size, "s_thick": slice thickness, "res_r": voxel size}``.  ``loss = {"name": "ncc" | "mse"}``:
+    global masked NCC  -(cov^2) / (var_I var_J + eps)  or the mean squared difference per slice, both functions of the six
+    moment sums {count, sum I, sum I^2, sum I J, sum J, sum J^2} over the valid pixels (mask set, PSF weight > 0), in double.
+
+    Level l: volume blurred (sigma 0.5 * 2^l voxels) and resampled to ``res_r * 2^l``; slices blurred in-plane and resampled
+    to ``res_s * 2^l``, the mask resampled and thresholded at 0.5; the PSF is that of a slice on the level's grid.  A slice
+    with fewer than ``min_valid`` valid pixels at its pose when a level starts keeps its pose for that level (loss 0).
+
+    Two evaluation paths with one definition of the loss.  Fused (``torch.ops.nesvor.svr_similarity``, csrc/svr.hip): the 13
+    poses of a finite-difference gradient of all active slices in one call, the accept test a K = 1 call.  Composed: one
+    ``slice_acquisition`` per pose and fp64 torch sums - used for PSFs the kernel refuses (more than 1024 elements) and
+    forced with ``NESVOR_SVR=composed``."""
+
+    def __init__(self, num_levels: int, num_steps: int, step_size: float, max_iter: int, optimizer: Dict, loss: Dict,
+                 min_valid: int = 32) -> None:
+        self.num_levels, self.num_steps, self.step_size, self.max_iter = num_levels, num_steps, step_size, max_iter
+        self.auto_grad = False
+        self.current_level = num_levels - 1
+        if optimizer.get("name") != "gd":
+            raise Exception("unknown optimizer")
+        self.momentum = float(optimizer.get("momentum", 0))
+        if not isinstance(loss, dict) or loss.get("name") not in ("ncc", "mse") or not set(loss) <= {"name", "eps"}:
+            raise Exception("unknown loss")
+        self._kind, self._eps = loss["name"], float(loss.get("eps", 1e-6))
+        self.min_valid = min_valid
+        self.trans_first = True
+
+    # ---- pyramid -------------------------------------------------------------------------------------------
+    @staticmethod
+    def _level(level: int, slices: torch.Tensor, slices_mask: torch.Tensor, volume: torch.Tensor, params: Dict) -> _SliceLevel:
+        f = 2.0**level
+        res_s, res_r, s_thick = params["res_s"], params["res_r"], params["s_thick"]
+        sigma = 0.5 * f
+        vol = resample(gaussian_blur(volume, sigma, truncated=4.0), [1.0] * 3, [f] * 3)
+        sl = resample(gaussian_blur(slices, sigma, truncated=4.0), [1.0] * 2, [f] * 2)
+        mask = resample(slices_mask.to(slices.dtype), [1.0] * 2, [f] * 2) > 0.5
+        psf = get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / (res_r * f)), device=volume.device)
+        return _SliceLevel(vol[0, 0].contiguous(), sl[:, 0].contiguous(), mask[:, 0].contiguous(), psf, res_s / res_r, res_r * f)
+
+    # ---- objective -------------------------------------------------------------------------------------------
+    @staticmethod
+    def _fused_path(lv: _SliceLevel) -> bool:
+        from .ops import SVR_MAX_PSF_ELEMENTS
+
+        return os.environ.get("NESVOR_SVR", "") != "composed" and lv.psf.numel() <= SVR_MAX_PSF_ELEMENTS
+
+    def _sums(self, thetas_deg: torch.Tensor, lv: _SliceLevel, ids: Optional[torch.Tensor]) -> torch.Tensor:
+        """Moment sums of slices ``ids`` (None: all) under K poses each: thetas_deg (m,K,6) -> (m,K,6) float64."""
+        m, K = thetas_deg.shape[:2]
+        pose = RigidTransform(thetas_deg.reshape(-1, 6) * self._unit(thetas_deg), trans_first=self.trans_first)
+        mats = mat_update_resolution(pose.matrix(), 1, lv.voxel).view(m, K, 3, 4).contiguous()
+        slices = lv.slices if ids is None else lv.slices[ids]
+        mask = lv.mask if ids is None else lv.mask[ids]
+        if self._fused_path(lv):
+            return torch.ops.nesvor.svr_similarity(lv.volume, lv.psf, mats, slices, mask, lv.res_slice)
+        out = torch.empty((m, K, 6), dtype=torch.float64, device=mats.device)
+        J = slices.double()
+        for k in range(K):
+            sim, weight = slice_acquisition(mats[:, k], lv.volume[None, None], None, mask[:, None], lv.psf, slices.shape[-2:],
+                                            lv.res_slice, True, False)
+            valid = (mask & (weight[:, 0] > 0)).double()
+            Ik, Jk = sim[:, 0].double() * valid, J * valid
+            out[:, k] = torch.stack([t.sum((1, 2)) for t in (valid, Ik, Ik * Ik, Ik * Jk, Jk, Jk * Jk)], -1)
+        return out
+
+    def _loss_of(self, sums: torch.Tensor) -> torch.Tensor:
+        """(..., 6) moment sums -> loss; an entry without a valid pixel has loss 0."""
+        cnt = sums[..., 0]
+        ok = cnt > 0
+        sI, sII, sIJ, sJ, sJJ = ((sums[..., j] / torch.where(ok, cnt, torch.ones_like(cnt))) for j in range(1, 6))
+        if self._kind == "mse":
+            loss = sII - 2 * sIJ + sJJ
+        else:
+            cross = sIJ - sI * sJ
+            loss = -(cross * cross) / ((sII - sI * sI) * (sJJ - sJ * sJ) + self._eps)
+        return torch.where(ok, loss, torch.zeros_like(loss)).float()
+
+    @staticmethod
+    def _ids(idx: torch.Tensor, lv: _SliceLevel) -> Optional[torch.Tensor]:
+        """The slices behind batch entries ``idx`` of the level's descent (None: all of them, in order)."""
+        ids = lv.index[idx]
+        return None if ids.shape[0] == lv.slices.shape[0] else ids  # (an increasing subset of full length is the identity)
+
+    def _trial_at(self, idx: torch.Tensor, theta: torch.Tensor, lv: _SliceLevel) -> torch.Tensor:
+        return self._loss_of(self._sums(theta[:, None], lv, self._ids(idx, lv)))[:, 0]
+
+    def _gradient_at(self, idx: torch.Tensor, cur: torch.Tensor, lv: _SliceLevel, step: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        e = torch.zeros((13, 6), dtype=cur.dtype, device=cur.device)  # the pose and its 12 perturbations
+        j = torch.arange(6, device=cur.device)
+        e[1 + 2 * j, j] = step
+        e[2 + 2 * j, j] = -step
+        l = self._loss_of(self._sums(cur[:, None] + e[None], lv, self._ids(idx, lv)))
+        return l[:, 0], l[:, 1::2] - l[:, 2::2]
+
+    @torch.no_grad()
+    def evaluate(self, theta: torch.Tensor, slices: torch.Tensor, slices_mask: torch.Tensor, volume: torch.Tensor,
+                 params: Dict, trans_first: bool = True, level: int = 0) -> torch.Tensor:
+        """The loss of every slice at pose ``theta`` (n,6) [rad | mm] on pyramid level ``level`` -> (n,)."""
+        self.trans_first = trans_first
+        lv = self._level(level, slices, slices_mask, volume, params)
+        return self._loss_of(self._sums((theta / self._unit(theta))[:, None], lv, None))[:, 0]
+
+    @torch.no_grad()
+    def __call__(self, theta: torch.Tensor, slices: torch.Tensor, slices_mask: torch.Tensor, volume: torch.Tensor,
+                 params: Dict, trans_first: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+        self.trans_first = trans_first
+        unit = self._unit(theta)
+        theta0 = theta.clone()
+        cur = (theta.detach() / unit).clone()
+        n = theta.shape[0]
+        loss = torch.zeros(n, dtype=theta.dtype, device=theta.device)
+        for level in range(self.num_levels - 1, -1, -1):
+            self.current_level = level
+            lv = self._level(level, slices, slices_mask, volume, params)
+            count = self._sums(cur[:, None], lv, None)[:, 0, 0]
+            lv.index = torch.nonzero(count >= self.min_valid).flatten()
+            loss = torch.zeros(n, dtype=theta.dtype, device=theta.device)
+            if lv.index.numel() == 0:
+                continue
+            sub = cur[lv.index]
+            step = self.step_size * 2**level
+            state: Dict = {}  # the momentum buffer lives for one level
+            for _ in range(self.num_steps):
+                sub, sub_loss = self._round(sub, lv, step, state)
+                step /= 2
+            cur[lv.index] = sub
+            loss[lv.index] = sub_loss
         return theta0 + (cur * unit - theta0), loss
 
 
@@ -294,4 +459,93 @@ def register_stacks(dataset: List, res_s: float = 1.0) -> List:
     logging.debug("time for stack registration: %f s", time.time() - t0)
     for s, t in zip(dataset, out):
         s.transformation = t
+    return dataset
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --registration svr
+# ---------------------------------------------------------------------------------------------------------------------
+def _pad_to(stack: torch.Tensor, size: int) -> Tuple[torch.Tensor, Tuple[float, float]]:
+    """(n,1,h,w) zero-padded to (n,1,size,size); also the padded frame's centre relative to the old one, in pixels (x, y)."""
+    dx1 = (size - stack.shape[-1]) // 2
+    dx2 = (size - stack.shape[-1]) - dx1
+    dy1 = (size - stack.shape[-2]) // 2
+    dy2 = (size - stack.shape[-2]) - dy1
+    return F.pad(stack, (dx1, dx2, dy1, dy2)), ((dx2 - dx1) / 2, (dy2 - dy1) / 2)
+
+
+def _in_plane_shift(n: int, shift_xy: Tuple[float, float], device) -> RigidTransform:
+    mat = torch.eye(3, 4, dtype=torch.float32, device=device).repeat(n, 1, 1)
+    mat[:, 0, 3], mat[:, 1, 3] = shift_xy
+    return RigidTransform(mat)
+
+
+def _common_frame(stacks: List[torch.Tensor], transforms: List[RigidTransform], res_s: float
+                  ) -> Tuple[torch.Tensor, RigidTransform, List[RigidTransform]]:
+    """Stacks (n_j,1,h_j,w_j) of ``res_s`` pixels padded to one square size and concatenated, with the poses of the padded
+    frames.  A padded frame's centre may sit half a pixel off the slice's, so  pose of the frame = pose o in-plane shift:
+    every pixel keeps its place in the world.  Also returns the shifts per stack, to take a frame's pose back to its slice's
+    (``frame_pose.compose(shift.inv())``)."""
+    size = max(max(s.shape[-2:]) for s in stacks)
+    padded, shifts = zip(*[_pad_to(s, size) for s in stacks])
+    to_frame = [_in_plane_shift(s.shape[0], (sx * res_s, sy * res_s), s.device) for s, (sx, sy) in zip(stacks, shifts)]
+    poses = RigidTransform.cat([p.compose(t) for p, t in zip(transforms, to_frame)])
+    return torch.cat(padded).contiguous(), poses, to_frame
+
+
+def reconstruct_from_slices(mats: torch.Tensor, slices: torch.Tensor, res_s: float, s_thick: float, res_r: float,
+                            volume_shape: Sequence[int]) -> torch.Tensor:
+    """The volume the slice registration aligns to (svort/inference.py:370-406): equalised back-projection, then one CG
+    step on the normal equations over the non-zero pixels.  mats (n,3,4) in voxels of ``res_r``, slices (n,1,h,w)."""
+    from .srr import SRR, PSFreconstruction
+
+    params = {"psf": get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / res_r), device=slices.device),
+              "slice_shape": slices.shape[-2:], "interp_psf": False, "res_s": res_s, "res_r": res_r, "s_thick": s_thick,
+              "volume_shape": tuple(int(s) for s in volume_shape)}
+    volume = PSFreconstruction(mats, slices, None, None, params)
+    return SRR(n_iter=1, use_CG=True)(mats, slices, volume, params, slices_mask=slices > 0)
+
+
+def _cover_shape(poses: RigidTransform, mask: torch.Tensor, res_s: float, s_thick: float, res_r: float) -> Tuple[int, int, int]:
+    """(D,H,W) of a volume of ``res_r`` voxels, centred at the origin, that holds every masked pixel of the posed slices
+    (mask (n,1,h,w)) with the slice thickness and a few voxels to spare."""
+    h, w = mask.shape[-2:]
+    grid = meshgrid((w, h), (res_s, res_s), device=mask.device)  # (h,w,2), centred
+    pts = torch.cat([grid, torch.zeros_like(grid[..., :1])], -1)[None].expand(mask.shape[0], -1, -1, -1)
+    world = mat_transform_points(poses.matrix()[:, None, None], pts, True)[mask[:, 0]]
+    half = world.abs().amax(0) + s_thick  # x, y, z
+    size = [2 * int(math.ceil(float(v) / res_r)) + 5 for v in half.tolist()]
+    return size[2], size[1], size[0]
+
+
+def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = None, n_outer: int = 3) -> List:
+    """``--registration svr``: stack registration (``register_stacks``), then ``n_outer`` rounds of  reconstruct a volume
+    from all slices at their current poses  /  register every non-empty slice rigidly to it (``SVR``, global NCC); the
+    per-slice poses are written back into the stacks.  ``res_r``: voxel size of the intermediate volume (default ``res_s``)."""
+    dataset = register_stacks(dataset, res_s)
+    t0 = time.time()
+    res_r = res_s if res_r is None else res_r
+    s_thick = float(sum(s.thickness for s in dataset) / len(dataset))
+    stacks = [resample(s.slices * s.mask, (s.resolution_x, s.resolution_y), (res_s, res_s)) for s in dataset]
+    slices, poses, to_frame = _common_frame(stacks, [s.transformation for s in dataset], res_s)
+    mask = slices > 0
+    keep = torch.nonzero(mask.flatten(1).any(1)).flatten()
+    slices, mask = slices[keep].contiguous(), mask[keep].contiguous()
+    theta = poses.axisangle()[keep].clone()
+    svr = SVR(num_levels=3, num_steps=4, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1}, loss={"name": "ncc"})
+    params = {"res_s": res_s, "s_thick": s_thick, "res_r": res_r}
+    for it in range(n_outer):
+        current = RigidTransform(theta)
+        shape = _cover_shape(current, mask, res_s, s_thick, res_r)
+        volume = reconstruct_from_slices(mat_update_resolution(current.matrix(), 1, res_r), slices, res_s, s_thick, res_r, shape)
+        theta, loss = svr(theta, slices, mask, volume, params, True)
+        logging.debug("slice registration round %d: volume %s, mean NCC %f", it, shape, -float(loss.mean()))
+    full = poses.axisangle().clone()
+    full[keep] = theta
+    start = 0
+    for s, t in zip(dataset, to_frame):
+        n = s.slices.shape[0]
+        s.transformation = RigidTransform(full[start:start + n]).compose(t.inv())
+        start += n
+    logging.debug("time for slice registration: %f s", time.time() - t0)
     return dataset

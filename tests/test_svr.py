@@ -1,0 +1,381 @@
+"""Slice-to-volume registration (``--registration svr``): the fused similarity kernel (csrc/svr.hip) against the sums
+composed from the acquisition operator, the ``SVR`` descent on both evaluation paths, the ``register_slices`` pipeline
+and its command line."""
+import os
+
+import pytest
+import torch
+
+H_W = (19, 23)  # 437 pixels: two workgroups per slice, the second one ragged
+RES_SLICE = 1.5
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CPU
+# ---------------------------------------------------------------------------------------------------------------------
+def test_parser_accepts_svr_and_keeps_the_defaults():
+    from nesvor_amd.cli import build_parser
+
+    p = build_parser()
+    a = p.parse_args(["reconstruct", "--input-stacks", "a.nii.gz", "--output-volume", "v.nii.gz", "--registration", "svr"])
+    b = p.parse_args(["register", "--input-stacks", "a.nii.gz", "--output-slices", "out", "--registration", "svr"])
+    assert a.registration == b.registration == "svr"
+    assert p.parse_args(["reconstruct", "--input-stacks", "a.nii.gz", "--output-volume", "v.nii.gz"]).registration == "none"
+    assert p.parse_args(["register", "--input-stacks", "a.nii.gz", "--output-slices", "out"]).registration == "stack"
+
+
+def test_svr_level_shapes_resolution_and_psf():
+    """Level l: volume at res_r 2^l, slices and mask at res_s 2^l (sizes int(size / 2^l)), pixel size res_s / res_r voxels,
+    PSF of a slice of s_thick on voxels of res_r 2^l: in-plane extent unchanged, through-plane extent shrinking."""
+    from nesvor_amd.registration import SVR
+    from nesvor_amd.utils import get_PSF
+
+    g = torch.Generator().manual_seed(0)
+    volume = torch.rand(1, 1, 20, 24, 28, generator=g)
+    slices = torch.rand(3, 1, 17, 22, generator=g)
+    mask = torch.zeros(3, 1, 17, 22, dtype=torch.bool)
+    mask[:, :, 4:13, 5:18] = True
+    params = {"res_s": 1.5, "s_thick": 6.0, "res_r": 1.0}
+    for level, vol_shape, sl_shape in ((0, (20, 24, 28), (3, 17, 22)), (1, (10, 12, 14), (3, 8, 11))):
+        lv = SVR._level(level, slices, mask, volume, params)
+        assert tuple(lv.volume.shape) == vol_shape and tuple(lv.slices.shape) == sl_shape
+        assert tuple(lv.mask.shape) == sl_shape and lv.mask.dtype == torch.bool and lv.mask.any() and not lv.mask.all()
+        assert lv.res_slice == 1.5 and lv.voxel == 2.0**level
+        expect = get_PSF(res_ratio=(1.5, 1.5, 6.0 / 2.0**level))
+        assert lv.psf.shape == expect.shape and torch.equal(lv.psf, expect)
+        assert lv.volume.is_contiguous() and lv.slices.is_contiguous() and lv.mask.is_contiguous()
+    assert tuple(SVR._level(0, slices, mask, volume, params).psf.shape) == (13, 5, 5)  # (get_PSF caps the radius at int(2 sigma + 1) = 6)
+    assert tuple(SVR._level(1, slices, mask, volume, params).psf.shape) == (9, 5, 5)
+
+
+def test_svr_refuses_other_losses():
+    from nesvor_amd.registration import SVR
+
+    for loss in ({"name": "ncc", "win": 9}, {"name": "ssim"}, lambda s, x, y: x):
+        with pytest.raises(Exception, match="unknown loss"):
+            SVR(2, 2, 2, 5, {"name": "gd", "momentum": 0.1}, loss)
+
+
+def test_common_frame_keeps_every_pixel_in_place_and_round_trips_the_poses():
+    """Stacks of odd and even sizes padded to one square frame: where the padding is uneven the frame's centre sits half a
+    pixel off the slice's, and the frame's pose makes up for it - a pixel's world position is the same before and after,
+    and taking the shift off again restores the slice's pose."""
+    from nesvor_amd.registration import _common_frame
+    from nesvor_amd.transform import RigidTransform, mat_transform_points
+
+    res = 1.5
+    g = torch.Generator().manual_seed(5)
+    shapes = [(3, 7, 10), (2, 8, 5), (2, 10, 10), (1, 9, 6)]  # (n, h, w): even / odd paddings on either axis, and none
+    stacks = [torch.rand(n, 1, h, w, generator=g) + 0.5 for n, h, w in shapes]
+
+    def random_poses(n):  # as matrices: the axis-angle conversion is a HIP kernel
+        a = 0.5 * torch.randn(n, 3, generator=g)
+        skew = torch.zeros(n, 3, 3)
+        skew[:, 0, 1], skew[:, 0, 2], skew[:, 1, 2] = -a[:, 2], a[:, 1], -a[:, 0]
+        return RigidTransform(torch.cat([torch.linalg.matrix_exp(skew - skew.transpose(1, 2)), 10 * torch.randn(n, 3, 1, generator=g)], -1))
+
+    poses = [random_poses(n) for n, _, _ in shapes]
+    slices, frame_poses, to_frame = _common_frame(stacks, poses, res)
+    assert tuple(slices.shape) == (8, 1, 10, 10) and len(frame_poses) == 8
+    shifts = torch.stack([t.matrix()[0, :2, 3] for t in to_frame]) / res  # (x, y) in pixels
+    assert torch.equal(shifts, torch.tensor([[0.0, 0.5], [0.5, 0.0], [0.0, 0.0], [0.0, 0.5]]))
+
+    def world(pose_mats, values):  # position of every pixel of (n,1,h,w) frames centred on their poses -> (n,h,w,3)
+        h, w = values.shape[-2:]
+        y, x = torch.meshgrid(torch.arange(h) - (h - 1) / 2, torch.arange(w) - (w - 1) / 2, indexing="ij")
+        pts = torch.stack([x * res, y * res, torch.zeros_like(x)], -1)[None].expand(values.shape[0], -1, -1, -1)
+        return mat_transform_points(pose_mats[:, None, None], pts, True)
+
+    start = 0
+    for st, pose, t in zip(stacks, poses, to_frame):
+        n = st.shape[0]
+        before = world(pose.matrix(), st)[st[:, 0] > 0]
+        frames = slices[start:start + n]
+        after = world(frame_poses.matrix()[start:start + n], frames)[frames[:, 0] > 0]  # (the padding is zero, the stack is not)
+        assert before.shape == after.shape
+        torch.testing.assert_close(after, before, rtol=0, atol=1e-4)  # fp32 positions of up to ~40 mm
+        assert torch.equal(frames[:, 0][frames[:, 0] > 0], st[:, 0][st[:, 0] > 0])
+        back = frame_poses[start:start + n].compose(t.inv())
+        torch.testing.assert_close(back.matrix(), pose.matrix(), rtol=0, atol=1e-4)
+        start += n
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GPU: the kernel's sums
+# ---------------------------------------------------------------------------------------------------------------------
+_CASE = {}
+
+
+def _case(device):
+    """Volume, PSF, slices, mask and 27 poses per slice; the expected sums (composed from slice_acquisition, fp64) are
+    computed once per mask variant and shared."""
+    if _CASE:
+        return _CASE
+    from nesvor_amd.transform import RigidTransform
+    from nesvor_amd.utils import get_PSF
+
+    g = torch.Generator().manual_seed(1234)
+    D, H, W = 24, 28, 32  # non-cubic: an axis swap shows
+    z, y, x = torch.meshgrid(torch.linspace(-1, 1, D), torch.linspace(-1, 1, H), torch.linspace(-1, 1, W), indexing="ij")
+    vol = torch.exp(-2.0 * (x * x + 1.5 * y * y + 2.0 * z * z)) + 0.1 * torch.rand(D, H, W, generator=g)
+    n, K = 5, 27
+    h, w = H_W
+    base = torch.zeros(n, 6)
+    base[0, 5] = 100.0  # wholly outside the volume
+    base[1, 3] = 17.0  # half outside
+    base[2] = torch.tensor([0.10, -0.05, 0.20, 1.0, -2.0, 3.0])
+    base[3] = torch.tensor([-0.30, 0.20, 0.05, -1.5, 0.5, -4.0])
+    base[4] = torch.tensor([0.05, 0.40, -0.10, 0.0, 1.0, 1.0])
+    off = torch.cat([0.02 * torch.randn(n, K, 3, generator=g), 0.5 * torch.randn(n, K, 3, generator=g)], -1)
+    ax = (base[:, None] + off).reshape(-1, 6).to(device)
+    _CASE["transforms"] = RigidTransform(ax).matrix().view(n, K, 3, 4).contiguous()
+    _CASE["vol"] = vol.to(device).contiguous()
+    _CASE["psf"] = get_PSF(res_ratio=(1.5, 1.5, 3), device=device)
+    _CASE["slices"] = torch.rand(n, h, w, generator=g).to(device).contiguous()
+    mask = torch.rand(n, h, w, generator=g) > 0.2  # random holes
+    mask[4] = False  # ... and one slice fully masked out
+    _CASE["mask"] = mask.to(device).contiguous()
+    _CASE["expected"] = {}
+    return _CASE
+
+
+def _expected(case, masked):
+    """(n, 27, 6) fp64: per pose one slice_acquisition (need_weight, no interp_psf); valid = mask and weight > 0."""
+    if masked in case["expected"]:
+        return case["expected"][masked]
+    from nesvor_amd.slice_acquisition import slice_acquisition
+
+    tf, J = case["transforms"], case["slices"].double()
+    mask = case["mask"] if masked else None
+    out = torch.empty(tf.shape[0], tf.shape[1], 6, dtype=torch.float64, device=tf.device)
+    for k in range(tf.shape[1]):
+        I, wgt = slice_acquisition(tf[:, k].contiguous(), case["vol"][None, None], None, None if mask is None else mask[:, None],
+                                   case["psf"], H_W, RES_SLICE, True, False)
+        valid = wgt[:, 0] > 0
+        if mask is not None:
+            valid = valid & mask
+        v = valid.double()
+        Ik, Jk = I[:, 0].double() * v, J * v
+        out[:, k] = torch.stack([t.sum((1, 2)) for t in (v, Ik, Ik * Ik, Ik * Jk, Jk, Jk * Jk)], -1)
+    case["expected"][masked] = out
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("masked", [True, False])
+@pytest.mark.parametrize("K", [13, 1, 14, 27])
+def test_sums_equal_the_composed_operator(device, K, masked):
+    """Count exactly; the five sums within rtol 1e-5 / atol 1e-9.  Derived, not measured: all terms are non-negative, so the
+    fp32 pairwise sum of a wave's 64 terms is within 6 x 2^-24 ~ 4e-7 relative; a pixel value may differ from the other
+    kernel's by a few fp32 roundings; everything else is fp64 - 1e-5 leaves an order of magnitude over that."""
+    c = _case(device)
+    ref = _expected(c, masked)[:, :K]
+    out = torch.ops.nesvor.svr_similarity(c["vol"], c["psf"], c["transforms"][:, :K].contiguous(), c["slices"],
+                                          c["mask"] if masked else None, RES_SLICE)
+    assert out.shape == (5, K, 6) and out.dtype == torch.float64
+    print(f"K={K} masked={masked}: counts {out[:, 0, 0].tolist()} (expected {ref[:, 0, 0].tolist()}), "
+          f"max rel diff {float(((out - ref).abs() / ref.abs().clamp(min=1e-30)).max()):.3e}")
+    assert torch.equal(out[..., 0], ref[..., 0])
+    torch.testing.assert_close(out[..., 1:], ref[..., 1:], rtol=1e-5, atol=1e-9)
+    empty = ref[..., 0] == 0
+    assert bool(empty[0].all()) and (not masked or bool(empty[4].all()))  # the slice outside, the slice masked out
+    assert bool((ref[1:4, :, 0] > 0).all()) and float(ref[1, 0, 0]) < 0.75 * float(ref[2, 0, 0])  # half outside: fewer pixels
+    assert bool((out[empty] == 0).all())
+
+
+@pytest.mark.gpu
+def test_sums_are_reproducible(device):
+    c = _case(device)
+    args = (c["vol"], c["psf"], c["transforms"][:, :13].contiguous(), c["slices"], c["mask"], RES_SLICE)
+    assert torch.equal(torch.ops.nesvor.svr_similarity(*args), torch.ops.nesvor.svr_similarity(*args))
+
+
+@pytest.mark.gpu
+def test_refusals_and_large_psf_fallback(device, monkeypatch):
+    from nesvor_amd import _lib
+    from nesvor_amd.registration import SVR
+    from nesvor_amd.slice_acquisition import slice_acquisition
+    from nesvor_amd.transform import RigidTransform, mat_update_resolution
+
+    c = _case(device)
+    tf = c["transforms"][:, :1].contiguous()
+    big = torch.full((11, 11, 11), 1.0 / 1331, device=device)
+    lib = _lib.load()
+    sums = torch.zeros(5, 1, 6, dtype=torch.float64, device=device)
+    nbytes = lib.nesvor_svr_similarity_workspace_bytes(5, 1, *H_W)
+    assert nbytes == 8 * 6 * 5 * 1 * 2
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+    call = lambda psf, n, K, nb: lib.nesvor_svr_similarity(
+        _lib.ptr(c["vol"]), 24, 28, 32, _lib.ptr(psf), *psf.shape, _lib.ptr(tf), _lib.ptr(c["slices"]), None, n, K, *H_W, RES_SLICE,
+        _lib.ptr(sums), _lib.ptr(ws), nb, _lib.stream_ptr())
+    assert call(big, 5, 1, nbytes) != 0  # more than 1024 taps: an error, not a fault
+    assert call(c["psf"], 5, 1, nbytes - 8) != 0  # workspace too small
+    assert call(c["psf"], -1, 1, nbytes) != 0
+    assert call(c["psf"], 0, 1, nbytes) == 0 and call(c["psf"], 5, 0, nbytes) == 0  # no-ops
+    torch.cuda.synchronize()
+    assert float(sums.abs().sum()) == 0.0  # nothing was written by any of them
+    with pytest.raises(RuntimeError, match="svr similarity"):
+        torch.ops.nesvor.svr_similarity(c["vol"], big, tf, c["slices"], None, RES_SLICE)
+    with pytest.raises(RuntimeError, match="contiguous"):
+        torch.ops.nesvor.svr_similarity(c["vol"].transpose(0, 1), c["psf"], tf, c["slices"], None, RES_SLICE)
+    with pytest.raises(RuntimeError, match="contiguous"):
+        torch.ops.nesvor.svr_similarity(c["vol"], c["psf"], c["transforms"][:, :1], c["slices"], None, RES_SLICE)
+    with pytest.raises(NotImplementedError, match="Could not run 'nesvor::svr_similarity'"):
+        torch.ops.nesvor.svr_similarity(c["vol"].cpu(), c["psf"].cpu(), tf.cpu(), c["slices"].cpu(), None, RES_SLICE)
+    with pytest.raises(RuntimeError, match="torch.float32"):
+        torch.ops.nesvor.svr_similarity(c["vol"].double(), c["psf"], tf, c["slices"], None, RES_SLICE)
+
+    # SVR with a PSF the kernel refuses (3 mm pixels, 6 mm slices on 1 mm voxels: 11 x 11 x 13 elements) evaluates the loss on the
+    # composed path, by itself: the loss is the one written out here from slice_acquisition
+    params = {"res_s": 3.0, "s_thick": 6.0, "res_r": 1.0}
+    svr = SVR(1, 1, 1, 2, {"name": "gd", "momentum": 0.0}, {"name": "ncc"})
+    g = torch.Generator().manual_seed(3)
+    slices = torch.rand(3, 1, 9, 10, generator=g).to(device)
+    mask = (torch.rand(3, 1, 9, 10, generator=g) > 0.1).to(device)
+    theta = torch.tensor([[0.1, 0.0, -0.1, 1.0, 0.0, -2.0], [0.0, 0.2, 0.0, 0.0, 2.0, 3.0], [0.0, 0.0, 0.0, 0.0, 0.0, 50.0]], device=device)
+    volume = c["vol"][None, None]
+    lv = svr._level(0, slices, mask, volume, params)
+    assert lv.psf.numel() > 1024 and not svr._fused_path(lv)
+    loss = svr.evaluate(theta, slices, mask, volume, params, True)
+    mats = mat_update_resolution(RigidTransform(theta).matrix(), 1, 1.0)
+    I, wgt = slice_acquisition(mats, lv.volume[None, None], None, lv.mask[:, None], lv.psf, (9, 10), 3.0, True, False)
+    v = (lv.mask & (wgt[:, 0] > 0)).double()
+    cnt = v.sum((1, 2))
+    assert float(cnt[2]) == 0 and float(loss[2]) == 0.0 and bool((cnt[:2] > 32).all())
+    mean = lambda t: (t * v).sum((1, 2))[:2] / cnt[:2]
+    Id, Jd = I[:, 0].double(), lv.slices.double()
+    cov = mean(Id * Jd) - mean(Id) * mean(Jd)
+    ref = -(cov * cov) / ((mean(Id * Id) - mean(Id) ** 2) * (mean(Jd * Jd) - mean(Jd) ** 2) + 1e-6)
+    torch.testing.assert_close(loss[:2].double(), ref, rtol=1e-5, atol=1e-7)
+    out, _ = svr(theta, slices, mask, volume, params, True)  # ... and the descent runs on it
+    assert torch.isfinite(out).all() and torch.equal(out[2], theta[2])  # (no valid pixel: the pose is kept)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GPU: the descent
+# ---------------------------------------------------------------------------------------------------------------------
+def _pose_errors(theta, true_tf, keep):
+    """Median rotation error (degrees) and translation error (mm, of the slice centre in the world) over `keep`."""
+    from nesvor_amd.transform import RigidTransform
+
+    a, b = RigidTransform(theta).matrix(trans_first=False)[keep], true_tf.matrix(trans_first=False)[keep]
+    rel = a[:, :, :3].transpose(1, 2) @ b[:, :, :3]
+    cos = ((rel[:, 0, 0] + rel[:, 1, 1] + rel[:, 2, 2] - 1) / 2).clamp(-1, 1)
+    return float(torch.rad2deg(torch.acos(cos)).median()), float((a[:, :, 3] - b[:, :, 3]).norm(dim=1).median())
+
+
+@pytest.mark.gpu
+def test_fused_descent_follows_its_definition_and_recovers_motion(device, monkeypatch):
+    from nesvor_amd.phantom import phantom3d, simulate_stacks
+    from nesvor_amd.registration import SVR
+
+    vol = torch.tensor(phantom3d(n=64), dtype=torch.float32, device=device)
+    slices, true_tf = simulate_stacks(vol, n_stacks=1, res_s=1.5, s_thick=3, motion_deg=3, motion_mm=1.5, seed=0)
+    images = torch.stack([s.image for s in slices]).contiguous()  # (n,1,h,w)
+    mask = torch.stack([s.mask for s in slices]).contiguous()
+    theta0 = torch.cat([s.transformation.axisangle() for s in slices], 0)
+    keep = mask.flatten(1).sum(1) >= 200
+    assert int(keep.sum()) >= 15
+    params = {"res_s": 1.5, "s_thick": 3.0, "res_r": 1.0}
+    volume = vol[None, None]
+    new = lambda: SVR(num_levels=2, num_steps=3, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1}, loss={"name": "ncc"})
+    monkeypatch.delenv("NESVOR_SVR", raising=False)
+    svr = new()
+    loss0 = svr.evaluate(theta0, images, mask, volume, params, True)
+    theta_f, loss_f = svr(theta0.clone(), images, mask, volume, params, True)
+    monkeypatch.setenv("NESVOR_SVR", "composed")
+    theta_c, loss_c = new()(theta0.clone(), images, mask, volume, params, True)
+    monkeypatch.delenv("NESVOR_SVR")
+    rot0, tr0 = _pose_errors(theta0, true_tf, keep)
+    rot_f, tr_f = _pose_errors(theta_f, true_tf, keep)
+    rot_c, tr_c = _pose_errors(theta_c, true_tf, keep)
+    print(f"median errors (deg, mm): start {rot0:.3f} {tr0:.3f}; fused {rot_f:.3f} {tr_f:.3f}; composed {rot_c:.3f} {tr_c:.3f}; "
+          f"loss start {float(loss0[keep].mean()):.4f} fused {float(loss_f[keep].mean()):.4f} composed {float(loss_c[keep].mean()):.4f}; "
+          f"worst loss change {float((loss_f - loss0)[keep].max()):.3e}")
+    assert bool((loss_f[keep] <= loss0[keep]).all())
+    assert rot_f < rot0 and tr_f < tr0
+    assert rot_c < rot0 and tr_c < tr0  # (the yardstick itself works at this input)
+    # against the composed path on the same input; 25 %: accept / reject decisions that flip on near-ties between two
+    # summation orders.  Composed path, measured once on MI355X: median errors 0.955 deg / 0.465 mm (start 4.189 deg / 2.527 mm)
+    assert rot_f <= 1.25 * rot_c and tr_f <= 1.25 * tr_c
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GPU: pipeline and command line
+# ---------------------------------------------------------------------------------------------------------------------
+_RES_S, _THICK = 1.5, 3.0
+
+
+def _phantom_stacks(device):
+    """Three 48^3-phantom stacks with inter-slice motion, at their nominal poses."""
+    from nesvor_amd.image import Stack
+    from nesvor_amd.phantom import phantom3d, simulate_stacks
+    from nesvor_amd.transform import RigidTransform
+
+    vol = torch.tensor(phantom3d(n=48), dtype=torch.float32, device=device)
+    slices, _ = simulate_stacks(vol, n_stacks=3, res_s=_RES_S, s_thick=_THICK, motion_deg=2, motion_mm=1, seed=0)
+    n = len(slices) // 3
+    stacks = []
+    for j in range(3):
+        ss = slices[j * n:(j + 1) * n]
+        img = torch.stack([s.image for s in ss]).contiguous()
+        stacks.append(Stack(img, img > 0, RigidTransform.cat([s.transformation for s in ss]), resolution_x=_RES_S, resolution_y=_RES_S,
+                            thickness=_THICK, gap=_THICK))
+    return stacks
+
+
+def _simulated_ncc(stacks):
+    """Mean over the non-empty slices of the global NCC between the acquired slices and the slices simulated from the volume
+    reconstructed at the stacks' poses (the reference's ``simulated_ncc``); lower = better."""
+    from nesvor_amd.registration import _cover_shape, reconstruct_from_slices
+    from nesvor_amd.slice_acquisition import slice_acquisition
+    from nesvor_amd.transform import RigidTransform, mat_update_resolution
+    from nesvor_amd.utils import get_PSF, ncc_loss
+
+    img = torch.cat([s.slices * s.mask for s in stacks]).contiguous()
+    poses = RigidTransform.cat([s.transformation for s in stacks])
+    m = img > 0
+    keep = m.flatten(1).any(1)
+    img, m, poses = img[keep].contiguous(), m[keep].contiguous(), poses[keep]
+    mats = mat_update_resolution(poses.matrix(), 1, _RES_S)
+    volume = reconstruct_from_slices(mats, img, _RES_S, _THICK, _RES_S, _cover_shape(poses, m, _RES_S, _THICK, _RES_S))
+    sim = slice_acquisition(mats, volume, None, m, get_PSF(res_ratio=(1, 1, _THICK / _RES_S), device=img.device), img.shape[-2:], 1.0,
+                            False, False)
+    return float(ncc_loss(sim, img, m, win=None, reduction="none").mean())
+
+
+@pytest.mark.gpu
+def test_register_slices_improves_on_stack_registration_and_is_reproducible(device):
+    from nesvor_amd.registration import register_slices, register_stacks
+
+    ncc_stack = _simulated_ncc(register_stacks(_phantom_stacks(device), res_s=_RES_S))
+    first = register_slices(_phantom_stacks(device), res_s=_RES_S)
+    ncc_svr = _simulated_ncc(first)
+    print(f"mean simulated NCC: stack registration {ncc_stack:.4f}, slice registration {ncc_svr:.4f}")
+    assert ncc_svr < ncc_stack
+    second = register_slices(_phantom_stacks(device), res_s=_RES_S)
+    for a, b in zip(first, second):
+        assert torch.equal(a.transformation.matrix(), b.transformation.matrix())
+
+
+@pytest.mark.gpu
+def test_cli_register_svr(tmp_path, device):
+    from nesvor_amd import cli
+    from nesvor_amd.image import Volume
+    from nesvor_amd.transform import RigidTransform
+
+    paths, n_nonempty = [], 0
+    for j, st in enumerate(_phantom_stacks(device)):
+        img = st.slices[:, 0]
+        n_nonempty += int((img > 0).flatten(1).any(1).sum())
+        ax = st.transformation.axisangle().mean(0, keepdim=True)  # stack centre pose
+        p = str(tmp_path / f"stack{j}.nii.gz")
+        Volume(img, img > 0, RigidTransform(ax), _RES_S, _RES_S, _THICK).save(p, masked=False)
+        paths.append(p)
+    out = str(tmp_path / "slices")
+    cli.main(["register", "--input-stacks", *paths, "--thicknesses", "3", "3", "3", "--registration", "svr", "--output-slices", out,
+              "--verbose", "0"])
+    assert len([f for f in os.listdir(out) if not f.startswith("mask")]) == n_nonempty > 30
+    with pytest.raises(NotImplementedError, match="svr"):
+        cli.main(["register", "--input-stacks", *paths, "--registration", "svort", "--output-slices", str(tmp_path / "never"),
+                  "--verbose", "0"])
