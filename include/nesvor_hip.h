@@ -826,6 +826,21 @@ int nesvor_svr_similarity(const float* vol, int D, int H, int W, const float* ps
                           int w, float res_slice, double* sums, void* workspace, size_t workspace_bytes, void* stream);
 int64_t nesvor_svr_similarity_workspace_bytes(int n, int K, int h, int w);
 
+/* ----------------------------------------------------------------------
+ * One descent step of the classical super-resolution reconstruction with the edge-preserving prior, in one launch
+ * (the loop body of the reference's SRR, svort/srr.py:117-131, whose prior gradient dR is :139-160):
+ *   out[a] = x[a] - alpha * (grad[a] + beta * dR(x)[a])
+ * x, grad, out (D,H,W) fp32.  For an interior voxel dR is the sum over its 26 neighbours o of  t / sqrt(1 + d t),
+ * d = x[a] - x[a+o], t = d / (|o|^2 delta^2); dR is 0 on every border voxel (everywhere when min(D,H,W) < 3), where the
+ * result is x - alpha * grad exactly.  beta is the effective multiplier (the reference's beta * delta^2).  clamp != 0:
+ * negative results become 0, NaN stays NaN.  The 26 terms are added in a fixed order without atomics: bit-reproducible.
+ * out == grad is allowed (saves a buffer).  hipErrorInvalidValue, without a launch: a null pointer, a dimension below 1,
+ * D H W > INT_MAX, out overlapping x (the stencil reads neighbours), out overlapping grad partially.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbol to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_srr_step(const float* x, const float* grad, float* out, int D, int H, int W, float alpha, float beta,
+                    float delta, int clamp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,10 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
                                            | --input-slices DIR   --output-volume v.nii.gz [--output-model m.pt]
                                            [--output-slices DIR] [--simulated-slices DIR]  [training flags]
     python -m nesvor_amd.cli register      --input-stacks a.nii.gz b.nii.gz --output-slices DIR [--registration stack|svr|none]
+    python -m nesvor_amd.cli svr           --input-stacks a.nii.gz b.nii.gz c.nii.gz [--stack-masks ...] [--thicknesses ...]
+                                           | --input-slices DIR   --output-volume v.nii.gz [--output-slices DIR]
+                                           [--simulated-slices DIR] [--registration svr|stack|none] [--output-resolution 0.8]
+                                           [--n-iter-srr 30] [--srr-beta 0.02] [--srr-delta 0.1]
     python -m nesvor_amd.cli sample-volume --input-model m.pt --output-volume v.nii.gz [--output-resolution 0.8] ...
     python -m nesvor_amd.cli sample-slices --input-model m.pt --input-slices DIR --simulated-slices DIR
 
@@ -20,6 +24,9 @@ the kernels' bias-free forms, and ``--fp16-loss-scaling`` with fp16 operands und
 
 Not in the reference (it is single-process): ``torchrun --nproc-per-node N -m nesvor_amd.cli reconstruct ...`` trains data-parallel,
 one process per GPU (nesvor_amd/ddp.py); rank 0 samples and writes the outputs.  The other commands stay single-process.
+
+Also not in the reference: ``svr``, the classical pipeline without an INR - registration (default ``svr``), then a
+super-resolution reconstruction by gradient descent with the edge-preserving prior (nesvor_amd/svr.py, csrc/srr.hip).
 """
 import argparse
 import logging
@@ -127,6 +134,27 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_argument_group("registration")
     g.add_argument("--registration", default="stack", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
+    _common_flags(p)
+
+    p = sub.add_parser("svr")
+    g = p.add_argument_group("input")
+    g.add_argument("--input-stacks", nargs="+", type=str)
+    g.add_argument("--thicknesses", nargs="+", type=float)
+    g.add_argument("--stack-masks", nargs="+", type=str)
+    g.add_argument("--input-slices", type=str)
+    g = p.add_argument_group("output")
+    g.add_argument("--output-volume", type=str, required=True)
+    g.add_argument("--output-resolution", default=0.8, type=float)
+    g.add_argument("--output-intensity-mean", default=700.0, type=float)
+    g.add_argument("--output-slices", type=str)
+    g.add_argument("--simulated-slices", type=str)
+    g = p.add_argument_group("registration")
+    g.add_argument("--registration", default="svr", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
+    g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
+    g = p.add_argument_group("super-resolution reconstruction")
+    g.add_argument("--n-iter-srr", default=30, type=int, help="descent steps")
+    g.add_argument("--srr-beta", default=0.02, type=float, help="weight of the edge-preserving prior")
+    g.add_argument("--srr-delta", default=0.1, type=float, help="edge scale of the prior, in normalised intensities")
     _common_flags(p)
 
     p = sub.add_parser("sample-volume")
@@ -327,6 +355,12 @@ def reconstruct(args: Namespace) -> None:
             dist.destroy_process_group()
 
 
+def svr_cmd(args: Namespace) -> None:
+    from .svr import svr_command
+
+    _outputs(svr_command(args), args)
+
+
 def sample_volume_cmd(args: Namespace) -> None:
     from .sample import sample_volume
 
@@ -353,7 +387,7 @@ def main(argv=None) -> None:
         return  # under a launcher only `reconstruct` is data-parallel: one process does the rest
     _setup(args)
     t0 = time.time()
-    {"reconstruct": reconstruct, "register": register_cmd, "sample-volume": sample_volume_cmd,
+    {"reconstruct": reconstruct, "register": register_cmd, "svr": svr_cmd, "sample-volume": sample_volume_cmd,
      "sample-slices": sample_slices_cmd}[args.command](args)
     logging.info("Command 'nesvor %s' finished, overall time: %.1f s", args.command, time.time() - t0)
 

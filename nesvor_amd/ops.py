@@ -313,6 +313,39 @@ _op("svr_similarity(Tensor vol, Tensor psf, Tensor transforms, Tensor slices, Te
 
 
 # =====================================================================================================================
+# one descent step of the classical reconstruction with the edge-preserving prior (csrc/srr.hip):
+# out = x - alpha (grad + beta dR(x)), dR = srr.edge_prior_gradient, in one launch
+# =====================================================================================================================
+def srr_step_into(x, grad, out, alpha, beta, delta, clamp):
+    """``out`` <- the step; ``out`` may be ``grad`` itself, must not overlap ``x`` (the library refuses it).  Returns ``out``."""
+    _lib.require_device(x, grad, out, dtype=torch.float32, name="srr_step x/grad/out")
+    if x.ndim < 3 or x.numel() != int(x.shape[-3]) * int(x.shape[-2]) * int(x.shape[-1]):
+        raise RuntimeError("srr_step: one volume (..., D, H, W) expected")
+    if grad.shape != x.shape or out.shape != x.shape:
+        raise RuntimeError("srr_step: x, grad and out must have one shape")
+    with torch.cuda.device(x.device):
+        err = _lib.load().nesvor_srr_step(_lib.ptr(x), _lib.ptr(grad), _lib.ptr(out), *(int(s) for s in x.shape[-3:]), float(alpha),
+                                          float(beta), float(delta), int(bool(clamp)), _lib.stream_ptr())
+    _lib.check(err, "srr step")
+    return out
+
+
+def _srr_step(x, grad, alpha, beta, delta, clamp):
+    return srr_step_into(x, grad, torch.empty_like(x), alpha, beta, delta, clamp)
+
+
+def _srr_step_inplace(x, grad, alpha, beta, delta, clamp):
+    srr_step_into(x, grad, grad, alpha, beta, delta, clamp)
+
+
+_op("srr_step(Tensor x, Tensor grad, float alpha, float beta, float delta, bool clamp) -> Tensor", _srr_step,
+    fake=lambda x, grad, alpha, beta, delta, clamp: torch.empty_like(x))
+# the same step written over the gradient (out == grad): the solver's loop needs no third volume
+_op("srr_step_(Tensor x, Tensor(a!) grad, float alpha, float beta, float delta, bool clamp) -> ()", _srr_step_inplace,
+    fake=lambda *a: None)
+
+
+# =====================================================================================================================
 # multi-resolution hash-grid encoding (tinycudann.Encoding "HashGrid"; the scalars are its encoding_config)
 # =====================================================================================================================
 _SPECS = {}

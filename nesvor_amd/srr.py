@@ -6,9 +6,12 @@ with its exact adjoint A^T, both native HIP kernels (csrc/slice_acq.hip).  On to
 * ``conjugate_gradient`` solves the (weighted, optionally Tikhonov-damped) normal equations; every scalar of the
   recurrence stays a 0-d device tensor, so an n-iteration solve issues no host synchronisation unless ``tol`` > 0;
 * ``SRR`` with ``use_CG=False`` runs the reference's gradient descent with the edge-preserving prior; the prior's
-  gradient is evaluated for all 26 neighbours at once instead of one sliced pass per neighbour.
+  gradient is evaluated for all 26 neighbours at once instead of one sliced pass per neighbour;
+* ``srr_descent`` is that descent as a function of the operator, with a step length bounded from the operator itself
+  (``descent_step_bound``) and, on a HIP fp32 volume, the whole update in one launch (``nesvor_srr_step``, csrc/srr.hip).
 Host logic only; SURVEY.md 8(f) rank 1.
 """
+import os
 from typing import Callable, Optional
 
 import torch
@@ -149,3 +152,60 @@ class SRR(nn.Module):
     @staticmethod
     def dR(v, delta):
         return edge_prior_gradient(v, delta)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the descent as a solver of its own: a step length that is safe for any number of stacks, the update in one launch
+# ---------------------------------------------------------------------------------------------------------------------
+# Gershgorin bound of the prior's Jacobian in units of 1 / delta^2: the slope of t / sqrt(1 + d t) in d is at most
+# 1 / (|o|^2 delta^2); a row holds it once on the diagonal and once off it for each of the 6 + 12 + 8 neighbours
+PRIOR_SLOPE_BOUND = 2 * (6 + 12 / 2 + 8 / 3)
+
+
+def descent_step_bound(op, p: Optional[torch.Tensor], beta_eff: float, like: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """L = max_v (A^T (p * A 1))_v + PRIOR_SLOPE_BOUND * beta_eff, a 0-d tensor: an upper bound of the largest eigenvalue of
+    the descent's Hessian  A^T diag(p) A + multiplier * J(dR).  A^T diag(p) A is symmetric with non-negative entries, so its
+    largest row sum - one forward of a volume of ones and one adjoint - bounds its norm; the second term bounds the prior's
+    Jacobian by Gershgorin.  ``beta_eff`` is the prior's multiplier in units of the slope bound 1 / delta^2, that is the
+    multiplier of dR divided by delta^2 (the ``beta`` of ``SRR``'s constructor and of ``srr_descent``).  With alpha = 1 / L
+    a step cannot increase the quadratic data term, whatever the number of overlapping stacks.  ``like``: a volume whose
+    shape, dtype and device the volume of ones takes (default: ``op.volume_shape`` on ``op.transforms``'s)."""
+    if like is None:
+        like = torch.empty((1, 1) + tuple(int(s) for s in op.volume_shape), dtype=op.transforms.dtype, device=op.transforms.device)
+    cover = op.forward(torch.ones_like(like))
+    return op.adjoint(cover if p is None else cover * p).max() + PRIOR_SLOPE_BOUND * beta_eff
+
+
+def _fused_step(x: torch.Tensor) -> bool:
+    return os.environ.get("NESVOR_SRR", "") != "composed" and x.is_cuda and x.dtype == torch.float32
+
+
+def srr_descent(op, slices: torch.Tensor, volume: torch.Tensor, n_iter: int, beta: float, delta: float,
+                p: Optional[torch.Tensor] = None, alpha: Optional[float] = None, clamp_every: bool = False) -> torch.Tensor:
+    """``n_iter`` steps of the reference's descent (srr.py:117-131)
+        x <- x - alpha (A^T (p * (A x - y)) + beta delta^2 dR(x)),
+    the result clamped at 0 after the last step (``clamp_every``: after every step).  ``alpha=None``: 1 / L of
+    ``descent_step_bound`` (read back once, before the loop; the loop itself issues no host synchronisation).  ``volume``
+    (1,1,D,H,W), the shape the adjoint returns, is left as it is.  On a HIP fp32 volume the update is ``torch.ops.nesvor.srr_step_`` (csrc/srr.hip), written over the
+    gradient the adjoint just returned, so the iterate and the gradient ping-pong between two buffers; ``NESVOR_SRR=composed``,
+    a host tensor or another dtype take the torch expression of ``SRR.forward`` (``edge_prior_gradient``)."""
+    beta_eff = beta * delta * delta
+    if alpha is None:
+        alpha = 1.0 / float(descent_step_bound(op, p, beta, like=volume))
+    alpha = float(alpha)  # (a device scalar is read here, not once per step)
+    fused = _fused_step(volume)
+    x = volume.contiguous() if fused else volume.clone()
+    for it in range(n_iter):
+        misfit = op.forward(x) - slices
+        grad = op.adjoint(misfit if p is None else misfit * p)
+        clamp = clamp_every or it + 1 == n_iter
+        if fused:
+            torch.ops.nesvor.srr_step_(x, grad, alpha, beta_eff, delta, clamp)
+            x = grad
+        else:
+            if beta_eff:
+                grad.add_(edge_prior_gradient(x, delta), alpha=beta_eff)
+            x.sub_(grad, alpha=alpha)
+            if clamp:
+                x.clamp_(min=0)
+    return x if n_iter > 0 else volume.clamp(min=0)

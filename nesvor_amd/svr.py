@@ -1,0 +1,147 @@
+"""Classical slice-to-volume reconstruction (the ``svr`` command): motion-corrected slices -> a volume, without training
+an INR.  The pipeline the survey's row f1 calls "a classical SRR baseline": the slices of all stacks on one padded frame
+(``registration._common_frame``), a world-aligned volume that covers them (``registration._cover_shape``), the equalised
+back-projection ``PSFreconstruction`` as start and ``srr.srr_descent`` - gradient descent on the weighted data term with the
+edge-preserving prior, one fused HIP launch per update (csrc/srr.hip) - to refine it.
+
+Out of scope here: outlier rejection, per-slice intensity scales, per-stack PSFs for unequal thicknesses (the mean thickness
+is used, as the registration does) and a volume mask input.
+"""
+import logging
+import time
+from argparse import Namespace
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from .image import Slice, Volume
+from .registration import _common_frame, _cover_shape, resample
+from .srr import AcquisitionOperator, PSFreconstruction, srr_descent
+from .transform import RigidTransform, mat_update_resolution
+from .utils import get_PSF
+
+MIXED_SLICES_MESSAGE = ("--input-slices needs slices of one pixel size and one thickness (what the `register` command writes); "
+                        "pass the stacks through --input-stacks instead")
+
+
+def _as_list(v) -> List:
+    return list(v) if isinstance(v, (list, tuple)) else [v]
+
+
+def _frame(slices, mask, poses, res_s: float) -> Tuple[torch.Tensor, torch.Tensor, RigidTransform]:
+    """Stacks (n_j,1,h_j,w_j) (or one), their masks (or None: the non-zero pixels) and poses -> the non-empty slices on one
+    padded frame (n,1,s,s), their masks (the non-zero masked pixels) and the frames' poses."""
+    stacks, poses = _as_list(slices), _as_list(poses)
+    if mask is not None:
+        stacks = [s * m.to(s.dtype) for s, m in zip(stacks, _as_list(mask))]
+    images, frame_poses, _ = _common_frame(stacks, poses, res_s)
+    m = images > 0
+    keep = torch.nonzero(m.flatten(1).any(1)).flatten()
+    return images[keep].contiguous(), m[keep].contiguous(), frame_poses[keep]
+
+
+def _operator(images: torch.Tensor, m: torch.Tensor, frame_poses: RigidTransform, res_s: float, s_thick: float, res_r: float,
+              volume_shape: Sequence[int]) -> Tuple[AcquisitionOperator, Dict]:
+    params = {"psf": get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / res_r), device=images.device),
+              "slice_shape": images.shape[-2:], "interp_psf": False, "res_s": res_s, "res_r": res_r, "s_thick": s_thick,
+              "volume_shape": tuple(int(s) for s in volume_shape)}
+    mats = mat_update_resolution(frame_poses.matrix(), 1, res_r).contiguous()
+    return AcquisitionOperator(mats, params, None, m), params
+
+
+def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r: float, n_iter: int = 30, beta: float = 0.02,
+                       delta: float = 0.1) -> Volume:
+    """Slices at their poses -> the reconstructed ``Volume``: world-aligned (identity pose, centred at the origin), voxel size
+    ``res_r``, large enough for every masked pixel; its mask is the set of voxels a masked pixel's PSF reaches (A^T 1 > 0).
+
+    slices: a stack (n,1,h,w) of ``res_s`` pixels or a list of stacks; mask: the same of bool, or None (the non-zero pixels);
+    poses: a ``RigidTransform`` per stack (one pose per slice).  ``beta`` / ``delta``: the prior's weight and edge scale as the
+    reference's ``SRR`` takes them; ``n_iter`` descent steps of length 1 / L (``srr.descent_step_bound``) from the equalised
+    back-projection."""
+    images, m, frame_poses = _frame(slices, mask, poses, res_s)
+    if images.shape[0] == 0:
+        raise ValueError("reconstruct_volume: every slice is empty")
+    shape = _cover_shape(frame_poses, m, res_s, s_thick, res_r)
+    op, params = _operator(images, m, frame_poses, res_s, s_thick, res_r, shape)
+    start = PSFreconstruction(op.transforms, images, m, None, params)
+    x = srr_descent(op, images, start, n_iter, beta, delta)
+    cover = op.adjoint(torch.ones_like(images)) > 0
+    return Volume(x[0, 0], cover[0, 0], None, res_r, res_r, res_r)
+
+
+def simulate_slices(volume: Volume, slices, mask, poses, res_s: float, s_thick: float) -> List[Slice]:
+    """A x at the slices' poses through the acquisition operator: one ``Slice`` (on the padded frame, with the frame's pose and
+    the acquired slice's mask) per non-empty input slice."""
+    images, m, frame_poses = _frame(slices, mask, poses, res_s)
+    res_r = float(volume.resolution_x)
+    op, _ = _operator(images, m, frame_poses, res_s, s_thick, res_r, volume.image.shape)
+    sim = op.forward(volume.image[None, None].contiguous())
+    return [Slice(sim[k], m[k], frame_poses[k], res_s, res_s, s_thick) for k in range(sim.shape[0])]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the command
+# ---------------------------------------------------------------------------------------------------------------------
+def _group(slices: List[Slice], res_s: Optional[float]) -> Tuple[List[torch.Tensor], List[torch.Tensor], List[RigidTransform], float]:
+    """Runs of slices with one shape and pixel size -> stacks (n_j,1,h,w) resampled in-plane to ``res_s`` (None: the finest
+    pixel size among them), their masks and poses.  ``resample`` keeps the centre of the frame, so the poses stay."""
+    if res_s is None:
+        res_s = min(min(float(s.resolution_x), float(s.resolution_y)) for s in slices)
+    key = lambda s: (tuple(s.image.shape), float(s.resolution_x), float(s.resolution_y))
+    runs: List[List[Slice]] = []
+    for s in slices:
+        if runs and key(runs[-1][0]) == key(s):
+            runs[-1].append(s)
+        else:
+            runs.append([s])
+    stacks, masks, poses = [], [], []
+    for run in runs:
+        img = torch.stack([s.image * s.mask.to(s.image.dtype) for s in run])  # (n,1,h,w)
+        rx, ry = float(run[0].resolution_x), float(run[0].resolution_y)
+        if abs(rx - res_s) > 1e-3 * res_s or abs(ry - res_s) > 1e-3 * res_s:
+            img = resample(img, (rx, ry), (res_s, res_s))
+        stacks.append(img.contiguous())
+        masks.append(img > 0)
+        poses.append(RigidTransform.cat([s.transformation for s in run]))
+    return stacks, masks, poses, res_s
+
+
+def svr_command(args: Namespace) -> Dict:
+    """``nesvor_amd.cli svr``: load, register (``cli.register``), reconstruct; returns what ``cli._outputs`` writes."""
+    from . import cli
+    from .image_io import load_slices
+
+    if args.input_slices is None and args.input_stacks is None:
+        raise SystemExit("No image data provided! Use --input-slices or --input-stacks to input data.")
+    t0 = time.time()
+    if args.input_slices is not None:
+        if args.input_stacks or args.stack_masks or args.thicknesses:
+            logging.warning("Since <input-slices> is provided, <input-stacks>, <stack_masks> and <thicknesses> would be ignored.")
+        slices = [s for s in load_slices(args.input_slices, args.device) if bool(s.mask.any())]
+        if not slices:
+            raise SystemExit("No non-empty slice found in --input-slices")
+        sizes = [(float(s.resolution_x), float(s.resolution_y), float(s.resolution_z)) for s in slices]
+        res_s, s_thick = sizes[0][0], sizes[0][2]
+        if any(abs(rx - res_s) > 1e-3 or abs(ry - res_s) > 1e-3 or abs(rz - s_thick) > 1e-3 for rx, ry, rz in sizes):
+            raise SystemExit(MIXED_SLICES_MESSAGE)
+        stacks, masks, poses, res_s = _group(slices, res_s)
+    else:
+        loaded = cli._load_stacks(args)
+        thick = [float(s.thickness) for s in loaded]
+        s_thick = sum(thick) / len(thick)
+        if max(thick) - min(thick) > 0.01 * s_thick:
+            logging.warning("The stacks' thicknesses differ (%s): the mean, %.3f mm, is used for all of them", thick, s_thick)
+        slices = cli.register(args, loaded)  # non-empty slices, each stack normalised by its 0.99 quantile
+        stacks, masks, poses, res_s = _group(slices, None)
+    logging.info("Data loading and registration finished in %.1f s (%d slices, pixel size %.3f mm, thickness %.3f mm)",
+                 time.time() - t0, len(slices), res_s, s_thick)
+    t0 = time.time()
+    volume = reconstruct_volume(stacks, masks, poses, res_s, s_thick, args.output_resolution, args.n_iter_srr, args.srr_beta,
+                                args.srr_delta)
+    if args.device.type == "cuda":
+        torch.cuda.synchronize(args.device)
+    logging.info("Reconstruction finished in %.1f s (volume %s)", time.time() - t0, tuple(volume.image.shape))
+    data = {"output_volume": volume, "output_slices": slices}
+    if args.simulated_slices:
+        data["simulated_slices"] = simulate_slices(volume, stacks, masks, poses, res_s, s_thick)
+    return data
