@@ -11,7 +11,7 @@ from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int32, c_int6
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# NESVOR_HIP_LIB: load another build of the same ABI (tools/ablate_hashgrid.py times variants of one kernel this way)
+# NESVOR_HIP_LIB: load another build of the same ABI (tools/hg_variants.py times variants of one kernel this way)
 LIB_PATH = os.environ.get("NESVOR_HIP_LIB") or os.path.join(_HERE, "lib", "libnesvor_hip.so")
 MAX_LEVELS = 32
 ABI_VERSION = 38

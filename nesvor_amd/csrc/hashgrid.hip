@@ -53,18 +53,9 @@
 #include "adam.h"
 #include "../../include/nesvor_hip.h"
 
-// Timing ablations (tools/ablate_hashgrid.py): -DNESVOR_ABLATE=<bits> compiles pieces of the aggregation pass out.
-// Results are wrong with any bit set; the default build has none.
-#ifndef NESVOR_ABLATE
-#define NESVOR_ABLATE 0
-#endif
-#define NESVOR_ABL(bit) ((NESVOR_ABLATE & (bit)) != 0)
-#ifndef NESVOR_SORT_SPAN
-#define NESVOR_SORT_SPAN 256  // samples sorted together by Morton code: the whole workgroup (64 = per wave and 128: same time within 1 %)
-#endif
-
 namespace {
 
+constexpr int kSortSpan = 256;  // samples sorted together by Morton code: the whole workgroup (measured: 64 = per wave and 128 take the same time within 1 %; not kept)
 constexpr uint32_t kPrimeY = 2654435761u;
 constexpr uint32_t kPrimeZ = 805459861u;
 
@@ -204,19 +195,19 @@ __device__ __forceinline__ uint32_t cloud_sort_key(const nesvor_grid_t& g, bool 
 }
 
 // Lattice box of a cloud at one level, from the cloud's bounding box [ulo, uhi] (locate() is monotone in u): first cell (x, y, z),
-// cells spanned - 1 (x, y, z; they wrap for out-of-range input), vertices of the box (0: it does not fit `max_slots`, or boxes
-// are off), largest slot a sample's first corner may take.  The per-cloud forward and the aggregation pass both call this.
-__device__ __forceinline__ void lattice_box(const LevelParams& p, const float (&ulo)[3], const float (&uhi)[3], bool boxes_on, uint32_t max_slots,
+// cells spanned - 1 (x, y, z; they wrap for out-of-range input), vertices of the box (0: it does not fit `max_slots`),
+// largest slot a sample's first corner may take.  The per-cloud forward and the aggregation pass both call this.
+__device__ __forceinline__ void lattice_box(const LevelParams& p, const float (&ulo)[3], const float (&uhi)[3], uint32_t max_slots,
                                             uint32_t (&b)[8]) {
   const CellPos blo = locate(p, ulo[0], ulo[1], ulo[2]), bhi = locate(p, uhi[0], uhi[1], uhi[2]);
   const uint32_t ex = bhi.gx - blo.gx, ey = bhi.gy - blo.gy, ez = bhi.gz - blo.gz;
-  const bool fits = boxes_on && ex < max_slots && ey < max_slots && ez < max_slots &&
+  const bool fits = ex < max_slots && ey < max_slots && ez < max_slots &&
                     (uint64_t)(ex + 2u) * (ey + 2u) * (ez + 2u) <= (uint64_t)max_slots;
   const uint32_t nx = ex + 2u, nxy = nx * (ey + 2u), vol = fits ? nxy * (ez + 2u) : 0u;
   b[0] = blo.gx; b[1] = blo.gy; b[2] = blo.gz; b[3] = ex; b[4] = ey; b[5] = ez; b[6] = vol;
   b[7] = fits ? vol - 2u - nx - nxy : 0u;  // = slot (inside the box) of the first corner of the box's last cell
 }
-// Address bits of the spatially addressed merge table (NESVOR_HG_SPATIAL), a | b << 8 | c << 16 for x, y, z: dealt one at a time
+// Address bits of the spatially addressed merge table, a | b << 8 | c << 16 for x, y, z: dealt one at a time
 // to the axis whose box extent per slot is the largest.
 __device__ __forceinline__ uint32_t window_bits(uint32_t ex, uint32_t ey, uint32_t ez, int log2_slots) {
   const uint32_t vx = min(ex, 1023u) + 2u, vy = min(ey, 1023u) + 2u, vz = min(ez, 1023u) + 2u;
@@ -232,18 +223,18 @@ __device__ __forceinline__ uint32_t window_bits(uint32_t ex, uint32_t ey, uint32
 
 // ---- what the aggregation pass of the backward (hashgrid_bwd_aggregate below) derives from the sample positions alone, and the
 // per-cloud forward can therefore hand to it
-#ifndef NESVOR_HG_SLOTS
-#define NESVOR_HG_SLOTS 1024      // merge-table slots at F <= 2.  A/B (gpurun_out/s2j2): 2048 slots at two workgroups per CU (66 KB of LDS) let levels
-                                  // 12-13 take the box path, and the pass goes from 0.346 to 0.505 ms: it lives on its four waves per SIMD
-#endif
+constexpr int kAggSlotsF2 = 1024;            // merge-table slots at F <= 2.  Measured: 2048 slots at two workgroups per CU (66 KB of LDS) let levels
+                                              // 12-13 take the box path, and the pass goes from 0.346 to 0.505 ms: it lives on its four waves per SIMD; not kept
+constexpr int kAggMinBlocks = 4;              // workgroups per CU of the aggregation pass at F <= 2 (its launch bound)
+constexpr int kFwdCloudSlots = 512;           // slots per LDS copy of the per-cloud forward at F <= 2 (measurements at its kSlots)
 constexpr int kMaxChunks = 256;               // table chunks (queues) per level
 constexpr int kAggMaxGroup = 8;               // levels per box round of the aggregation pass
-template <int F> constexpr int agg_slots() { return F <= 2 ? NESVOR_HG_SLOTS : (F == 4 ? 512 : 256); }
+template <int F> constexpr int agg_slots() { return F <= 2 ? kAggSlotsF2 : (F == 4 ? 512 : 256); }
 // Cloud plan: one record of plan_words(L) 32-bit words per workgroup (R = plan_rows(L) = L + 1 rounded up to a multiple of 4, so
 // that every array starts on a 16-byte boundary; 1152 bytes at L = 16):
 //   [0, 6)   bounding box of the cloud's samples (float bits: min x, y, z, max x, y, z)
 //   [6]      box_end (levels [0, box_end) address the merge table by box slot)        [7]  0
-//   [8, 8 + 8 R)   lbox[level][8] as lattice_box() returns it with agg_slots<F>() slots and the plan's box_slots switch
+//   [8, 8 + 8 R)   lbox[level][8] as lattice_box() returns it with agg_slots<F>() slots
 //   then R words each: lwin[], slot_off[], bkt_off[], grp_end[], rnd_slots[], rnd_bkts[] - window_bits() and the
 //   RoundSchedule of levels [0, L) under agg_slots<F>() slots, kMaxChunks buckets, kAggMaxGroup levels per round and the
 //   backward plan's n_chunks[]; rows of levels >= L are zero.
@@ -252,7 +243,6 @@ __host__ __device__ constexpr uint32_t plan_rows(int L) { return (uint32_t)(L + 
 __host__ __device__ constexpr uint32_t plan_words(int L) { return 8u + 14u * plan_rows(L); }
 struct CloudPlanArgs {  // what the forward needs of the backward's BwdPlan to write the records
   uint32_t n_chunks[NESVOR_MAX_LEVELS];
-  uint32_t box_slots;
 };
 
 template <int F>
@@ -414,15 +404,9 @@ __global__ __launch_bounds__(256) void hashgrid_fwd(const nesvor_grid_t g, const
 // LDS copy (512 slots) together share a round (levels 0-6, 7-8, 9-10, 11 for the bench's clouds), and the next round's table
 // entries are in flight while the current round interpolates (two copies, one barrier per round).  Levels whose box
 // does not fit (the finest one or two of a cloud; almost all for unclustered points) gather from global memory.
-// A/B switches of the per-cloud forward (round 4): packed fp32 blend, scalar-base row stores (11 % fewer VALU instructions per
+// The blend is packed fp32 and the row stores take a scalar base (round 4; measured: 11 % fewer VALU instructions per
 // wave; the launch takes 0.075 ms with or without them - it is latency-bound at full occupancy, profiles/r04_pmc_sq_hashgrid_fwd_cloud_summary.txt -
-// and gathers issued as scalar-base inline asm with an explicit vmcnt(0) cost 0.003 ms: the wait also drains the row stores)
-#ifndef NESVOR_FWD_PK
-#define NESVOR_FWD_PK 1
-#endif
-#ifndef NESVOR_FWD_SSTORE
-#define NESVOR_FWD_SSTORE 1
-#endif
+// and gathers issued as scalar-base inline asm with an explicit vmcnt(0) cost 0.003 ms: the wait also drains the row stores; not kept)
 // Unclustered input (round 6, NESVOR_LAYOUT_UNCLUSTERED on the forward): `perm` = the points in the order of a coarse lattice's
 // cells (sort_points below: the same order the unclustered backward uses); workgroup w takes points perm[256 w ..], so that
 // its lattice boxes are small again and the box rounds reach the middle levels.  Row-major output goes straight to the
@@ -440,10 +424,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
                                                           uint8_t* __restrict__ order = nullptr,        // the cloud order hashgrid_bwd_aggregate writes with order_mode == 1
                                                           uint32_t* __restrict__ cloud_plan = nullptr,  // one cloud plan record per workgroup (layout: plan_words())
                                                           const CloudPlanArgs cpa = CloudPlanArgs{}) {
-#ifndef NESVOR_FWD_CLOUD_SLOTS
-#define NESVOR_FWD_CLOUD_SLOTS 512
-#endif
-  constexpr int kSlots = F <= 2 ? NESVOR_FWD_CLOUD_SLOTS : (F == 4 ? 512 : 256);  // slots per copy (two copies).  Measured at F = 2 (N = 2^20 cloud points): 256/512: 0.075 ms, 1024: 0.079, 2048: 0.101, 4096: 0.193 - the finer levels gather from L2 as fast as a bigger copy serves them, and the copy costs occupancy
+  constexpr int kSlots = F <= 2 ? kFwdCloudSlots : (F == 4 ? 512 : 256);  // slots per copy (two copies).  Measured at F = 2 (N = 2^20 cloud points): 256/512: 0.075 ms, 1024: 0.079, 2048: 0.101, 4096: 0.193 - the finer levels gather from L2 as fast as a bigger copy serves them, and the copy costs occupancy
   constexpr int kMaxGroup = 8;
   constexpr int NRB = kSlots / 256;
   __shared__ __attribute__((aligned(16))) float tcache[2][kSlots * F];
@@ -466,7 +447,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
     // the backward's sort of the cloud, done here where the SIMDs have issue slots to spare; in a scope of its own, in front of
     // the level rounds: its registers are dead before they start.  The forward itself keeps processing thread = sample.
     uint32_t sv = cloud_sort_key(g, valid, ux, uy, uz, tid);
-    bitonic_sort<NESVOR_SORT_SPAN>(sv, tid, sortbuf);
+    bitonic_sort<kSortSpan>(sv, tid, sortbuf);
     order[(int64_t)blockIdx.x * 256 + tid] = (uint8_t)(sv & 255u);
   }
   {
@@ -491,7 +472,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
       // (per-lane index into the kernel arguments = vector loads from the kernarg segment: measured FASTER here than the uniform
       //  loop of scalar loads + selects that the aggregation pass uses - forward 71.8 -> 75.0 us with it)
       const LevelParams p = load_level(g, tid);
-      lattice_box(p, ulo, uhi, true, (uint32_t)kSlots, b);
+      lattice_box(p, ulo, uhi, (uint32_t)kSlots, b);
       lpar[tid][0] = p.res; lpar[tid][1] = p.size; lpar[tid][2] = p.offset; lpar[tid][3] = p.hashed;
     }
     if (tid <= L) {
@@ -517,7 +498,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
       uint32_t win = 0u, nch = 0u;
       if (lv < L) {
         const LevelParams p = load_level(g, lv);
-        lattice_box(p, ulo, uhi, cpa.box_slots != 0u, kAggSlots, b);
+        lattice_box(p, ulo, uhi, kAggSlots, b);
         win = window_bits(b[3], b[4], b[5], __builtin_ctz(kAggSlots));
         nch = cpa.n_chunks[lv];
       }
@@ -542,7 +523,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
   const int box_end = __builtin_amdgcn_readfirstlane(box_end_s);
   auto sgpr = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
   // feature-major rows: scalar row base + the lane's 32-bit byte offset (4 i < 2^32) - no vector address arithmetic per store
-  const bool off32 = NESVOR_FWD_SSTORE && N < ((int64_t)1 << 30);
+  const bool off32 = N < ((int64_t)1 << 30);
   const uint32_t i4 = (uint32_t)i * 4u;
   float pe_mx = 0.f;
   auto store_pe = [&](int level, const float (&acc)[F]) __attribute__((always_inline)) {
@@ -570,7 +551,7 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_cloud(const nesvor_grid_t g,
     }
   };
   auto blend = [&](const CellPos& c, const float (&v)[8][F], float (&acc)[F]) __attribute__((always_inline)) {
-    if constexpr (F == 2 && NESVOR_FWD_PK) {
+    if constexpr (F == 2) {
       // packed fp32 (v_pk_mul_f32 / v_pk_fma_f32: two lanes of fp32 per instruction): the x-pair of every weight and the two
       // features of every corner go through one instruction each - the same products and fused multiply-adds in the same
       // order as the scalar form below (bit-identical), 18 instead of 31 VALU instructions per level
@@ -796,7 +777,7 @@ constexpr int kOwnerLdsFloats = 8192;         // 32 KiB accumulator per owner wo
                                               // fewer, hotter queue counters on one side, more reservations per workgroup on the other)
 
 struct BwdPlan {
-  uint32_t shift[NESVOR_MAX_LEVELS];           // per level: chunk = 2^shift entries (at most kOwnerLdsFloats / F; the finest levels take half)
+  uint32_t shift[NESVOR_MAX_LEVELS];           // per level: chunk = 2^shift entries (the largest with at most kOwnerLdsFloats / F)
   uint32_t n_buckets;
   uint32_t n_chunks[NESVOR_MAX_LEVELS];
   uint32_t bucket_base[NESVOR_MAX_LEVELS];     // first global bucket id of the level
@@ -804,7 +785,6 @@ struct BwdPlan {
   uint32_t slice[NESVOR_MAX_LEVELS];           // records per owner workgroup of the level
   uint64_t rec_off[NESVOR_MAX_LEVELS];         // first record of the level's queues
   uint32_t n_sub;                              // sub-queues per bucket = XCCs of the device partition (1, 2, 4 or 8)
-  uint32_t box_slots;                          // 0: the merge table is always hashed (A/B switch NESVOR_HASHGRID_BOX=0)
   int32_t level_begin, level_end;              // this launch handles levels [level_begin, level_end) (all by default)
   int32_t accumulate_u;                        // input gradient: add to grad_u instead of overwriting (later launches of a split backward)
 };
@@ -835,7 +815,7 @@ __device__ __forceinline__ unsigned long long to_fixed(float x) {
   const int32_t lo = __float2int_rn(fmaf(-t, 0x1p32f, x));  // (to nearest: a truncation bias would add up over the adds of a slot)
   return ((unsigned long long)(uint32_t)((int32_t)t + (lo >> 31)) << 32) | (unsigned long long)(uint32_t)lo;
 }
-// NESVOR_HG_F64FIX=1 (build flag, off): the conversion through the fp64 pipe.  x s + 1.5 2^52 (one v_cvt_f64_f32, one v_fma_f64
+// NESVOR_HG_F64FIX=1 (build flag, off; DESIGN.md section 8 item 1 - the named next step, not a rejected arm): the conversion through the fp64 pipe.  x s + 1.5 2^52 (one v_cvt_f64_f32, one v_fma_f64
 // rounding to nearest) has the exponent of 2^52 for every |x s| < 2^50, so its bit pattern is M + q with M = 0x4338000000000000
 // and q = rint(x s) as a two's-complement integer: 2 instructions per value where to_fixed takes 7 and the scaling an eighth.
 // The 64-bit LDS adds sum N M + sum q; the low 51 bits of M are zero, so the low 51 bits of a slot are sum q mod 2^51 - read
@@ -862,30 +842,20 @@ __device__ __forceinline__ float from_fixed(unsigned long long q) {
   return fmaf((float)((int32_t)(q >> 32) + (int32_t)(lo >> 31)), 0x1p32f, (float)(int32_t)lo);
 }
 
-
-// NESVOR_FIXED32 (build macro, F == 2 only): a merge-table slot holds both features as two 32-bit fixed-point fields of one
-// 64-bit word (one ds_add_u64 per corner, 3 VALU instructions per value) instead of one 64-bit fixed-point word per
-// feature.  Resolution: 2^-22 of 256 max|dy| of the workgroup and level (the 64-bit form resolves 2^-52).  Off by default.
-#ifndef NESVOR_FIXED32
-#define NESVOR_FIXED32 0
-#endif
+// A merge-table slot holds one 64-bit fixed-point word per feature.  Tried at F == 2: both features as two 32-bit fixed-point
+// fields of one 64-bit word (one ds_add_u64 per corner, 3 VALU instructions per value), scaled by the workgroup's max |dy| of the
+// launch or of each level.  Resolution: 2^-22 of 256 max|dy| of the workgroup and level (the 64-bit form resolves 2^-52); not kept.
 
 // BOUND: max |dy| comes from the caller (`dy_bound`) and the pass over dy that determines it is compiled out.  A template
 // parameter, not a run-time branch: with the branch in place the compiler restructured the pass it guards, and the kernel
 // WITHOUT a bound ran 3x slower on uniform points (4.9 vs 1.6 ms) and 4 % slower on PSF clouds (tools/hg_variants.py).
-#ifndef NESVOR_HG_MINBLOCKS
-#define NESVOR_HG_MINBLOCKS 4
-#endif
-// NESVOR_HG_SPATIAL (default): the hashed merge table of the fine levels (boxes that do not fit the table) is addressed by the
+// The hashed merge table of the fine levels (boxes that do not fit the table) is addressed by the
 // low bits of the vertex's lattice coordinates - slot = x mod 2^a | (y mod 2^b) << a | (z mod 2^c) << (a + b), a + b + c =
 // log2(slots), the bits dealt to the axes by the extent of the workgroup's box - instead of a multiplicative hash of the entry
 // index.  Two vertices of a cloud then share a first slot only if they lie a whole window apart: replaying 200 PSF clouds
 // (tools/sim_spatial_hash.py) 0.6 / 11 / 59 vertices per cloud miss their first slot at levels 13 / 14 / 15 against 41 / 89 / 176
 // with the multiplicative hash (313 / 462 / 672 vertices in 1024 slots), and every miss is a serial LDS round trip per probe.
-// Misses walk on by double hashing as before.  0: multiplicative hash, table size following the previous level's count.
-#ifndef NESVOR_HG_SPATIAL
-#define NESVOR_HG_SPATIAL 1
-#endif
+// Misses walk on by double hashing.  (The multiplicative hash sized its table by the previous level's count; not kept.)
 // -DNESVOR_HG_TIMELINE=1 (tools/hg_timeline.py): thread 0 of the first 64 workgroups of the aggregation pass writes (site, time)
 // marks - s_memtime, the 100 MHz constant clock - at its barriers; nesvor_debug_hg_timeline() copies them out.  Where a
 // workgroup's ~65 us go, phase by phase, without a profiler in the way.
@@ -906,8 +876,8 @@ __device__ unsigned long long g_hg_timeline[kTlWgs][kTlMarks];
 // PLAN: the cloud's order comes from `order` and its bounding box, lattice boxes, window bits and round schedule from its record
 // in `cloud_plan` - both written by hashgrid_fwd_cloud for the same u, N, grid and chunking, all levels in one launch.  A template
 // parameter like BOUND, for the same reason.
-template <int F, int LAYOUT, bool INPUT_GRAD, bool MERGE, bool BOUND = false, bool PLAN = false>
-__global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2)) void hashgrid_bwd_aggregate(const nesvor_grid_t g, const BwdPlan plan,
+template <int F, int LAYOUT, bool INPUT_GRAD, bool BOUND = false, bool PLAN = false>
+__global__ __launch_bounds__(256, F <= 2 ? kAggMinBlocks : (F == 4 ? 3 : 2)) void hashgrid_bwd_aggregate(const nesvor_grid_t g, const BwdPlan plan,
                                                               const float* __restrict__ u,
                                                               const float* __restrict__ table,
                                                               const float* __restrict__ dpe,
@@ -921,13 +891,11 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
                                                               const uint32_t* __restrict__ perm,   // null, or the points in lattice-cell order (unclustered input: sort_points below): workgroup w takes points perm[256 w ..]
                                                               int dy_by_slot,                      // 1: dpe is already in that order (row r = point perm[r]): gather_dy_rows_kernel
                                                               const uint32_t* __restrict__ cloud_plan = nullptr) {  // PLAN: the forward's records (plan_words())
-  static_assert(!PLAN || (MERGE && F <= 2), "the cloud plan exists for the merging pass at F <= 2");
+  static_assert(!PLAN || F <= 2, "the cloud plan exists at F <= 2");
   // the queue tails of the NEXT backward (the other of the workspace's two tail regions) are zero-filled here, so that
   // no launch of its own is needed for it
   for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < (uint32_t)kSubQueues * kTailStride; t += gridDim.x * 256u) tails_next[t] = 0u;
-  constexpr bool kPack = (F == 2) && (NESVOR_FIXED32 != 0);
-  constexpr bool kPerLevel = kPack && (NESVOR_FIXED32 >= 2);  // packed fields scaled by the workgroup's max |dy| of EACH level
-  constexpr int kWords = kPack ? 1 : F;  // 64-bit words per slot
+  constexpr int kWords = F;  // 64-bit words per slot
   __shared__ uint32_t bcount[kMaxChunks];
   // per bucket of the current round: box rounds hold uint4 (reserved position, first record of the sub-queue, capacity,
   // level); the single-level rounds hold uint2 (position, first record) double-buffered by level parity
@@ -947,21 +915,16 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
   // retry), and the sum no longer depends on the order of the adds
   __shared__ __attribute__((aligned(16))) unsigned long long tvals[kSlots * kWords];
   // box rounds: the table entries of the round's lattice boxes ([slot][F]); the input gradient reads its 8 corners here
-  __shared__ __attribute__((aligned(16))) float tcache[INPUT_GRAD && MERGE ? kSlots * F : 1];
+  __shared__ __attribute__((aligned(16))) float tcache[INPUT_GRAD ? kSlots * F : 1];
   __shared__ float gmax[4];           // per wave max |dy| over all levels of this launch
-  __shared__ uint32_t lmax_bits[NESVOR_MAX_LEVELS + 1];  // kPerLevel: max |dy| of the workgroup's samples per level (float bits)
-  __shared__ float lscale[NESVOR_MAX_LEVELS + 1][2];     // kPerLevel: fixed-point scale of a level and its inverse
   __shared__ uint32_t merge_stat[2];  // records inserted / drained at the current level (hashed table)
-  __shared__ uint32_t slots_log2;     // slots of the hashed table used at the current level: 256 .. kSlots, ~4x the
-                                      // previous level's distinct vertices (they grow ~1.3-1.5x per level), so that
-                                      // the drain only walks what can be occupied
   __shared__ uint32_t merge_off;      // set once merging stops paying: finer levels skip the table
   __shared__ uint32_t prev_cnt;       // vertices that received something at the previous level (0: unknown)
   __shared__ float ubox[4][6];        // per wave min / max of the samples' coordinates
   // per level: first cell (x,y,z), cells spanned - 1 (x,y,z), vertices of the lattice box (0: the box does not fit the
   // table), largest slot a sample's first corner may take
   __shared__ uint32_t lbox[NESVOR_MAX_LEVELS + 1][8];
-  __shared__ uint32_t lwin[NESVOR_MAX_LEVELS + 1];  // NESVOR_HG_SPATIAL: address bits of x | y << 8 | z << 16 in the hashed merge table
+  __shared__ uint32_t lwin[NESVOR_MAX_LEVELS + 1];  // address bits of x | y << 8 | z << 16 in the hashed merge table
   // box rounds (groups of consecutive levels whose boxes share the table): per level the first slot of its box, the
   // first (round-local) bucket of its chunks, and the end of its round
   __shared__ uint32_t slot_off[NESVOR_MAX_LEVELS + 1], bkt_off[NESVOR_MAX_LEVELS + 1], grp_end[NESVOR_MAX_LEVELS + 1];
@@ -988,10 +951,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
   for (int t = tid; t < kSlots; t += 256) tkeys[t] = kEmpty;
   for (int t = tid; t < kSlots * kWords; t += 256) tvals[t] = 0ull;
   if (tid < 2) merge_stat[tid] = 0;
-  if (tid == 0) { merge_off = MERGE ? 0u : 1u; slots_log2 = __builtin_ctz(kSlots); prev_cnt = 0u; }
-  if constexpr (kPerLevel) {
-    if (tid <= NESVOR_MAX_LEVELS) lmax_bits[tid] = 0u;
-  }
+  if (tid == 0) { merge_off = 0u; prev_cnt = 0u; }
 
   // ---- sort the workgroup's samples by Morton code of the finest-level cell
   uint32_t sv;
@@ -1007,13 +967,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     // a later launch of a split backward (data parallel: coarse levels after the fine ones) re-uses the order the first
     // launch found - same samples, same key - and so does a backward behind a forward that wrote it
     if (order_mode == 2) sv = (uint32_t)order[base + tid];
-    else
-#pragma unroll 1
-    for (int rep = 0; rep < (NESVOR_ABL(1) ? 2 : 1); ++rep) {
-      if (rep) sv ^= 0x80000000u;  // (ablation: something to sort the second time)
-      bitonic_sort<NESVOR_SORT_SPAN>(sv, tid, sortbuf);
-      if (rep) sv ^= 0x80000000u;
-    }
+    else bitonic_sort<kSortSpan>(sv, tid, sortbuf);
   }
   HG_TICK(1);  // sorted
   if (order_mode == 1) order[base + tid] = (uint8_t)(sv & 255u);
@@ -1036,7 +990,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     }
   };
 
-  if constexpr (MERGE) {
+  {
     // bounding box of the workgroup's samples: locate() is monotone in u, so the lattice box of every level follows
     // from these six numbers
     float lo[3] = {ux, uy, uz}, hi[3] = {ux, uy, uz};
@@ -1049,19 +1003,14 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     }
     // ONE fixed-point scale for the whole launch of this workgroup: max |dy| over its samples and all levels (eight
     // levels' loads in flight at a time).  The adds of one slot sum to at most 256 max|dy| (corner weights of a sample
-    // sum to 1), which is mapped below 2^61 (2^30 for the packed 32-bit fields); 64-bit words then resolve
+    // sum to 1), which is mapped below 2^61; 64-bit words then resolve
     // max|dy| 2^-52, far below an fp32 ulp of any gradient that matters next to the largest one.
     // With a caller-supplied bound (the producer of dy knows its largest magnitude: nesvor_mlp_backward_bounded) that pass
     // over dy - 134 MB at N = 2^20, read a second time level by level below - is skipped: 64-bit words leave room for a
     // bound that is orders of magnitude above this workgroup's own maximum.
     float m = 0.f;
-    if constexpr (kPerLevel) __syncthreads();  // lmax_bits zero-filled (no barrier before this point when the sort is skipped)
-    if constexpr (BOUND) {
-      m = *dy_bound;
-      if constexpr (kPerLevel) {  // (a global bound: every level gets the same scale)
-        if (tid < NESVOR_MAX_LEVELS) lmax_bits[tid] = __float_as_uint(m);
-      }
-    } else
+    if constexpr (BOUND) m = *dy_bound;
+    else
     for (int l0 = plan.level_begin; l0 < level_end; l0 += 8) {
       float d[8][F];
 #pragma unroll
@@ -1078,10 +1027,6 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
 #pragma unroll
         for (int f = 0; f < F; ++f) ml = fmaxf(ml, fabsf(d[q][f]));
         m = fmaxf(m, ml);
-        if constexpr (kPerLevel) {
-          ml = wave_max_f32_dpp(ml);
-          if (lane == 0 && l0 + q < level_end) atomicMax(&lmax_bits[l0 + q], __float_as_uint(ml));
-        }
       }
     }
     m = wave_max_f32_dpp(m);
@@ -1097,7 +1042,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
   HG_TICK(2);  // bounding box / max |dy| published
   float ulo[3] = {0.f, 0.f, 0.f}, uhi[3] = {0.f, 0.f, 0.f};
   float fscale = 1.f, finv = 1.f;
-  if constexpr (MERGE) {
+  {
     if constexpr (!PLAN) {
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
@@ -1110,8 +1055,8 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     {
       float mx = 256.f * fmaxf(fmaxf(gmax[0], gmax[1]), fmaxf(gmax[2], gmax[3]));
       mx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mx)));
-      // (slot sums stay below 2^30 in the packed fields, 2^49 in the 51-bit words, 2^61 in the 64-bit ones)
-      int sexp = (kPack ? 29 : (NESVOR_HG_F64FIX ? 48 : 60)) - ((int)((__float_as_uint(mx) >> 23) & 0xFFu) - 127);
+      // (slot sums stay below 2^49 in the 51-bit words, 2^61 in the 64-bit ones)
+      int sexp = (NESVOR_HG_F64FIX ? 48 : 60) - ((int)((__float_as_uint(mx) >> 23) & 0xFFu) - 127);
       sexp = sexp > 100 ? 100 : (sexp < -100 ? -100 : sexp);
       fscale = __uint_as_float((uint32_t)(sexp + 127) << 23);
       finv = __uint_as_float((uint32_t)(127 - sexp) << 23);
@@ -1125,14 +1070,6 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
       lpar[lv][0] = p.res; lpar[lv][1] = p.size; lpar[lv][2] = p.offset; lpar[lv][3] = p.hashed;
       lpar[lv][4] = plan.cap[lv]; lpar[lv][5] = plan.bucket_base[lv]; lpar[lv][6] = (uint32_t)plan.rec_off[lv];
       lpar[lv][7] = plan.shift[lv];
-      if constexpr (kPerLevel) {
-        // a slot sums at most 256 values of at most max |dy| each: mapped below 2^30
-        const float mxl = 256.f * __uint_as_float(lmax_bits[lv]);
-        int se = 29 - ((int)((__float_as_uint(mxl) >> 23) & 0xFFu) - 127);
-        se = se > 100 ? 100 : (se < -100 ? -100 : se);
-        lscale[lv][0] = __uint_as_float((uint32_t)(se + 127) << 23);
-        lscale[lv][1] = __uint_as_float((uint32_t)(127 - se) << 23);
-      }
     };
     if constexpr (PLAN) {
       // the cloud's record, 16 bytes per thread from the last thread down (wave 0 fills lpar meanwhile); every array of the record
@@ -1166,7 +1103,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
       const int tl_ = tid < g.n_levels ? tid : 0;
       const LevelParams p = load_level(g, tl_);
       if (tid < g.n_levels) {
-        lattice_box(p, ulo, uhi, plan.box_slots != 0u, (uint32_t)kSlots, b);
+        lattice_box(p, ulo, uhi, (uint32_t)kSlots, b);
         lwin[tid] = window_bits(b[3], b[4], b[5], __builtin_ctz(kSlots));
         nch = plan.n_chunks[tl_];
         fill_lpar(tid, p);
@@ -1189,7 +1126,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     __syncthreads();
     HG_TICK(3);  // lattice boxes and round schedule
   }
-  const int box_end = MERGE ? __builtin_amdgcn_readfirstlane(box_end_s) : plan.level_begin;
+  const int box_end = __builtin_amdgcn_readfirstlane(box_end_s);
   auto sgpr = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };  // wave-uniform values
 
   // Everything of a level that needs no shared state beyond the box cache: corner slots / indices, run-summed corner
@@ -1283,66 +1220,45 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
                      : "+v"(val[k][f]) : "v"(m));                                                          \
       flag |= __builtin_amdgcn_update_dpp(0, flag, CTRL, 0xf, 0xf, true);                                  \
     }
-    if constexpr (!NESVOR_ABL(2)) {
-      // all values are written before this point and two wait states pass before the first DPP read
+    // all values are written before this point and two wait states pass before the first DPP read
 #define NESVOR_FENCE8(f) asm volatile("s_nop 1" : "+v"(val[0][f]), "+v"(val[1][f]), "+v"(val[2][f]), "+v"(val[3][f]), "+v"(val[4][f]), "+v"(val[5][f]), "+v"(val[6][f]), "+v"(val[7][f]))
-      NESVOR_FENCE8(0);
-      if constexpr (F >= 2) NESVOR_FENCE8(1);
-      if constexpr (F >= 4) { NESVOR_FENCE8(2); NESVOR_FENCE8(3); }
-      if constexpr (F >= 8) { NESVOR_FENCE8(4); NESVOR_FENCE8(5); NESVOR_FENCE8(6); NESVOR_FENCE8(7); }
+    NESVOR_FENCE8(0);
+    if constexpr (F >= 2) NESVOR_FENCE8(1);
+    if constexpr (F >= 4) { NESVOR_FENCE8(2); NESVOR_FENCE8(3); }
+    if constexpr (F >= 8) { NESVOR_FENCE8(4); NESVOR_FENCE8(5); NESVOR_FENCE8(6); NESVOR_FENCE8(7); }
 #undef NESVOR_FENCE8
-      // a step only does something for lanes that have not yet seen the head of their run: at the fine levels runs
-      // are one to three lanes long and the wide steps are skipped (wave-uniform test)
-      NESVOR_SCAN_STEP(1, 0x111)
+    // a step only does something for lanes that have not yet seen the head of their run: at the fine levels runs
+    // are one to three lanes long and the wide steps are skipped (wave-uniform test)
+    NESVOR_SCAN_STEP(1, 0x111)
+    if (__ballot(flag == 0)) {
+      NESVOR_SCAN_STEP(2, 0x112)
       if (__ballot(flag == 0)) {
-        NESVOR_SCAN_STEP(2, 0x112)
-        if (__ballot(flag == 0)) {
-          NESVOR_SCAN_STEP(4, 0x114)
-          if (__ballot(flag == 0)) NESVOR_SCAN_STEP(8, 0x118)
-        }
+        NESVOR_SCAN_STEP(4, 0x114)
+        if (__ballot(flag == 0)) NESVOR_SCAN_STEP(8, 0x118)
       }
     }
 #undef NESVOR_SCAN_STEP
   };
 
   // one corner's F values -> the slot's fixed-point words
-  auto scale_of = [&](uint32_t lv) __attribute__((always_inline)) { return kPerLevel ? lscale[lv][0] : fscale; };
-  auto inv_of = [&](uint32_t lv) __attribute__((always_inline)) { return kPerLevel ? lscale[lv][1] : finv; };
-  auto slot_add = [&](uint32_t slot, const float (&v)[F], float fscale) __attribute__((always_inline)) {
-    if constexpr (kPack) {
-      const int32_t q0 = __float2int_rn(v[0] * fscale), q1 = __float2int_rn(v[1] * fscale);
-      // ((int64)q1 << 32) + (int64)q0: the low field's sign borrows from the high field; undone when the slot is read
-      atomicAdd(&tvals[slot], ((unsigned long long)(uint32_t)(q1 + (q0 >> 31)) << 32) | (unsigned long long)(uint32_t)q0);
-    } else {
+  auto slot_add = [&](uint32_t slot, const float (&v)[F]) __attribute__((always_inline)) {
 #pragma unroll
-      for (int f = 0; f < F; ++f) {
-        if constexpr (NESVOR_HG_F64FIX != 0) atomicAdd(&tvals[f * kSlots + slot], to_fixed51(v[f], (double)fscale));
-        else atomicAdd(&tvals[f * kSlots + slot], to_fixed(v[f] * fscale));
-      }
+    for (int f = 0; f < F; ++f) {
+      if constexpr (NESVOR_HG_F64FIX != 0) atomicAdd(&tvals[f * kSlots + slot], to_fixed51(v[f], (double)fscale));
+      else atomicAdd(&tvals[f * kSlots + slot], to_fixed(v[f] * fscale));
     }
   };
   // read + clear one slot; false: nothing was added (or everything cancelled exactly)
-  auto slot_take = [&](uint32_t slot, float (&v)[F], float finv) __attribute__((always_inline)) -> bool {
+  auto slot_take = [&](uint32_t slot, float (&v)[F]) __attribute__((always_inline)) -> bool {
     bool any = false;
-    if constexpr (kPack) {
-      const unsigned long long w = tvals[slot];
-      any = w != 0ull;
-      if (any) {
-        const int32_t lo = (int32_t)(uint32_t)w;
-        const int32_t hi = (int32_t)(uint32_t)(w >> 32) - (lo >> 31);
-        v[0] = (float)lo * finv; v[1] = (float)hi * finv;
-        tvals[slot] = 0ull;
-      }
-    } else {
-      unsigned long long w[F];
+    unsigned long long w[F];
 #pragma unroll
-      for (int f = 0; f < F; ++f) { w[f] = tvals[f * kSlots + slot]; any = any || w[f] != 0ull; }
-      if (any) {
+    for (int f = 0; f < F; ++f) { w[f] = tvals[f * kSlots + slot]; any = any || w[f] != 0ull; }
+    if (any) {
 #pragma unroll
-        for (int f = 0; f < F; ++f) {
-          v[f] = (NESVOR_HG_F64FIX != 0 ? from_fixed51(w[f]) : from_fixed(w[f])) * finv;
-          tvals[f * kSlots + slot] = 0ull;
-        }
+      for (int f = 0; f < F; ++f) {
+        v[f] = (NESVOR_HG_F64FIX != 0 ? from_fixed51(w[f]) : from_fixed(w[f])) * finv;
+        tvals[f * kSlots + slot] = 0ull;
       }
     }
     return any;
@@ -1363,7 +1279,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
   //     R(r) reserve queue space (returning global atomics, ~2 us, hidden behind:)
   //                                               | P(r+1) per level of round r+1: prepare + insert the run tails
   constexpr int NRB = kSlots / 256;  // slots per thread: thread t owns slots t, t + 256, ... (fill and drain)
-  if constexpr (MERGE) {
+  {
     // keys (tkeys) and table entries (tcache) of the slots of round [ra, rb): a slot is read and written by its owner
     // thread only, so only the table copy needs the barrier that follows.  The loads are returned in `feat` so that
     // they can fly while the caller does other work; store_feat() puts them into tcache.
@@ -1415,13 +1331,12 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
 #pragma unroll
         for (int f = 0; f < F; ++f) dy_a[f] = dy_b[f];
         if (lv + 2 < level_end) load_dy(lv + 2, dy_b);
-        const float fs_lv = scale_of((uint32_t)lv);
         // (Lane-transposed inserts for waves with few run tails - four tails park their values in an LDS strip, 64 lanes convert and
         //  add one value each - were measured in round 4 and bought nothing: a coarse level's time is its latency chain, not the
         //  130 conversion instructions.  DESIGN_LOG.md / profiles/r04_hashgrid_ab_transposed_inserts.log.)
-        if (!NESVOR_ABL(4) && tail) {
+        if (tail) {
 #pragma unroll
-          for (int k = 0; k < 8; ++k) slot_add(s0 + (k & 1) + ((k >> 1) & 1) * nx + (k >> 2) * nxy, val[k], fs_lv);
+          for (int k = 0; k < 8; ++k) slot_add(s0 + (k & 1) + ((k >> 1) & 1) * nx + (k >> 2) * nxy, val[k]);
         }
       }
     };
@@ -1444,7 +1359,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
         __syncthreads();  // -- insertions of round [ra, rb) complete; bbase4 of the previous round published
         HG_TICK(0x20 | ra);  // inserts of the round starting at level ra complete
         // W(r-1)
-        if (have_prev && !NESVOR_ABL(8)) {
+        if (have_prev) {
 #pragma unroll
           for (int j = 0; j < NRB; ++j) {
             if (!(rmask & (1u << j))) continue;
@@ -1485,7 +1400,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
 #pragma unroll
           for (int f = 0; f < F; ++f) rval[j][f] = 0.f;
           const uint32_t slot = (uint32_t)j * 256u + (uint32_t)tid;
-          if (slot < n_slots && slot_take(slot, rval[j], inv_of(lk[j] >> 27))) {
+          if (slot < n_slots && slot_take(slot, rval[j])) {
             const uint32_t lv = lk[j] >> 27;
             rkey[j] = lk[j] & kKeyMask;
             const uint32_t bucket = bkt_off[lv] + (rkey[j] >> lpar[lv][7]);
@@ -1515,7 +1430,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
           const uint32_t cnt = bcount[tid];
           bcount[tid] = 0;
           uint32_t pos0 = 0;
-          if (cnt && !NESVOR_ABL(16)) pos0 = atomicAdd(&tails[sub * kTailStride + lpar[lv][5] + chunk], cnt);
+          if (cnt) pos0 = atomicAdd(&tails[sub * kTailStride + lpar[lv][5] + chunk], cnt);
           mine = make_uint4(pos0, lpar[lv][6] + (chunk * plan.n_sub + sub) * cap, cap, (uint32_t)lv);
         }
         // ... hidden behind P(r+1)
@@ -1533,12 +1448,12 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
       // (cell-ordered uniform points: ~600 of the 780 vertices of a level-11 box): the finer levels write direct records.
       // (Rounds 1-4 only looked at a hashed level after it had been inserted.)
       if (tid == 0) {
-        if (NESVOR_HG_SPATIAL && merge_stat[1] * 2u > (uint32_t)kSlots) merge_off = 1u;
+        if (merge_stat[1] * 2u > (uint32_t)kSlots) merge_off = 1u;
         prev_cnt = merge_stat[1];
         merge_stat[1] = 0u;
       }
       // W(last box round)
-      if (!NESVOR_ABL(8)) {
+      {
 #pragma unroll
         for (int j = 0; j < NRB; ++j) {
           if (!(rmask & (1u << j))) continue;
@@ -1571,7 +1486,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
     uint32_t su = 0, nxu = 1, nxyu = 1;  // (box-only outputs of prepare)
     bool tail, tail_n = false;
     prepare(std::false_type{}, level, dy_a, idx, su, nxu, nxyu, val, tail);
-    bool merge = MERGE;
+    bool merge = true;
     // Second half of a level, specialised on the number NR of records a thread can hold (table slots per thread in
     // merge mode, the 8 corners otherwise) so that the merge path does not carry 8 record registers sets through the
     // next level's prepare(): reserve queue space, prepare the next level, write the records.
@@ -1588,7 +1503,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
       uint32_t my_base = 0;
       if (tid < nb) {
         const uint32_t cnt = bcount[tid];
-        if (cnt && !NESVOR_ABL(16)) my_base = atomicAdd(&tails[sub * kTailStride + plan.bucket_base[lu] + tid], cnt);
+        if (cnt) my_base = atomicAdd(&tails[sub * kTailStride + plan.bucket_base[lu] + tid], cnt);
         bcount[tid] = 0;
       }
       if (merge && tid == 255) {
@@ -1597,11 +1512,8 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
         const uint32_t drained = merge_stat[1];
         if (drained * 4u > merge_stat[0] * 3u || drained * 10u > (uint32_t)kSlots * 7u) merge_off = 1u;
         // (the next level at this level's growth: keep it below ~4/5 of the slots)
-        if (NESVOR_HG_SPATIAL && prev_cnt != 0u && (uint64_t)drained * drained * 5u > (uint64_t)prev_cnt * (uint32_t)kSlots * 4u) merge_off = 1u;
+        if (prev_cnt != 0u && (uint64_t)drained * drained * 5u > (uint64_t)prev_cnt * (uint32_t)kSlots * 4u) merge_off = 1u;
         prev_cnt = drained;
-        uint32_t lg = 8;
-        while ((1u << lg) < 4u * drained && (1u << lg) < (uint32_t)kSlots) ++lg;
-        slots_log2 = lg;
         merge_stat[0] = 0; merge_stat[1] = 0;
       }
       // ... and hide its latency behind the next level's register-only work
@@ -1619,7 +1531,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
       char* const level_rec = reinterpret_cast<char*>(records) + plan.rec_off[lu] * (uint64_t)(4 * (1 + F));
 #pragma unroll
       for (int k = 0; k < NR; ++k) {
-        if (NESVOR_ABL(8) || !(rmask & (1u << k))) continue;
+        if (!(rmask & (1u << k))) continue;
         const uint2 bb = bbase[level & 1][rkey[k] >> plan.shift[lu]];
         const uint32_t pos = bb.x + rank[k];
         if (pos < cap) {
@@ -1643,17 +1555,17 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
       }
       tail = tail_n;
     };
-    if constexpr (MERGE) {
+    {
       for (; level < level_end && merge_off == 0u; ++level) {
         constexpr int NR = kSlots / 256;
         uint32_t rkey[NR], rank[NR], rmask = 0;
         float rval[NR][F];
-        const uint32_t slog = NESVOR_HG_SPATIAL ? (uint32_t)__builtin_ctz(kSlots) : slots_log2, smask = (1u << slog) - 1u;
-        if (!NESVOR_ABL(4) && tail) {
+        constexpr uint32_t smask = (uint32_t)kSlots - 1u;
+        if (tail) {
           uint32_t h[8];
           uint32_t pending = 0;
           // claim / find the 8 slots: first probes issued together, collisions walked one by one
-          if constexpr (NESVOR_HG_SPATIAL != 0) {
+          {
             const uint32_t wb = sgpr(lwin[level]);
             const uint32_t ba = wb & 255u, bb = (wb >> 8) & 255u, bc = wb >> 16;
             const uint32_t mx = (1u << ba) - 1u, my = (1u << bb) - 1u, mz = (1u << bc) - 1u;
@@ -1663,9 +1575,6 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
             const uint32_t hz[2] = {(z0 & mz) << (ba + bb), ((z0 + 1u) & mz) << (ba + bb)};
 #pragma unroll
             for (int k = 0; k < 8; ++k) h[k] = hx[k & 1] | hy[(k >> 1) & 1] | hz[k >> 2];
-          } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) h[k] = (idx[k] * 2654435761u) >> (32 - slog);
           }
           uint32_t prev[8];
 #pragma unroll
@@ -1695,7 +1604,7 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
 #pragma unroll
               for (int f = 0; f < F; ++f) atomicAdd(grad_table + ((size_t)g.offset[__builtin_amdgcn_readfirstlane(level)] + idx[k]) * F + f, val[k][f]);
             } else {
-              slot_add(h[k], val[k], scale_of((uint32_t)level));
+              slot_add(h[k], val[k]);
             }
           }
         }
@@ -1706,19 +1615,18 @@ __global__ __launch_bounds__(256, F <= 2 ? NESVOR_HG_MINBLOCKS : (F == 4 ? 3 : 2
         HG_TICK(0xD0 | level);  // ... by everyone
         // drain: slot -> register record, slot cleared for the next level
         uint32_t mine = 0;
-        const uint32_t n_slots = 1u << slog;  // slots in use at this level: thread t drains t, t + 256, ...
+        // thread t drains slots t, t + 256, ...
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
           rkey[j] = 0; rank[j] = 0;
 #pragma unroll
           for (int f = 0; f < F; ++f) rval[j][f] = 0.f;
           const uint32_t slot = (uint32_t)j * 256u + (uint32_t)tid;
-          if (slot >= n_slots) continue;
           const uint32_t key = tkeys[slot];
           if (key != kEmpty) {
             tkeys[slot] = kEmpty;
             rmask |= 1u << j; rkey[j] = key;
-            slot_take(slot, rval[j], inv_of((uint32_t)level));
+            slot_take(slot, rval[j]);
             rank[j] = atomicAdd(&bcount[key >> plan.shift[__builtin_amdgcn_readfirstlane(level)]], 1u);
             ++mine;
           }
@@ -1768,31 +1676,29 @@ struct OwnerAdam {
   AdamArgs a;
 };
 
-template <int F, bool COALESCED, bool ADAM = false>
+template <int F, bool ADAM = false>
 __global__ __launch_bounds__(kOwnerThreads) void hashgrid_bwd_owner(const nesvor_grid_t g, const BwdPlan plan,
                                                           const uint32_t* __restrict__ tails,
                                                           const uint32_t* __restrict__ records,
                                                           float* __restrict__ grad_table, const OwnerAdam adam,
-                                                          uint32_t id_stride,  // workgroup id -> (id * id_stride) mod grid: coprime to the grid size (1: identity)
+                                                          uint32_t id_stride,  // workgroup id -> (id * id_stride) mod grid: always 1 (a stride coprime to the grid size was measured; not kept)
                                                           uint32_t wg_base) {  // flat id of the launch's first workgroup (a launch for a level range starts at its first level's)
   __shared__ __attribute__((aligned(16))) float acc[kOwnerLdsFloats];
   __shared__ uint32_t ticket_s;
   const int tid = threadIdx.x;
-  // decode (level, chunk, slice) from the flat workgroup id
-  // (-DNESVOR_OWNER_FINE_FIRST=1: the workgroups of the finest level - the longest queues, 21 K records per chunk at level 15 of a
-  //  PSF-cloud batch - get the lowest ids and start first.  Measured in the step, two alternating rounds: owner launch 95-97 us
-  //  against 84-85, 1031-1033 against 1045-1050 it/s: the coarse levels' short workgroups fill the gaps better when they lead.
-  //  -DNESVOR_OWNER_PF=2 / 4 (more of a chunk's AdamW operands requested before the record phase): 86-87 / 90-91 us against 87.)
-#ifndef NESVOR_OWNER_FINE_FIRST
-#define NESVOR_OWNER_FINE_FIRST 0
-#endif
+  // decode (level, chunk, slice) from the flat workgroup id, coarse levels first
+  // (measured: the workgroups of the finest level - the longest queues, 21 K records per chunk at level 15 of a PSF-cloud batch -
+  //  given the lowest ids so that they start first.  In the step, two alternating rounds: owner launch 95-97 us against 84-85,
+  //  1031-1033 against 1045-1050 it/s: the coarse levels' short workgroups fill the gaps better when they lead; not kept.
+  //  More of a chunk's AdamW operands requested before the record phase, 2 / 4 float4 per thread and array: 86-87 / 90-91 us
+  //  against 87; not kept.)
   uint32_t wg = (uint32_t)(((uint64_t)blockIdx.x * id_stride) % gridDim.x) + wg_base;
-  int level = NESVOR_OWNER_FINE_FIRST ? g.n_levels - 1 : 0;
+  int level = 0;
   uint32_t spl = 0;
-  for (;; level += NESVOR_OWNER_FINE_FIRST ? -1 : 1) {
+  for (;; ++level) {
     spl = (plan.cap[level] * plan.n_sub + plan.slice[level] - 1) / plan.slice[level];
     const uint32_t cnt = plan.n_chunks[level] * spl;
-    if (wg < cnt || (NESVOR_OWNER_FINE_FIRST ? level == 0 : level + 1 >= g.n_levels)) break;
+    if (wg < cnt || level + 1 >= g.n_levels) break;
     wg -= cnt;
   }
   if (level < plan.level_begin || level >= plan.level_end) return;  // split backward: another launch owns this level
@@ -1800,29 +1706,24 @@ __global__ __launch_bounds__(kOwnerThreads) void hashgrid_bwd_owner(const nesvor
   const uint32_t gb = plan.bucket_base[level] + chunk;
   // the bucket's records = the concatenation of its sub-queues; record r of that virtual queue sits at
   // r + sum over the sub-queues that end at or before r of their unused tail
-  // Latencies taken out of the workgroup's serial chain (round 4; NESVOR_OWNER_EARLY=0 restores the old order): the queue tails
+  // Latencies taken out of the workgroup's serial chain (round 4): the queue tails
   // are requested first and the LDS accumulator is zero-filled while they fly (it used to wait behind the early-exit test on
   // them); with ADAM the first float4 of the chunk's parameters / moments / old gradient per thread - which depend on nothing
   // the record phase produces - is requested here as well and lands under the record phase.
-#ifndef NESVOR_OWNER_EARLY
-#define NESVOR_OWNER_EARLY 1
-#endif
   uint32_t traw[kSubQueues];
 #pragma unroll
   for (int x = 0; x < kSubQueues; ++x) traw[x] = (uint32_t)x < plan.n_sub ? tails[x * kTailStride + gb] : 0u;
   const uint32_t e0 = chunk << plan.shift[level];
   const uint32_t ne = min((uint32_t)(1u << plan.shift[level]), g.size[level] - e0);
-  // NESVOR_OWNER_PF float4 per thread and array (parameters, both moments, old gradient) are requested here, before the record
-  // phase: 1 = the first of a full chunk's four sweeps (round 4), 4 = the whole chunk (64 more VGPRs: two workgroups per CU)
-#ifndef NESVOR_OWNER_PF
-#define NESVOR_OWNER_PF 1
-#endif
-  constexpr int kPF = NESVOR_OWNER_PF;
+  // kPF float4 per thread and array (parameters, both moments, old gradient) are requested here, before the record phase: 1 = the
+  // first of a full chunk's four sweeps (round 4); 4 = the whole chunk takes 64 more VGPRs: two workgroups per CU; not kept.
+  // (Arrays of one element: written as scalars, the ADAM kernels at F = 4 and 8 come out with three more SGPRs.)
+  constexpr int kPF = 1;
   float4 pf_p[kPF], pf_m[kPF], pf_v[kPF], pf_o[kPF];
 #pragma unroll
   for (int j = 0; j < kPF; ++j) pf_p[j] = pf_m[j] = pf_v[j] = pf_o[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   bool prefetched = false;
-  if constexpr (ADAM && NESVOR_OWNER_EARLY) {
+  if constexpr (ADAM) {
     const uint32_t nf = ne * F;
     if (nf % 4u == 0u) {
       const size_t first = ((size_t)g.offset[level] + e0) * F;
@@ -1839,9 +1740,7 @@ __global__ __launch_bounds__(kOwnerThreads) void hashgrid_bwd_owner(const nesvor
       }
     }
   }
-  if (NESVOR_OWNER_EARLY) {
-    for (int t = tid; t < kOwnerLdsFloats / 4; t += kOwnerThreads) reinterpret_cast<float4*>(acc)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  for (int t = tid; t < kOwnerLdsFloats / 4; t += kOwnerThreads) reinterpret_cast<float4*>(acc)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
   uint32_t n = 0;
   uint32_t pre[kSubQueues], gap[kSubQueues];  // pre[x]: first virtual index of sub-queue x; gap[x]: hole before it
 #pragma unroll
@@ -1863,9 +1762,6 @@ __global__ __launch_bounds__(kOwnerThreads) void hashgrid_bwd_owner(const nesvor
   if (ADAM ? slice >= n_part : r0 >= n) return;
   const uint32_t r1 = max(r0, min(n, r0 + plan.slice[level]));
   const bool sole_writer = n <= plan.slice[level];
-  if (!NESVOR_OWNER_EARLY) {
-    for (int t = tid; t < kOwnerLdsFloats / 4; t += kOwnerThreads) reinterpret_cast<float4*>(acc)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
   __syncthreads();
   const uint32_t mask = (1u << plan.shift[level]) - 1u;
   const uint32_t* rec = records + (plan.rec_off[level] + (uint64_t)chunk * plan.n_sub * plan.cap[level]) * (1 + F);
@@ -1884,40 +1780,13 @@ __global__ __launch_bounds__(kOwnerThreads) void hashgrid_bwd_owner(const nesvor
       for (int f = 0; f < F; ++f) lds_add_f32_cas(&acc[local * F + f], v[f]);
     }
   };
-  // Records of one pixel sit next to each other in the queue and repeat the same few table entries
-  // (shared cell corners), so neighbouring lanes must NOT take neighbouring records (measured: the
-  // coalesced walk is 2x slower from compare-and-swap retries): each thread walks its own contiguous
-  // sub-range, which spreads the lanes over the whole slice.
-  // (sub-ranges are multiples of 32 records = 3 x 128 B so that a cache line is fetched by one thread only)
-#ifndef NESVOR_OWNER_UNROLL
-#define NESVOR_OWNER_UNROLL 8
-#endif
-  constexpr int kUnroll = NESVOR_OWNER_UNROLL;  // records in flight per thread
-  if constexpr (COALESCED) {
-    // merged queues: a workgroup of the aggregation pass emits every vertex once per level, so neighbouring
-    // records no longer repeat a table entry and neighbouring lanes can take neighbouring records
-#if defined(NESVOR_OWNER_PRED) && NESVOR_OWNER_PRED
-    // batches of kUnroll predicated loads per thread: a bucket of a few thousand records (the common case) is one or two
-    // batches - one or two memory latencies - instead of a batch loop plus a one-record-at-a-time tail loop
-    for (uint32_t r = r0 + tid; r < r1; r += kUnroll * kOwnerThreads) {
-      uint32_t key[kUnroll];
-      float v[kUnroll][F];
-#pragma unroll
-      for (int j = 0; j < kUnroll; ++j) {
-        const uint32_t rr = r + j * kOwnerThreads;
-        key[j] = 0xFFFFFFFFu;
-        if (rr < r1) {
-          const uint32_t* q = rec + (size_t)slot_of(rr) * (1 + F);
-          key[j] = q[0];
-#pragma unroll
-          for (int f = 0; f < F; ++f) v[j][f] = __uint_as_float(q[1 + f]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kUnroll; ++j)
-        if (key[j] != 0xFFFFFFFFu) add_record(key[j], v[j]);
-    }
-#else
+  // The queues are merged: a workgroup of the aggregation pass emits every vertex once per level, so neighbouring records do
+  // not repeat a table entry and neighbouring lanes take neighbouring records.  (Before the merge, records of one pixel sat
+  // next to each other and repeated the same few table entries - shared cell corners - and the coalesced walk was 2x slower
+  // from compare-and-swap retries; each thread then walked a contiguous sub-range of its own.  Batches of kUnroll predicated
+  // loads per thread instead of a batch loop plus a one-record-at-a-time tail loop: tried; not kept.)
+  constexpr int kUnroll = 8;  // records in flight per thread
+  {
     uint32_t r = r0 + tid;
     for (; r + (kUnroll - 1) * kOwnerThreads < r1; r += kUnroll * kOwnerThreads) {
       uint32_t key[kUnroll];
@@ -1939,31 +1808,6 @@ __global__ __launch_bounds__(kOwnerThreads) void hashgrid_bwd_owner(const nesvor
       for (int f = 0; f < F; ++f) v[f] = __uint_as_float(q[1 + f]);
       add_record(q[0], v);
     }
-#endif
-  } else {
-  const uint32_t per = (((r1 - r0 + kOwnerThreads - 1) / kOwnerThreads) + 31u) & ~31u;
-  uint32_t r = r0 + tid * per;
-  const uint32_t rend = min(r1, r + per);
-  for (; r + kUnroll <= rend; r += kUnroll) {
-    uint32_t key[kUnroll];
-    float v[kUnroll][F];
-#pragma unroll
-    for (int j = 0; j < kUnroll; ++j) {
-      const uint32_t* q = rec + (size_t)slot_of(r + j) * (1 + F);
-      key[j] = q[0];
-#pragma unroll
-      for (int f = 0; f < F; ++f) v[j][f] = __uint_as_float(q[1 + f]);
-    }
-#pragma unroll
-    for (int j = 0; j < kUnroll; ++j) add_record(key[j], v[j]);
-  }
-  for (; r < rend; ++r) {
-    const uint32_t* q = rec + (size_t)slot_of(r) * (1 + F);
-    float v[F];
-#pragma unroll
-    for (int f = 0; f < F; ++f) v[f] = __uint_as_float(q[1 + f]);
-    add_record(q[0], v);
-  }
   }
   __syncthreads();
   float* out = grad_table + ((size_t)g.offset[level] + e0) * F;
@@ -2023,10 +1867,7 @@ __global__ __launch_bounds__(kOwnerThreads) void hashgrid_bwd_owner(const nesvor
     }
     return;
   }
-#ifndef NESVOR_OWNER_F4
-#define NESVOR_OWNER_F4 1
-#endif
-  if (NESVOR_OWNER_F4 && sole_writer && (ne * F) % 4u == 0u) {
+  if (sole_writer && (ne * F) % 4u == 0u) {
     // only writer of the chunk: plain read-modify-write, four floats at a time where any of them is non-zero (chunks and
     // level offsets are multiples of 8 entries, so the float4 accesses are aligned)
     const float4* a4 = reinterpret_cast<const float4*>(acc);
@@ -2061,10 +1902,9 @@ inline bool make_plan(const nesvor_grid_t* g, int64_t N, BwdPlan* plan, uint64_t
   const int F = g->n_features;
   uint32_t shift0 = 0;
   while ((1u << (shift0 + 1)) * (uint32_t)F <= (uint32_t)kOwnerLdsFloats) ++shift0;
-  // NESVOR_HASHGRID_FINE_LEVELS (tuning hook, default 0): that many of the finest levels take half-size chunks (twice the
-  // owner workgroups, half as long queues).  Measured on PSF clouds at N = 2^20: owner pass 0.050-0.054 ms for 0..4,
-  // aggregation pass +1-3 % - the longest queues are not what sets the owner pass's duration.
-  static const int fine_levels = []() { const char* e = getenv("NESVOR_HASHGRID_FINE_LEVELS"); return e ? atoi(e) : 0; }();
+  // (Half-size chunks for the finest 1..4 levels - twice the owner workgroups, half as long queues - measured on PSF clouds at
+  //  N = 2^20: owner pass 0.050-0.054 ms either way, aggregation pass +1-3 % - the longest queues are not what sets the owner
+  //  pass's duration; not kept.)
   // XCCs of the current device (partition): 32 CUs each on gfx950
   static const uint32_t n_xcc = []() {
     int dev = 0, cus = 0;
@@ -2082,8 +1922,7 @@ inline bool make_plan(const nesvor_grid_t* g, int64_t N, BwdPlan* plan, uint64_t
   uint32_t nb = 0;
   uint64_t off = 0;
   for (int l = 0; l < g->n_levels; ++l) {
-    uint32_t shift = shift0;
-    if (l >= g->n_levels - fine_levels && shift > 8 && ((g->size[l] + (1u << (shift - 1)) - 1) >> (shift - 1)) <= (uint32_t)kMaxChunks) --shift;
+    const uint32_t shift = shift0;
     plan->shift[l] = shift;
     const uint32_t nc = (g->size[l] + (1u << shift) - 1) >> shift;
     if (nc > (uint32_t)kMaxChunks) return false;
@@ -2119,8 +1958,6 @@ inline bool make_plan(const nesvor_grid_t* g, int64_t N, BwdPlan* plan, uint64_t
     plan->n_chunks[l] = 0; plan->bucket_base[l] = nb; plan->cap[l] = 0; plan->slice[l] = kOwnerSlice; plan->rec_off[l] = off;
   }
   plan->n_buckets = nb;
-  static const uint32_t box = []() { const char* e = getenv("NESVOR_HASHGRID_BOX"); return (e == nullptr || atoi(e) != 0) ? 1u : 0u; }();
-  plan->box_slots = box;
   plan->level_begin = 0; plan->level_end = g->n_levels; plan->accumulate_u = 0;
   if (off > 0xFFFFFFFFull) return false;  // records are addressed by 32-bit record numbers
   *n_records = off;
@@ -2443,17 +2280,16 @@ int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table,
     dy_by_slot = 1;
   }
   {
-    static const bool merge = []() { const char* e = getenv("NESVOR_HASHGRID_MERGE"); return e == nullptr || atoi(e) != 0; }();
-#define NESVOR_LAUNCH_AGG(IG, MG, BD)                                                                                     \
-    hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, IG, MG, BD>), grid, block, 0, st, *g, plan, u, table, dpe, gt, gu, \
+#define NESVOR_LAUNCH_AGG(IG, BD)                                                                                         \
+    hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, IG, BD>), grid, block, 0, st, *g, plan, u, table, dpe, gt, gu, \
                        tails, tails_next, records, N, dy_bound, order, order_mode, perm, dy_by_slot)
 #define NESVOR_LAUNCH_AGG_PLAN(IG, BD)                                                                                      \
-    hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, IG, true, BD, true>), grid, block, 0, st, *g, plan, u, table, dpe, gt, gu, \
+    hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, IG, BD, true>), grid, block, 0, st, *g, plan, u, table, dpe, gt, gu, \
                        tails, tails_next, records, N, dy_bound, order, order_mode, perm, dy_by_slot, cloud_plan)
-    const bool bounded = dy_bound != nullptr && merge;  // (the bound only scales the merge table's fixed-point sums)
+    const bool bounded = dy_bound != nullptr;  // (the bound scales the merge table's fixed-point sums)
     bool planned = false;
     if constexpr (F <= 2) {
-      if (cloud_plan != nullptr && merge) {  // (without merging there are no boxes and no rounds: the order alone is used)
+      if (cloud_plan != nullptr) {
         planned = true;
         if (gu != nullptr) { if (bounded) NESVOR_LAUNCH_AGG_PLAN(true, true); else NESVOR_LAUNCH_AGG_PLAN(true, false); }
         else { if (bounded) NESVOR_LAUNCH_AGG_PLAN(false, true); else NESVOR_LAUNCH_AGG_PLAN(false, false); }
@@ -2461,34 +2297,26 @@ int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table,
     }
 #undef NESVOR_LAUNCH_AGG_PLAN
     if (planned) { }
-    else if (gu != nullptr) { if (bounded) NESVOR_LAUNCH_AGG(true, true, true); else if (merge) NESVOR_LAUNCH_AGG(true, true, false); else NESVOR_LAUNCH_AGG(true, false, false); }
-    else { if (bounded) NESVOR_LAUNCH_AGG(false, true, true); else if (merge) NESVOR_LAUNCH_AGG(false, true, false); else NESVOR_LAUNCH_AGG(false, false, false); }
+    else if (gu != nullptr) { if (bounded) NESVOR_LAUNCH_AGG(true, true); else NESVOR_LAUNCH_AGG(true, false); }
+    else { if (bounded) NESVOR_LAUNCH_AGG(false, true); else NESVOR_LAUNCH_AGG(false, false); }
 #undef NESVOR_LAUNCH_AGG
   }
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
 owner_stage:
   if (stages & 2) {
-    static const int coalesced = []() { const char* e = getenv("NESVOR_OWNER_COALESCED"); return e == nullptr ? 1 : atoi(e); }();
     OwnerAdam oa{};
-    // NESVOR_OWNER_STRIDE=<odd number> (A/B switch): deal the (level, chunk) pairs to the workgroup ids with that stride instead
-    // of level by level; raised to the next number coprime to the grid size
-    static const uint32_t want = []() { const char* e = getenv("NESVOR_OWNER_STRIDE"); return e ? (uint32_t)atoi(e) : 1u; }();
     // only the workgroups of this launch's level range (a launch over all ids, the others returning at once, cost the pipelined
     // table update of the training step 30 us per pair of launches: gpurun_out/r06g)
-    const uint32_t wg_base = NESVOR_OWNER_FINE_FIRST ? 0u : owner_grid(g, plan, 0, plan.level_begin);
-    const uint32_t og = NESVOR_OWNER_FINE_FIRST ? owner_grid(g, plan) : owner_grid(g, plan, plan.level_begin, plan.level_end);
+    const uint32_t wg_base = owner_grid(g, plan, 0, plan.level_begin);
+    const uint32_t og = owner_grid(g, plan, plan.level_begin, plan.level_end);
     if (og == 0u) return (int)hipGetLastError();
-    uint32_t id_stride = want < 1u ? 1u : want;
-    auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
-    while (id_stride > 1u && gcd(id_stride, og) != 1u) ++id_stride;
+    const uint32_t id_stride = 1u;  // (kept as a kernel argument: without it the ADAM kernels at F = 4 and 8 take one more SGPR)
     if (adam != nullptr) {
       oa = *adam;
       oa.done = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + 2 * kTailBytes);
-      hipLaunchKernelGGL((hashgrid_bwd_owner<F, true, true>), dim3(og), dim3(kOwnerThreads), 0, st, *g, plan, tails, records, gt, oa, id_stride, wg_base);
-    } else if (coalesced)
       hipLaunchKernelGGL((hashgrid_bwd_owner<F, true>), dim3(og), dim3(kOwnerThreads), 0, st, *g, plan, tails, records, gt, oa, id_stride, wg_base);
-    else
+    } else
       hipLaunchKernelGGL((hashgrid_bwd_owner<F, false>), dim3(og), dim3(kOwnerThreads), 0, st, *g, plan, tails, records, gt, oa, id_stride, wg_base);
   }
   return (int)hipGetLastError();
@@ -2563,7 +2391,6 @@ int launch_fwd_plan(const nesvor_grid_t* g, const float* u, const float* table, 
     uint64_t n_rec;
     if (!make_plan(g, N, &plan, &n_rec, queue_scale)) return (int)hipErrorInvalidValue;
     for (int l = 0; l < NESVOR_MAX_LEVELS; ++l) cpa.n_chunks[l] = plan.n_chunks[l];
-    cpa.box_slots = plan.box_slots;
   }
   hipLaunchKernelGGL((hashgrid_fwd_cloud<F, LAYOUT>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, *g, u, table, pe, N, pe_absmax,
                      (const uint32_t*)nullptr, (float*)nullptr, 0, NESVOR_MAX_LEVELS, order, cloud_plan, cpa);

@@ -40,21 +40,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWidth = 64;      // hidden width (the reference's default and BASELINE's config)
 constexpr int kHB = kWidth / 16;  // feature blocks per hidden layer
-#ifndef NESVOR_MLP_G
-#define NESVOR_MLP_G 2
-#endif
-constexpr int kG = NESVOR_MLP_G;  // 16-sample groups per wave per tile; 2 keeps the kernels under 128 VGPRs (>= 4 waves/SIMD)
+constexpr int kG = 2;  // 16-sample groups per wave per tile; 2 keeps the kernels under 128 VGPRs (>= 4 waves/SIMD); the % (4 * kG) gates assume it
 constexpr int kMaxLayers = NESVOR_MAX_MLP_LAYERS;  // linear layers incl. the output layer
-
-// Timing experiments only (tools/mlp_variants.py; results are wrong by construction): NESVOR_MLP_ABLATE bit 1 wraps every
-// access to the saved hidden activations into the first 4096 groups (a 16 MiB window per layer that stays in L2 / MALL),
-// bit 2 does the same to the sample index of the input / output / gradient streams, bit 4 removes the VALU work of split3(),
-// bit 8 skips the construction of the weight images in LDS.
-#ifndef NESVOR_MLP_ABLATE
-#define NESVOR_MLP_ABLATE 0
-#endif
-__device__ __forceinline__ int64_t hgroup(int64_t gi) { return (NESVOR_MLP_ABLATE & 1) ? (gi & 4095) : gi; }
-__device__ __forceinline__ int64_t sgroup(int64_t gi) { return (NESVOR_MLP_ABLATE & 2) ? (gi & 4095) : gi; }
 
 struct MlpArgs {
   const float* W[kMaxLayers];   // nn.Linear weights, (out, in) row-major
@@ -185,12 +172,6 @@ struct Split2 { s16x4 hi, lo; };
 // (plain asm, not volatile: a pure function of its inputs - the scheduler may move and merge it; `m` is wave-uniform)
 __device__ __forceinline__ Split2 split2(const f32x4& v, float m) {
   uint32_t h0, h1, l0, l1;
-  if (NESVOR_MLP_ABLATE & 4) {  // timing experiment: the split's VALU work removed
-    Split2 r;
-    r.hi = __builtin_bit_cast(s16x4, f32x2{v[0], v[1]});
-    r.lo = r.hi;
-    return r;
-  }
   asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h0) : "v"(v[0]), "s"(m));
   asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h0) : "v"(v[1]), "s"(m));
   asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h1) : "v"(v[2]), "s"(m));
@@ -323,7 +304,6 @@ __device__ __forceinline__ MlpScales mlp_scales(const float* __restrict__ prep, 
 // (BF16: the image holds bf16 elements at the same element indices, i.e. it uses the first half of the fp32 carve)
 template <int BF16 = 0>
 __device__ void build_image(float* img, const float* __restrict__ W, int out_dim, int in_dim, int ob_n, int kb_n) {
-  if (NESVOR_MLP_ABLATE & 8) return;  // timing experiment: what the image build costs a launch
   const int total = ob_n * kb_n * 256;
   for (int e = threadIdx.x; e < total; e += blockDim.x) {
     const int r = e & 3, lane = (e >> 2) & 63, blk = e >> 8;
@@ -337,7 +317,6 @@ __device__ void build_image(float* img, const float* __restrict__ W, int out_dim
 // transposed image: rows i = input features (ib blocks), k = output features (kb blocks)
 template <int BF16 = 0>
 __device__ void build_image_T(float* img, const float* __restrict__ W, int out_dim, int in_dim, int ib_n, int kb_n) {
-  if (NESVOR_MLP_ABLATE & 8) return;
   const int total = ib_n * kb_n * 256;
   for (int e = threadIdx.x; e < total; e += blockDim.x) {
     const int r = e & 3, lane = (e >> 2) & 63, blk = e >> 8;
@@ -351,12 +330,11 @@ __device__ void build_image_T(float* img, const float* __restrict__ W, int out_d
 
 // The same two images with compile-time shapes (no run-time division per element) and the global loads of eight elements
 // per thread in flight at once: the generic builders above walk one dependent load per iteration - 27 to 42 L2 round trips per
-// thread before the first tile, 6-11 us of every launch of the pipelined forward (tools/mlp_variants.py, -DNESVOR_MLP_ABLATE=8).
+// thread before the first tile, 6-11 us of every launch of the pipelined forward (measured with the builds compiled out).
 // T: transposed image (build_image_T); A_N / B_N = (ob_n, kb_n) or (ib_n, kb_n) of the generic versions.
 // SPL: two fp16 planes hi | lo of `total` elements each of W * scale (split2's arithmetic) - the size of the fp32 carve.
 template <int BF16, bool SPL, bool T, int A_N, int B_N, int THREADS>
 __device__ __forceinline__ void build_image_ct(float* img, const float* __restrict__ W, int out_dim, int in_dim, float scale = 1.f) {
-  if (NESVOR_MLP_ABLATE & 8) return;
   constexpr int total = A_N * B_N * 256;
   constexpr int U = 8;
   for (int e0 = threadIdx.x; e0 < total; e0 += THREADS * U) {
@@ -394,7 +372,7 @@ __device__ __forceinline__ void build_image_ct(float* img, const float* __restri
 // scale - and a workgroup copies them: 16-byte loads, all of a thread's in flight at once, no arithmetic.  Measured in the step
 // (in-job A/B, profiles/r06_mlp_image_build.log): the four MLP launches -3.4 us of 129 us at 2^17
 // points per iteration, within noise at 2^20 (the builds had been brought down to ~1 us per launch in round 4; an ablation
-// with the builds compiled out, -DNESVOR_MLP_ABLATE=8, had suggested 30 us - it trains on garbage images, the poses turn NaN and
+// with the builds compiled out had suggested 30 us - it trains on garbage images, the poses turn NaN and
 // every kernel of that step gets faster for reasons that have nothing to do with the builds).  Layout of a network's buffer, in fp16 elements, layer
 // after layer (l = 0 .. n_hidden):   [F hi | F lo | T hi | T lo],  each plane E_l = (output blocks) x (input blocks) x 256 elements,
 // F = the forward image (build_image_ct<.., T = false, output blocks, input blocks>), T = the transposed one (T = true, input
@@ -690,7 +668,7 @@ __device__ __forceinline__ float fetch_input(const MlpArgs& a, int kk, int64_t n
 template <int KB1>
 __device__ __forceinline__ void load_x_fast(const MlpArgs& a, int64_t gi, int j, int q, f32x4 (&x)[KB1]) {
   const int ka_blocks = a.k_a >> 4;
-  const int64_t n = sgroup(gi) * 16 + j;
+  const int64_t n = gi * 16 + j;
 #pragma unroll
   for (int kb = 0; kb < KB1; ++kb) {
     if (kb < ka_blocks) {
@@ -710,7 +688,7 @@ __device__ __forceinline__ void load_x_fast(const MlpArgs& a, int64_t gi, int j,
 template <int KB1>
 __device__ __forceinline__ void store_dx_fast(const MlpArgs& a, int64_t gi, int j, int q, const f32x4 (&dx)[KB1]) {
   const int ka_blocks = a.k_a >> 4;
-  const int64_t n = sgroup(gi) * 16 + j;
+  const int64_t n = gi * 16 + j;
 #pragma unroll
   for (int kb = 0; kb < KB1; ++kb) {
     if (kb < ka_blocks) {
@@ -733,7 +711,7 @@ __device__ __forceinline__ void store_dx_fast(const MlpArgs& a, int64_t gi, int 
   }
 }
 __device__ __forceinline__ f32x4 load_dy_fast(const MlpArgs& a, int64_t gi, int j, int q) {
-  const int64_t n = sgroup(gi) * 16 + j;
+  const int64_t n = gi * 16 + j;
   f32x4 g;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -825,15 +803,13 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
 // OUT1 (split mode, out_dim == 1: sigma_net, b_net): the output layer is a dot product per sample - 16 fp32 FMAs per lane and
 // a sum over the four feature quads - instead of twelve MFMAs on 15/16 padding plus the 3-way split of the last hidden layer
 // (4 fragments x 14 VALU), which nothing else needs.
-#ifndef NESVOR_FWD_MINBLOCKS
-#define NESVOR_FWD_MINBLOCKS 2  // (round 4: with the scalar-base input addressing the split-mode instantiations need 144-156 VGPRs - three
-                                // workgroups would fit a CU; launch_kb explains why two are launched)
-#endif
+constexpr int kFwdMinBlocks = 2;  // (round 4: with the scalar-base input addressing the split-mode instantiations need 144-156 VGPRs - three
+                                  // workgroups would fit a CU; launch_kb explains why two are launched)
 // SPLM: 0 fp32 MFMAs, 1 (true) the split mode, 2 the split mode's leading term alone (nesvor_mlp_t.bf16_operands == 4: scaled fp16
 // operands, ONE MFMA per product - same scales, images and save formats, a third of the matrix work and half of the splitting)
 // NOB (mode 4 only): a bias-free network (NULL nesvor_mlp_t.bias) - the accumulators start at zero, no bias is staged or added.
 template <int KB1, int NH, int SPLM, bool SAVE, bool COMPACT = false, bool OUT1 = false, bool NOB = false>
-__global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? NESVOR_FWD_MINBLOCKS : 1) void mlp_fwd_pf_kernel(const MlpArgs a) {
+__global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? kFwdMinBlocks : 1) void mlp_fwd_pf_kernel(const MlpArgs a) {
   constexpr bool SPL = SPLM != 0;
   static_assert(!NOB || SPLM == 2, "NOB: mode-4 instantiations only");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -914,7 +890,7 @@ __global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? NESVOR_FWD_MINBLOCKS
     for (int g = 0; g < kG; ++g) {
       const int64_t gi = g0 + g;
       const int64_t pixel = a.spg_shift >= 0 ? (gi >> a.spg_shift) : gi / spg;
-      const char* bbase = reinterpret_cast<const char*>(a.xb) + sgroup(gi) * 64;
+      const char* bbase = reinterpret_cast<const char*>(a.xb) + gi * 64;
       const char* abase = reinterpret_cast<const char*>(a.xa) + pixel * (int64_t)(a.k_a * 4);
 #pragma unroll
       for (int kb = 0; kb < KB1; ++kb) {
@@ -1036,7 +1012,7 @@ __global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? NESVOR_FWD_MINBLOCKS
       for (int l = 0; l < NH; ++l)
 #pragma unroll
         for (int g = 0; g < kG; ++g) {
-          const char* hbase = reinterpret_cast<const char*>(a.H[l]) + hgroup(g0 + g) * (int64_t)(kHB * 64 * 16);
+          const char* hbase = reinterpret_cast<const char*>(a.H[l]) + (g0 + g) * (int64_t)(kHB * 64 * 16);
           // (split mode: the layer's values leave in true units - an exact multiplication by a power of two)
           static_for<kHB>([&](auto ob) {
             f32x4 hv = h[l][g][decltype(ob)::value];
@@ -1048,11 +1024,11 @@ __global__ __launch_bounds__(256, (SPLM != 0 && KB1 <= 2) ? NESVOR_FWD_MINBLOCKS
     if constexpr (SAVE && COMPACT) {
 #pragma unroll
       for (int g = 0; g < kG; ++g)
-        store_b32_s_nt<0>(reinterpret_cast<const char*>(a.Hm) + hgroup(g0 + g) * 256, (uint32_t)lane * 4u, hmask[g]);
+        store_b32_s_nt<0>(reinterpret_cast<const char*>(a.Hm) + (g0 + g) * 256, (uint32_t)lane * 4u, hmask[g]);
     }
 #pragma unroll
     for (int g = 0; g < kG; ++g) {
-      const char* ybase = reinterpret_cast<const char*>(a.y) + sgroup(g0 + g) * 64;
+      const char* ybase = reinterpret_cast<const char*>(a.y) + (g0 + g) * 64;
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (4 * q + r < a.out_dim) store_b32_s<0>(ybase, yoff[r], o[g][0][r]);
@@ -1734,31 +1710,22 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = lane & 15, q = lane >> 4;               // chain: sample j, feature quad q;  dW: feature j, sample quad q
   const int role = wave >> 2, pair = wave & 3;
-#ifndef NESVOR_MLP_PAIR_SYNC
-#define NESVOR_MLP_PAIR_SYNC 1
-#endif
   // The tiles are private to a pair (chain wave w, dW wave w + 4): the per-group hand-over needs the two waves of the
   // pair to meet, not all eight.  A two-party barrier on LDS flags (each side publishes the iteration it has finished and
   // waits for the other's; LDS operations of a wave complete in order, so the flag follows the tile traffic) keeps the four
-  // pairs of a workgroup out of lockstep.  NESVOR_MLP_PAIR_SYNC=0: the workgroup barrier.
+  // pairs of a workgroup out of lockstep (the workgroup barrier in its place was measured; not kept).
   __shared__ int arrive[2][4];
   if (threadIdx.x < 8) arrive[threadIdx.x >> 2][threadIdx.x & 3] = 0;
   __syncthreads();
   MLP_TL(unsigned long long tl_sync = 0ull; unsigned long long tl_wait = 0ull; unsigned long long tl_t0 = 0ull;)
   auto pair_sync = [&](int it) __attribute__((always_inline)) {
     MLP_TL(const unsigned long long ts_ = __builtin_amdgcn_s_memtime();)
-    if (NESVOR_MLP_PAIR_SYNC) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      if (lane == 0) __hip_atomic_store(&arrive[role][pair], it + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifndef NESVOR_MLP_SPIN_SLEEP
-#define NESVOR_MLP_SPIN_SLEEP 1
-#endif
-      while (__hip_atomic_load(&arrive[1 - role][pair], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < it + 1)
-        __builtin_amdgcn_s_sleep(NESVOR_MLP_SPIN_SLEEP);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-      __syncthreads();
-    }
+    constexpr int kSpinSleep = 1;  // s_sleep argument between two looks at the other side's flag
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_store(&arrive[role][pair], it + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    while (__hip_atomic_load(&arrive[1 - role][pair], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < it + 1)
+      __builtin_amdgcn_s_sleep(kSpinSleep);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     MLP_TL(tl_sync += __builtin_amdgcn_s_memtime() - ts_;)
   };
   // split mode: tile 0 (dY) fp32 without padding, the NH x 4 dpre tiles as fp16 planes (see stage_planes)
@@ -1800,16 +1767,16 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
     for (int r = 0; r < 4; ++r) yoff[r] = (uint32_t)(((int64_t)min(4 * q + r, a.out_dim - 1) * a.N + j) * 4);
     auto issue_group = [&](int64_t gi, float (&gy)[4], RawH (&hs)[NH][kHB], float& mk) __attribute__((always_inline)) {
       // dY rows 4q .. 4q+3 of sample j: group base in SGPRs, the lane's part (row * N + j, below 2^30 floats: off32) in one VGPR each
-      const char* ybase = reinterpret_cast<const char*>(a.y) + sgroup(gi) * 64;
+      const char* ybase = reinterpret_cast<const char*>(a.y) + gi * 64;
 #pragma unroll
       for (int r = 0; r < 4; ++r) issue_load_b32_s<0>(gy[r], ybase, yoff[r]);
       if constexpr (COMPACT) {
-        issue_load_b32_s<0>(mk, reinterpret_cast<const char*>(a.Hm) + hgroup(gi) * 256, (uint32_t)lane * 4u);
+        issue_load_b32_s<0>(mk, reinterpret_cast<const char*>(a.Hm) + gi * 256, (uint32_t)lane * 4u);
       } else {
         const uint32_t voff = (uint32_t)lane * (4u * kHBytes);
 #pragma unroll
         for (int l = 0; l < NH; ++l) {
-          const char* base = reinterpret_cast<const char*>(a.H[l]) + hgroup(gi) * (int64_t)(kHB * 256 * kHBytes);  // wave-uniform
+          const char* base = reinterpret_cast<const char*>(a.H[l]) + gi * (int64_t)(kHB * 256 * kHBytes);  // wave-uniform
           static_for<kHB>([&](auto IB) {
             constexpr int ib = decltype(IB)::value;
             if constexpr (BF16) issue_load_b64_s<ib * 256 * kHBytes>(hs[l][ib], base, voff);
@@ -2048,7 +2015,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
       auto issue_xc = [&](int64_t gi, float (&xc)[KB1][4]) __attribute__((always_inline)) {
         const int64_t pixel = a.spg_shift >= 0 ? (gi >> a.spg_shift) : gi / (a.S >> 4);
         const char* abase = a.xa != nullptr ? reinterpret_cast<const char*>(a.xa) + pixel * (int64_t)(a.k_a * 4) : reinterpret_cast<const char*>(a.xb);
-        const char* bbase = reinterpret_cast<const char*>(a.xb) + sgroup(gi) * 64;
+        const char* bbase = reinterpret_cast<const char*>(a.xb) + gi * 64;
         const uint32_t n4 = (uint32_t)a.N * 4u;
         const uint32_t xc_offa = (uint32_t)(4 * q * 4);
         const uint32_t xc_offb = (uint32_t)(a.b_row0 + 4 * q) * n4 + (uint32_t)(j * 4);
@@ -2209,7 +2176,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
       const uint32_t voff = (uint32_t)((((j >> 2) * 16 + 4 * q) * 4 + (j & 3)) * kHBytes);
 #pragma unroll
       for (int l = kL0; l < NH; ++l) {
-        const char* base = reinterpret_cast<const char*>(a.H[l]) + hgroup(gi) * (int64_t)(kHB * 256 * kHBytes);  // wave-uniform
+        const char* base = reinterpret_cast<const char*>(a.H[l]) + gi * (int64_t)(kHB * 256 * kHBytes);  // wave-uniform
         static_for<kHB>([&](auto IB) {
           static_for<4>([&](auto T) {
             constexpr int ib = decltype(IB)::value, t = decltype(T)::value;
@@ -2225,7 +2192,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_ws_kernel(const MlpArgs a) {
       // type picks one after the loads have landed
       const int64_t pixel = a.spg_shift >= 0 ? (gi >> a.spg_shift) : gi / (a.S >> 4);
       const char* abase = a.xa != nullptr ? reinterpret_cast<const char*>(a.xa) + pixel * (int64_t)(a.k_a * 4) : reinterpret_cast<const char*>(a.xb);
-      const char* bbase = reinterpret_cast<const char*>(a.xb) + sgroup(gi) * 64;
+      const char* bbase = reinterpret_cast<const char*>(a.xb) + gi * 64;
       // lane parts of the addresses (32-bit byte offsets, see off32): pixel feature 16 kb + j / row (b_row0 + row), samples 4q..
       // - formed here, per group, not kept in registers across the loop (the kernel sits at the 256-register limit)
       const uint32_t n4 = (uint32_t)a.N * 4u;

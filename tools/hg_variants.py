@@ -2,7 +2,7 @@
 the owner pass and the forward are timed on the PSF-cloud distribution (N = 2^20, feature-major) and the table gradient
 is checked against the atomic kernel of the same build.
 
-    python tools/hg_variants.py base: fixed32:-DNESVOR_FIXED32=1
+    python tools/hg_variants.py base: f64fix:-DNESVOR_HG_F64FIX=1
 """
 import os, subprocess, sys
 os.environ.setdefault("NESVOR_HASHGRID_QUEUE", "worst")  # timing tool: worst-case queues from the first call

@@ -44,7 +44,7 @@ def med_of(pred):
 
 fwd = med_of(lambda k: k.startswith("hashgrid_fwd_cloud"))
 agg = med_of(lambda k: k.startswith("hashgrid_bwd_aggregate"))
-own = med_of(lambda k: k.startswith("hashgrid_bwd_owner") and k.split(">")[0].replace(" ", "").endswith("false"))  # <F, COALESCED, ADAM = false>
+own = med_of(lambda k: k.startswith("hashgrid_bwd_owner") and k.split(">")[0].replace(" ", "").endswith("false"))  # <F, ADAM = false>: the last argument tells the two owner kernels apart
 own_adam = med_of(lambda k: k.startswith("hashgrid_bwd_owner") and k.split(">")[0].replace(" ", "").endswith("true"))
 table_params = int(sys.argv[3]) if len(sys.argv) > 3 else 7854240  # the headline table (L=16, F=2, T=2^19): AdamW moves 28 B per parameter
 if fwd and agg and (own or own_adam):

@@ -2,7 +2,7 @@
 saving the hidden activations) and the fused backward of the two networks of the bench config are timed at N = 2^20 in
 the default (split-bf16) evaluation mode.
 
-    python tools/mlp_variants.py base: hidden_in_cache:-DNESVOR_MLP_ABLATE=1 all_in_cache:-DNESVOR_MLP_ABLATE=3
+    python tools/mlp_variants.py base: variant:-DNAME=VALUE
 """
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

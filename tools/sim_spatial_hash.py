@@ -1,5 +1,5 @@
 """How many vertices of a PSF cloud miss their first slot in the hashed merge table of the hash-grid backward's aggregation
-pass (csrc/hashgrid.hip, NESVOR_HG_SPATIAL), CPU only: 200 synthetic clouds of 256 samples (sigma 0.77 / 0.77 / 1.27 mm in a
+pass (csrc/hashgrid.hip, the hashed merge table of the fine levels), CPU only: 200 synthetic clouds of 256 samples (sigma 0.77 / 0.77 / 1.27 mm in a
 130 mm cube, the distribution of tools/hg_variants.py), levels 12-15 of the headline grid (base 9, scale 1.26), 1024 slots.
 
   multiplicative:  slot = (entry index * 2654435761) >> 22          (rounds 1-4)
