@@ -841,6 +841,26 @@ int64_t nesvor_svr_similarity_workspace_bytes(int n, int K, int h, int w);
 int nesvor_srr_step(const float* x, const float* grad, float* out, int D, int H, int W, float alpha, float beta,
                     float delta, int clamp, void* stream);
 
+/* ----------------------------------------------------------------------
+ * E-step of the robust statistics of the classical reconstruction (nesvor_amd/robust.py; the EM scheme of
+ * Kuklisova-Murgasova et al. 2012): pixel posteriors and the per-slice sums of one EM round in one pass.
+ * sim (n,h,w) fp32 the simulated slices A x, y (n,h,w) fp32 the acquired ones, mask (n,h,w) bytes or NULL, scale (n) fp32,
+ * model: three DEVICE floats {sigma2, c, m} (read by the kernel: the caller's loop needs no host synchronisation).
+ * For a valid pixel (mask NULL or its byte set) of slice k
+ *   e = scale[k] * y - sim,   g = exp(-e^2 / (2 sigma2)) / sqrt(2 pi sigma2),   p = c g / (c g + (1 - c) m);
+ * p = 0 on every other pixel.  p (n,h,w) fp32 and stats (n,7) fp64 are fully written (no memset needed):
+ *   stats[k] = { n_k, sum p, sum p e^2, sum (1 - p)^2, sum p y sim, sum p y^2, sum e^2 }   over the valid pixels of slice k;
+ * a slice without a valid pixel yields seven exact zeros, n_k is exact.  The sums are reproducible (no atomics: per-workgroup
+ * partials in the workspace, added in workgroup order by a second launch).  workspace: device memory of at least
+ * nesvor_robust_estep_workspace_bytes(n, h, w) bytes (0 for sizes the call treats as a no-op or refuses).
+ * n == 0: no-op, returns 0.  hipErrorInvalidValue, without a launch: n < 0, h or w below 1, h w > INT_MAX - 256, more than
+ * INT_MAX workgroups (n * ceil(h w / 256)), a null pointer other than mask, a workspace that is missing or too small.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_robust_estep(const float* sim, const float* y, const uint8_t* mask, const float* scale, const float* model, int n,
+                        int h, int w, float* p, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_robust_estep_workspace_bytes(int n, int h, int w);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,8 @@ _SIGNATURES = {
                                c_size_t, _P], c_int),
     "nesvor_svr_similarity_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
     "nesvor_srr_step": ([_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_int, _P], c_int),
+    "nesvor_robust_estep": ([_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P], c_int),
+    "nesvor_robust_estep_workspace_bytes": ([c_int, c_int, c_int], c_int64),
 }
 
 

@@ -9,6 +9,7 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
                                            | --input-slices DIR   --output-volume v.nii.gz [--output-slices DIR]
                                            [--simulated-slices DIR] [--registration svr|stack|none] [--output-resolution 0.8]
                                            [--n-iter-srr 30] [--srr-beta 0.02] [--srr-delta 0.1]
+                                           [--outlier-rejection [--robust-rounds 3] [--slice-weights FILE.json]]
     python -m nesvor_amd.cli sample-volume --input-model m.pt --output-volume v.nii.gz [--output-resolution 0.8] ...
     python -m nesvor_amd.cli sample-slices --input-model m.pt --input-slices DIR --simulated-slices DIR
 
@@ -155,6 +156,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--n-iter-srr", default=30, type=int, help="descent steps")
     g.add_argument("--srr-beta", default=0.02, type=float, help="weight of the edge-preserving prior")
     g.add_argument("--srr-delta", default=0.1, type=float, help="edge scale of the prior, in normalised intensities")
+    g.add_argument("--outlier-rejection", action="store_true",
+                   help="robust statistics: EM pixel and slice weights and per-slice intensity scales (nesvor_amd/robust.py)")
+    g.add_argument("--robust-rounds", default=3, type=int, help="EM rounds the descent steps are split into (with --outlier-rejection)")
+    g.add_argument("--slice-weights", type=str, help="JSON file for the final slice weights and scales (with --outlier-rejection)")
     _common_flags(p)
 
     p = sub.add_parser("sample-volume")
@@ -184,12 +189,16 @@ def merge_args(args_old: Namespace, args_new: Namespace) -> Namespace:
 
 def stacks_to_slices(stacks) -> List:
     """``--registration none``: every non-empty slice of every stack at its nominal pose, each stack normalised by
-    the 0.99 quantile of its masked intensities (svort/inference.py:553-560)."""
+    the 0.99 quantile of its masked intensities (svort/inference.py:553-560).  Every slice carries the index of its stack in
+    ``stacks`` and its own index inside that stack (``stack_idx``, ``slice_idx``)."""
     slices = []
-    for stack in stacks:
+    for j, stack in enumerate(stacks):
         nonempty = stack.mask.flatten(1).any(1)
         stack.slices /= torch.quantile(stack.slices[stack.mask], 0.99)
-        slices.extend(stack[nonempty])
+        kept = stack[nonempty]
+        for s, k in zip(kept, torch.nonzero(nonempty).flatten().tolist()):
+            s.stack_idx, s.slice_idx = j, k
+        slices.extend(kept)
     return slices
 
 

@@ -346,6 +346,42 @@ _op("srr_step_(Tensor x, Tensor(a!) grad, float alpha, float beta, float delta, 
 
 
 # =====================================================================================================================
+# E-step of the robust statistics of the classical reconstruction (csrc/robust.hip): pixel posteriors p and the seven
+# per-slice sums of one EM round in one pass over (sim, y, mask); the host logic is nesvor_amd/robust.py
+# =====================================================================================================================
+def _robust_estep(sim, y, mask, scale, model):
+    _lib.require_device(sim, y, scale, model, dtype=torch.float32, name="robust_estep sim/y/scale/model")
+    m = mask if (mask is not None and mask.numel() > 0) else None
+    if m is not None:
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError(f"robust_estep mask must be torch.bool or torch.uint8, got {m.dtype}")
+        _lib.require_device(m, name="robust_estep mask")
+    if sim.ndim < 3 or y.shape != sim.shape or (m is not None and m.shape != sim.shape):
+        raise RuntimeError("robust_estep: sim, y and mask (n, ..., h, w) of one shape expected")
+    if any(t is not None and t.device != sim.device for t in (y, m, scale, model)):
+        raise RuntimeError("robust_estep: sim, y, mask, scale and model must be on one device")
+    n, h, w = int(sim.shape[0]), int(sim.shape[-2]), int(sim.shape[-1])
+    if sim.numel() != n * h * w or (m is not None and m.numel() != n * h * w):
+        raise RuntimeError("robust_estep: sim / y / mask must hold n x h x w elements")
+    if scale.numel() != n or model.numel() != 3:
+        raise RuntimeError("robust_estep: scale (n) and model {sigma2, c, m} (3) expected")
+    p = torch.empty_like(sim)
+    stats = torch.empty((n, 7), dtype=torch.float64, device=sim.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_robust_estep_workspace_bytes(n, h, w))
+    workspace = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=sim.device)
+    with torch.cuda.device(sim.device):
+        err = lib.nesvor_robust_estep(_lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), _lib.ptr(model), n, h, w, _lib.ptr(p),
+                                      _lib.ptr(stats), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "robust estep")
+    return p, stats
+
+
+_op("robust_estep(Tensor sim, Tensor y, Tensor? mask, Tensor scale, Tensor model) -> (Tensor p, Tensor stats)", _robust_estep,
+    fake=lambda sim, y, mask, scale, model: (torch.empty_like(sim), sim.new_empty((sim.shape[0], 7), dtype=torch.float64)))
+
+
+# =====================================================================================================================
 # multi-resolution hash-grid encoding (tinycudann.Encoding "HashGrid"; the scalars are its encoding_config)
 # =====================================================================================================================
 _SPECS = {}

@@ -4,9 +4,15 @@ an INR.  The pipeline the survey's row f1 calls "a classical SRR baseline": the 
 back-projection ``PSFreconstruction`` as start and ``srr.srr_descent`` - gradient descent on the weighted data term with the
 edge-preserving prior, one fused HIP launch per update (csrc/srr.hip) - to refine it.
 
-Out of scope here: outlier rejection, per-slice intensity scales, per-stack PSFs for unequal thicknesses (the mean thickness
-is used, as the registration does) and a volume mask input.
+Optional robust statistics (``--outlier-rejection``; ``reconstruct_volume(robust_rounds=R)``, nesvor_amd/robust.py): the EM
+scheme of Kuklisova-Murgasova et al. 2012 gives every pixel a posterior weight, every slice a weight and an intensity scale;
+the descent is split into R rounds, each on the weights and scaled slices the statistics of the current A x give.  One pass
+of a fused HIP kernel per round (csrc/robust.hip).  Without the flag the pipeline is the plain one, bit for bit.
+
+Out of scope here: bias fields, robust weights inside the ``--registration svr`` rounds, per-stack PSFs for unequal
+thicknesses (the mean thickness is used, as the registration does) and a volume mask input.
 """
+import json
 import logging
 import time
 from argparse import Namespace
@@ -16,6 +22,7 @@ import torch
 
 from .image import Slice, Volume
 from .registration import _common_frame, _cover_shape, resample
+from .robust import RobustStatistics
 from .srr import AcquisitionOperator, PSFreconstruction, srr_descent
 from .transform import RigidTransform, mat_update_resolution
 from .utils import get_PSF
@@ -28,16 +35,22 @@ def _as_list(v) -> List:
     return list(v) if isinstance(v, (list, tuple)) else [v]
 
 
-def _frame(slices, mask, poses, res_s: float) -> Tuple[torch.Tensor, torch.Tensor, RigidTransform]:
+def _frame_keep(slices, mask, poses, res_s: float) -> Tuple[torch.Tensor, torch.Tensor, RigidTransform, torch.Tensor]:
     """Stacks (n_j,1,h_j,w_j) (or one), their masks (or None: the non-zero pixels) and poses -> the non-empty slices on one
-    padded frame (n,1,s,s), their masks (the non-zero masked pixels) and the frames' poses."""
+    padded frame (n,1,s,s), their masks (the non-zero masked pixels), the frames' poses and the kept slices' indices in the
+    concatenated input."""
     stacks, poses = _as_list(slices), _as_list(poses)
     if mask is not None:
         stacks = [s * m.to(s.dtype) for s, m in zip(stacks, _as_list(mask))]
     images, frame_poses, _ = _common_frame(stacks, poses, res_s)
     m = images > 0
     keep = torch.nonzero(m.flatten(1).any(1)).flatten()
-    return images[keep].contiguous(), m[keep].contiguous(), frame_poses[keep]
+    return images[keep].contiguous(), m[keep].contiguous(), frame_poses[keep], keep
+
+
+def _frame(slices, mask, poses, res_s: float) -> Tuple[torch.Tensor, torch.Tensor, RigidTransform]:
+    """``_frame_keep`` without the indices."""
+    return _frame_keep(slices, mask, poses, res_s)[:3]
 
 
 def _operator(images: torch.Tensor, m: torch.Tensor, frame_poses: RigidTransform, res_s: float, s_thick: float, res_r: float,
@@ -50,21 +63,40 @@ def _operator(images: torch.Tensor, m: torch.Tensor, frame_poses: RigidTransform
 
 
 def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r: float, n_iter: int = 30, beta: float = 0.02,
-                       delta: float = 0.1) -> Volume:
+                       delta: float = 0.1, robust_rounds: int = 0, robust_out: Optional[Dict] = None) -> Volume:
     """Slices at their poses -> the reconstructed ``Volume``: world-aligned (identity pose, centred at the origin), voxel size
     ``res_r``, large enough for every masked pixel; its mask is the set of voxels a masked pixel's PSF reaches (A^T 1 > 0).
 
     slices: a stack (n,1,h,w) of ``res_s`` pixels or a list of stacks; mask: the same of bool, or None (the non-zero pixels);
     poses: a ``RigidTransform`` per stack (one pose per slice).  ``beta`` / ``delta``: the prior's weight and edge scale as the
     reference's ``SRR`` takes them; ``n_iter`` descent steps of length 1 / L (``srr.descent_step_bound``) from the equalised
-    back-projection."""
-    images, m, frame_poses = _frame(slices, mask, poses, res_s)
+    back-projection.
+
+    ``robust_rounds`` R > 0: outlier rejection and slice scales (nesvor_amd/robust.py).  The statistics are initialised on A x
+    of the back-projection; then R times: one EM round on the current A x, and ``n_iter // R`` descent steps (the remainder
+    goes to the last round) on the scaled slices with the pixel weights p * slice weight; the step length is bounded anew
+    for every round's weights (one scalar read per round).  ``robust_out``, a dict, then receives ``slice_weight`` and
+    ``scale`` (n, one entry per non-empty slice, in the order of the concatenated input) and ``keep`` (their indices there).
+    More rounds than descent steps are cut to ``n_iter`` (at least one), so no round runs without a step.
+    ``robust_rounds=0`` is the plain pipeline and leaves ``robust_out`` alone."""
+    images, m, frame_poses, keep = _frame_keep(slices, mask, poses, res_s)
     if images.shape[0] == 0:
         raise ValueError("reconstruct_volume: every slice is empty")
     shape = _cover_shape(frame_poses, m, res_s, s_thick, res_r)
     op, params = _operator(images, m, frame_poses, res_s, s_thick, res_r, shape)
     start = PSFreconstruction(op.transforms, images, m, None, params)
-    x = srr_descent(op, images, start, n_iter, beta, delta)
+    if robust_rounds > 0:
+        x = start
+        rounds = max(1, min(robust_rounds, n_iter))
+        stats = RobustStatistics().init(op.forward(x), images, m)
+        for r in range(rounds):
+            stats.update(op.forward(x), images, m)
+            steps = n_iter // rounds + (n_iter % rounds if r + 1 == rounds else 0)
+            x = srr_descent(op, stats.scaled(images), x, steps, beta, delta, p=stats.weights())
+        if robust_out is not None:
+            robust_out.update(slice_weight=stats.slice_weight, scale=stats.scale, keep=keep)
+    else:
+        x = srr_descent(op, images, start, n_iter, beta, delta)
     cover = op.adjoint(torch.ones_like(images)) > 0
     return Volume(x[0, 0], cover[0, 0], None, res_r, res_r, res_r)
 
@@ -113,11 +145,16 @@ def svr_command(args: Namespace) -> Dict:
 
     if args.input_slices is None and args.input_stacks is None:
         raise SystemExit("No image data provided! Use --input-slices or --input-stacks to input data.")
+    if getattr(args, "slice_weights", None) and not getattr(args, "outlier_rejection", False):
+        raise SystemExit("--slice-weights needs --outlier-rejection: without it no slice weights are estimated")
     t0 = time.time()
     if args.input_slices is not None:
         if args.input_stacks or args.stack_masks or args.thicknesses:
             logging.warning("Since <input-slices> is provided, <input-stacks>, <stack_masks> and <thicknesses> would be ignored.")
-        slices = [s for s in load_slices(args.input_slices, args.device) if bool(s.mask.any())]
+        loaded = load_slices(args.input_slices, args.device)
+        for i, s in enumerate(loaded):  # the files carry no stack: a slice is known by its place in the folder's numeric order
+            s.slice_idx = i
+        slices = [s for s in loaded if bool(s.mask.any())]
         if not slices:
             raise SystemExit("No non-empty slice found in --input-slices")
         sizes = [(float(s.resolution_x), float(s.resolution_y), float(s.resolution_z)) for s in slices]
@@ -136,11 +173,29 @@ def svr_command(args: Namespace) -> Dict:
     logging.info("Data loading and registration finished in %.1f s (%d slices, pixel size %.3f mm, thickness %.3f mm)",
                  time.time() - t0, len(slices), res_s, s_thick)
     t0 = time.time()
-    volume = reconstruct_volume(stacks, masks, poses, res_s, s_thick, args.output_resolution, args.n_iter_srr, args.srr_beta,
-                                args.srr_delta)
+    robust: Dict = {}
+    if getattr(args, "outlier_rejection", False):
+        if args.robust_rounds < 1:
+            raise SystemExit("--robust-rounds must be at least 1")
+        volume = reconstruct_volume(stacks, masks, poses, res_s, s_thick, args.output_resolution, args.n_iter_srr, args.srr_beta,
+                                    args.srr_delta, robust_rounds=args.robust_rounds, robust_out=robust)
+    else:
+        volume = reconstruct_volume(stacks, masks, poses, res_s, s_thick, args.output_resolution, args.n_iter_srr, args.srr_beta,
+                                    args.srr_delta)
     if args.device.type == "cuda":
         torch.cuda.synchronize(args.device)
     logging.info("Reconstruction finished in %.1f s (volume %s)", time.time() - t0, tuple(volume.image.shape))
+    if robust:
+        weight, scale, keep = robust["slice_weight"].tolist(), robust["scale"].tolist(), robust["keep"].tolist()
+        logging.info("Outlier rejection: %d of %d slices ended with a weight below 0.5; slice scales %.3f .. %.3f",
+                     sum(w < 0.5 for w in weight), len(weight), min(scale), max(scale))
+        if getattr(args, "slice_weights", None):
+            # stack: the index among --input-stacks, slice: the index inside that stack; with --input-slices stack is null and
+            # slice the file's place in the folder's numeric order
+            rows = [{"stack": slices[k].stack_idx, "slice": slices[k].slice_idx, "weight": w, "scale": s}
+                    for k, w, s in zip(keep, weight, scale)]
+            with open(args.slice_weights, "w") as f:
+                json.dump(rows, f, indent=1)
     data = {"output_volume": volume, "output_slices": slices}
     if args.simulated_slices:
         data["simulated_slices"] = simulate_slices(volume, stacks, masks, poses, res_s, s_thick)
