@@ -861,6 +861,25 @@ int nesvor_robust_estep(const float* sim, const float* y, const uint8_t* mask, c
                         int h, int w, float* p, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 int64_t nesvor_robust_estep_workspace_bytes(int n, int h, int w);
 
+/* ----------------------------------------------------------------------
+ * Masked moments of slice pairs, the sums the stack quality scores are functions of (nesvor_amd/assess.py): NCC of
+ * adjacent slices, the Gram matrix of a stack.  slices (n,h,w) fp32, mask (n,h,w) bytes or NULL, pairs (P,2) DEVICE int32.
+ * For pair p = (a, b) over the pixels valid in both slices (both mask bytes set; every pixel when mask is NULL)
+ *   moments[p] = { count, sum a, sum b, sum a^2, sum b^2, sum a b }        fp64, (P,6), fully written (no memset needed);
+ * a pair without a common valid pixel yields six exact zeros, the count is exact.  Products are fp32, sums fp32 inside one
+ * wave (64 terms) and fp64 beyond; reproducible (no atomics: per-workgroup partials in the workspace, added in workgroup
+ * order by a second launch).  Self-pairs and repeated pairs are legal; (b, a) yields the bits of (a, b) with columns
+ * 1 <-> 2 and 3 <-> 4 swapped.  The pair indices are NOT checked on the device: the caller range-checks them (0 <= index < n)
+ * on the host before the upload.  workspace: device memory of at least nesvor_pair_moments_workspace_bytes(P, h, w) bytes
+ * (0 for sizes the call treats as a no-op or refuses).
+ * P == 0: no-op, returns 0.  hipErrorInvalidValue, without a launch: P < 0, n, h or w below 1, h w > INT_MAX - 256, more than
+ * INT_MAX workgroups (P * ceil(h w / 256)), a null pointer other than mask, a workspace that is missing or too small.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_pair_moments(const float* slices, const uint8_t* mask, int n, int h, int w, const int32_t* pairs, int P,
+                        double* moments, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_pair_moments_workspace_bytes(int P, int h, int w);
+
 #ifdef __cplusplus
 }
 #endif

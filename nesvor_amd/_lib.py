@@ -226,6 +226,8 @@ _SIGNATURES = {
     "nesvor_srr_step": ([_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_int, _P], c_int),
     "nesvor_robust_estep": ([_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P], c_int),
     "nesvor_robust_estep_workspace_bytes": ([c_int, c_int, c_int], c_int64),
+    "nesvor_pair_moments": ([_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, c_size_t, _P], c_int),
+    "nesvor_pair_moments_workspace_bytes": ([c_int, c_int, c_int], c_int64),
 }
 
 

@@ -5,11 +5,15 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
                                            | --input-slices DIR   --output-volume v.nii.gz [--output-model m.pt]
                                            [--output-slices DIR] [--simulated-slices DIR]  [training flags]
     python -m nesvor_amd.cli register      --input-stacks a.nii.gz b.nii.gz --output-slices DIR [--registration stack|svr|none]
+                                           [--template-stack 0|K|auto] [--template-metric ncc|matrix-rank|volume]
     python -m nesvor_amd.cli svr           --input-stacks a.nii.gz b.nii.gz c.nii.gz [--stack-masks ...] [--thicknesses ...]
                                            | --input-slices DIR   --output-volume v.nii.gz [--output-slices DIR]
                                            [--simulated-slices DIR] [--registration svr|stack|none] [--output-resolution 0.8]
                                            [--n-iter-srr 30] [--srr-beta 0.02] [--srr-delta 0.1]
                                            [--outlier-rejection [--robust-rounds 3] [--slice-weights FILE.json]]
+                                           [--template-stack 0|K|auto] [--template-metric ncc|matrix-rank|volume]
+    python -m nesvor_amd.cli assess        --input-stacks a.nii.gz b.nii.gz c.nii.gz [--stack-masks ...] [--thicknesses ...]
+                                           [--metric ncc|matrix-rank|volume] [--output-json FILE.json]
     python -m nesvor_amd.cli sample-volume --input-model m.pt --output-volume v.nii.gz [--output-resolution 0.8] ...
     python -m nesvor_amd.cli sample-slices --input-model m.pt --input-slices DIR --simulated-slices DIR
 
@@ -28,6 +32,13 @@ one process per GPU (nesvor_amd/ddp.py); rank 0 samples and writes the outputs. 
 
 Also not in the reference: ``svr``, the classical pipeline without an INR - registration (default ``svr``), then a
 super-resolution reconstruction by gradient descent with the edge-preserving prior (nesvor_amd/svr.py, csrc/srr.hip).
+
+Also not in the reference (upstream added an ``assess`` command in later releases): ``assess`` scores every input stack for
+motion (nesvor_amd/assess.py, csrc/assess.hip; ``ncc`` of adjacent slices, ``matrix-rank`` = effective rank of the stack's
+data matrix, ``volume`` of the mask; higher is better) and ranks them; ``--template-stack`` on ``reconstruct``, ``register`` and
+``svr`` names the stack that ``--registration stack`` / ``svr`` align the others to and centre the world frame on - an index
+(default 0, the first file, as before) or ``auto`` = the best stack under ``--template-metric``.  The output slices keep the
+input order.  With ``--registration none`` or ``--input-slices`` the two flags are ignored with a warning.
 """
 import argparse
 import logging
@@ -102,6 +113,14 @@ def _common_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--debug", action="store_true")
 
 
+def _template_flags(g) -> None:
+    g.add_argument("--template-stack", default="0", type=str,
+                   help="(not in the reference) the stack the registration aligns the others to and centres the world frame on: an "
+                        "index among --input-stacks, or 'auto' = the best stack under --template-metric (nesvor_amd/assess.py)")
+    g.add_argument("--template-metric", default="ncc", type=str, choices=["ncc", "matrix-rank", "volume"],
+                   help="the score --template-stack auto ranks the stacks by")
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="nesvor_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = parser.add_subparsers(dest="command", required=True)
@@ -122,6 +141,7 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_argument_group("registration")
     g.add_argument("--registration", default="none", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
+    _template_flags(g)
     _training_flags(p)
     _common_flags(p)
 
@@ -135,6 +155,7 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_argument_group("registration")
     g.add_argument("--registration", default="stack", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
+    _template_flags(g)
     _common_flags(p)
 
     p = sub.add_parser("svr")
@@ -152,6 +173,7 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_argument_group("registration")
     g.add_argument("--registration", default="svr", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
+    _template_flags(g)
     g = p.add_argument_group("super-resolution reconstruction")
     g.add_argument("--n-iter-srr", default=30, type=int, help="descent steps")
     g.add_argument("--srr-beta", default=0.02, type=float, help="weight of the edge-preserving prior")
@@ -160,6 +182,17 @@ def build_parser() -> argparse.ArgumentParser:
                    help="robust statistics: EM pixel and slice weights and per-slice intensity scales (nesvor_amd/robust.py)")
     g.add_argument("--robust-rounds", default=3, type=int, help="EM rounds the descent steps are split into (with --outlier-rejection)")
     g.add_argument("--slice-weights", type=str, help="JSON file for the final slice weights and scales (with --outlier-rejection)")
+    _common_flags(p)
+
+    p = sub.add_parser("assess")
+    g = p.add_argument_group("input")
+    g.add_argument("--input-stacks", nargs="+", type=str, required=True)
+    g.add_argument("--thicknesses", nargs="+", type=float)
+    g.add_argument("--stack-masks", nargs="+", type=str)
+    g = p.add_argument_group("assessment")
+    g.add_argument("--metric", default="ncc", type=str, choices=["ncc", "matrix-rank", "volume"],
+                   help="per-stack score, higher is better (nesvor_amd/assess.py)")
+    g.add_argument("--output-json", type=str, help="JSON file for the list of per-stack results")
     _common_flags(p)
 
     p = sub.add_parser("sample-volume")
@@ -282,29 +315,57 @@ def _load_stacks(args: Namespace) -> List:
 
 def register(args: Namespace, stacks: List) -> List:
     """Stacks -> motion-corrected slices (cli/commands.py:171-176): ``none`` keeps the nominal poses, ``stack``
-    registers every stack to the first one, ``svr`` then registers every slice to a volume reconstructed from all of
+    registers every stack to the template (``--template-stack``: the first one by default, ``auto`` = the best stack under
+    ``--template-metric``, nesvor_amd/assess.py), ``svr`` then registers every slice to a volume reconstructed from all of
     them (``register_slices``); the SVoRT-based choices need the pretrained transformer (out of scope)."""
     if args.registration not in ("none", "stack", "svr"):
         raise NotImplementedError(f"--registration {args.registration}: the SVoRT transformer is out of scope of this "
                                   "build; register with the reference and pass the result through --input-slices, or use "
                                   "--registration svr / stack / none")
+    if args.registration == "none":
+        warn_template_ignored(args, "--registration none")
+        return stacks_to_slices(stacks)
+    from .assess import choose_template
+
+    # the template only names the registration's target: the stacks, and stack_idx / slice_idx of the slices, stay in input order
+    template = choose_template(stacks, getattr(args, "template_stack", "0"), getattr(args, "template_metric", "ncc"))
     if args.registration == "stack":
         from .registration import register_stacks
 
         t1 = time.time()
-        stacks = register_stacks(stacks)
+        stacks = register_stacks(stacks, template=template)
         logging.info("Stack registration finished in %.1f s", time.time() - t1)
     elif args.registration == "svr":
         from .registration import register_slices
 
         t1 = time.time()
-        stacks = register_slices(stacks)
+        stacks = register_slices(stacks, template=template)
         logging.info("Slice-to-volume registration finished in %.1f s", time.time() - t1)
     return stacks_to_slices(stacks)
 
 
+def warn_template_ignored(args: Namespace, why: str) -> None:
+    """``--template-stack`` / ``--template-metric`` only act where stacks are registered."""
+    if str(getattr(args, "template_stack", "0")) != "0" or getattr(args, "template_metric", "ncc") != "ncc":
+        logging.warning("--template-stack / --template-metric are ignored with %s: no stack is registered to a template", why)
+
+
 def register_cmd(args: Namespace) -> None:
     _outputs({"output_slices": register(args, _load_stacks(args))}, args)
+
+
+def assess_cmd(args: Namespace) -> None:
+    import json
+
+    from .assess import assess_stacks, format_table
+
+    rows = assess_stacks(_load_stacks(args), args.metric)
+    logging.info("Stack assessment (%s, higher is better):\n%s", args.metric, format_table(rows))
+    for row, path in zip(rows, args.input_stacks):
+        row["input_stack"] = path
+    if args.output_json:
+        with open(args.output_json, "w") as f:  # (a score of nan - no countable pair - is written as null)
+            json.dump([{k: None if isinstance(v, float) and v != v else v for k, v in row.items()} for row in rows], f, indent=1)
 
 
 def reconstruct(args: Namespace) -> None:
@@ -317,6 +378,8 @@ def reconstruct(args: Namespace) -> None:
     if args.input_slices is not None and (args.input_stacks or args.stack_masks or args.thicknesses):
         logging.warning("Since <input-slices> is provided, <input-stacks>, <stack_masks> and <thicknesses> would be ignored.")
         args.input_stacks = args.stack_masks = args.thicknesses = None
+    if args.input_slices is not None:
+        warn_template_ignored(args, "--input-slices")
     for name in ("stack_masks", "thicknesses"):
         if getattr(args, name) is not None and len(getattr(args, name)) != len(args.input_stacks):
             raise SystemExit(f"The numbers of {name.replace('_', ' ')} and input stacks are different!")
@@ -396,7 +459,7 @@ def main(argv=None) -> None:
         return  # under a launcher only `reconstruct` is data-parallel: one process does the rest
     _setup(args)
     t0 = time.time()
-    {"reconstruct": reconstruct, "register": register_cmd, "svr": svr_cmd, "sample-volume": sample_volume_cmd,
+    {"reconstruct": reconstruct, "register": register_cmd, "svr": svr_cmd, "assess": assess_cmd, "sample-volume": sample_volume_cmd,
      "sample-slices": sample_slices_cmd}[args.command](args)
     logging.info("Command 'nesvor %s' finished, overall time: %.1f s", args.command, time.time() - t0)
 

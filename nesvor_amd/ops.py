@@ -382,6 +382,44 @@ _op("robust_estep(Tensor sim, Tensor y, Tensor? mask, Tensor scale, Tensor model
 
 
 # =====================================================================================================================
+# masked moments of slice pairs for the stack quality assessment (csrc/assess.hip): {count, sum a, sum b, sum a^2, sum b^2,
+# sum a b} per pair over the pixels valid in both slices; the host logic (and the range check of the pair indices, which the
+# kernel does not repeat) is nesvor_amd/assess.py
+# =====================================================================================================================
+def _pair_moments(slices, mask, pairs):
+    _lib.require_device(slices, dtype=torch.float32, name="pair_moments slices")
+    _lib.require_device(pairs, dtype=torch.int32, name="pair_moments pairs")
+    m = mask if (mask is not None and mask.numel() > 0) else None
+    if m is not None:
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError(f"pair_moments mask must be torch.bool or torch.uint8, got {m.dtype}")
+        _lib.require_device(m, name="pair_moments mask")
+    if slices.ndim < 3 or (m is not None and m.shape != slices.shape):
+        raise RuntimeError("pair_moments: slices and mask (n, ..., h, w) of one shape expected")
+    if pairs.ndim != 2 or pairs.shape[1] != 2:
+        raise RuntimeError("pair_moments: pairs (P, 2) expected")
+    if any(t is not None and t.device != slices.device for t in (m, pairs)):
+        raise RuntimeError("pair_moments: slices, mask and pairs must be on one device")
+    n, h, w = int(slices.shape[0]), int(slices.shape[-2]), int(slices.shape[-1])
+    if slices.numel() != n * h * w:
+        raise RuntimeError("pair_moments: slices / mask must hold n x h x w elements")
+    P = int(pairs.shape[0])
+    moments = torch.empty((P, 6), dtype=torch.float64, device=slices.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_pair_moments_workspace_bytes(P, h, w))
+    workspace = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=slices.device)
+    with torch.cuda.device(slices.device):
+        err = lib.nesvor_pair_moments(_lib.ptr(slices), _lib.ptr(m), n, h, w, _lib.ptr(pairs), P, _lib.ptr(moments),
+                                      _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "pair moments")
+    return moments
+
+
+_op("pair_moments(Tensor slices, Tensor? mask, Tensor pairs) -> Tensor", _pair_moments,
+    fake=lambda slices, mask, pairs: slices.new_empty((pairs.shape[0], 6), dtype=torch.float64))
+
+
+# =====================================================================================================================
 # multi-resolution hash-grid encoding (tinycudann.Encoding "HashGrid"; the scalars are its encoding_config)
 # =====================================================================================================================
 _SPECS = {}

@@ -447,10 +447,19 @@ def stack_registration(transforms_list: List[List[RigidTransform]], transform_ta
     return out
 
 
-def register_stacks(dataset: List, res_s: float = 1.0) -> List:
+def register_stacks(dataset: List, res_s: float = 1.0, template: int = 0) -> List:
     """``--registration stack``: in-plane resampling of the masked stacks to ``res_s`` mm (parse_data), stack
     registration to the first stack, new per-slice poses written into the stacks (run_svort with svort=False, vvr=True).
-    As in the reference, the slice spacing of the output poses is the MEAN thickness of the input stacks."""
+    As in the reference, the slice spacing of the output poses is the MEAN thickness of the input stacks.
+
+    ``template`` (not in the reference; ``--template-stack``, nesvor_amd/assess.py) names the stack the others are registered
+    to and the world frame is centred on: that stack is moved to the front for the registration, the poses land in the stacks
+    themselves, and the list comes back in input order.  ``template=0`` is the reference's behaviour."""
+    if template != 0:
+        if not 0 <= template < len(dataset):
+            raise ValueError(f"template stack {template} out of range: {len(dataset)} stacks")
+        register_stacks([dataset[template]] + [s for j, s in enumerate(dataset) if j != template], res_s)
+        return dataset
     t0 = time.time()
     stacks = [resample(s.slices * s.mask, (s.resolution_x, s.resolution_y), (res_s, res_s)) for s in dataset]
     transforms = [s.transformation for s in dataset]
@@ -518,11 +527,12 @@ def _cover_shape(poses: RigidTransform, mask: torch.Tensor, res_s: float, s_thic
     return size[2], size[1], size[0]
 
 
-def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = None, n_outer: int = 3) -> List:
-    """``--registration svr``: stack registration (``register_stacks``), then ``n_outer`` rounds of  reconstruct a volume
-    from all slices at their current poses  /  register every non-empty slice rigidly to it (``SVR``, global NCC); the
-    per-slice poses are written back into the stacks.  ``res_r``: voxel size of the intermediate volume (default ``res_s``)."""
-    dataset = register_stacks(dataset, res_s)
+def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = None, n_outer: int = 3, template: int = 0) -> List:
+    """``--registration svr``: stack registration (``register_stacks``, to the stack ``template``), then ``n_outer`` rounds of
+    reconstruct a volume from all slices at their current poses  /  register every non-empty slice rigidly to it (``SVR``,
+    global NCC); the per-slice poses are written back into the stacks.  ``res_r``: voxel size of the intermediate volume
+    (default ``res_s``)."""
+    dataset = register_stacks(dataset, res_s, template)
     t0 = time.time()
     res_r = res_s if res_r is None else res_r
     s_thick = float(sum(s.thickness for s in dataset) / len(dataset))

@@ -151,6 +151,7 @@ def svr_command(args: Namespace) -> Dict:
     if args.input_slices is not None:
         if args.input_stacks or args.stack_masks or args.thicknesses:
             logging.warning("Since <input-slices> is provided, <input-stacks>, <stack_masks> and <thicknesses> would be ignored.")
+        cli.warn_template_ignored(args, "--input-slices")
         loaded = load_slices(args.input_slices, args.device)
         for i, s in enumerate(loaded):  # the files carry no stack: a slice is known by its place in the folder's numeric order
             s.slice_idx = i
