@@ -880,6 +880,48 @@ int nesvor_pair_moments(const float* slices, const uint8_t* mask, int n, int h, 
                         double* moments, void* workspace, size_t workspace_bytes, void* stream);
 int64_t nesvor_pair_moments_workspace_bytes(int P, int h, int w);
 
+/* ----------------------------------------------------------------------
+ * Bias field correction (nesvor_amd/bias.py; N4-style: histogram sharpening and a multilevel cubic B-spline fit of the log
+ * field): the three per-iteration passes over a stack taken as a (D,H,W) array in index space.  Common to all three:
+ * v (D,H,W) fp32 the log intensities, f (D,H,W) fp32 the log field, mask (D,H,W) bytes or NULL (any set byte = valid voxel,
+ * NULL = all valid), u = v - f in double.  range: two DEVICE floats {lo, hi} (read by the kernels: the caller's loop needs no
+ * host synchronisation); slope = (hi - lo) / (n_bins - 1) and the bin coordinate c = (u - lo) / slope clamped to
+ * [0, n_bins - 1] (a NaN counts as 0), both in double.  The B-spline lattice has S spans and C = S + 3 control points per
+ * axis; per axis a table pair of the voxel indices 0 .. n - 1: s* (n) int32 the first control index (clamped to [0, S - 1] on
+ * the device) and t* (n,4) fp32 the four uniform cubic basis values on control indices s .. s + 3.  Results are fully
+ * written (no memset needed) and bit-identical from run to run: no floating-point atomics; fp32 sums only inside one wave
+ * (64 terms), fp64 beyond; partials in the workspace, added in a fixed order by small follow-up launches.  workspace: device
+ * memory of at least the matching *_workspace_bytes(...) bytes (0 for sizes the call refuses).
+ * hipErrorInvalidValue, without a launch: a null pointer other than mask, a dimension below 1, D H W > INT_MAX - 256,
+ * S < 1 or C > 16, n_bins < 2 or n_bins > 1024, a workspace that is missing or too small.
+ *
+ * nesvor_n4_histogram: hist (n_bins) fp64, the fractionally binned histogram of u over the valid voxels: with
+ *   i = min(floor c, n_bins - 2) a voxel adds 1 - (c - i) to bin i and c - i to bin i + 1.  Integer LDS atomics on fixed-point
+ *   weights with the quantum 2^-32 (a voxel adds round((c - i) 2^32) and 2^32 minus that: the total is the exact count; a
+ *   bin is within 2^-33 per touching voxel of the fp64 sum), per-workgroup 64-bit bins added by the second launch.
+ * nesvor_n4_fit: lut (n_bins) fp64 the sharpened histogram's conditional expectation E; the residual of a valid voxel is
+ *   r = u - (E[j] (1 - t) + E[j+1] t), j = min(floor c, n_bins - 2), t = c - j.  With w_k the product of a voxel's three axis
+ *   weights on control point k:  weight[k] = sum_p w_kp^2,  lattice[k] = sum_p w_kp^3 r_p / (sum_c w_cp^2) / weight[k]
+ *   (0 where weight[k] is 0), both (C,C,C) fp64, over the valid voxels p.  One pass contracts x per (z,y) row, two small
+ *   launches contract y, then z, in ascending index order.
+ * nesvor_n4_update: f += sum_k lattice[k] w_k IN PLACE on every voxel (the sum in double, rounded once); stats: five fp64
+ *   {count, sum g, sum g^2, min u_new, max u_new} over the valid voxels, g = expm1(the voxel's increment), u_new = v - f_new
+ *   (+inf / -inf without a valid voxel): the stop test and the next iteration's range.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_n4_histogram(const float* v, const float* f, const uint8_t* mask, int D, int H, int W, const float* range,
+                        int n_bins, double* hist, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_n4_histogram_workspace_bytes(int D, int H, int W, int n_bins);
+int nesvor_n4_fit(const float* v, const float* f, const uint8_t* mask, const float* range, const double* lut, int n_bins,
+                  const float* tz, const float* ty, const float* tx, const int32_t* sz, const int32_t* sy, const int32_t* sx,
+                  int D, int H, int W, int S, double* lattice, double* weight, void* workspace, size_t workspace_bytes,
+                  void* stream);
+int64_t nesvor_n4_fit_workspace_bytes(int D, int H, int W, int S);
+int nesvor_n4_update(const double* lattice, const float* tz, const float* ty, const float* tx, const int32_t* sz,
+                     const int32_t* sy, const int32_t* sx, int S, float* f, const float* v, const uint8_t* mask, int D, int H,
+                     int W, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_n4_update_workspace_bytes(int D, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

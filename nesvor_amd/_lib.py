@@ -228,6 +228,12 @@ _SIGNATURES = {
     "nesvor_robust_estep_workspace_bytes": ([c_int, c_int, c_int], c_int64),
     "nesvor_pair_moments": ([_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, c_size_t, _P], c_int),
     "nesvor_pair_moments_workspace_bytes": ([c_int, c_int, c_int], c_int64),
+    "nesvor_n4_histogram": ([_P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, c_size_t, _P], c_int),
+    "nesvor_n4_histogram_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
+    "nesvor_n4_fit": ([_P] * 5 + [c_int] + [_P] * 6 + [c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P], c_int),
+    "nesvor_n4_fit_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
+    "nesvor_n4_update": ([_P] * 7 + [c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P], c_int),
+    "nesvor_n4_update_workspace_bytes": ([c_int, c_int, c_int], c_int64),
 }
 
 

@@ -14,6 +14,8 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
                                            [--template-stack 0|K|auto] [--template-metric ncc|matrix-rank|volume]
     python -m nesvor_amd.cli assess        --input-stacks a.nii.gz b.nii.gz c.nii.gz [--stack-masks ...] [--thicknesses ...]
                                            [--metric ncc|matrix-rank|volume] [--output-json FILE.json]
+    python -m nesvor_amd.cli correct-bias-field --input-stacks a.nii.gz b.nii.gz [--stack-masks ...]
+                                           --output-corrected-stacks ca.nii.gz cb.nii.gz [--output-bias-fields fa.nii.gz fb.nii.gz]
     python -m nesvor_amd.cli sample-volume --input-model m.pt --output-volume v.nii.gz [--output-resolution 0.8] ...
     python -m nesvor_amd.cli sample-slices --input-model m.pt --input-slices DIR --simulated-slices DIR
 
@@ -39,6 +41,13 @@ data matrix, ``volume`` of the mask; higher is better) and ranks them; ``--templ
 ``svr`` names the stack that ``--registration stack`` / ``svr`` align the others to and centre the world frame on - an index
 (default 0, the first file, as before) or ``auto`` = the best stack under ``--template-metric``.  The output slices keep the
 input order.  With ``--registration none`` or ``--input-slices`` the two flags are ignored with a warning.
+
+Also not in the reference (upstream added both in later releases, on SimpleITK's N4): ``correct-bias-field`` estimates the smooth
+multiplicative coil bias of every input stack (nesvor_amd/bias.py, csrc/bias.hip: histogram sharpening and a multilevel
+B-spline fit of the log field, this project's own definition) and writes the corrected stacks and, with
+``--output-bias-fields``, the fields ``exp(f)``; ``--bias-field-correction`` on ``reconstruct``, ``register``, ``svr`` and
+``assess`` applies the same correction to the stacks as they are loaded, before assessment, template choice and registration.
+The ``--*-n4`` flags (levels, iterations, tolerance, control points, bins, FWHM, noise) are shared by the five commands.
 """
 import argparse
 import logging
@@ -121,6 +130,27 @@ def _template_flags(g) -> None:
                    help="the score --template-stack auto ranks the stacks by")
 
 
+def _bias_flags(p: argparse.ArgumentParser, switch: bool = True) -> None:
+    g = p.add_argument_group("bias field correction (not in the reference; nesvor_amd/bias.py)")
+    if switch:
+        g.add_argument("--bias-field-correction", action="store_true",
+                       help="remove the smooth multiplicative bias of every input stack as it is loaded (N4-style)")
+    g.add_argument("--n-levels-n4", default=4, type=int, help="B-spline levels; level l has (n-control-points - 3) 2^l spans per axis")
+    g.add_argument("--n-iter-n4", default=50, type=int, help="iterations per level at most")
+    g.add_argument("--tol-n4", default=0.001, type=float, help="a level ends when the field's relative change falls below this")
+    g.add_argument("--n-control-points-n4", default=4, type=int, help="control points per axis on the first level")
+    g.add_argument("--n-bins-n4", default=200, type=int, help="histogram bins")
+    g.add_argument("--fwhm-n4", default=0.15, type=float, help="FWHM of the Gaussian the histogram is deconvolved with (log intensity)")
+    g.add_argument("--noise-n4", default=0.01, type=float, help="Wiener filter noise")
+
+
+def bias_options(args: Namespace) -> Dict:
+    """The keyword arguments of ``bias.correct_bias_field`` from the ``--*-n4`` flags (defaults where a Namespace lacks them)."""
+    return {"n_levels": getattr(args, "n_levels_n4", 4), "n_iter": getattr(args, "n_iter_n4", 50), "tol": getattr(args, "tol_n4", 1e-3),
+            "n_control_points": getattr(args, "n_control_points_n4", 4), "n_bins": getattr(args, "n_bins_n4", 200),
+            "fwhm": getattr(args, "fwhm_n4", 0.15), "noise": getattr(args, "noise_n4", 0.01)}
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="nesvor_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = parser.add_subparsers(dest="command", required=True)
@@ -143,6 +173,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
     _training_flags(p)
+    _bias_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("register")
@@ -156,6 +187,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--registration", default="stack", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
+    _bias_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("svr")
@@ -182,6 +214,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="robust statistics: EM pixel and slice weights and per-slice intensity scales (nesvor_amd/robust.py)")
     g.add_argument("--robust-rounds", default=3, type=int, help="EM rounds the descent steps are split into (with --outlier-rejection)")
     g.add_argument("--slice-weights", type=str, help="JSON file for the final slice weights and scales (with --outlier-rejection)")
+    _bias_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("assess")
@@ -193,6 +226,17 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--metric", default="ncc", type=str, choices=["ncc", "matrix-rank", "volume"],
                    help="per-stack score, higher is better (nesvor_amd/assess.py)")
     g.add_argument("--output-json", type=str, help="JSON file for the list of per-stack results")
+    _bias_flags(p)
+    _common_flags(p)
+
+    p = sub.add_parser("correct-bias-field")
+    g = p.add_argument_group("input")
+    g.add_argument("--input-stacks", nargs="+", type=str, required=True)
+    g.add_argument("--stack-masks", nargs="+", type=str)
+    g = p.add_argument_group("output")
+    g.add_argument("--output-corrected-stacks", nargs="+", type=str, required=True)
+    g.add_argument("--output-bias-fields", nargs="+", type=str, help="the estimated fields exp(f), one file per input stack")
+    _bias_flags(p, switch=False)
     _common_flags(p)
 
     p = sub.add_parser("sample-volume")
@@ -310,6 +354,12 @@ def _load_stacks(args: Namespace) -> List:
         if args.thicknesses is not None:
             st.thickness = args.thicknesses[i]
         stacks.append(st)
+    if getattr(args, "bias_field_correction", False):
+        from . import bias
+
+        t0 = time.time()
+        bias.correct_stacks(stacks, **bias_options(args))
+        logging.info("Bias field correction of %d stacks finished in %.1f s", len(stacks), time.time() - t0)
     return stacks
 
 
@@ -366,6 +416,23 @@ def assess_cmd(args: Namespace) -> None:
     if args.output_json:
         with open(args.output_json, "w") as f:  # (a score of nan - no countable pair - is written as null)
             json.dump([{k: None if isinstance(v, float) and v != v else v for k, v in row.items()} for row in rows], f, indent=1)
+
+
+def correct_bias_field_cmd(args: Namespace) -> None:
+    from . import bias
+    from .image_io import save_stack
+
+    for name in ("output_corrected_stacks", "output_bias_fields", "stack_masks"):
+        if getattr(args, name, None) is not None and len(getattr(args, name)) != len(args.input_stacks):
+            raise SystemExit(f"The numbers of {name.replace('_', ' ')} and input stacks are different!")
+    args.thicknesses = None
+    args.bias_field_correction = False  # (the stacks are corrected below, where the fields are at hand)
+    stacks = _load_stacks(args)
+    fields = bias.correct_stacks(stacks, **bias_options(args))
+    for i, (st, field) in enumerate(zip(stacks, fields)):
+        save_stack(args.output_corrected_stacks[i], st)
+        if args.output_bias_fields is not None:
+            save_stack(args.output_bias_fields[i], st, torch.exp(field).to(st.slices.dtype))
 
 
 def reconstruct(args: Namespace) -> None:
@@ -459,7 +526,8 @@ def main(argv=None) -> None:
         return  # under a launcher only `reconstruct` is data-parallel: one process does the rest
     _setup(args)
     t0 = time.time()
-    {"reconstruct": reconstruct, "register": register_cmd, "svr": svr_cmd, "assess": assess_cmd, "sample-volume": sample_volume_cmd,
+    {"reconstruct": reconstruct, "register": register_cmd, "svr": svr_cmd, "assess": assess_cmd,
+     "correct-bias-field": correct_bias_field_cmd, "sample-volume": sample_volume_cmd,
      "sample-slices": sample_slices_cmd}[args.command](args)
     logging.info("Command 'nesvor %s' finished, overall time: %.1f s", args.command, time.time() - t0)
 

@@ -148,6 +148,22 @@ def load_stack(path_vol: str, path_mask: Optional[str] = None, device=torch.devi
                  gap=float(resolutions[2]))
 
 
+def save_stack(path: str, stack: Stack, data: Optional[torch.Tensor] = None) -> None:
+    """Writes ``stack.slices`` - or ``data``, a tensor of that shape, on the stack's geometry - so that ``load_stack`` reads back
+    the same array, resolutions and slice poses.  The inverse of ``affine2transformation`` for what ``load_stack`` produces:
+    parallel slices with one rotation and in-plane offset, ``gap`` apart along z (the file's z resolution; a thickness that
+    differs from the gap is not stored, as in the reference).  Unmasked: the array is written as it is."""
+    img = stack.slices if data is None else data
+    if tuple(img.shape) != tuple(stack.slices.shape):
+        raise ValueError(f"save_stack: data of the stack's shape {tuple(stack.slices.shape)} expected, got {tuple(img.shape)}")
+    img = img.reshape(img.shape[0], img.shape[-2], img.shape[-1])
+    mat = stack.transformation.matrix(trans_first=True)  # (n,3,4): slice 0's rotation, the centre of the slices' offsets
+    centre = torch.cat((mat[:1, :, :3], mat[:, :, 3:].mean(0, keepdim=True)), -1)
+    affine = transformation2affine(img, RigidTransform(centre, trans_first=True), float(stack.resolution_x), float(stack.resolution_y),
+                                   float(stack.gap))
+    save_nii_volume(path, img, affine)
+
+
 def load_volume(path_vol: str, path_mask: Optional[str] = None, device=torch.device("cpu")) -> Volume:
     vol, mask, resolutions, affine = _load_with_mask(path_vol, path_mask)
     t, m, transformation = affine2transformation(torch.tensor(vol, device=device), torch.tensor(mask, device=device),

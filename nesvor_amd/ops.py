@@ -420,6 +420,117 @@ _op("pair_moments(Tensor slices, Tensor? mask, Tensor pairs) -> Tensor", _pair_m
 
 
 # =====================================================================================================================
+# the three per-iteration passes of the bias field correction (csrc/bias.hip) over a stack as a (D,H,W) array: the histogram
+# of u = v - f, the B-spline lattice fitted to the residual, and f += the lattice's field with the statistics of the step; the
+# host logic (tables, sharpening, levels, stop test) is nesvor_amd/bias.py
+# =====================================================================================================================
+def _n4_volume(what, v, f, mask):
+    """The argument checks the three ops share; -> (mask or None, D, H, W)."""
+    _lib.require_device(v, f, dtype=torch.float32, name=f"{what} v/f")
+    m = mask if (mask is not None and mask.numel() > 0) else None
+    if m is not None:
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError(f"{what} mask must be torch.bool or torch.uint8, got {m.dtype}")
+        _lib.require_device(m, name=f"{what} mask")
+    if v.ndim != 3 or f.shape != v.shape or (m is not None and m.shape != v.shape):
+        raise RuntimeError(f"{what}: v, f and mask (D, H, W) of one shape expected")
+    if f.device != v.device or (m is not None and m.device != v.device):
+        raise RuntimeError(f"{what}: v, f and mask must be on one device")
+    return m, int(v.shape[0]), int(v.shape[1]), int(v.shape[2])
+
+
+def _n4_tables(what, v, tables, spans, S):
+    """tz, ty, tx (n,4) fp32 and sz, sy, sx (n) int32 for the axes of v."""
+    _lib.require_device(*tables, dtype=torch.float32, name=f"{what} basis tables")
+    _lib.require_device(*spans, dtype=torch.int32, name=f"{what} span tables")
+    for n, t, s in zip(v.shape, tables, spans):
+        if tuple(t.shape) != (n, 4) or tuple(s.shape) != (n,):
+            raise RuntimeError(f"{what}: per axis a basis table (n, 4) and a span table (n) expected")
+        if t.device != v.device or s.device != v.device:
+            raise RuntimeError(f"{what}: the tables must be on the device of v")
+    if S < 1 or S + 3 > 16:
+        raise RuntimeError(f"{what}: S spans with 1 <= S and S + 3 <= 16 control points per axis expected, got S = {S}")
+
+
+def _n4_range(what, v, rng, n_bins):
+    _lib.require_device(rng, dtype=torch.float32, name=f"{what} range")
+    if rng.numel() != 2 or rng.device != v.device:
+        raise RuntimeError(f"{what}: range, two floats {{lo, hi}} on the device of v, expected")
+    if not 2 <= n_bins <= 1024:
+        raise RuntimeError(f"{what}: 2 <= n_bins <= 1024 expected, got {n_bins}")
+
+
+def _n4_workspace(nbytes, device):
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
+
+
+def _n4_histogram(v, f, mask, rng, n_bins):
+    m, D, H, W = _n4_volume("n4_histogram", v, f, mask)
+    _n4_range("n4_histogram", v, rng, n_bins)
+    hist = torch.empty(n_bins, dtype=torch.float64, device=v.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_n4_histogram_workspace_bytes(D, H, W, n_bins))
+    workspace = _n4_workspace(nbytes, v.device)
+    with torch.cuda.device(v.device):
+        err = lib.nesvor_n4_histogram(_lib.ptr(v), _lib.ptr(f), _lib.ptr(m), D, H, W, _lib.ptr(rng), n_bins, _lib.ptr(hist),
+                                      _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "n4 histogram")
+    return hist
+
+
+def _n4_fit(v, f, mask, rng, lut, tz, ty, tx, sz, sy, sx, S):
+    m, D, H, W = _n4_volume("n4_fit", v, f, mask)
+    _lib.require_device(lut, dtype=torch.float64, name="n4_fit lut")
+    if lut.ndim != 1 or lut.device != v.device:
+        raise RuntimeError("n4_fit: lut (n_bins) on the device of v expected")
+    n_bins = int(lut.shape[0])
+    _n4_range("n4_fit", v, rng, n_bins)
+    _n4_tables("n4_fit", v, (tz, ty, tx), (sz, sy, sx), S)
+    C = S + 3
+    lattice = torch.empty((C, C, C), dtype=torch.float64, device=v.device)
+    weight = torch.empty((C, C, C), dtype=torch.float64, device=v.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_n4_fit_workspace_bytes(D, H, W, S))
+    workspace = _n4_workspace(nbytes, v.device)
+    with torch.cuda.device(v.device):
+        err = lib.nesvor_n4_fit(_lib.ptr(v), _lib.ptr(f), _lib.ptr(m), _lib.ptr(rng), _lib.ptr(lut), n_bins, _lib.ptr(tz), _lib.ptr(ty),
+                                _lib.ptr(tx), _lib.ptr(sz), _lib.ptr(sy), _lib.ptr(sx), D, H, W, S, _lib.ptr(lattice), _lib.ptr(weight),
+                                _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "n4 fit")
+    return lattice, weight
+
+
+def _n4_update(lattice, tz, ty, tx, sz, sy, sx, S, f, v, mask):
+    m, D, H, W = _n4_volume("n4_update_", v, f, mask)
+    _n4_tables("n4_update_", v, (tz, ty, tx), (sz, sy, sx), S)
+    _lib.require_device(lattice, dtype=torch.float64, name="n4_update_ lattice")
+    if tuple(lattice.shape) != (S + 3,) * 3 or lattice.device != v.device:
+        raise RuntimeError("n4_update_: lattice (C, C, C) with C = S + 3 on the device of v expected")
+    stats = torch.empty(5, dtype=torch.float64, device=v.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_n4_update_workspace_bytes(D, H, W))
+    workspace = _n4_workspace(nbytes, v.device)
+    with torch.cuda.device(v.device):
+        err = lib.nesvor_n4_update(_lib.ptr(lattice), _lib.ptr(tz), _lib.ptr(ty), _lib.ptr(tx), _lib.ptr(sz), _lib.ptr(sy), _lib.ptr(sx), S,
+                                   _lib.ptr(f), _lib.ptr(v), _lib.ptr(m), D, H, W, _lib.ptr(stats), _lib.ptr(workspace), nbytes,
+                                   _lib.stream_ptr())
+    _lib.check(err, "n4 update")
+    return stats
+
+
+_op("n4_histogram(Tensor v, Tensor f, Tensor? mask, Tensor range, int n_bins) -> Tensor", _n4_histogram,
+    fake=lambda v, f, mask, rng, n_bins: v.new_empty((n_bins,), dtype=torch.float64))
+_op("n4_fit(Tensor v, Tensor f, Tensor? mask, Tensor range, Tensor lut, Tensor tz, Tensor ty, Tensor tx, Tensor sz, Tensor sy, Tensor sx, "
+    "int S) -> (Tensor lattice, Tensor weight)", _n4_fit,
+    fake=lambda v, f, mask, rng, lut, tz, ty, tx, sz, sy, sx, S: (v.new_empty((S + 3,) * 3, dtype=torch.float64),
+                                                                 v.new_empty((S + 3,) * 3, dtype=torch.float64)))
+# f += the lattice's field, in place; returns {count, sum g, sum g^2, min u_new, max u_new}
+_op("n4_update_(Tensor lattice, Tensor tz, Tensor ty, Tensor tx, Tensor sz, Tensor sy, Tensor sx, int S, Tensor(a!) f, Tensor v, "
+    "Tensor? mask) -> Tensor", _n4_update,
+    fake=lambda lattice, tz, ty, tx, sz, sy, sx, S, f, v, mask: v.new_empty((5,), dtype=torch.float64))
+
+
+# =====================================================================================================================
 # multi-resolution hash-grid encoding (tinycudann.Encoding "HashGrid"; the scalars are its encoding_config)
 # =====================================================================================================================
 _SPECS = {}
