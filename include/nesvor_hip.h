@@ -922,6 +922,31 @@ int nesvor_n4_update(const double* lattice, const float* tz, const float* ty, co
                      int W, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 int64_t nesvor_n4_update_workspace_bytes(int D, int H, int W);
 
+/* ----------------------------------------------------------------------
+ * Structural exclusion of the classical reconstruction (nesvor_amd/structural.py): the local SSIM map of the acquired slices
+ * against the simulated ones and the per-slice sums of the slice similarity in one pass.
+ * sim (n,h,w) fp32 the simulated slices A x, y (n,h,w) fp32 the acquired ones, mask (n,h,w) bytes or NULL, scale (n) DEVICE
+ * fp32.  With I = scale[k] y and J = sim on the valid pixels (mask NULL or its byte set) and 0 elsewhere, v the validity as
+ * 0 / 1 and S the separable 11-tap Gaussian window (sigma 1.5, taps normalised to sum 1, zero padding, along x first, taps
+ * added in ascending order from 0):
+ *   Wt = S(v),  muI = S(I) / Wt,  muJ = S(J) / Wt,  sI = S(I I) / Wt - muI^2,  sJ = S(J J) / Wt - muJ^2,  sIJ = S(I J) / Wt - muI muJ,
+ *   ssim = (2 muI muJ + c1) (2 sIJ + c2) / ((muI^2 + muJ^2 + c1) (sI + sJ + c2))       at valid pixels, 0 on every other pixel,
+ * all in fp32 without contraction.  ssim (n,h,w) fp32 and stats (n,8) fp64 are fully written (no memset needed):
+ *   stats[k] = { n_k, sum ssim, #(ssim < threshold), sum I, sum J, sum I^2, sum J^2, sum I J }   over the valid pixels of slice k;
+ * a slice without a valid pixel yields eight exact zeros, both counts are exact.  Products are fp32, the sums double from the
+ * first add.  The sums are reproducible (no atomics:
+ * per-workgroup partials in the workspace, added in workgroup order by a second launch).  workspace: device memory of at
+ * least nesvor_structural_ssim_workspace_bytes(n, h, w) bytes (0 for sizes the call treats as a no-op or refuses).
+ * n == 0: no-op, returns 0.  hipErrorInvalidValue, without a launch: n < 0, h or w below 1, h w > INT_MAX - 256, more than
+ * INT_MAX workgroups (n * ceil(h / 16) * ceil(w / 16)), a null pointer other than mask, a workspace that is missing or too
+ * small, a negative or non-finite c1, c2 or threshold.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_structural_ssim(const float* sim, const float* y, const uint8_t* mask, const float* scale, int n, int h, int w,
+                           float c1, float c2, float threshold, float* ssim, double* stats, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int64_t nesvor_structural_ssim_workspace_bytes(int n, int h, int w);
+
 #ifdef __cplusplus
 }
 #endif

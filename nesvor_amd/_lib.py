@@ -234,6 +234,8 @@ _SIGNATURES = {
     "nesvor_n4_fit_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
     "nesvor_n4_update": ([_P] * 7 + [c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P], c_int),
     "nesvor_n4_update_workspace_bytes": ([c_int, c_int, c_int], c_int64),
+    "nesvor_structural_ssim": ([_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, c_size_t, _P], c_int),
+    "nesvor_structural_ssim_workspace_bytes": ([c_int, c_int, c_int], c_int64),
 }
 
 

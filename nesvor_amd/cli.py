@@ -10,7 +10,8 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
                                            | --input-slices DIR   --output-volume v.nii.gz [--output-slices DIR]
                                            [--simulated-slices DIR] [--registration svr|stack|none] [--output-resolution 0.8]
                                            [--n-iter-srr 30] [--srr-beta 0.02] [--srr-delta 0.1]
-                                           [--outlier-rejection [--robust-rounds 3] [--slice-weights FILE.json]]
+                                           [--outlier-rejection] [--structural-exclusion [--local-ssim-threshold 0.4]
+                                           [--global-ncc-threshold 0.5]] [--robust-rounds 3] [--slice-weights FILE.json]
                                            [--template-stack 0|K|auto] [--template-metric ncc|matrix-rank|volume]
     python -m nesvor_amd.cli assess        --input-stacks a.nii.gz b.nii.gz c.nii.gz [--stack-masks ...] [--thicknesses ...]
                                            [--metric ncc|matrix-rank|volume] [--output-json FILE.json]
@@ -34,6 +35,10 @@ one process per GPU (nesvor_amd/ddp.py); rank 0 samples and writes the outputs. 
 
 Also not in the reference: ``svr``, the classical pipeline without an INR - registration (default ``svr``), then a
 super-resolution reconstruction by gradient descent with the edge-preserving prior (nesvor_amd/svr.py, csrc/srr.hip).
+``--outlier-rejection`` adds the EM pixel and slice weights and slice scales (nesvor_amd/robust.py), ``--structural-exclusion``
+drops slices whose correlation with their simulation is below ``--global-ncc-threshold`` and pixels whose local SSIM is
+below ``--local-ssim-threshold`` (nesvor_amd/structural.py, csrc/structural.hip); ``--robust-rounds`` splits the descent for
+either, ``--slice-weights`` writes what either decided per slice.
 
 Also not in the reference (upstream added an ``assess`` command in later releases): ``assess`` scores every input stack for
 motion (nesvor_amd/assess.py, csrc/assess.hip; ``ncc`` of adjacent slices, ``matrix-rank`` = effective rank of the stack's
@@ -212,8 +217,16 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--srr-delta", default=0.1, type=float, help="edge scale of the prior, in normalised intensities")
     g.add_argument("--outlier-rejection", action="store_true",
                    help="robust statistics: EM pixel and slice weights and per-slice intensity scales (nesvor_amd/robust.py)")
-    g.add_argument("--robust-rounds", default=3, type=int, help="EM rounds the descent steps are split into (with --outlier-rejection)")
-    g.add_argument("--slice-weights", type=str, help="JSON file for the final slice weights and scales (with --outlier-rejection)")
+    g.add_argument("--robust-rounds", default=3, type=int,
+                   help="rounds the descent steps are split into (with --outlier-rejection and / or --structural-exclusion)")
+    g.add_argument("--slice-weights", type=str,
+                   help="JSON file with one row per slice: the final weight and scale (with --outlier-rejection), ncc, pixel_share "
+                        "and excluded (with --structural-exclusion)")
+    g.add_argument("--structural-exclusion", action="store_true",
+                   help="drop slices that do not correlate with their simulation and pixels of low local SSIM (nesvor_amd/structural.py)")
+    g.add_argument("--local-ssim-threshold", default=0.4, type=float, help="a pixel is kept where its local SSIM is at least this")
+    g.add_argument("--global-ncc-threshold", default=0.5, type=float,
+                   help="a slice is kept where its correlation with its simulation is at least this")
     _bias_flags(p)
     _common_flags(p)
 

@@ -382,6 +382,45 @@ _op("robust_estep(Tensor sim, Tensor y, Tensor? mask, Tensor scale, Tensor model
 
 
 # =====================================================================================================================
+# structural exclusion of the classical reconstruction (csrc/structural.hip): the local SSIM map of scale_k y against sim and
+# the eight per-slice sums of the slice similarity in one pass; the definition and the decisions are nesvor_amd/structural.py
+# =====================================================================================================================
+def _structural_ssim(sim, y, mask, scale, threshold, dynamic_range):
+    _lib.require_device(sim, y, scale, dtype=torch.float32, name="structural_ssim sim/y/scale")
+    m = mask if (mask is not None and mask.numel() > 0) else None
+    if m is not None:
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError(f"structural_ssim mask must be torch.bool or torch.uint8, got {m.dtype}")
+        _lib.require_device(m, name="structural_ssim mask")
+    if sim.ndim < 3 or y.shape != sim.shape or (m is not None and m.shape != sim.shape):
+        raise RuntimeError("structural_ssim: sim, y and mask (n, ..., h, w) of one shape expected")
+    if any(t is not None and t.device != sim.device for t in (y, m, scale)):
+        raise RuntimeError("structural_ssim: sim, y, mask and scale must be on one device")
+    n, h, w = int(sim.shape[0]), int(sim.shape[-2]), int(sim.shape[-1])
+    if sim.numel() != n * h * w or (m is not None and m.numel() != n * h * w):
+        raise RuntimeError("structural_ssim: sim / y / mask must hold n x h x w elements")
+    if scale.numel() != n:
+        raise RuntimeError("structural_ssim: scale (n) expected")
+    ssim = torch.empty_like(sim)
+    stats = torch.empty((n, 8), dtype=torch.float64, device=sim.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_structural_ssim_workspace_bytes(n, h, w))
+    workspace = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=sim.device)
+    c1, c2 = (0.01 * dynamic_range) ** 2, (0.03 * dynamic_range) ** 2
+    with torch.cuda.device(sim.device):
+        err = lib.nesvor_structural_ssim(_lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), n, h, w, c1, c2, float(threshold),
+                                         _lib.ptr(ssim), _lib.ptr(stats), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "structural ssim")
+    return ssim, stats
+
+
+_op("structural_ssim(Tensor sim, Tensor y, Tensor? mask, Tensor scale, float threshold, float dynamic_range) -> (Tensor ssim, Tensor stats)",
+    _structural_ssim,
+    fake=lambda sim, y, mask, scale, threshold, dynamic_range: (torch.empty_like(sim),
+                                                                sim.new_empty((sim.shape[0], 8), dtype=torch.float64)))
+
+
+# =====================================================================================================================
 # masked moments of slice pairs for the stack quality assessment (csrc/assess.hip): {count, sum a, sum b, sum a^2, sum b^2,
 # sum a b} per pair over the pixels valid in both slices; the host logic (and the range check of the pair indices, which the
 # kernel does not repeat) is nesvor_amd/assess.py

@@ -9,6 +9,11 @@ scheme of Kuklisova-Murgasova et al. 2012 gives every pixel a posterior weight, 
 the descent is split into R rounds, each on the weights and scaled slices the statistics of the current A x give.  One pass
 of a fused HIP kernel per round (csrc/robust.hip).  Without the flag the pipeline is the plain one, bit for bit.
 
+Optional structural exclusion (``--structural-exclusion``; ``reconstruct_volume(structural=StructuralExclusion())``,
+nesvor_amd/structural.py): after the EM round, if any, every round compares each slice with its simulation - a local SSIM map
+drops pixels, the slice's correlation drops whole slices - and the descent runs on what is kept.  One pass of a fused HIP
+kernel per round (csrc/structural.hip).  Without the flag nothing changes.
+
 Out of scope here: bias fields, robust weights inside the ``--registration svr`` rounds, per-stack PSFs for unequal
 thicknesses (the mean thickness is used, as the registration does) and a volume mask input.
 """
@@ -24,6 +29,7 @@ from .image import Slice, Volume
 from .registration import _common_frame, _cover_shape, resample
 from .robust import RobustStatistics
 from .srr import AcquisitionOperator, PSFreconstruction, srr_descent
+from .structural import StructuralExclusion
 from .transform import RigidTransform, mat_update_resolution
 from .utils import get_PSF
 
@@ -63,7 +69,8 @@ def _operator(images: torch.Tensor, m: torch.Tensor, frame_poses: RigidTransform
 
 
 def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r: float, n_iter: int = 30, beta: float = 0.02,
-                       delta: float = 0.1, robust_rounds: int = 0, robust_out: Optional[Dict] = None) -> Volume:
+                       delta: float = 0.1, robust_rounds: int = 0, robust_out: Optional[Dict] = None,
+                       structural: Optional[StructuralExclusion] = None, structural_out: Optional[Dict] = None) -> Volume:
     """Slices at their poses -> the reconstructed ``Volume``: world-aligned (identity pose, centred at the origin), voxel size
     ``res_r``, large enough for every masked pixel; its mask is the set of voxels a masked pixel's PSF reaches (A^T 1 > 0).
 
@@ -78,14 +85,37 @@ def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r:
     for every round's weights (one scalar read per round).  ``robust_out``, a dict, then receives ``slice_weight`` and
     ``scale`` (n, one entry per non-empty slice, in the order of the concatenated input) and ``keep`` (their indices there).
     More rounds than descent steps are cut to ``n_iter`` (at least one), so no round runs without a step.
-    ``robust_rounds=0`` is the plain pipeline and leaves ``robust_out`` alone."""
+    ``robust_rounds=0`` is the plain pipeline and leaves ``robust_out`` alone.
+
+    ``structural``, a ``StructuralExclusion`` (nesvor_amd/structural.py): the descent is split into ``robust_rounds`` rounds
+    (``structural.rounds``, 3 by default, if that is 0; cut to ``n_iter`` as above).  Each round takes A x once, runs the EM round on it if ``robust_rounds`` > 0,
+    then ``structural.update`` on the slices with the robust scales (or as they are), and descends with the pixel weights
+    ``structural.weights()`` (times the robust ones) on the robustly scaled slices (or as they are).  Decisions are taken anew
+    every round.  ``structural_out`` then receives ``ncc``, ``slice_keep`` and ``pixel_share`` (n, as above) and ``keep``.
+    ``structural=None`` leaves everything above as it is."""
     images, m, frame_poses, keep = _frame_keep(slices, mask, poses, res_s)
     if images.shape[0] == 0:
         raise ValueError("reconstruct_volume: every slice is empty")
     shape = _cover_shape(frame_poses, m, res_s, s_thick, res_r)
     op, params = _operator(images, m, frame_poses, res_s, s_thick, res_r, shape)
     start = PSFreconstruction(op.transforms, images, m, None, params)
-    if robust_rounds > 0:
+    if structural is not None:
+        x = start
+        rounds = max(1, min(robust_rounds if robust_rounds > 0 else structural.rounds, n_iter))
+        stats = RobustStatistics().init(op.forward(x), images, m) if robust_rounds > 0 else None
+        for r in range(rounds):
+            sim = op.forward(x)
+            if stats is not None:
+                stats.update(sim, images, m)
+            structural.update(sim, images, m, None if stats is None else stats.scale)
+            p = structural.weights() if stats is None else stats.weights() * structural.weights()
+            steps = n_iter // rounds + (n_iter % rounds if r + 1 == rounds else 0)
+            x = srr_descent(op, images if stats is None else stats.scaled(images), x, steps, beta, delta, p=p)
+        if stats is not None and robust_out is not None:
+            robust_out.update(slice_weight=stats.slice_weight, scale=stats.scale, keep=keep)
+        if structural_out is not None:
+            structural_out.update(ncc=structural.ncc, slice_keep=structural.slice_keep, pixel_share=structural.pixel_share(), keep=keep)
+    elif robust_rounds > 0:
         x = start
         rounds = max(1, min(robust_rounds, n_iter))
         stats = RobustStatistics().init(op.forward(x), images, m)
@@ -145,7 +175,8 @@ def svr_command(args: Namespace) -> Dict:
 
     if args.input_slices is None and args.input_stacks is None:
         raise SystemExit("No image data provided! Use --input-slices or --input-stacks to input data.")
-    if getattr(args, "slice_weights", None) and not getattr(args, "outlier_rejection", False):
+    use_structural = bool(getattr(args, "structural_exclusion", False))
+    if getattr(args, "slice_weights", None) and not getattr(args, "outlier_rejection", False) and not use_structural:
         raise SystemExit("--slice-weights needs --outlier-rejection: without it no slice weights are estimated")
     t0 = time.time()
     if args.input_slices is not None:
@@ -175,7 +206,16 @@ def svr_command(args: Namespace) -> Dict:
                  time.time() - t0, len(slices), res_s, s_thick)
     t0 = time.time()
     robust: Dict = {}
-    if getattr(args, "outlier_rejection", False):
+    structural: Dict = {}
+    if use_structural:
+        if args.robust_rounds < 1:
+            raise SystemExit("--robust-rounds must be at least 1")
+        exclusion = StructuralExclusion(args.local_ssim_threshold, args.global_ncc_threshold, rounds=args.robust_rounds)
+        robust_rounds = args.robust_rounds if getattr(args, "outlier_rejection", False) else 0
+        volume = reconstruct_volume(stacks, masks, poses, res_s, s_thick, args.output_resolution, args.n_iter_srr, args.srr_beta,
+                                    args.srr_delta, robust_rounds=robust_rounds, robust_out=robust, structural=exclusion,
+                                    structural_out=structural)
+    elif getattr(args, "outlier_rejection", False):
         if args.robust_rounds < 1:
             raise SystemExit("--robust-rounds must be at least 1")
         volume = reconstruct_volume(stacks, masks, poses, res_s, s_thick, args.output_resolution, args.n_iter_srr, args.srr_beta,
@@ -186,17 +226,30 @@ def svr_command(args: Namespace) -> Dict:
     if args.device.type == "cuda":
         torch.cuda.synchronize(args.device)
     logging.info("Reconstruction finished in %.1f s (volume %s)", time.time() - t0, tuple(volume.image.shape))
+    rows = None
     if robust:
         weight, scale, keep = robust["slice_weight"].tolist(), robust["scale"].tolist(), robust["keep"].tolist()
         logging.info("Outlier rejection: %d of %d slices ended with a weight below 0.5; slice scales %.3f .. %.3f",
                      sum(w < 0.5 for w in weight), len(weight), min(scale), max(scale))
-        if getattr(args, "slice_weights", None):
-            # stack: the index among --input-stacks, slice: the index inside that stack; with --input-slices stack is null and
-            # slice the file's place in the folder's numeric order
-            rows = [{"stack": slices[k].stack_idx, "slice": slices[k].slice_idx, "weight": w, "scale": s}
-                    for k, w, s in zip(keep, weight, scale)]
-            with open(args.slice_weights, "w") as f:
-                json.dump(rows, f, indent=1)
+        # stack: the index among --input-stacks, slice: the index inside that stack; with --input-slices stack is null and
+        # slice the file's place in the folder's numeric order
+        rows = [{"stack": slices[k].stack_idx, "slice": slices[k].slice_idx, "weight": w, "scale": s}
+                for k, w, s in zip(keep, weight, scale)]
+    if structural:
+        ncc, share, kept = structural["ncc"].tolist(), structural["pixel_share"].tolist(), structural["slice_keep"].tolist()
+        keep = structural["keep"].tolist()
+        logging.info("Structural exclusion: %d of %d slices ended excluded; %.1f %% of the pixels of the others kept",
+                     len(kept) - sum(kept), len(kept), 100.0 * sum(s for s, k in zip(share, kept) if k) / max(sum(kept), 1))
+        if not any(kept):
+            logging.warning("Structural exclusion: every slice ended excluded (no slice correlates with its simulation above %g): "
+                            "the last round descended on the prior alone", args.global_ncc_threshold)
+        if rows is None:
+            rows = [{"stack": slices[k].stack_idx, "slice": slices[k].slice_idx} for k in keep]
+        for row, r, s, k in zip(rows, ncc, share, kept):
+            row.update(ncc=r, pixel_share=s, excluded=not k)
+    if rows is not None and getattr(args, "slice_weights", None):
+        with open(args.slice_weights, "w") as f:
+            json.dump(rows, f, indent=1)
     data = {"output_volume": volume, "output_slices": slices}
     if args.simulated_slices:
         data["simulated_slices"] = simulate_slices(volume, stacks, masks, poses, res_s, s_thick)
