@@ -15,12 +15,9 @@
 // build has -ffp-contract=off; sqrtf and / are correctly rounded, expf is the library's, the one torch's fp32 exp calls).  {sigma2, c, m} are read from device memory:
 // the EM loop never synchronises with the host.
 //
-// Sums are reproducible, as in svr.hip: fp32 only inside one wave's DPP reduction (64 terms), then double; every workgroup
-// stores its seven partials to the workspace and a second small launch adds them in workgroup order.  No atomics, no memset.
-// The count is exact (at most 64 ones per wave in fp32, integers in double from there).
+// The seven sums are added in the reproducible order of slice_sums.h: bit-identical from run to run, the count exact.
 #include <hip/hip_runtime.h>
-#include <limits.h>
-#include "common.h"
+#include "slice_sums.h"
 #include "../../include/nesvor_hip.h"
 
 namespace {
@@ -32,10 +29,8 @@ __global__ __launch_bounds__(256) void robust_estep_kernel(const float* __restri
                                                            const uint8_t* __restrict__ mask, const float* __restrict__ scale,
                                                            const float* __restrict__ model, int hw, int wgs, float* __restrict__ p,
                                                            double* __restrict__ partial) {
-  __shared__ float red[4][kStats];
   const int in = blockIdx.x / wgs, wg = blockIdx.x - in * wgs;
   const int pix = wg * 256 + (int)threadIdx.x;  // the host checked hw <= INT_MAX - 256
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool inside = pix < hw;
   const size_t idx = (size_t)in * hw + (inside ? pix : 0);
   const bool on = inside && (mask == nullptr || mask[idx]);
@@ -54,38 +49,16 @@ __global__ __launch_bounds__(256) void robust_estep_kernel(const float* __restri
     pyy = py * yv;
   }
   if (inside) p[idx] = pv;
-  const float s0 = wave_sum_dpp(on ? 1.f : 0.f), s1 = wave_sum_dpp(pv), s2 = wave_sum_dpp(pv * e2), s3 = wave_sum_dpp(q2),
-              s4 = wave_sum_dpp(pys), s5 = wave_sum_dpp(pyy), s6 = wave_sum_dpp(e2);
-  if (lane == 0) {
-    red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; red[wave][3] = s3;
-    red[wave][4] = s4; red[wave][5] = s5; red[wave][6] = s6;
-  }
-  __syncthreads();
-  if (threadIdx.x < kStats) {
-    const int j = threadIdx.x;
-    const double t = ((double)red[0][j] + (double)red[1][j]) + ((double)red[2][j] + (double)red[3][j]);
-    partial[((size_t)in * wgs + wg) * kStats + j] = t;
-  }
-}
-
-// stats[k][j] = the partials of slice k added in workgroup order
-__global__ __launch_bounds__(256) void robust_reduce_kernel(const double* __restrict__ partial, int64_t total, int wgs,
-                                                            double* __restrict__ stats) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int64_t k = t / kStats;
-  const int j = (int)(t - k * kStats);
-  double s = 0.0;
-  for (int g = 0; g < wgs; ++g) s += partial[((size_t)k * wgs + g) * kStats + j];
-  stats[t] = s;
+  const float sums[kStats] = {wave_sum_dpp(on ? 1.f : 0.f), wave_sum_dpp(pv),  wave_sum_dpp(pv * e2), wave_sum_dpp(q2),
+                              wave_sum_dpp(pys),            wave_sum_dpp(pyy), wave_sum_dpp(e2)};
+  slice_sums::store_workgroup_sums(sums,partial + ((size_t)in * wgs + wg) * kStats);
 }
 
 }  // namespace
 
 extern "C" int64_t nesvor_robust_estep_workspace_bytes(int n, int h, int w) {
   if (n < 1 || h < 1 || w < 1) return 0;
-  const int64_t wgs = ((int64_t)h * w + 255) / 256;
-  return (int64_t)sizeof(double) * kStats * n * wgs;
+  return slice_sums::Plan<kStats>{n, slice_sums::pixel_workgroups(h, w)}.workspace_bytes();
 }
 
 extern "C" int nesvor_robust_estep(const float* sim, const float* y, const uint8_t* mask, const float* scale, const float* model,
@@ -95,18 +68,11 @@ extern "C" int nesvor_robust_estep(const float* sim, const float* y, const uint8
   if (n < 0 || h < 1 || w < 1) return (int)hipErrorInvalidValue;
   if (sim == nullptr || y == nullptr || scale == nullptr || model == nullptr || p == nullptr || stats == nullptr)
     return (int)hipErrorInvalidValue;
-  // pixel indices inside a slice are ints; one workgroup per 256 pixels of a slice
-  if ((int64_t)h * w > INT_MAX - 256) return (int)hipErrorInvalidValue;
-  const int64_t wgs = ((int64_t)h * w + 255) / 256;
-  if (wgs * n > INT_MAX) return (int)hipErrorInvalidValue;
-  const int64_t need = nesvor_robust_estep_workspace_bytes(n, h, w);
-  if (workspace == nullptr || (int64_t)workspace_bytes < need) return (int)hipErrorInvalidValue;
+  const slice_sums::Plan<kStats> plan{n, slice_sums::pixel_workgroups(h, w)};
+  if (!plan.accepts(h, w, plan.wgs * n, workspace, workspace_bytes)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)workspace;
-  hipLaunchKernelGGL(robust_estep_kernel, dim3((unsigned)(wgs * n)), dim3(256), 0, st, sim, y, mask, scale, model, h * w, (int)wgs, p,
-                     partial);
-  const int64_t total = (int64_t)n * kStats;
-  hipLaunchKernelGGL(robust_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)partial, total,
-                     (int)wgs, stats);
+  hipLaunchKernelGGL(robust_estep_kernel, dim3((unsigned)(plan.wgs * n)), dim3(256), 0, st, sim, y, mask, scale, model, h * w,
+                     (int)plan.wgs, p, (double*)workspace);
+  plan.reduce(workspace, stats, st);
   return (int)hipGetLastError();
 }

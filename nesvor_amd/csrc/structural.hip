@@ -25,17 +25,15 @@
 //
 // The per-pixel arithmetic is that of the torch expression in fp32, operation for operation (the build has -ffp-contract=off; the
 // divisions are correctly rounded); the taps are the host's doubles rounded to fp32, as gaussian_taps(torch.float32) gives them.
-// scale_k is read from device memory.  Sums are reproducible, as in robust.hip: a DPP reduction per wave, the four waves added in
-// a fixed order, every workgroup stores its eight partials to the workspace and a second small launch adds them in workgroup
-// order.  No atomics, no memset.  The two counts are summed in fp32 inside a wave (at most 64 ones: exact); the six float sums are
-// summed in double from the first add (wave_sum_f64): an fp32 wave sum, as robust.hip has it, missed the bound the kernel is
-// held to ("twice the fp32 expression's error plus one fp32 ulp of the largest sum") on the 17 valid pixels of a 5 x 5 slice,
-// where one ulp of the sum is all the expression with its fp64 sums leaves.
+// scale_k is read from device memory.  The eight sums are added in the reproducible order of slice_sums.h, a workgroup being a
+// tile.  The two counts are summed in fp32 inside a wave (at most 64 ones: exact); the six float sums are summed in double from
+// the first add (wave_sum_f64): an fp32 wave sum, as robust.hip has it, missed the bound the kernel is held to ("twice the fp32
+// expression's error plus one fp32 ulp of the largest sum") on the 17 valid pixels of a 5 x 5 slice, where one ulp of the sum
+// is all the expression with its fp64 sums leaves.
 #include <hip/hip_runtime.h>
-#include <limits.h>
 #include <float.h>
 #include <math.h>
-#include "common.h"
+#include "slice_sums.h"
 #include "../../include/nesvor_hip.h"
 
 namespace {
@@ -48,30 +46,6 @@ constexpr int kHaloPitch = 48;                 // = 16 mod 32, >= kHalo
 constexpr int kRows = kHalo * kTile;           // 416 horizontally filtered values per moment
 
 struct Taps { float g[kTaps]; };
-
-// wave_sum_dpp (common.h) in double: the same DPP butterflies on the two halves of a double, no LDS crossbar traffic.  Every
-// lane of the wave must be active.  Result is wave-uniform.
-template <int kCtrl>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, kCtrl, 0xf, 0xf, true);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), kCtrl, 0xf, 0xf, true);
-  return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
-}
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, lane);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), lane);
-  return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
-}
-__device__ __forceinline__ double wave_sum_f64(float x) {
-  double v = (double)x;
-  v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);  // row_half_mirror
-  v += dpp_f64<0x140>(v);  // row_mirror
-  return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
 
 // grid: n * tiles workgroups, tiles = tiles_y * tiles_x per slice.  partial: (n, tiles, 8) doubles.
 __global__ __launch_bounds__(256) void structural_ssim_kernel(const float* __restrict__ sim, const float* __restrict__ y,
@@ -162,24 +136,15 @@ __global__ __launch_bounds__(256) void structural_ssim_kernel(const float* __res
   const double s0 = (double)wave_sum_dpp(on ? 1.f : 0.f), s2 = (double)wave_sum_dpp(on && value < threshold ? 1.f : 0.f);
   const double s1 = wave_sum_f64(value), s3 = wave_sum_f64(iv), s4 = wave_sum_f64(jv), s5 = wave_sum_f64(iv * iv),
                s6 = wave_sum_f64(jv * jv), s7 = wave_sum_f64(iv * jv);
+  // Step 2 of slice_sums.h, written out: through slice_sums::store_workgroup_sums (or any other spelling tried) the compiler's
+  // SLP vectoriser repacks the tap loops above into v_pk_add_f32 / v_pk_mul_f32 - the same values, but the kernel then measured
+  // 1 to 4 % slower on 128 x 128 slices in five of five alternating runs.
   if (lane == 0) {
     red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; red[wave][3] = s3;
     red[wave][4] = s4; red[wave][5] = s5; red[wave][6] = s6; red[wave][7] = s7;
   }
   __syncthreads();
   if (tid < kStats) partial[((size_t)in * tiles + tile) * kStats + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-}
-
-// stats[k][j] = the partials of slice k added in workgroup order
-__global__ __launch_bounds__(256) void structural_reduce_kernel(const double* __restrict__ partial, int64_t total, int tiles,
-                                                                double* __restrict__ stats) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int64_t k = t / kStats;
-  const int j = (int)(t - k * kStats);
-  double s = 0.0;
-  for (int g = 0; g < tiles; ++g) s += partial[((size_t)k * tiles + g) * kStats + j];
-  stats[t] = s;
 }
 
 int64_t tiles_of(int h, int w) { return (((int64_t)h + kTile - 1) / kTile) * (((int64_t)w + kTile - 1) / kTile); }
@@ -190,7 +155,7 @@ bool usable(float v) { return v >= 0.f && v <= FLT_MAX; }  // false for a negati
 
 extern "C" int64_t nesvor_structural_ssim_workspace_bytes(int n, int h, int w) {
   if (n < 1 || h < 1 || w < 1) return 0;
-  return (int64_t)sizeof(double) * kStats * n * tiles_of(h, w);
+  return slice_sums::Plan<kStats>{n, tiles_of(h, w)}.workspace_bytes();
 }
 
 extern "C" int nesvor_structural_ssim(const float* sim, const float* y, const uint8_t* mask, const float* scale, int n, int h, int w,
@@ -199,12 +164,9 @@ extern "C" int nesvor_structural_ssim(const float* sim, const float* y, const ui
   if (n == 0) return 0;
   if (n < 0 || h < 1 || w < 1) return (int)hipErrorInvalidValue;
   if (sim == nullptr || y == nullptr || scale == nullptr || ssim == nullptr || stats == nullptr) return (int)hipErrorInvalidValue;
-  if ((int64_t)h * w > INT_MAX - 256) return (int)hipErrorInvalidValue;
   if (!usable(c1) || !usable(c2) || !usable(threshold)) return (int)hipErrorInvalidValue;
-  const int64_t tiles = tiles_of(h, w);
-  if (tiles * n > INT_MAX) return (int)hipErrorInvalidValue;
-  const int64_t need = nesvor_structural_ssim_workspace_bytes(n, h, w);
-  if (workspace == nullptr || (int64_t)workspace_bytes < need) return (int)hipErrorInvalidValue;
+  const slice_sums::Plan<kStats> plan{n, tiles_of(h, w)};  // a workgroup per tile
+  if (!plan.accepts(h, w, plan.wgs * n, workspace, workspace_bytes)) return (int)hipErrorInvalidValue;
   // g[t] = exp(-(t - 5)^2 / (2 1.5^2)) normalised to sum 1, in double, rounded to fp32 once
   Taps taps;
   double g[kTaps], sum = 0.0;
@@ -214,11 +176,8 @@ extern "C" int nesvor_structural_ssim(const float* sim, const float* y, const ui
   }
   for (int t = 0; t < kTaps; ++t) taps.g[t] = (float)(g[t] / sum);
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)workspace;
-  hipLaunchKernelGGL(structural_ssim_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, st, sim, y, mask, scale, h, w,
-                     (int)((w + kTile - 1) / kTile), (int)tiles, taps, c1, c2, threshold, ssim, partial);
-  const int64_t total = (int64_t)n * kStats;
-  hipLaunchKernelGGL(structural_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)partial, total,
-                     (int)tiles, stats);
+  hipLaunchKernelGGL(structural_ssim_kernel, dim3((unsigned)(plan.wgs * n)), dim3(256), 0, st, sim, y, mask, scale, h, w,
+                     (int)((w + kTile - 1) / kTile), (int)plan.wgs, taps, c1, c2, threshold, ssim, (double*)workspace);
+  plan.reduce(workspace, stats, st);
   return (int)hipGetLastError();
 }

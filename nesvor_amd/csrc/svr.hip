@@ -13,11 +13,10 @@
 // the one that operator produces.  (The skip test is written in its negated form: a NaN coordinate skips the tap instead
 // of indexing the volume.)
 //
-// Sums are reproducible: fp32 only inside one wave's DPP reduction (64 non-negative terms), then double; every workgroup
-// stores its partials to the workspace and a second small launch adds them in workgroup order.  No atomics, no memset.
+// The sums are added in the reproducible order of slice_sums.h.  A workgroup serves all poses of its 256 pixels, so it parks
+// the wave sums per pose inside the pose loop and combines them after one barrier at the end, in that header's order.
 #include <hip/hip_runtime.h>
-#include <limits.h>
-#include "common.h"
+#include "slice_sums.h"
 #include "../../include/nesvor_hip.h"
 
 namespace {
@@ -116,24 +115,11 @@ __global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __rest
   }
 }
 
-// sums[e][j] = the partials of entry e = (slice, pose) added in workgroup order
-__global__ __launch_bounds__(256) void svr_reduce_kernel(const double* __restrict__ partial, int64_t total, int wgs,
-                                                         double* __restrict__ sums) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int64_t e = t / kSums;
-  const int j = (int)(t - e * kSums);
-  double s = 0.0;
-  for (int g = 0; g < wgs; ++g) s += partial[((size_t)e * wgs + g) * kSums + j];
-  sums[t] = s;
-}
-
 }  // namespace
 
 extern "C" int64_t nesvor_svr_similarity_workspace_bytes(int n, int K, int h, int w) {
   if (n < 1 || K < 1 || h < 1 || w < 1) return 0;
-  const int64_t wgs = ((int64_t)h * w + 255) / 256;
-  return (int64_t)sizeof(double) * kSums * n * K * wgs;
+  return slice_sums::Plan<kSums>{(int64_t)n * K, slice_sums::pixel_workgroups(h, w)}.workspace_bytes();
 }
 
 extern "C" int nesvor_svr_similarity(const float* vol, int D, int H, int W, const float* psf, int d_p, int h_p, int w_p,
@@ -143,14 +129,13 @@ extern "C" int nesvor_svr_similarity(const float* vol, int D, int H, int W, cons
   if (K <= 0 || n == 0) return 0;
   if (D < 1 || H < 1 || W < 1 || h < 1 || w < 1 || n < 1 || d_p < 1 || h_p < 1 || w_p < 1) return (int)hipErrorInvalidValue;
   if ((int64_t)d_p * h_p * w_p > kMaxTaps) return (int)hipErrorInvalidValue;
-  // voxel and pixel indices inside a slice are ints; one workgroup per 256 pixels of a slice
-  if ((int64_t)D * H * W > INT_MAX || (int64_t)h * w > INT_MAX - 256) return (int)hipErrorInvalidValue;
-  const int64_t wgs = ((int64_t)h * w + 255) / 256;
-  if (wgs * n > INT_MAX || (int64_t)n * K > INT_MAX) return (int)hipErrorInvalidValue;
-  const int64_t need = nesvor_svr_similarity_workspace_bytes(n, K, h, w);
-  if (workspace == nullptr || (int64_t)workspace_bytes < need) return (int)hipErrorInvalidValue;
+  // voxel indices are ints; an entry is a (slice, pose), a workgroup serves all poses of its 256 pixels
+  if ((int64_t)D * H * W > INT_MAX || (int64_t)n * K > INT_MAX) return (int)hipErrorInvalidValue;
+  const slice_sums::Plan<kSums> plan{(int64_t)n * K, slice_sums::pixel_workgroups(h, w)};
+  if (!plan.accepts(h, w, plan.wgs * n, workspace, workspace_bytes)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   double* partial = (double*)workspace;
+  const int64_t wgs = plan.wgs;
   const dim3 grid((unsigned)(wgs * n)), block(256);
   int k = 0;
   while (k < K) {  // 13 poses per pass (one finite-difference gradient), single poses otherwise
@@ -164,8 +149,6 @@ extern "C" int nesvor_svr_similarity(const float* vol, int D, int H, int W, cons
       k += 1;
     }
   }
-  const int64_t total = (int64_t)n * K * kSums;
-  hipLaunchKernelGGL(svr_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)partial, total,
-                     (int)wgs, sums);
+  plan.reduce(workspace, sums, st);
   return (int)hipGetLastError();
 }

@@ -56,6 +56,41 @@ def _opt(t: torch.Tensor) -> Optional[torch.Tensor]:
     return t if t.numel() > 0 else None
 
 
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """``nbytes`` of 8-byte aligned scratch (at least one element, so that its pointer is never null)."""
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
+
+
+def _byte_mask(what: str, mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The optional validity mask of the classical-pipeline ops: bool or uint8 (any set byte counts), empty means none."""
+    if mask is None or mask.numel() == 0:
+        return None
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"{what} mask must be torch.bool or torch.uint8, got {mask.dtype}")
+    _lib.require_device(mask, name=f"{what} mask")
+    return mask
+
+
+def _and(names) -> str:
+    return ", ".join(names[:-1]) + " and " + names[-1]
+
+
+def _slice_stack(what: str, stacks: dict, mask, others: dict):
+    """The checks of a slice stack: the named ``stacks`` and the mask are (n, ..., h, w) of one shape holding n x h x w
+    elements, on one device with the named ``others``; -> (mask or None, n, h, w)."""
+    m = _byte_mask(what, mask)
+    tensors = [*stacks.values()] + ([] if m is None else [m])
+    first = tensors[0]
+    if first.ndim < 3 or any(t.shape != first.shape for t in tensors):
+        raise RuntimeError(f"{what}: {_and([*stacks, 'mask'])} (n, ..., h, w) of one shape expected")
+    if any(t.device != first.device for t in (*tensors, *others.values())):
+        raise RuntimeError(f"{what}: {_and([*stacks, 'mask', *others])} must be on one device")
+    n, h, w = int(first.shape[0]), int(first.shape[-2]), int(first.shape[-1])
+    if first.numel() != n * h * w:
+        raise RuntimeError(f"{what}: {' / '.join([*stacks, 'mask'])} must hold n x h x w elements")
+    return m, n, h, w
+
+
 # =====================================================================================================================
 # rigid-transform conversions (reference module nesvor.transform_convert_cuda; float32 and float64)
 # =====================================================================================================================
@@ -299,7 +334,7 @@ def _svr_similarity(vol, psf, transforms, slices, slices_mask, res_slice):
     sums = torch.empty((n, K, 6), dtype=torch.float64, device=vol.device)
     lib = _lib.load()
     nbytes = int(lib.nesvor_svr_similarity_workspace_bytes(n, K, h, w))
-    workspace = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=vol.device)
+    workspace = _workspace(nbytes, vol.device)
     with torch.cuda.device(vol.device):
         err = lib.nesvor_svr_similarity(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), _lib.ptr(psf), *(int(s) for s in psf.shape),
                                         _lib.ptr(transforms), _lib.ptr(slices), _lib.ptr(sm), n, K, h, w, float(res_slice),
@@ -351,25 +386,14 @@ _op("srr_step_(Tensor x, Tensor(a!) grad, float alpha, float beta, float delta, 
 # =====================================================================================================================
 def _robust_estep(sim, y, mask, scale, model):
     _lib.require_device(sim, y, scale, model, dtype=torch.float32, name="robust_estep sim/y/scale/model")
-    m = mask if (mask is not None and mask.numel() > 0) else None
-    if m is not None:
-        if m.dtype not in (torch.bool, torch.uint8):
-            raise RuntimeError(f"robust_estep mask must be torch.bool or torch.uint8, got {m.dtype}")
-        _lib.require_device(m, name="robust_estep mask")
-    if sim.ndim < 3 or y.shape != sim.shape or (m is not None and m.shape != sim.shape):
-        raise RuntimeError("robust_estep: sim, y and mask (n, ..., h, w) of one shape expected")
-    if any(t is not None and t.device != sim.device for t in (y, m, scale, model)):
-        raise RuntimeError("robust_estep: sim, y, mask, scale and model must be on one device")
-    n, h, w = int(sim.shape[0]), int(sim.shape[-2]), int(sim.shape[-1])
-    if sim.numel() != n * h * w or (m is not None and m.numel() != n * h * w):
-        raise RuntimeError("robust_estep: sim / y / mask must hold n x h x w elements")
+    m, n, h, w = _slice_stack("robust_estep", {"sim": sim, "y": y}, mask, {"scale": scale, "model": model})
     if scale.numel() != n or model.numel() != 3:
         raise RuntimeError("robust_estep: scale (n) and model {sigma2, c, m} (3) expected")
     p = torch.empty_like(sim)
     stats = torch.empty((n, 7), dtype=torch.float64, device=sim.device)
     lib = _lib.load()
     nbytes = int(lib.nesvor_robust_estep_workspace_bytes(n, h, w))
-    workspace = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=sim.device)
+    workspace = _workspace(nbytes, sim.device)
     with torch.cuda.device(sim.device):
         err = lib.nesvor_robust_estep(_lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), _lib.ptr(model), n, h, w, _lib.ptr(p),
                                       _lib.ptr(stats), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
@@ -387,25 +411,14 @@ _op("robust_estep(Tensor sim, Tensor y, Tensor? mask, Tensor scale, Tensor model
 # =====================================================================================================================
 def _structural_ssim(sim, y, mask, scale, threshold, dynamic_range):
     _lib.require_device(sim, y, scale, dtype=torch.float32, name="structural_ssim sim/y/scale")
-    m = mask if (mask is not None and mask.numel() > 0) else None
-    if m is not None:
-        if m.dtype not in (torch.bool, torch.uint8):
-            raise RuntimeError(f"structural_ssim mask must be torch.bool or torch.uint8, got {m.dtype}")
-        _lib.require_device(m, name="structural_ssim mask")
-    if sim.ndim < 3 or y.shape != sim.shape or (m is not None and m.shape != sim.shape):
-        raise RuntimeError("structural_ssim: sim, y and mask (n, ..., h, w) of one shape expected")
-    if any(t is not None and t.device != sim.device for t in (y, m, scale)):
-        raise RuntimeError("structural_ssim: sim, y, mask and scale must be on one device")
-    n, h, w = int(sim.shape[0]), int(sim.shape[-2]), int(sim.shape[-1])
-    if sim.numel() != n * h * w or (m is not None and m.numel() != n * h * w):
-        raise RuntimeError("structural_ssim: sim / y / mask must hold n x h x w elements")
+    m, n, h, w = _slice_stack("structural_ssim", {"sim": sim, "y": y}, mask, {"scale": scale})
     if scale.numel() != n:
         raise RuntimeError("structural_ssim: scale (n) expected")
     ssim = torch.empty_like(sim)
     stats = torch.empty((n, 8), dtype=torch.float64, device=sim.device)
     lib = _lib.load()
     nbytes = int(lib.nesvor_structural_ssim_workspace_bytes(n, h, w))
-    workspace = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=sim.device)
+    workspace = _workspace(nbytes, sim.device)
     c1, c2 = (0.01 * dynamic_range) ** 2, (0.03 * dynamic_range) ** 2
     with torch.cuda.device(sim.device):
         err = lib.nesvor_structural_ssim(_lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), n, h, w, c1, c2, float(threshold),
@@ -428,25 +441,14 @@ _op("structural_ssim(Tensor sim, Tensor y, Tensor? mask, Tensor scale, float thr
 def _pair_moments(slices, mask, pairs):
     _lib.require_device(slices, dtype=torch.float32, name="pair_moments slices")
     _lib.require_device(pairs, dtype=torch.int32, name="pair_moments pairs")
-    m = mask if (mask is not None and mask.numel() > 0) else None
-    if m is not None:
-        if m.dtype not in (torch.bool, torch.uint8):
-            raise RuntimeError(f"pair_moments mask must be torch.bool or torch.uint8, got {m.dtype}")
-        _lib.require_device(m, name="pair_moments mask")
-    if slices.ndim < 3 or (m is not None and m.shape != slices.shape):
-        raise RuntimeError("pair_moments: slices and mask (n, ..., h, w) of one shape expected")
     if pairs.ndim != 2 or pairs.shape[1] != 2:
         raise RuntimeError("pair_moments: pairs (P, 2) expected")
-    if any(t is not None and t.device != slices.device for t in (m, pairs)):
-        raise RuntimeError("pair_moments: slices, mask and pairs must be on one device")
-    n, h, w = int(slices.shape[0]), int(slices.shape[-2]), int(slices.shape[-1])
-    if slices.numel() != n * h * w:
-        raise RuntimeError("pair_moments: slices / mask must hold n x h x w elements")
+    m, n, h, w = _slice_stack("pair_moments", {"slices": slices}, mask, {"pairs": pairs})
     P = int(pairs.shape[0])
     moments = torch.empty((P, 6), dtype=torch.float64, device=slices.device)
     lib = _lib.load()
     nbytes = int(lib.nesvor_pair_moments_workspace_bytes(P, h, w))
-    workspace = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=slices.device)
+    workspace = _workspace(nbytes, slices.device)
     with torch.cuda.device(slices.device):
         err = lib.nesvor_pair_moments(_lib.ptr(slices), _lib.ptr(m), n, h, w, _lib.ptr(pairs), P, _lib.ptr(moments),
                                       _lib.ptr(workspace), nbytes, _lib.stream_ptr())
@@ -466,11 +468,7 @@ _op("pair_moments(Tensor slices, Tensor? mask, Tensor pairs) -> Tensor", _pair_m
 def _n4_volume(what, v, f, mask):
     """The argument checks the three ops share; -> (mask or None, D, H, W)."""
     _lib.require_device(v, f, dtype=torch.float32, name=f"{what} v/f")
-    m = mask if (mask is not None and mask.numel() > 0) else None
-    if m is not None:
-        if m.dtype not in (torch.bool, torch.uint8):
-            raise RuntimeError(f"{what} mask must be torch.bool or torch.uint8, got {m.dtype}")
-        _lib.require_device(m, name=f"{what} mask")
+    m = _byte_mask(what, mask)
     if v.ndim != 3 or f.shape != v.shape or (m is not None and m.shape != v.shape):
         raise RuntimeError(f"{what}: v, f and mask (D, H, W) of one shape expected")
     if f.device != v.device or (m is not None and m.device != v.device):
@@ -499,17 +497,13 @@ def _n4_range(what, v, rng, n_bins):
         raise RuntimeError(f"{what}: 2 <= n_bins <= 1024 expected, got {n_bins}")
 
 
-def _n4_workspace(nbytes, device):
-    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
-
-
 def _n4_histogram(v, f, mask, rng, n_bins):
     m, D, H, W = _n4_volume("n4_histogram", v, f, mask)
     _n4_range("n4_histogram", v, rng, n_bins)
     hist = torch.empty(n_bins, dtype=torch.float64, device=v.device)
     lib = _lib.load()
     nbytes = int(lib.nesvor_n4_histogram_workspace_bytes(D, H, W, n_bins))
-    workspace = _n4_workspace(nbytes, v.device)
+    workspace = _workspace(nbytes, v.device)
     with torch.cuda.device(v.device):
         err = lib.nesvor_n4_histogram(_lib.ptr(v), _lib.ptr(f), _lib.ptr(m), D, H, W, _lib.ptr(rng), n_bins, _lib.ptr(hist),
                                       _lib.ptr(workspace), nbytes, _lib.stream_ptr())
@@ -530,7 +524,7 @@ def _n4_fit(v, f, mask, rng, lut, tz, ty, tx, sz, sy, sx, S):
     weight = torch.empty((C, C, C), dtype=torch.float64, device=v.device)
     lib = _lib.load()
     nbytes = int(lib.nesvor_n4_fit_workspace_bytes(D, H, W, S))
-    workspace = _n4_workspace(nbytes, v.device)
+    workspace = _workspace(nbytes, v.device)
     with torch.cuda.device(v.device):
         err = lib.nesvor_n4_fit(_lib.ptr(v), _lib.ptr(f), _lib.ptr(m), _lib.ptr(rng), _lib.ptr(lut), n_bins, _lib.ptr(tz), _lib.ptr(ty),
                                 _lib.ptr(tx), _lib.ptr(sz), _lib.ptr(sy), _lib.ptr(sx), D, H, W, S, _lib.ptr(lattice), _lib.ptr(weight),
@@ -548,7 +542,7 @@ def _n4_update(lattice, tz, ty, tx, sz, sy, sx, S, f, v, mask):
     stats = torch.empty(5, dtype=torch.float64, device=v.device)
     lib = _lib.load()
     nbytes = int(lib.nesvor_n4_update_workspace_bytes(D, H, W))
-    workspace = _n4_workspace(nbytes, v.device)
+    workspace = _workspace(nbytes, v.device)
     with torch.cuda.device(v.device):
         err = lib.nesvor_n4_update(_lib.ptr(lattice), _lib.ptr(tz), _lib.ptr(ty), _lib.ptr(tx), _lib.ptr(sz), _lib.ptr(sy), _lib.ptr(sx), S,
                                    _lib.ptr(f), _lib.ptr(v), _lib.ptr(m), D, H, W, _lib.ptr(stats), _lib.ptr(workspace), nbytes,
