@@ -78,6 +78,9 @@ int nesvor_slice_acq_forward(const float* transforms, const float* vol, const ui
  *   * double precision is built (the *_f64 entry points below; the reference dispatches float and double).
  *   * PSF size: any (the forward kernel keeps PSFs of up to 1024 taps as an LDS list of their non-zero taps and walks
  *     larger ones in global memory; the others read the dense PSF array).
+ *   * volume size: the kernels index voxels with int; every entry point of the group returns hipErrorInvalidValue for
+ *     D H W > INT_MAX before anything is launched or written.
+ *   * empty stack (n h w = 0): nothing is launched; the backwards zero-fill grad_vol / grad_transforms.
  *
  * Adjoint operator A^T (+ optional equalisation) and backward of A, linear-interpolation mode.
  * Replace `nesvor.slice_acq_cuda.adjoint_forward` / `.backward`

@@ -413,6 +413,14 @@ __global__ __launch_bounds__(256) void slice_acq_adjoint_bwd(const T* __restrict
   if (threadIdx.x < 12) grad_transforms[(size_t)k * 12 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
+// The kernels above index voxels with int (zf * Sz + yf * Sy + xf): every entry point refuses a larger volume before a launch.
+inline bool volume_too_large(int D, int H, int W) { return (int64_t)D * H * W > (int64_t)INT_MAX; }
+
+// A gradient of an empty stack (no launch writes it) is zero, not whatever its buffer held.
+template <typename T> int zero_fill(T* p, int64_t count, hipStream_t st) {
+  if (p == nullptr || count <= 0) return 0;
+  return (int)hipMemsetAsync(p, 0, sizeof(T) * (size_t)count, st);
+}
 
 template <typename T>
 int slice_acq_adjoint_backward_impl(const T* transforms, T* grad_vol, const T* vol_weight,
@@ -420,8 +428,9 @@ int slice_acq_adjoint_backward_impl(const T* transforms, T* grad_vol, const T* v
                                                  const uint8_t* slices_mask, const T* vol, T* grad_slices,
                                                  T* grad_transforms, int D, int H, int W, int d_p, int h_p, int w_p,
                                                  int n, int h, int w, T res_slice, int equalize, void* stream) {
-  if ((int64_t)n * h * w <= 0) return 0;
+  if (volume_too_large(D, H, W)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
+  if ((int64_t)n * h * w <= 0) return zero_fill(grad_transforms, (int64_t)n * 12, st);  // (grad_slices has no element)
   if (equalize) {
     if (vol_weight == nullptr || vol == nullptr) return (int)hipErrorInvalidValue;
     const int64_t nv = (int64_t)D * H * W;
@@ -438,6 +447,7 @@ int slice_acq_forward_impl(const T* transforms, const T* vol, const uint8_t* vol
                                         const uint8_t* slices_mask, const T* psf, T* slices,
                                         T* slices_weight, int D, int H, int W, int d_p, int h_p, int w_p, int n,
                                         int h, int w, T res_slice, int interp_psf, void* stream) {
+  if (volume_too_large(D, H, W)) return (int)hipErrorInvalidValue;
   const int64_t total = (int64_t)n * h * w;
   if (total <= 0) return 0;
   const bool lds = (int64_t)d_p * h_p * w_p <= kMaxTaps;
@@ -456,6 +466,7 @@ int slice_acq_adjoint_forward_impl(const T* transforms, const T* psf, const T* s
                                                 const uint8_t* slices_mask, const uint8_t* vol_mask, T* vol,
                                                 T* vol_weight, T* scratch, int D, int H, int W, int d_p, int h_p,
                                                 int w_p, int n, int h, int w, T res_slice, int equalize, void* stream) {
+  if (volume_too_large(D, H, W)) return (int)hipErrorInvalidValue;
   const int64_t np = (int64_t)n * h * w, nv = (int64_t)D * H * W;
   if (nv <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
@@ -475,9 +486,13 @@ int slice_acq_backward_impl(const T* transforms, const T* vol, const uint8_t* vo
                                          const T* psf, const T* grad_slices, const uint8_t* slices_mask,
                                          T* grad_vol, T* grad_transforms, T* scratch, int D, int H, int W,
                                          int d_p, int h_p, int w_p, int n, int h, int w, T res_slice, void* stream) {
+  if (volume_too_large(D, H, W)) return (int)hipErrorInvalidValue;
   const int64_t np = (int64_t)n * h * w, nv = (int64_t)D * H * W;
-  if (np <= 0 || nv <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
+  if (np <= 0 || nv <= 0) {
+    const int e = zero_fill(grad_vol, nv, st);
+    return e != 0 ? e : zero_fill(grad_transforms, (int64_t)n * 12, st);
+  }
   T* coef = scratch;
   hipLaunchKernelGGL(slice_acq_pixel_coef<T>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, transforms, psf, grad_slices,
                      slices_mask, coef, (T*)nullptr, D, H, W, d_p, h_p, w_p, n, h, w, res_slice, 1);
@@ -711,6 +726,7 @@ template <typename T>
 int slice_acq_backward_interp_impl(const T* transforms, const T* vol, const uint8_t* vol_mask, const T* psf, const T* grad_slices,
                                    const uint8_t* slices_mask, T* grad_vol, T* grad_transforms, int D, int H, int W, int d_p,
                                    int h_p, int w_p, int n, int h, int w, T res_slice, void* stream) {
+  if (volume_too_large(D, H, W)) return (int)hipErrorInvalidValue;
   const int64_t np = (int64_t)n * h * w;
   if (np <= 0 || (int64_t)D * H * W <= 0) return 0;
   if (d_p < 2 || h_p < 2 || w_p < 2) return 0;  // no interior cell in the PSF: every tap is skipped
@@ -722,6 +738,7 @@ template <typename T>
 int slice_acq_adjoint_forward_interp_impl(const T* transforms, const T* psf, const T* slices, const uint8_t* slices_mask,
                                           const uint8_t* vol_mask, T* vol, T* vol_weight, int D, int H, int W, int d_p, int h_p,
                                           int w_p, int n, int h, int w, T res_slice, int equalize, void* stream) {
+  if (volume_too_large(D, H, W)) return (int)hipErrorInvalidValue;
   const int64_t np = (int64_t)n * h * w, nv = (int64_t)D * H * W;
   if (np <= 0 || nv <= 0) return 0;
   if (equalize && vol_weight == nullptr) return (int)hipErrorInvalidValue;
@@ -738,6 +755,7 @@ int slice_acq_adjoint_backward_interp_impl(const T* transforms, T* grad_vol, con
                                            const T* psf, const T* slices, const uint8_t* slices_mask, const T* vol, T* grad_slices,
                                            T* grad_transforms, int D, int H, int W, int d_p, int h_p, int w_p, int n, int h, int w,
                                            T res_slice, int equalize, void* stream) {
+  if (volume_too_large(D, H, W)) return (int)hipErrorInvalidValue;
   const int64_t np = (int64_t)n * h * w;
   if (np <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;

@@ -211,7 +211,9 @@ def _sa_backward(transforms, vol, vol_mask, psf, grad_slices, slices_mask, res_s
     _lib.require_device(transforms, vol, psf, grad_slices, dtype=vol.dtype, name="slice_acq backward input")
     vm, sm = _mask(vol_mask), _mask(slices_mask)
     n, h, w = grad_slices.shape[0], grad_slices.shape[-2], grad_slices.shape[-1]
-    new = torch.zeros_like if interp_psf else torch.empty_like  # the interp kernels accumulate (atomics) into their outputs
+    # the interp kernels accumulate (atomics) into their outputs; the linear ones write every element, and the entry point
+    # zero-fills both gradients itself when the stack is empty (n h w = 0: nothing is launched)
+    new = torch.zeros_like if interp_psf else torch.empty_like
     grad_vol = new(vol) if need_vol_grad else None
     grad_tf = new(transforms) if need_transforms_grad else None
     scratch = () if interp_psf else (_lib.ptr(torch.empty(n * h * w, dtype=vol.dtype, device=vol.device)),)

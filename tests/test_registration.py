@@ -47,6 +47,50 @@ def test_ncc_loss_properties():
     assert float(ncc_loss(I, J, win=None, reduction="mean")) == pytest.approx(-1.0, abs=1e-3)
 
 
+def test_vvr_reference_helper_equals_grid_sample_in_float64():
+    """tests/vvr_reference.py (the yardstick of tests/test_gpu_vvr_similarity.py) against F.grid_sample in float64 - bilinear,
+    zero padding, align_corners=True - on a non-cubic volume with a third of the points outside it: samples and all five sums
+    to 1e-12.  Then the measurement the GPU module's COORD_TOL rests on, which needs no kernel: the helper with fp32
+    coordinates against itself with fp64 coordinates on that module's generic inputs."""
+    import torch.nn.functional as F
+
+    import test_gpu_vvr_similarity as G
+    import vvr_reference as R
+    from oracle import transform_convert as tc
+
+    g = torch.Generator().manual_seed(3)
+    D, H, W = 6, 11, 9
+    src = torch.randn(D, H, W, generator=g)
+    unit = torch.tensor([2.0 / (W - 1) / 1.5, 2.0 / (H - 1), 2.0 / (D - 1) / 2.0])
+    points = (torch.rand(4001, 3, generator=g) * 2 - 1) * torch.tensor([9.0, 7.5, 7.5])
+    points[:3] = torch.tensor([[6.0, 5.0, 5.0], [-6.0, -5.0, -5.0], [6.0, -5.0, 0.0]])  # corners and an edge of the volume
+    target = torch.randn(4001, generator=g)
+    mats = tc.axisangle2mat_forward(torch.randn(5, 6, generator=g) * torch.tensor([0.5, 0.5, 0.5, 2.0, 2.0, 2.0]))
+    mats[0] = torch.eye(3, 4)
+    sums, tsums, mags, tmags = R.vvr_sums(src, points, target, mats, unit, torch.float64, with_abs=True)
+    p, m, J = points.double(), mats.double(), target.double()
+    inside = 0
+    for k in range(5):
+        moved = (p + m[k, :, 3]) @ m[k, :, :3].t() * unit.double()
+        ref = F.grid_sample(src.double()[None, None], moved.view(1, -1, 1, 1, 3), mode="bilinear", padding_mode="zeros",
+                            align_corners=True).view(-1)
+        inside += int((moved.abs() <= 1).all(1).sum())
+        scale = float(ref.abs().max())
+        assert float((R.sample(src, points, mats[k], unit) - ref).abs().max()) <= 1e-12 * scale
+        expect = torch.stack([ref.sum(), (ref * ref).sum(), (ref * J).sum()])
+        assert bool(((sums[k] - expect).abs() <= 1e-12 * mags[k]).all())
+        assert bool((mags[k] >= sums[k].abs() * (1 - 1e-12)).all())
+    assert 0.2 < inside / (5 * 4001) < 0.8
+    assert bool(((tsums - torch.stack([J.sum(), (J * J).sum()])).abs() <= 1e-12 * tmags).all())
+    # the coordinate-rounding term of an fp32 kernel, between references
+    c = G._generic()
+    s64, _, mags, _ = R.vvr_sums(c["src"], c["points"], c["target"], c["mats"], G._unit32(c), torch.float64, with_abs=True)
+    s32, _ = R.vvr_sums(c["src"], c["points"], c["target"], c["mats"], G._unit32(c), torch.float32)
+    rel = float(((s32 - s64).abs() / mags).max())
+    print(f"generic case: largest |fp32-coordinate reference - fp64 reference| / sum |terms| {rel:.3e}")
+    assert rel <= G.COORD_TOL / 4 and 4 * G.COORD_MEASURED <= G.COORD_TOL <= 40 * G.COORD_MEASURED
+
+
 @pytest.mark.gpu
 def test_device_filters_without_a_convolution_library_match_the_cpu_convolutions(device):
     """On a HIP device `gaussian_blur` and the box window of `ncc_loss` run as shifted multiply-adds (the first MIOpen
