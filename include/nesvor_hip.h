@@ -950,6 +950,53 @@ int nesvor_structural_ssim(const float* sim, const float* y, const uint8_t* mask
                            size_t workspace_bytes, void* stream);
 int64_t nesvor_structural_ssim_workspace_bytes(int n, int h, int w);
 
+/* ----------------------------------------------------------------------
+ * Stack masking (nesvor_amd/masking.py): which voxels of a stack count.  slices (n,h,w) fp32, mask (n,h,w) bytes or NULL
+ * (any set byte = valid, NULL = all valid), transforms (n,3,4) fp32 the slices' poses [R | t] with x' = R (x + t).  Pixel
+ * (r, c) of slice s lies at p = R_s (x + t_s), x = ((c - (w - 1) / 2) rx, (r - (h - 1) / 2) ry, 0); positions and tests are
+ * double.  Results are fully written (no memset needed) and bit-identical from run to run: no global atomics, per-workgroup
+ * partials in the workspace combined in workgroup order by small follow-up launches, integer LDS atomics in the histogram.
+ * workspace: device memory of at least the matching *_workspace_bytes(...) bytes (0 for sizes the call refuses, and for
+ * nesvor_otsu_threshold, which needs none and ignores the argument).
+ * hipErrorInvalidValue, without a launch: a null pointer other than the optional ones named below, a dimension below 1,
+ * h w > INT_MAX - 256, more than INT_MAX workgroups (n * ceil(h w / 256)), n_bins < 2 or n_bins > 1024, a workspace that is
+ * missing or too small; nesvor_stack_mask also: rx or ry not positive and finite, a volume without volume_geometry or with
+ * a dimension below 1 or more than INT_MAX voxels, n_others or n_slabs below 0, n_others > 0 with a null slab table;
+ * nesvor_otsu_histogram also: n h w > INT_MAX - 256.
+ *
+ * nesvor_stack_mask: out_mask (n,h,w) bytes 0 / 1 and stats (n,3) fp64 {count, min, max} of the kept intensities per slice
+ *   (+inf / -inf without one; a NaN intensity never enters min or max; the count is exact).  A valid voxel is kept if it
+ *   passes every rule that is given, in this order:
+ *   threshold (one DEVICE float or NULL): intensity > threshold[0] (false for a NaN);
+ *   volume (vd,vh,vw) bytes or NULL with volume_geometry, 15 DEVICE doubles: the world-to-lattice matrix (3,4) [M | t] and
+ *     the voxel sizes {x, y, z}: with u = (M p + t) / size + (shape_xyz - 1) / 2 the trilinear interpolation of the 0 / 1
+ *     array (any set byte = 1, 0 off the lattice) at u is >= 0.5;
+ *   slabs (n_slabs,3,4) DEVICE doubles, the world-to-slice matrices [M | t] (q = M p + t) of the slices of n_others other
+ *     stacks, stack k owning rows slab_offsets[k] .. slab_offsets[k + 1] - 1 (DEVICE int32, n_others + 1, clamped to the
+ *     table on the device) with the half-extents slab_extents[k] = {x, y, z} (DEVICE doubles): for every k some row has
+ *     |q_x| <= x, |q_y| <= y and |q_z| <= z.  n_others == 0: no such rule.  The table goes through LDS 64 rows at a time.
+ * nesvor_otsu_histogram: hist (n_bins) int64, the counts of the valid voxels' intensities v over range = two DEVICE
+ *   doubles {lo, hi}: bin min(floor((v - lo) / ((hi - lo) / n_bins)), n_bins - 1), the coordinate in double; a voxel whose
+ *   coordinate is not >= 0 (a NaN intensity, a flat or empty range) is not counted.
+ * nesvor_otsu_threshold: threshold, one DEVICE float: with the bin centres m_i = lo + (i + 0.5) (hi - lo) / n_bins and, for
+ *   the split after bin i (i = 0 .. n_bins - 2), var_i = w0 w1 (mu0 - mu1)^2 from the class weights and the class means of the
+ *   centres (0 where a class is empty), in double, the running sums added in ascending bin order: (float) m_i of the first
+ *   maximum; -inf for fewer than two counted voxels or a range that is not lo < hi.  One workgroup.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_stack_mask(const float* slices, const uint8_t* mask, const float* transforms, int n, int h, int w, double rx,
+                      double ry, const float* threshold, const uint8_t* volume, int vd, int vh, int vw,
+                      const double* volume_geometry, const double* slabs, const double* slab_extents,
+                      const int32_t* slab_offsets, int n_others, int n_slabs, uint8_t* out_mask, double* stats,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_stack_mask_workspace_bytes(int n, int h, int w);
+int nesvor_otsu_histogram(const float* slices, const uint8_t* mask, int n, int h, int w, const double* range, int n_bins,
+                          int64_t* hist, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_otsu_histogram_workspace_bytes(int n, int h, int w, int n_bins);
+int nesvor_otsu_threshold(const int64_t* hist, const double* range, int n_bins, float* threshold, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int64_t nesvor_otsu_threshold_workspace_bytes(int n_bins);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,13 @@ _SIGNATURES = {
     "nesvor_n4_update_workspace_bytes": ([c_int, c_int, c_int], c_int64),
     "nesvor_structural_ssim": ([_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, c_size_t, _P], c_int),
     "nesvor_structural_ssim_workspace_bytes": ([c_int, c_int, c_int], c_int64),
+    "nesvor_stack_mask": ([_P, _P, _P, c_int, c_int, c_int, c_double, c_double, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int,
+                           _P, _P, _P, c_size_t, _P], c_int),
+    "nesvor_stack_mask_workspace_bytes": ([c_int, c_int, c_int], c_int64),
+    "nesvor_otsu_histogram": ([_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, c_size_t, _P], c_int),
+    "nesvor_otsu_histogram_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
+    "nesvor_otsu_threshold": ([_P, _P, c_int, _P, _P, c_size_t, _P], c_int),
+    "nesvor_otsu_threshold_workspace_bytes": ([c_int], c_int64),
 }
 
 

@@ -53,6 +53,19 @@ B-spline fit of the log field, this project's own definition) and writes the cor
 ``--output-bias-fields``, the fields ``exp(f)``; ``--bias-field-correction`` on ``reconstruct``, ``register``, ``svr`` and
 ``assess`` applies the same correction to the stacks as they are loaded, before assessment, template choice and registration.
 The ``--*-n4`` flags (levels, iterations, tolerance, control points, bins, FWHM, noise) are shared by the five commands.
+
+Also not in the reference (upstream added the four switches in later releases; the definitions are nesvor_amd/masking.py's,
+csrc/masking.hip): on the five commands that read stacks
+
+    [--volume-mask FILE] [--stacks-intersection] [--background-threshold T] [--otsu-thresholding [--n-bins-otsu 256]]
+    [--output-stack-masks FILE ...]
+
+narrow every stack's mask as the stacks are loaded, before bias correction, assessment, template choice and registration, in
+this order: intensity above ``T``; the world-space mask volume, interpolated at the voxel, at least 0.5; some slice of every
+other stack contains the voxel (ignored with a warning beside ``--volume-mask`` and with one stack); intensity above Otsu's
+threshold of the voxels kept so far.  ``--output-stack-masks`` writes the final masks, one file per stack.  A stack left without
+a voxel ends the command; with ``--input-slices`` the flags are ignored with a warning.  ``--sample-mask FILE`` on ``reconstruct``
+and ``sample-volume`` samples the model on that mask volume instead of the stored one.
 """
 import argparse
 import logging
@@ -149,6 +162,34 @@ def _bias_flags(p: argparse.ArgumentParser, switch: bool = True) -> None:
     g.add_argument("--noise-n4", default=0.01, type=float, help="Wiener filter noise")
 
 
+def _mask_flags(p: argparse.ArgumentParser) -> None:
+    g = p.add_argument_group("stack masking (not in the reference; nesvor_amd/masking.py)")
+    g.add_argument("--volume-mask", type=str,
+                   help="a 3-D mask in world space: a stack voxel is kept where the mask, interpolated at its position, is >= 0.5")
+    g.add_argument("--stacks-intersection", action="store_true",
+                   help="keep a stack voxel only where every other stack has a slice that contains it (ignored with --volume-mask)")
+    g.add_argument("--background-threshold", type=float, help="keep a stack voxel only where its intensity is above this")
+    g.add_argument("--otsu-thresholding", action="store_true",
+                   help="per stack, keep a voxel only where its intensity is above Otsu's threshold of the voxels kept so far")
+    g.add_argument("--n-bins-otsu", default=256, type=int, help="histogram bins of --otsu-thresholding")
+    g.add_argument("--output-stack-masks", nargs="+", type=str, help="write the final mask of every input stack, one file per stack")
+
+
+MASK_FLAGS = ("volume_mask", "stacks_intersection", "background_threshold", "otsu_thresholding", "output_stack_masks")
+
+
+def masking_requested(args: Namespace) -> bool:
+    """One of the stack masking switches (or ``--output-stack-masks``) is set."""
+    values = [getattr(args, name, None) for name in MASK_FLAGS]
+    return any(v is not None and v is not False for v in values)  # (a threshold of 0.0 is a request)
+
+
+def warn_masking_ignored(args: Namespace, why: str) -> None:
+    if masking_requested(args):
+        logging.warning("The stack masking flags (--volume-mask, --stacks-intersection, --background-threshold, --otsu-thresholding, "
+                        "--output-stack-masks) are ignored with %s: no stack is loaded", why)
+
+
 def bias_options(args: Namespace) -> Dict:
     """The keyword arguments of ``bias.correct_bias_field`` from the ``--*-n4`` flags (defaults where a Namespace lacks them)."""
     return {"n_levels": getattr(args, "n_levels_n4", 4), "n_iter": getattr(args, "n_iter_n4", 50), "tol": getattr(args, "tol_n4", 1e-3),
@@ -173,12 +214,14 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--simulated-slices", type=str)
     g.add_argument("--output-model", type=str)
     g.add_argument("--mask-threshold", type=float, default=1.0)
+    g.add_argument("--sample-mask", type=str, help="a 3-D mask the output volume is sampled on, instead of the mask of the slices")
     g = p.add_argument_group("registration")
     g.add_argument("--registration", default="none", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
     _training_flags(p)
     _bias_flags(p)
+    _mask_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("register")
@@ -193,6 +236,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
     _bias_flags(p)
+    _mask_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("svr")
@@ -228,6 +272,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--global-ncc-threshold", default=0.5, type=float,
                    help="a slice is kept where its correlation with its simulation is at least this")
     _bias_flags(p)
+    _mask_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("assess")
@@ -240,6 +285,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="per-stack score, higher is better (nesvor_amd/assess.py)")
     g.add_argument("--output-json", type=str, help="JSON file for the list of per-stack results")
     _bias_flags(p)
+    _mask_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("correct-bias-field")
@@ -250,6 +296,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--output-corrected-stacks", nargs="+", type=str, required=True)
     g.add_argument("--output-bias-fields", nargs="+", type=str, help="the estimated fields exp(f), one file per input stack")
     _bias_flags(p, switch=False)
+    _mask_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("sample-volume")
@@ -258,6 +305,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--output-volume", type=str, required=True)
     _output_volume_flags(g)
     g.add_argument("--mask-threshold", type=float, default=1.0)
+    g.add_argument("--sample-mask", type=str, help="a 3-D mask the volume is sampled on, instead of the mask stored with the model")
     _common_flags(p)
 
     p = sub.add_parser("sample-slices")
@@ -367,6 +415,8 @@ def _load_stacks(args: Namespace) -> List:
         if args.thicknesses is not None:
             st.thickness = args.thicknesses[i]
         stacks.append(st)
+    if masking_requested(args):
+        _mask_stacks(args, stacks)
     if getattr(args, "bias_field_correction", False):
         from . import bias
 
@@ -374,6 +424,35 @@ def _load_stacks(args: Namespace) -> List:
         bias.correct_stacks(stacks, **bias_options(args))
         logging.info("Bias field correction of %d stacks finished in %.1f s", len(stacks), time.time() - t0)
     return stacks
+
+
+def _mask_stacks(args: Namespace, stacks: List) -> None:
+    """The stack masking switches on the loaded stacks (nesvor_amd/masking.py), and ``--output-stack-masks``."""
+    from . import masking
+    from .image_io import load_volume, save_stack
+
+    out = getattr(args, "output_stack_masks", None)
+    if out is not None and len(out) != len(args.input_stacks):
+        raise SystemExit("The numbers of output stack masks and input stacks are different!")
+    t0 = time.time()
+    volume = load_volume(args.volume_mask, device=args.device) if getattr(args, "volume_mask", None) else None
+    masking.mask_stacks(stacks, volume_mask=volume, stacks_intersection=bool(getattr(args, "stacks_intersection", False)),
+                        background_threshold=getattr(args, "background_threshold", None),
+                        otsu_thresholding=bool(getattr(args, "otsu_thresholding", False)), n_bins_otsu=getattr(args, "n_bins_otsu", 256),
+                        names=[f"stack {i} ({f})" for i, f in enumerate(args.input_stacks)])
+    logging.info("Stack masking of %d stacks finished in %.1f s", len(stacks), time.time() - t0)
+    if out is not None:
+        for path, st in zip(out, stacks):
+            save_stack(path, st, st.mask.to(st.slices.dtype))
+
+
+def _sample_mask(args: Namespace, mask):
+    """``--sample-mask``: the mask volume of a file instead of ``mask``."""
+    if not getattr(args, "sample_mask", None):
+        return mask
+    from .image_io import load_volume
+
+    return load_volume(args.sample_mask, device=args.device)
 
 
 def register(args: Namespace, stacks: List) -> List:
@@ -460,6 +539,7 @@ def reconstruct(args: Namespace) -> None:
         args.input_stacks = args.stack_masks = args.thicknesses = None
     if args.input_slices is not None:
         warn_template_ignored(args, "--input-slices")
+        warn_masking_ignored(args, "--input-slices")
     for name in ("stack_masks", "thicknesses"):
         if getattr(args, name) is not None and len(getattr(args, name)) != len(args.input_stacks):
             raise SystemExit(f"The numbers of {name.replace('_', ' ')} and input stacks are different!")
@@ -494,7 +574,7 @@ def reconstruct(args: Namespace) -> None:
         if getattr(args, "rank", 0) == 0:  # (data parallel: the replicas are identical; the other ranks wait below)
             data = {"mask": mask, "output_model": model, "output_slices": output_slices}
             if args.output_volume:
-                data["output_volume"] = sample_volume(model, mask, args)
+                data["output_volume"] = sample_volume(model, _sample_mask(args, mask), args)
             if args.simulated_slices:
                 data["simulated_slices"] = sample_slices(model, output_slices, mask, args)
             _outputs(data, args)
@@ -521,7 +601,7 @@ def sample_volume_cmd(args: Namespace) -> None:
         args.inference_batch_size = 8 * args.batch_size
     if not getattr(args, "n_inference_samples", None):
         args.n_inference_samples = 2 * args.n_samples
-    _outputs({"output_volume": sample_volume(model, mask, args)}, args)
+    _outputs({"output_volume": sample_volume(model, _sample_mask(args, mask), args)}, args)
 
 
 def sample_slices_cmd(args: Namespace) -> None:

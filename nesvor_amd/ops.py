@@ -566,6 +566,107 @@ _op("n4_update_(Tensor lattice, Tensor tz, Tensor ty, Tensor tx, Tensor sz, Tens
 
 
 # =====================================================================================================================
+# stack masking (csrc/masking.hip): the per-voxel rules of one stack in one pass - intensity threshold, world-space mask
+# volume, intersection with the other stacks' slabs - with the per-slice {count, min, max} of the kept intensities, and Otsu's
+# threshold from an integer histogram without a host read; the definitions and the tables are nesvor_amd/masking.py
+# =====================================================================================================================
+def _f64(what, t, numel, like):
+    _lib.require_device(t, dtype=torch.float64, name=what)
+    if t.numel() != numel or t.device != like.device:
+        raise RuntimeError(f"{what}: {numel} doubles on the device of slices expected")
+
+
+def _stack_mask(slices, mask, transforms, resolution_x, resolution_y, threshold=None, volume=None, volume_geometry=None, slabs=None,
+                slab_extents=None, slab_offsets=None):
+    _lib.require_device(slices, transforms, threshold, dtype=torch.float32, name="stack_mask slices/transforms/threshold")
+    m, n, h, w = _slice_stack("stack_mask", {"slices": slices}, mask, {"transforms": transforms})
+    if tuple(transforms.shape) != (n, 3, 4):
+        raise RuntimeError("stack_mask: transforms (n, 3, 4) expected")
+    if threshold is not None and (threshold.numel() != 1 or threshold.device != slices.device):
+        raise RuntimeError("stack_mask: threshold, one float on the device of slices, expected")
+    vd = vh = vw = 0
+    if volume is not None:
+        if volume.dtype not in (torch.bool, torch.uint8) or volume.ndim != 3:
+            raise RuntimeError("stack_mask: volume (D, H, W) of torch.bool or torch.uint8 expected")
+        _lib.require_device(volume, name="stack_mask volume")
+        if volume.device != slices.device or volume_geometry is None:
+            raise RuntimeError("stack_mask: volume on the device of slices, with volume_geometry, expected")
+        _f64("stack_mask volume_geometry", volume_geometry, 15, slices)
+        vd, vh, vw = (int(s) for s in volume.shape)
+    n_others = n_slabs = 0
+    if slab_offsets is not None and slab_offsets.numel() > 1:
+        if slabs is None or slab_extents is None:
+            raise RuntimeError("stack_mask: slabs, slab_extents and slab_offsets go together")
+        _lib.require_device(slab_offsets, dtype=torch.int32, name="stack_mask slab_offsets")
+        n_others = int(slab_offsets.numel()) - 1
+        if slabs.ndim != 3 or tuple(slabs.shape[1:]) != (3, 4) or slab_offsets.device != slices.device:
+            raise RuntimeError("stack_mask: slabs (n_slabs, 3, 4) and slab_offsets on the device of slices expected")
+        n_slabs = int(slabs.shape[0])
+        _f64("stack_mask slabs", slabs, 12 * n_slabs, slices)
+        _f64("stack_mask slab_extents", slab_extents, 3 * n_others, slices)
+    out = torch.empty(slices.shape, dtype=torch.uint8, device=slices.device)
+    stats = torch.empty((n, 3), dtype=torch.float64, device=slices.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_stack_mask_workspace_bytes(n, h, w))
+    workspace = _workspace(nbytes, slices.device)
+    with torch.cuda.device(slices.device):
+        err = lib.nesvor_stack_mask(_lib.ptr(slices), _lib.ptr(m), _lib.ptr(transforms), n, h, w, float(resolution_x), float(resolution_y),
+                                    _lib.ptr(threshold), _lib.ptr(volume), vd, vh, vw, _lib.ptr(volume_geometry if volume is not None else None),
+                                    _lib.ptr(slabs if n_others else None), _lib.ptr(slab_extents if n_others else None),
+                                    _lib.ptr(slab_offsets if n_others else None), n_others, n_slabs, _lib.ptr(out), _lib.ptr(stats),
+                                    _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "stack mask")
+    return out, stats
+
+
+def _otsu_range(what, slices, rng, n_bins):
+    _f64(f"{what} range", rng, 2, slices)
+    if not 2 <= n_bins <= 1024:
+        raise RuntimeError(f"{what}: 2 <= n_bins <= 1024 expected, got {n_bins}")
+
+
+def _otsu_histogram(slices, mask, rng, n_bins):
+    _lib.require_device(slices, dtype=torch.float32, name="otsu_histogram slices")
+    m, n, h, w = _slice_stack("otsu_histogram", {"slices": slices}, mask, {"range": rng})
+    _otsu_range("otsu_histogram", slices, rng, n_bins)
+    hist = torch.empty(n_bins, dtype=torch.int64, device=slices.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_otsu_histogram_workspace_bytes(n, h, w, n_bins))
+    workspace = _workspace(nbytes, slices.device)
+    with torch.cuda.device(slices.device):
+        err = lib.nesvor_otsu_histogram(_lib.ptr(slices), _lib.ptr(m), n, h, w, _lib.ptr(rng), n_bins, _lib.ptr(hist), _lib.ptr(workspace),
+                                        nbytes, _lib.stream_ptr())
+    _lib.check(err, "otsu histogram")
+    return hist
+
+
+def _otsu_threshold(hist, rng):
+    _lib.require_device(hist, dtype=torch.int64, name="otsu_threshold hist")
+    if hist.ndim != 1:
+        raise RuntimeError("otsu_threshold: hist (n_bins) expected")
+    n_bins = int(hist.shape[0])
+    _otsu_range("otsu_threshold", hist, rng, n_bins)
+    out = torch.empty(1, dtype=torch.float32, device=hist.device)
+    lib = _lib.load()
+    with torch.cuda.device(hist.device):
+        err = lib.nesvor_otsu_threshold(_lib.ptr(hist), _lib.ptr(rng), n_bins, _lib.ptr(out), None, 0, _lib.stream_ptr())
+    _lib.check(err, "otsu threshold")
+    return out
+
+
+_op("stack_mask(Tensor slices, Tensor? mask, Tensor transforms, float resolution_x, float resolution_y, Tensor? threshold=None, "
+    "Tensor? volume=None, Tensor? volume_geometry=None, Tensor? slabs=None, Tensor? slab_extents=None, Tensor? slab_offsets=None) "
+    "-> (Tensor mask, Tensor stats)",
+    _stack_mask,
+    fake=lambda slices, mask, transforms, rx, ry, threshold=None, volume=None, vgeom=None, slabs=None, extents=None, offsets=None: (
+        slices.new_empty(slices.shape, dtype=torch.uint8), slices.new_empty((slices.shape[0], 3), dtype=torch.float64)))
+_op("otsu_histogram(Tensor slices, Tensor? mask, Tensor range, int n_bins) -> Tensor", _otsu_histogram,
+    fake=lambda slices, mask, rng, n_bins: slices.new_empty((n_bins,), dtype=torch.int64))
+_op("otsu_threshold(Tensor hist, Tensor range) -> Tensor", _otsu_threshold,
+    fake=lambda hist, rng: hist.new_empty((1,), dtype=torch.float32))
+
+
+# =====================================================================================================================
 # multi-resolution hash-grid encoding (tinycudann.Encoding "HashGrid"; the scalars are its encoding_config)
 # =====================================================================================================================
 _SPECS = {}

@@ -15,7 +15,8 @@ drops pixels, the slice's correlation drops whole slices - and the descent runs 
 kernel per round (csrc/structural.hip).  Without the flag nothing changes.
 
 Out of scope here: bias fields, robust weights inside the ``--registration svr`` rounds, per-stack PSFs for unequal
-thicknesses (the mean thickness is used, as the registration does) and a volume mask input.
+thicknesses (the mean thickness is used, as the registration does).  A volume mask, the stacks' intersection and intensity
+thresholds narrow the stacks' masks as they are loaded (``--volume-mask`` and the other stack masking flags, nesvor_amd/masking.py).
 """
 import json
 import logging
@@ -183,6 +184,7 @@ def svr_command(args: Namespace) -> Dict:
         if args.input_stacks or args.stack_masks or args.thicknesses:
             logging.warning("Since <input-slices> is provided, <input-stacks>, <stack_masks> and <thicknesses> would be ignored.")
         cli.warn_template_ignored(args, "--input-slices")
+        cli.warn_masking_ignored(args, "--input-slices")
         loaded = load_slices(args.input_slices, args.device)
         for i, s in enumerate(loaded):  # the files carry no stack: a slice is known by its place in the folder's numeric order
             s.slice_idx = i
