@@ -997,6 +997,34 @@ int nesvor_otsu_threshold(const int64_t* hist, const double* range, int n_bins, 
                           size_t workspace_bytes, void* stream);
 int64_t nesvor_otsu_threshold_workspace_bytes(int n_bins);
 
+/* ----------------------------------------------------------------------
+ * Slice bias fields of the classical reconstruction (nesvor_amd/slice_bias.py): one round of the smooth multiplicative field
+ * of every slice, estimated from the log-ratio of the slice to its simulation.
+ * sim (n,h,w) fp32 the simulated slices A x, y (n,h,w) fp32 the acquired ones, mask (n,h,w) bytes or NULL, scale (n) DEVICE
+ * fp32, weight (n,h,w) fp32 the pixel weights or NULL (ones), b (n,h,w) fp32 the current log-field.  With lo = min_intensity,
+ *   e = valid & (y > lo) & (sim > lo)   (valid: mask NULL or its byte set),
+ *   I = (scale[k] y) exp(-b),  r = clamp(log(I / sim), -log 2, log 2),  u = weight   on the eligible pixels, r = u = 0 elsewhere,
+ * and S the separable Gaussian window of `radius` R (2 R + 1 taps exp(-(t - R)^2 / (2 sigma_px^2)) normalised to sum 1 in
+ * double and rounded to fp32, zero padding, along x first, taps added in ascending order from 0):
+ *   num = S(u r),  den = S(u),  b_new = b + (den > 1e-3 ? num / den : 0)                                 on every pixel,
+ * all in fp32 without contraction.  b_new (n,h,w) fp32 and stats (n,5) fp64 are fully written (no memset needed):
+ *   stats[k] = { #e, sum u, sum u b_new, sum u r, sum (u r) r }   over the eligible pixels of slice k;
+ * a slice without one yields five exact zeros, the count is exact.  Products are fp32, the sums double from the first add.
+ * The sums are reproducible (no atomics: per-workgroup partials in the workspace, added in workgroup order by a third
+ * launch).  Centring a field and the rule for slices of little weight are the caller's (slice_bias.py).  workspace: device
+ * memory of at least nesvor_slice_bias_update_workspace_bytes(n, h, w) bytes (the partial sums and the two row-filtered
+ * intermediates; 0 for sizes the call treats as a no-op or refuses).
+ * n == 0: no-op, returns 0.  hipErrorInvalidValue, without a launch: n < 0, h or w below 1, h w > INT_MAX - 256, more than
+ * INT_MAX workgroups in either pass, a null pointer other than mask and weight, b_new == b (the row pass reads the
+ * neighbours' b), radius < 1 or radius > 48, a sigma_px that is not positive and finite, a workspace that is missing or too
+ * small.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_slice_bias_update(const float* sim, const float* y, const uint8_t* mask, const float* scale, const float* weight,
+                             const float* b, int n, int h, int w, double sigma_px, int radius, float min_intensity, float* b_new,
+                             double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_slice_bias_update_workspace_bytes(int n, int h, int w);
+
 #ifdef __cplusplus
 }
 #endif

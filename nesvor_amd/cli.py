@@ -12,6 +12,7 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
                                            [--n-iter-srr 30] [--srr-beta 0.02] [--srr-delta 0.1]
                                            [--outlier-rejection] [--structural-exclusion [--local-ssim-threshold 0.4]
                                            [--global-ncc-threshold 0.5]] [--robust-rounds 3] [--slice-weights FILE.json]
+                                           [--slice-bias-fields [--bias-sigma 12] [--output-corrected-slices DIR]]
                                            [--template-stack 0|K|auto] [--template-metric ncc|matrix-rank|volume]
     python -m nesvor_amd.cli assess        --input-stacks a.nii.gz b.nii.gz c.nii.gz [--stack-masks ...] [--thicknesses ...]
                                            [--metric ncc|matrix-rank|volume] [--output-json FILE.json]
@@ -38,7 +39,10 @@ super-resolution reconstruction by gradient descent with the edge-preserving pri
 ``--outlier-rejection`` adds the EM pixel and slice weights and slice scales (nesvor_amd/robust.py), ``--structural-exclusion``
 drops slices whose correlation with their simulation is below ``--global-ncc-threshold`` and pixels whose local SSIM is
 below ``--local-ssim-threshold`` (nesvor_amd/structural.py, csrc/structural.hip); ``--robust-rounds`` splits the descent for
-either, ``--slice-weights`` writes what either decided per slice.
+either, ``--slice-weights`` writes what either decided per slice.  ``--slice-bias-fields`` estimates, in the same rounds, a
+smooth multiplicative field per slice from the log-ratio of the slice to its simulation (Gaussian window of ``--bias-sigma`` mm;
+nesvor_amd/slice_bias.py, csrc/slice_bias.hip) and descends on the corrected slices; ``--output-corrected-slices`` writes them,
+and the rows of ``--slice-weights`` gain ``bias_rms``, the rms of a slice's log-field.
 
 Also not in the reference (upstream added an ``assess`` command in later releases): ``assess`` scores every input stack for
 motion (nesvor_amd/assess.py, csrc/assess.hip; ``ncc`` of adjacent slices, ``matrix-rank`` = effective rank of the stack's
@@ -262,7 +266,8 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--outlier-rejection", action="store_true",
                    help="robust statistics: EM pixel and slice weights and per-slice intensity scales (nesvor_amd/robust.py)")
     g.add_argument("--robust-rounds", default=3, type=int,
-                   help="rounds the descent steps are split into (with --outlier-rejection and / or --structural-exclusion)")
+                   help="rounds the descent steps are split into (with --outlier-rejection, --structural-exclusion and / or "
+                        "--slice-bias-fields)")
     g.add_argument("--slice-weights", type=str,
                    help="JSON file with one row per slice: the final weight and scale (with --outlier-rejection), ncc, pixel_share "
                         "and excluded (with --structural-exclusion)")
@@ -271,6 +276,12 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--local-ssim-threshold", default=0.4, type=float, help="a pixel is kept where its local SSIM is at least this")
     g.add_argument("--global-ncc-threshold", default=0.5, type=float,
                    help="a slice is kept where its correlation with its simulation is at least this")
+    g.add_argument("--slice-bias-fields", action="store_true",
+                   help="estimate a smooth multiplicative bias field per slice against its simulation (nesvor_amd/slice_bias.py)")
+    g.add_argument("--bias-sigma", default=12.0, type=float, metavar="MM",
+                   help="standard deviation of the Gaussian window of --slice-bias-fields, in mm")
+    g.add_argument("--output-corrected-slices", type=str, metavar="DIR",
+                   help="folder for the slices divided by their fields (with --slice-bias-fields)")
     _bias_flags(p)
     _mask_flags(p)
     _common_flags(p)
@@ -397,7 +408,7 @@ def _outputs(data: Dict, args: Namespace) -> None:
         data["output_volume"].save(args.output_volume)
     if getattr(args, "output_model", None) and "output_model" in data:
         save_model(args.output_model, data["output_model"], data["mask"], args)
-    for key in ("output_slices", "simulated_slices"):
+    for key in ("output_slices", "simulated_slices", "output_corrected_slices"):
         if getattr(args, key, None) and key in data:
             os.makedirs(getattr(args, key), exist_ok=True)
             save_slices(getattr(args, key), data[key])

@@ -436,6 +436,43 @@ _op("structural_ssim(Tensor sim, Tensor y, Tensor? mask, Tensor scale, float thr
 
 
 # =====================================================================================================================
+# slice bias fields of the classical reconstruction (csrc/slice_bias.hip): one round of the smoothed log-ratio of scale_k y to
+# sim - b_new on every pixel and the five per-slice sums - in two passes; the definition, the centring of a field and the rule
+# for slices of little weight are nesvor_amd/slice_bias.py
+# =====================================================================================================================
+def _slice_bias_update(sim, y, mask, scale, weight, b, sigma_px, min_intensity):
+    from .slice_bias import window_radius
+
+    _lib.require_device(sim, y, scale, b, dtype=torch.float32, name="slice_bias_update sim/y/scale/b")
+    stacks = {"sim": sim, "y": y, "b": b}
+    if weight is not None:
+        _lib.require_device(weight, dtype=torch.float32, name="slice_bias_update weight")
+        stacks["weight"] = weight
+    m, n, h, w = _slice_stack("slice_bias_update", stacks, mask, {"scale": scale})
+    if scale.numel() != n:
+        raise RuntimeError("slice_bias_update: scale (n) expected")
+    radius = window_radius(sigma_px)  # (raises for a sigma_px that is not positive and finite)
+    b_new = torch.empty_like(sim)
+    stats = torch.empty((n, 5), dtype=torch.float64, device=sim.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_slice_bias_update_workspace_bytes(n, h, w))
+    workspace = _workspace(nbytes, sim.device)
+    with torch.cuda.device(sim.device):
+        err = lib.nesvor_slice_bias_update(_lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), _lib.ptr(weight), _lib.ptr(b), n, h, w,
+                                           float(sigma_px), radius, float(min_intensity), _lib.ptr(b_new), _lib.ptr(stats),
+                                           _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "slice bias update")
+    return b_new, stats
+
+
+_op("slice_bias_update(Tensor sim, Tensor y, Tensor? mask, Tensor scale, Tensor? weight, Tensor b, float sigma_px, "
+    "float min_intensity) -> (Tensor b_new, Tensor stats)",
+    _slice_bias_update,
+    fake=lambda sim, y, mask, scale, weight, b, sigma_px, min_intensity: (torch.empty_like(sim),
+                                                                          sim.new_empty((sim.shape[0], 5), dtype=torch.float64)))
+
+
+# =====================================================================================================================
 # masked moments of slice pairs for the stack quality assessment (csrc/assess.hip): {count, sum a, sum b, sum a^2, sum b^2,
 # sum a b} per pair over the pixels valid in both slices; the host logic (and the range check of the pair indices, which the
 # kernel does not repeat) is nesvor_amd/assess.py

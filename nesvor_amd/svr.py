@@ -14,8 +14,13 @@ nesvor_amd/structural.py): after the EM round, if any, every round compares each
 drops pixels, the slice's correlation drops whole slices - and the descent runs on what is kept.  One pass of a fused HIP
 kernel per round (csrc/structural.hip).  Without the flag nothing changes.
 
-Out of scope here: bias fields, robust weights inside the ``--registration svr`` rounds, per-stack PSFs for unequal
-thicknesses (the mean thickness is used, as the registration does).  A volume mask, the stacks' intersection and intensity
+Optional slice bias fields (``--slice-bias-fields``; ``reconstruct_volume(slice_bias=SliceBias())``, nesvor_amd/slice_bias.py):
+every round estimates a smooth multiplicative field per slice from the log-ratio of the slice to its simulation, after the EM
+round and the structural step, if any, and the descent runs on the corrected slices.  Two passes of a fused HIP kernel per
+round (csrc/slice_bias.hip).  Without the flag nothing changes.
+
+Out of scope here: a gauge for the robust scales, robust weights and bias fields inside the ``--registration svr`` rounds,
+per-stack PSFs for unequal thicknesses (the mean thickness is used, as the registration does).  A volume mask, the stacks' intersection and intensity
 thresholds narrow the stacks' masks as they are loaded (``--volume-mask`` and the other stack masking flags, nesvor_amd/masking.py).
 """
 import json
@@ -29,6 +34,7 @@ import torch
 from .image import Slice, Volume
 from .registration import _common_frame, _cover_shape, resample
 from .robust import RobustStatistics
+from .slice_bias import MIN_WEIGHT, SliceBias, eligible
 from .srr import AcquisitionOperator, PSFreconstruction, srr_descent
 from .structural import StructuralExclusion
 from .transform import RigidTransform, mat_update_resolution
@@ -71,7 +77,8 @@ def _operator(images: torch.Tensor, m: torch.Tensor, frame_poses: RigidTransform
 
 def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r: float, n_iter: int = 30, beta: float = 0.02,
                        delta: float = 0.1, robust_rounds: int = 0, robust_out: Optional[Dict] = None,
-                       structural: Optional[StructuralExclusion] = None, structural_out: Optional[Dict] = None) -> Volume:
+                       structural: Optional[StructuralExclusion] = None, structural_out: Optional[Dict] = None,
+                       slice_bias: Optional[SliceBias] = None, slice_bias_out: Optional[Dict] = None) -> Volume:
     """Slices at their poses -> the reconstructed ``Volume``: world-aligned (identity pose, centred at the origin), voxel size
     ``res_r``, large enough for every masked pixel; its mask is the set of voxels a masked pixel's PSF reaches (A^T 1 > 0).
 
@@ -93,14 +100,49 @@ def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r:
     then ``structural.update`` on the slices with the robust scales (or as they are), and descends with the pixel weights
     ``structural.weights()`` (times the robust ones) on the robustly scaled slices (or as they are).  Decisions are taken anew
     every round.  ``structural_out`` then receives ``ncc``, ``slice_keep`` and ``pixel_share`` (n, as above) and ``keep``.
-    ``structural=None`` leaves everything above as it is."""
+    ``structural=None`` leaves everything above as it is.
+
+    ``slice_bias``, a ``SliceBias`` (nesvor_amd/slice_bias.py): the descent is split into ``robust_rounds`` rounds (if that is 0:
+    ``structural.rounds`` with ``structural``, else ``slice_bias.rounds``, 3 by default; cut to ``n_iter`` as above).  Each round takes A x once, runs the EM round,
+    if ``robust_rounds`` > 0, and the structural update, if any, on the slices corrected by the current fields, then
+    ``slice_bias.update`` on the acquired slices with the robust scales and the round's pixel weights, and descends on the
+    (robustly scaled) corrected slices with those weights.  ``slice_bias_out`` then receives ``b`` (the log-fields, as the
+    framed slices), ``stats`` (n,5), ``eligible`` (as ``b``, bool: the last round's eligible pixels), ``bias_rms`` (n, the rms of
+    ``b`` over them) and ``keep``; ``robust_out`` and ``structural_out`` as above.  ``slice_bias=None`` leaves everything above as
+    it is."""
     images, m, frame_poses, keep = _frame_keep(slices, mask, poses, res_s)
     if images.shape[0] == 0:
         raise ValueError("reconstruct_volume: every slice is empty")
     shape = _cover_shape(frame_poses, m, res_s, s_thick, res_r)
     op, params = _operator(images, m, frame_poses, res_s, s_thick, res_r, shape)
     start = PSFreconstruction(op.transforms, images, m, None, params)
-    if structural is not None:
+    if slice_bias is not None:
+        x = start
+        rounds = robust_rounds if robust_rounds > 0 else (structural.rounds if structural is not None else slice_bias.rounds)
+        rounds = max(1, min(rounds, n_iter))
+        stats = RobustStatistics().init(op.forward(x), images, m) if robust_rounds > 0 else None
+        for r in range(rounds):
+            sim = op.forward(x)
+            corrected = slice_bias.corrected(images)
+            p = None
+            if stats is not None:
+                stats.update(sim, corrected, m)
+                p = stats.weights()
+            if structural is not None:
+                structural.update(sim, corrected, m, None if stats is None else stats.scale)
+                p = structural.weights() if p is None else p * structural.weights()
+            slice_bias.update(sim, images, m, None if stats is None else stats.scale, p, res_s)
+            corrected = slice_bias.corrected(images)
+            steps = n_iter // rounds + (n_iter % rounds if r + 1 == rounds else 0)
+            x = srr_descent(op, corrected if stats is None else stats.scaled(corrected), x, steps, beta, delta, p=p)
+        if stats is not None and robust_out is not None:
+            robust_out.update(slice_weight=stats.slice_weight, scale=stats.scale, keep=keep)
+        if structural is not None and structural_out is not None:
+            structural_out.update(ncc=structural.ncc, slice_keep=structural.slice_keep, pixel_share=structural.pixel_share(), keep=keep)
+        if slice_bias_out is not None:
+            slice_bias_out.update(b=slice_bias.b, stats=slice_bias.stats, bias_rms=slice_bias.rms(sim, images, m),
+                                  eligible=eligible(sim, images, m, slice_bias.min_intensity), keep=keep)
+    elif structural is not None:
         x = start
         rounds = max(1, min(robust_rounds if robust_rounds > 0 else structural.rounds, n_iter))
         stats = RobustStatistics().init(op.forward(x), images, m) if robust_rounds > 0 else None
@@ -142,6 +184,14 @@ def simulate_slices(volume: Volume, slices, mask, poses, res_s: float, s_thick: 
     return [Slice(sim[k], m[k], frame_poses[k], res_s, res_s, s_thick) for k in range(sim.shape[0])]
 
 
+def corrected_slices(b: torch.Tensor, slices, mask, poses, res_s: float, s_thick: float) -> List[Slice]:
+    """y exp(-b) for the log-fields ``b`` that ``reconstruct_volume(slice_bias_out=...)`` returned: one ``Slice`` (on the padded
+    frame, with the frame's pose and the acquired slice's mask) per non-empty input slice."""
+    images, m, frame_poses = _frame(slices, mask, poses, res_s)
+    corrected = images * torch.exp(-b)
+    return [Slice(corrected[k], m[k], frame_poses[k], res_s, res_s, s_thick) for k in range(corrected.shape[0])]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the command
 # ---------------------------------------------------------------------------------------------------------------------
@@ -177,8 +227,11 @@ def svr_command(args: Namespace) -> Dict:
     if args.input_slices is None and args.input_stacks is None:
         raise SystemExit("No image data provided! Use --input-slices or --input-stacks to input data.")
     use_structural = bool(getattr(args, "structural_exclusion", False))
-    if getattr(args, "slice_weights", None) and not getattr(args, "outlier_rejection", False) and not use_structural:
+    use_bias = bool(getattr(args, "slice_bias_fields", False))
+    if getattr(args, "slice_weights", None) and not getattr(args, "outlier_rejection", False) and not use_structural and not use_bias:
         raise SystemExit("--slice-weights needs --outlier-rejection: without it no slice weights are estimated")
+    if getattr(args, "output_corrected_slices", None) and not use_bias:
+        raise SystemExit("--output-corrected-slices needs --slice-bias-fields: without it no field is estimated")
     t0 = time.time()
     if args.input_slices is not None:
         if args.input_stacks or args.stack_masks or args.thicknesses:
@@ -209,7 +262,20 @@ def svr_command(args: Namespace) -> Dict:
     t0 = time.time()
     robust: Dict = {}
     structural: Dict = {}
-    if use_structural:
+    fields: Dict = {}
+    if use_bias:
+        if args.robust_rounds < 1:
+            raise SystemExit("--robust-rounds must be at least 1")
+        if not args.bias_sigma > 0:
+            raise SystemExit("--bias-sigma must be positive")
+        exclusion = (StructuralExclusion(args.local_ssim_threshold, args.global_ncc_threshold, rounds=args.robust_rounds)
+                     if use_structural else None)
+        robust_rounds = args.robust_rounds if getattr(args, "outlier_rejection", False) else 0
+        volume = reconstruct_volume(stacks, masks, poses, res_s, s_thick, args.output_resolution, args.n_iter_srr, args.srr_beta,
+                                    args.srr_delta, robust_rounds=robust_rounds, robust_out=robust, structural=exclusion,
+                                    structural_out=structural, slice_bias=SliceBias(args.bias_sigma, rounds=args.robust_rounds),
+                                    slice_bias_out=fields)
+    elif use_structural:
         if args.robust_rounds < 1:
             raise SystemExit("--robust-rounds must be at least 1")
         exclusion = StructuralExclusion(args.local_ssim_threshold, args.global_ncc_threshold, rounds=args.robust_rounds)
@@ -249,10 +315,20 @@ def svr_command(args: Namespace) -> Dict:
             rows = [{"stack": slices[k].stack_idx, "slice": slices[k].slice_idx} for k in keep]
         for row, r, s, k in zip(rows, ncc, share, kept):
             row.update(ncc=r, pixel_share=s, excluded=not k)
+    if fields:
+        rms, updated = fields["bias_rms"].tolist(), (fields["stats"][:, 1] >= MIN_WEIGHT).tolist()
+        logging.info("Slice bias fields: the last round updated %d of %d slices (the others have too little weight); rms of the "
+                     "log-fields %.3f at most", sum(updated), len(updated), max(rms))
+        if rows is None:
+            rows = [{"stack": slices[k].stack_idx, "slice": slices[k].slice_idx} for k in fields["keep"].tolist()]
+        for row, v in zip(rows, rms):
+            row.update(bias_rms=v)
     if rows is not None and getattr(args, "slice_weights", None):
         with open(args.slice_weights, "w") as f:
             json.dump(rows, f, indent=1)
     data = {"output_volume": volume, "output_slices": slices}
+    if fields and getattr(args, "output_corrected_slices", None):
+        data["output_corrected_slices"] = corrected_slices(fields["b"], stacks, masks, poses, res_s, s_thick)
     if args.simulated_slices:
         data["simulated_slices"] = simulate_slices(volume, stacks, masks, poses, res_s, s_thick)
     return data
