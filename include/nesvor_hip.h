@@ -1025,6 +1025,48 @@ int nesvor_slice_bias_update(const float* sim, const float* y, const uint8_t* ma
                              double* stats, void* workspace, size_t workspace_bytes, void* stream);
 int64_t nesvor_slice_bias_update_workspace_bytes(int n, int h, int w);
 
+/* ----------------------------------------------------------------------
+ * Volume comparison (nesvor_amd/evaluate.py, the `evaluate` command): a volume X on the lattice of a reference volume R, and
+ * the 3-D SSIM map of the two with the sums of the error measures.
+ *
+ * nesvor_volume_resample.  reference (d,h,w) fp32 = I0 with reference_mask (d,h,w) bytes or NULL (all set), volume
+ * (vd,vh,vw) fp32 = X0 with volume_mask (vd,vh,vw) bytes or NULL; any set byte counts.  index_map: 12 HOST doubles, M (3,4)
+ * row-major, taking an R voxel index (x, y, z) to the continuous X voxel index in double, in the written order:
+ *   u_a = ((M[a][0] x + M[a][1] y) + M[a][2] z) + M[a][3],       a = 0, 1, 2 = the x, y, z axis of X (sizes vw, vh, vd).
+ * With eps = 2^-20 the voxel is inside where -eps <= u_a <= size_a - 1 + eps on the three axes; u is then clamped to
+ * [0, size - 1]; i0 = floor(u), f = (float)(u - floor(u)), i1 = min(i0 + 1, size - 1).  lerp(a, b, f) = a + f (b - a) in fp32
+ * without contraction, along x, then y, then z, interpolates J0 from X0 and mX from the volume mask as 0 / 1 (1 if NULL):
+ *   v = reference mask and inside and mX >= 0.5,      resampled = J0 on v and 0 elsewhere,      valid = v as 0 / 1.
+ * resampled (d,h,w) fp32, valid (d,h,w) bytes and stats (8) fp64 are fully written (no memset needed):
+ *   stats = { n = #v, n_ref = #reference mask, sum I, sum J, sum I^2, sum J^2, sum I J, max I }     over v, I = I0, J = J0;
+ * the counts and the maximum (-inf without a valid voxel) are exact, products are fp32, the sums double from the first add
+ * and reproducible (no atomics: per-workgroup partials in the workspace, combined in a fixed order by a second launch).
+ *
+ * nesvor_volume_ssim.  reference, resampled, valid as above, params a DEVICE float[4] = {a, b, c1, c2}.  With I = I0 and
+ * J' = a J0 + b (a multiply, then an add) on v and 0 elsewhere, and S the separable 11-tap Gaussian window of
+ * nesvor_structural_ssim with zero padding along x, then y, then z, taps added in ascending order from 0:
+ *   Wt = S(v),  muI = S(I) / Wt,  muJ = S(J') / Wt,  sI = S(I I) / Wt - muI^2,  sJ = S(J' J') / Wt - muJ^2,  sIJ = S(I J') / Wt - muI muJ,
+ *   ssim = (2 muI muJ + c1) (2 sIJ + c2) / ((muI^2 + muJ^2 + c1) (sI + sJ + c2))          on v, 0 on every other voxel,
+ * all in fp32 without contraction.  ssim (d,h,w) fp32 and stats (4) fp64 are fully written:
+ *   stats = { n, sum ssim, sum e^2, sum |e| }     over v, e = I - J';
+ * n is exact, the sums double from the first add and reproducible.  A workgroup owns a 16 x 16 in-plane tile and 32
+ * consecutive planes (EVALUATE_Z_CHUNK of nesvor_amd/ops.py).  ssim must not overlap an input.
+ *
+ * workspace: device memory of at least nesvor_volume_*_workspace_bytes(d, h, w) bytes (0 for sizes the call refuses):
+ * 64 bytes per 256 voxels for the resampling, 32 bytes per (16 x 16 tile, 32 planes) for the SSIM.
+ * hipErrorInvalidValue, without a launch: a null pointer other than the two masks, a dimension (of either volume) below 1,
+ * more than INT_MAX - 256 voxels (in either volume), more than INT_MAX workgroups, a non-finite entry of index_map, a
+ * workspace that is missing or too small.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_volume_resample(const float* reference, const uint8_t* reference_mask, int d, int h, int w, const float* volume,
+                           const uint8_t* volume_mask, int vd, int vh, int vw, const double* index_map, float* resampled,
+                           uint8_t* valid, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_volume_resample_workspace_bytes(int d, int h, int w);
+int nesvor_volume_ssim(const float* reference, const float* resampled, const uint8_t* valid, const float* params, int d, int h,
+                       int w, float* ssim, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_volume_ssim_workspace_bytes(int d, int h, int w);
+
 #ifdef __cplusplus
 }
 #endif

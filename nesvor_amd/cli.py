@@ -18,6 +18,9 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
                                            [--metric ncc|matrix-rank|volume] [--output-json FILE.json]
     python -m nesvor_amd.cli correct-bias-field --input-stacks a.nii.gz b.nii.gz [--stack-masks ...]
                                            --output-corrected-stacks ca.nii.gz cb.nii.gz [--output-bias-fields fa.nii.gz fb.nii.gz]
+    python -m nesvor_amd.cli evaluate      --reference-volume r.nii.gz [--reference-mask ...] --input-volumes a.nii.gz b.nii.gz
+                                           [--input-masks ...] [--intensity-fit none|scale|affine] [--dynamic-range L]
+                                           [--output-json FILE.json] [--output-ssim-maps ...] [--output-resampled ...]
     python -m nesvor_amd.cli sample-volume --input-model m.pt --output-volume v.nii.gz [--output-resolution 0.8] ...
     python -m nesvor_amd.cli sample-slices --input-model m.pt --input-slices DIR --simulated-slices DIR
 
@@ -70,6 +73,15 @@ other stack contains the voxel (ignored with a warning beside ``--volume-mask`` 
 threshold of the voxels kept so far.  ``--output-stack-masks`` writes the final masks, one file per stack.  A stack left without
 a voxel ends the command; with ``--input-slices`` the flags are ignored with a warning.  ``--sample-mask FILE`` on ``reconstruct``
 and ``sample-volume`` samples the model on that mask volume instead of the stored one.
+
+Also not in the reference: ``evaluate`` compares volumes with a reference volume (nesvor_amd/evaluate.py, csrc/evaluate.hip): every
+input volume is put onto the reference's lattice through the two files' poses (trilinear; ``svr`` writes a world-aligned lattice,
+``reconstruct`` the model's own) and PSNR, NRMSE, MAE, correlation and the mean of a 3-D SSIM are taken over the voxels both
+volumes cover, after the ``--intensity-fit`` of the volume to the reference.  The volumes must share a world frame - the
+reconstructions of one set of registered slices, or of one ``--input-slices`` folder, do; rigid alignment is out of scope.  It logs
+a table, ``--output-json`` writes the reports (a non-finite value as null), ``--output-ssim-maps`` / ``--output-resampled`` the maps
+on the reference's lattice.  A volume that shares no voxel with the reference is reported with a warning.
+``--device cpu``, which this command alone takes, runs the same definition as torch expressions on the host.
 """
 import argparse
 import logging
@@ -135,9 +147,18 @@ def _output_volume_flags(g) -> None:
     g.add_argument("--no-output-psf", action="store_true")
 
 
-def _common_flags(p: argparse.ArgumentParser) -> None:
+def _device_or_host(value: str):
+    return "cpu" if value == "cpu" else int(value)
+
+
+def _common_flags(p: argparse.ArgumentParser, host: bool = False) -> None:
+    """``host``: the command has a host path of its own, ``--device cpu`` selects it."""
     g = p.add_argument_group("common")
-    g.add_argument("--device", default=None, type=int, help="HIP device index (default 0; under a launcher: the rank's own device)")
+    if host:
+        g.add_argument("--device", default=None, type=_device_or_host,
+                       help="HIP device index (default 0), or 'cpu': the same definition as torch expressions on the host")
+    else:
+        g.add_argument("--device", default=None, type=int, help="HIP device index (default 0; under a launcher: the rank's own device)")
     g.add_argument("--verbose", type=int, default=1, choices=[0, 1, 2])
     g.add_argument("--output-log", type=str)
     g.add_argument("--seed", type=int, default=None)
@@ -310,6 +331,25 @@ def build_parser() -> argparse.ArgumentParser:
     _mask_flags(p)
     _common_flags(p)
 
+    p = sub.add_parser("evaluate")
+    g = p.add_argument_group("input (the volumes must share a world frame: nothing is aligned)")
+    g.add_argument("--reference-volume", type=str, required=True, help="the volume the others are compared with, on its lattice")
+    g.add_argument("--reference-mask", type=str, help="a mask on the reference's lattice instead of its positive voxels")
+    g.add_argument("--input-volumes", nargs="+", type=str, required=True,
+                   help="the volumes under test, on any lattice of the reference's world frame (the reconstructions of one set of "
+                        "registered slices, or of one --input-slices folder, share it); rigid alignment is out of scope")
+    g.add_argument("--input-masks", nargs="+", type=str, help="one mask per input volume instead of its positive voxels")
+    g = p.add_argument_group("comparison (nesvor_amd/evaluate.py)")
+    g.add_argument("--intensity-fit", default="scale", type=str, choices=["none", "scale", "affine"],
+                   help="fitted to the reference before the errors are taken: nothing, a gain, or a gain and an offset")
+    g.add_argument("--dynamic-range", type=float, metavar="L", help="the peak value of PSNR, NRMSE and SSIM (default: the reference's "
+                                                                    "largest intensity on the compared voxels)")
+    g = p.add_argument_group("output")
+    g.add_argument("--output-json", type=str, help="JSON file for the list of per-volume reports")
+    g.add_argument("--output-ssim-maps", nargs="+", type=str, help="the SSIM map of every input volume, on the reference's lattice")
+    g.add_argument("--output-resampled", nargs="+", type=str, help="every input volume on the reference's lattice")
+    _common_flags(p, host=True)
+
     p = sub.add_parser("sample-volume")
     p.add_argument("--input-model", type=str, required=True)
     g = p.add_argument_group("output")
@@ -380,6 +420,9 @@ def _setup(args: Namespace) -> None:
         return
     if args.seed is not None:
         torch.manual_seed(args.seed)
+    if args.device == "cpu":  # (`evaluate` alone offers it)
+        args.device = torch.device("cpu")
+        return
     args.device = torch.device("cuda", args.device or 0)
     torch.cuda.set_device(args.device)
 
@@ -538,6 +581,12 @@ def correct_bias_field_cmd(args: Namespace) -> None:
             save_stack(args.output_bias_fields[i], st, torch.exp(field).to(st.slices.dtype))
 
 
+def evaluate_cmd(args: Namespace) -> None:
+    from .evaluate import evaluate_command
+
+    evaluate_command(args)
+
+
 def reconstruct(args: Namespace) -> None:
     from .image_io import load_slices, load_stack
     from .sample import sample_slices, sample_volume
@@ -631,7 +680,7 @@ def main(argv=None) -> None:
     _setup(args)
     t0 = time.time()
     {"reconstruct": reconstruct, "register": register_cmd, "svr": svr_cmd, "assess": assess_cmd,
-     "correct-bias-field": correct_bias_field_cmd, "sample-volume": sample_volume_cmd,
+     "correct-bias-field": correct_bias_field_cmd, "evaluate": evaluate_cmd, "sample-volume": sample_volume_cmd,
      "sample-slices": sample_slices_cmd}[args.command](args)
     logging.info("Command 'nesvor %s' finished, overall time: %.1f s", args.command, time.time() - t0)
 

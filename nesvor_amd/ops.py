@@ -436,6 +436,75 @@ _op("structural_ssim(Tensor sim, Tensor y, Tensor? mask, Tensor scale, float thr
 
 
 # =====================================================================================================================
+# volume comparison (csrc/evaluate.hip): a volume on a reference volume's lattice with the first sums, and the 3-D SSIM map of
+# the two with the sums of the error measures; the definition, the fit between the two and the report are nesvor_amd/evaluate.py
+# =====================================================================================================================
+EVALUATE_Z_CHUNK = 32  # planes per workgroup of volume_ssim (kZChunk of csrc/evaluate.hip): a chunk warms up on the 10 planes before it
+
+
+def _volume(what, name, t, mask):
+    """A (D,H,W) fp32 volume and its optional mask; -> (mask or None, D, H, W)."""
+    _lib.require_device(t, dtype=torch.float32, name=f"{what} {name}")
+    m = _byte_mask(f"{what} {name}", mask)
+    if t.ndim != 3 or (m is not None and m.shape != t.shape):
+        raise RuntimeError(f"{what}: {name} and its mask (D, H, W) of one shape expected")
+    if m is not None and m.device != t.device:
+        raise RuntimeError(f"{what}: {name} and its mask must be on one device")
+    return m, int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+
+
+def _volume_resample(reference, reference_mask, volume, volume_mask, index_map):
+    mr, d, h, w = _volume("volume_resample", "reference", reference, reference_mask)
+    mx, vd, vh, vw = _volume("volume_resample", "volume", volume, volume_mask)
+    if volume.device != reference.device:
+        raise RuntimeError("volume_resample: reference and volume must be on one device")
+    if len(index_map) != 12:
+        raise RuntimeError("volume_resample: index_map, the 12 entries of a (3, 4) matrix, expected")
+    resampled = torch.empty_like(reference)
+    valid = torch.empty(reference.shape, dtype=torch.bool, device=reference.device)
+    stats = torch.empty(8, dtype=torch.float64, device=reference.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_volume_resample_workspace_bytes(d, h, w))
+    workspace = _workspace(nbytes, reference.device)
+    M = (ctypes.c_double * 12)(*[float(v) for v in index_map])
+    with torch.cuda.device(reference.device):
+        err = lib.nesvor_volume_resample(_lib.ptr(reference), _lib.ptr(mr), d, h, w, _lib.ptr(volume), _lib.ptr(mx), vd, vh, vw, M,
+                                         _lib.ptr(resampled), _lib.ptr(valid), _lib.ptr(stats), _lib.ptr(workspace), nbytes,
+                                         _lib.stream_ptr())
+    _lib.check(err, "volume resample")
+    return resampled, valid, stats
+
+
+def _volume_ssim(reference, resampled, valid, params):
+    _lib.require_device(params, dtype=torch.float32, name="volume_ssim params")
+    m, d, h, w = _volume("volume_ssim", "reference", reference, valid)
+    _lib.require_device(resampled, dtype=torch.float32, name="volume_ssim resampled")
+    if m is None or resampled.shape != reference.shape:
+        raise RuntimeError("volume_ssim: reference, resampled and valid (D, H, W) of one shape expected")
+    if params.numel() != 4 or any(t.device != reference.device for t in (resampled, params)):
+        raise RuntimeError("volume_ssim: params, four floats {a, b, c1, c2}, and resampled on the device of reference expected")
+    ssim = torch.empty_like(reference)
+    stats = torch.empty(4, dtype=torch.float64, device=reference.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_volume_ssim_workspace_bytes(d, h, w))
+    workspace = _workspace(nbytes, reference.device)
+    with torch.cuda.device(reference.device):
+        err = lib.nesvor_volume_ssim(_lib.ptr(reference), _lib.ptr(resampled), _lib.ptr(m), _lib.ptr(params), d, h, w, _lib.ptr(ssim),
+                                     _lib.ptr(stats), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "volume ssim")
+    return ssim, stats
+
+
+_op("volume_resample(Tensor reference, Tensor? reference_mask, Tensor volume, Tensor? volume_mask, float[] index_map) -> "
+    "(Tensor resampled, Tensor valid, Tensor stats)",
+    _volume_resample,
+    fake=lambda reference, reference_mask, volume, volume_mask, index_map: (
+        torch.empty_like(reference), reference.new_empty(reference.shape, dtype=torch.bool), reference.new_empty((8,), dtype=torch.float64)))
+_op("volume_ssim(Tensor reference, Tensor resampled, Tensor valid, Tensor params) -> (Tensor ssim, Tensor stats)", _volume_ssim,
+    fake=lambda reference, resampled, valid, params: (torch.empty_like(reference), reference.new_empty((4,), dtype=torch.float64)))
+
+
+# =====================================================================================================================
 # slice bias fields of the classical reconstruction (csrc/slice_bias.hip): one round of the smoothed log-ratio of scale_k y to
 # sim - b_new on every pixel and the five per-slice sums - in two passes; the definition, the centring of a field and the rule
 # for slices of little weight are nesvor_amd/slice_bias.py
