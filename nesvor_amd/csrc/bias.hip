@@ -33,8 +33,6 @@
 namespace {
 
 constexpr int kMaxC = 16;        // control points per axis
-constexpr int kMaxBins = 1024;   // histogram bins (8 KB of LDS as 64-bit counters or as the lookup table)
-constexpr int kHistWgs = 256;    // at most this many workgroups (and partial histograms) per histogram call
 constexpr int kStats = 5;        // {count, sum g, sum g^2, min u, max u}
 constexpr double kFixedOne = 4294967296.0;  // 2^32: one voxel in the histogram's fixed-point weights
 
@@ -44,17 +42,6 @@ __device__ __forceinline__ double bin_coord(double u, double lo, double slope, i
 }
 
 __device__ __forceinline__ int clamp_span(int s, int S) { return min(max(s, 0), S - 1); }
-
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // histogram.  grid: G <= kHistWgs workgroups striding over the voxels; partial: (G, n_bins) 64-bit fixed-point bins
@@ -279,12 +266,6 @@ __global__ __launch_bounds__(256) void n4_update_reduce_kernel(const double* __r
     stats[j] = t;
   }
 }
-
-// the checks the three entry points share: 0 = fine
-bool bad_volume(int D, int H, int W) {
-  return D < 1 || H < 1 || W < 1 || (int64_t)D * H * W > (int64_t)INT_MAX - 256;
-}
-int hist_wgs(int64_t N) { return (int)((N + 255) / 256 < kHistWgs ? (N + 255) / 256 : kHistWgs); }
 
 }  // namespace
 

@@ -1,6 +1,7 @@
-// Shared device helpers for the gfx950 kernels.
+// Shared device helpers for the gfx950 kernels, and a few host checks at the end.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #define NESVOR_WAVE 64
@@ -54,13 +55,25 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), lane);
   return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
 }
-__device__ __forceinline__ double wave_sum_f64(float x) {
-  double v = (double)x;
+__device__ __forceinline__ double wave_sum_f64(double v) {
   v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
   v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
   v += dpp_f64<0x141>(v);  // row_half_mirror
   v += dpp_f64<0x140>(v);  // row_mirror
   return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+__device__ __forceinline__ double wave_sum_f64(float x) { return wave_sum_f64((double)x); }
+
+// Full-wave min / max of doubles; every lane gets the result (fmin / fmax: a NaN never enters).
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  return v;
 }
 
 // Sum over the 16 lanes of a DPP row (VALU only); every lane of the row gets the row total.
@@ -191,3 +204,12 @@ __device__ __forceinline__ void lds_add_f32_cas(float* addr, float v) {
     old = atomicCAS(a, assumed, __float_as_uint(__uint_as_float(assumed) + v));
   } while (old != assumed);
 }
+
+// Host checks the volume and histogram launchers share (bias.hip, masking.hip, evaluate.hip).
+// A (d, h, w) volume whose voxel indices are ints, a workgroup indexing up to 255 past the last.
+inline bool bad_volume(int d, int h, int w) {
+  return d < 1 || h < 1 || w < 1 || (int64_t)d * h * w > (int64_t)INT_MAX - 256;
+}
+constexpr int kMaxBins = 1024;   // histogram bins (8 KB of LDS as 64-bit counters or as a lookup table)
+constexpr int kHistWgs = 256;    // at most this many workgroups (and partial histograms) per histogram call
+inline int hist_wgs(int64_t N) { return (int)((N + 255) / 256 < kHistWgs ? (N + 255) / 256 : kHistWgs); }

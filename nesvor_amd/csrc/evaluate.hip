@@ -10,9 +10,9 @@
 //     v = maskR and inside and mX >= 0.5;  J0 = 0 off v.  stats = { n, n_ref = #maskR, sum I, sum J, sum I^2, sum J^2, sum I J,
 //     max I } over v (I = I0, J = J0; max I = -inf without a valid voxel).
 //   nesvor_volume_ssim.  params = {a, b, c1, c2} in device memory.  J' = a J0 + b on v (a multiply, then an add) and 0 elsewhere,
-//     I = I0 on v and 0 elsewhere, e = I - J'.  S is the separable 11-tap Gaussian window of structural.hip with zero padding,
+//     I = I0 on v and 0 elsewhere, e = I - J'.  S is the separable 11-tap Gaussian window of window.h with zero padding,
 //     along x, then y, then z, taps added in ascending order from 0; Wt = S(v), the moments and the SSIM formula are
-//     structural.hip's.  ssim = 0 off v.  stats = { n, sum ssim, sum e^2, sum |e| } over v.
+//     structural.hip's (window::ssim_value).  ssim = 0 off v.  stats = { n, sum ssim, sum e^2, sum |e| } over v.
 //
 // Composed from torch operators the two are the gathers of sixteen corners with a dozen volume-sized temporaries and 3 x 11
 // shifted adds over six moment volumes: a few hundred launches.  Here each is one pass and a small reduce launch.
@@ -23,9 +23,8 @@
 //
 // The SSIM pass: a 256-thread workgroup owns a 16 x 16 in-plane tile and kZChunk consecutive planes.  It marches along z from
 // 5 planes before its first output plane to 5 after its last (10 planes of warm-up per chunk: the price of filling the machine
-// at small in-plane sizes); planes outside the volume are the window's zero padding.  Per plane the x and y passes are
-// structural.hip's, with its LDS layout (halo 3 x 26 x 48 floats, row-filtered moments 6 x 26 x 16 floats, conflict-free for
-// the reasons given there; 25 KB, two barriers per plane).  A thread keeps the six in-plane moments of its pixel for the last
+// at small in-plane sizes); planes outside the volume are the window's zero padding.  Per plane the halo, the x and y passes and their
+// LDS layout are window.h's (25 KB, two barriers per plane; the x pass is a copy, for the reason given at it).  A thread keeps the six in-plane moments of its pixel for the last
 // 11 planes in registers: the z step of the plane loop is specialised by the plane's index mod 11 (ring_step), so that every
 // ring index is a constant and plane p lives in slot (p - first plane) mod 11.  After plane p is in, output plane p - 5 is the
 // 11 slots in tap order.  The centre values of an output plane are read again from global memory (they left the halo five
@@ -45,27 +44,21 @@
 #include <limits.h>
 #include <math.h>
 #include "slice_sums.h"
+#include "window.h"
 #include "../../include/nesvor_hip.h"
 
 namespace {
 
+using window::kRadius;
+using window::kTaps;
+using window::kTile;
+using window::Taps;
+
 constexpr int kResampleStats = 8, kSsimStats = 4;
-constexpr int kTile = 16;                      // the tile's edge: 256 threads
-constexpr int kRadius = 5, kTaps = 2 * kRadius + 1;
-constexpr int kHalo = kTile + 2 * kRadius;     // 26
-constexpr int kHaloPitch = 48;                 // = 16 mod 32, >= kHalo (structural.hip)
-constexpr int kRows = kHalo * kTile;           // 416 row-filtered values per moment
 constexpr int kZChunk = 32;                    // output planes per workgroup (EVALUATE_Z_CHUNK of nesvor_amd/ops.py)
 constexpr double kEps = 1.0 / 1048576.0;       // 2^-20 voxels
 
-struct Taps { float g[kTaps]; };
 struct Map { double m[12]; };
-
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // One axis: the inside test on u, then the clamped taps.  i0, i1 in [0, n - 1] whatever u is.
 __device__ __forceinline__ bool axis_taps(double u, int n, int& i0, int& i1, float& f) {
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(256) void volume_resample_kernel(const float* __res
   const double s0 = (double)wave_sum_dpp(on ? 1.f : 0.f), s1 = (double)wave_sum_dpp(in_ref ? 1.f : 0.f);
   const double s2 = wave_sum_f64(iv), s3 = wave_sum_f64(jv), s4 = wave_sum_f64(iv * iv), s5 = wave_sum_f64(jv * jv),
                s6 = wave_sum_f64(iv * jv);
-  const double s7 = (double)wave_max_f32(on ? iv : -INFINITY);  // (fmaxf: a NaN intensity does not enter)
+  const double s7 = (double)wave_max(on ? iv : -INFINITY);  // (fmaxf: a NaN intensity does not enter)
   if (lane == 0) {
     red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; red[wave][3] = s3;
     red[wave][4] = s4; red[wave][5] = s5; red[wave][6] = s6; red[wave][7] = s7;
@@ -191,8 +184,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
                                                           const uint8_t* __restrict__ valid, const float* __restrict__ params,
                                                           int d, int h, int w, int tiles_x, int tiles, Taps taps,
                                                           float* __restrict__ ssim, double* __restrict__ partial) {
-  __shared__ float halo[3][kHalo * kHaloPitch];
-  __shared__ float mom[6][kRows];
+  __shared__ window::Lds lds;
   __shared__ double red[4][kSsimStats];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int chunk = blockIdx.x / tiles, tile = blockIdx.x - chunk * tiles;
@@ -217,34 +209,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
   for (int p = p_begin; p < p_end; ++p, s = s + 1 == kTaps ? 0 : s + 1) {
     float m[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (p >= 0 && p < d) {
-      // the halo: I, J', v; 0 off v and outside the plane (the window's zero padding)
-      const int c = tid & 31;
-      if (c < kHalo) {
-        const int hx = x0 + c - kRadius;
-        for (int r = tid >> 5; r < kHalo; r += 8) {
-          const int hy = y0 + r - kRadius;
-          float iv = 0.f, jv = 0.f, vv = 0.f;
-          if (hy >= 0 && hy < h && hx >= 0 && hx < w) {
-            const size_t idx = (size_t)p * plane + (size_t)hy * w + hx;
-            if (valid[idx]) {
-              iv = ref[idx];
-              jv = a * res[idx] + b;
-              vv = 1.f;
-            }
-          }
-          halo[0][r * kHaloPitch + c] = iv;
-          halo[1][r * kHaloPitch + c] = jv;
-          halo[2][r * kHaloPitch + c] = vv;
-        }
-      }
+      // the halo: I = ref, J' = a res + b on v, of plane p
+      window::stage_halo(lds, y0, x0, h, w, [&](int hy, int hx, float& iv, float& jv) {
+        const size_t idx = (size_t)p * plane + (size_t)hy * w + hx;
+        if (!valid[idx]) return false;
+        iv = ref[idx];
+        jv = a * res[idx] + b;
+        return true;
+      });
       __syncthreads();
-      // along x: the six moments of the 26 rows on the tile's 16 columns
-      for (int i = tid; i < kRows; i += 256) {
-        const int o = (i >> 4) * kHaloPitch + (i & 15);
+      // window::row_pass written out: called here (the same values, the same floating-point instructions) the kernel measured
+      // 2 to 7 % slower at 128^3 and 256^3 in five of five alternating runs; the other three calls cost nothing measurable.
+      for (int i = tid; i < window::kRows; i += 256) {
+        const int o = (i >> 4) * window::kHaloPitch + (i & 15);
         float av = 0.f, ai = 0.f, aj = 0.f, aii = 0.f, ajj = 0.f, aij = 0.f;
 #pragma unroll
         for (int t = 0; t < kTaps; ++t) {
-          const float g = taps.g[t], iv = halo[0][o + t], jv = halo[1][o + t], vv = halo[2][o + t];
+          const float g = taps.g[t], iv = lds.halo[0][o + t], jv = lds.halo[1][o + t], vv = lds.halo[2][o + t];
           av = av + g * vv;
           ai = ai + g * iv;
           aj = aj + g * jv;
@@ -252,17 +233,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
           ajj = ajj + g * (jv * jv);
           aij = aij + g * (iv * jv);
         }
-        mom[0][i] = av; mom[1][i] = ai; mom[2][i] = aj; mom[3][i] = aii; mom[4][i] = ajj; mom[5][i] = aij;
+        lds.mom[0][i] = av; lds.mom[1][i] = ai; lds.mom[2][i] = aj; lds.mom[3][i] = aii; lds.mom[4][i] = ajj; lds.mom[5][i] = aij;
       }
       __syncthreads();  // (the next plane's halo is written behind this barrier, its row pass writes mom behind its own first)
-      // along y
-#pragma unroll
-      for (int t = 0; t < kTaps; ++t) {
-        const float g = taps.g[t];
-        const int o = (ty + t) * kTile + tx;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) m[k] = m[k] + g * mom[k][o];
-      }
+      window::column_pass(lds, taps, ty, tx, m);
     }
 
     // along z: plane p goes to slot s; output plane q = p - 5 is planes p - 10 .. p in tap order
@@ -286,13 +260,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
       const size_t idx = (size_t)q * plane + (size_t)gy * w + gx;
       float value = 0.f;
       if (valid[idx]) {
-        const float wv = wsum[0], wi = wsum[1], wj = wsum[2], wii = wsum[3], wjj = wsum[4], wij = wsum[5];
         const float iv = ref[idx], jv = a * res[idx] + b;
-        const float mu_i = wi / wv, mu_j = wj / wv;
-        const float var_i = wii / wv - mu_i * mu_i, var_j = wjj / wv - mu_j * mu_j, cov = wij / wv - mu_i * mu_j;
-        const float num = (2.f * mu_i * mu_j + c1) * (2.f * cov + c2);
-        const float den = (mu_i * mu_i + mu_j * mu_j + c1) * (var_i + var_j + c2);
-        value = num / den;
+        value = window::ssim_value(wsum, c1, c2);
         const float e = iv - jv;
         sum_n += 1.0;
         sum_ssim += (double)value;
@@ -303,17 +272,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
     }
   }
 
-  // the thread sums are doubles already: the wave tree of wave_sum_f64 on them
-  double s4[kSsimStats] = {sum_n, sum_ssim, sum_e2, sum_abs};
-#pragma unroll
-  for (int j = 0; j < kSsimStats; ++j) {
-    double v = s4[j];
-    v += dpp_f64<0xB1>(v);
-    v += dpp_f64<0x4E>(v);
-    v += dpp_f64<0x141>(v);
-    v += dpp_f64<0x140>(v);
-    s4[j] = (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-  }
+  // (the thread sums are doubles already)
+  const double s4[kSsimStats] = {wave_sum_f64(sum_n), wave_sum_f64(sum_ssim), wave_sum_f64(sum_e2), wave_sum_f64(sum_abs)};
   if (lane == 0) {
 #pragma unroll
     for (int j = 0; j < kSsimStats; ++j) red[wave][j] = s4[j];
@@ -322,19 +282,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
   if (tid < kSsimStats) partial[(size_t)blockIdx.x * kSsimStats + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
-bool bad_shape(int d, int h, int w) {
-  return d < 1 || h < 1 || w < 1 || (int64_t)d * h * w > (int64_t)INT_MAX - 256;
-}
-
 int64_t resample_wgs(int d, int h, int w) { return ((int64_t)d * h * w + 255) / 256; }
 
-int64_t ssim_tiles(int h, int w) { return (((int64_t)h + kTile - 1) / kTile) * (((int64_t)w + kTile - 1) / kTile); }
-int64_t ssim_wgs(int d, int h, int w) { return (((int64_t)d + kZChunk - 1) / kZChunk) * ssim_tiles(h, w); }
+int64_t ssim_wgs(int d, int h, int w) { return (((int64_t)d + kZChunk - 1) / kZChunk) * slice_sums::tile_workgroups(h, w); }
 
 }  // namespace
 
 extern "C" int64_t nesvor_volume_resample_workspace_bytes(int d, int h, int w) {
-  if (bad_shape(d, h, w)) return 0;
+  if (bad_volume(d, h, w)) return 0;
   return (int64_t)sizeof(double) * kResampleStats * resample_wgs(d, h, w);
 }
 
@@ -343,7 +298,7 @@ extern "C" int nesvor_volume_resample(const float* reference, const uint8_t* ref
                                       uint8_t* valid, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
   if (reference == nullptr || volume == nullptr || index_map == nullptr || resampled == nullptr || valid == nullptr || stats == nullptr)
     return (int)hipErrorInvalidValue;
-  if (bad_shape(d, h, w) || bad_shape(vd, vh, vw)) return (int)hipErrorInvalidValue;
+  if (bad_volume(d, h, w) || bad_volume(vd, vh, vw)) return (int)hipErrorInvalidValue;
   Map map;
   for (int i = 0; i < 12; ++i) {
     if (!isfinite(index_map[i])) return (int)hipErrorInvalidValue;
@@ -360,7 +315,7 @@ extern "C" int nesvor_volume_resample(const float* reference, const uint8_t* ref
 }
 
 extern "C" int64_t nesvor_volume_ssim_workspace_bytes(int d, int h, int w) {
-  if (bad_shape(d, h, w) || ssim_wgs(d, h, w) > INT_MAX) return 0;
+  if (bad_volume(d, h, w) || ssim_wgs(d, h, w) > INT_MAX) return 0;
   return (int64_t)sizeof(double) * kSsimStats * ssim_wgs(d, h, w);
 }
 
@@ -368,21 +323,15 @@ extern "C" int nesvor_volume_ssim(const float* reference, const float* resampled
                                   int h, int w, float* ssim, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
   if (reference == nullptr || resampled == nullptr || valid == nullptr || params == nullptr || ssim == nullptr || stats == nullptr)
     return (int)hipErrorInvalidValue;
-  if (bad_shape(d, h, w)) return (int)hipErrorInvalidValue;
+  if (bad_volume(d, h, w)) return (int)hipErrorInvalidValue;
   const int64_t wgs = ssim_wgs(d, h, w);
   if (wgs > INT_MAX) return (int)hipErrorInvalidValue;
   if (workspace == nullptr || (int64_t)workspace_bytes < nesvor_volume_ssim_workspace_bytes(d, h, w)) return (int)hipErrorInvalidValue;
-  // g[t] = exp(-(t - 5)^2 / (2 1.5^2)) normalised to sum 1, in double, rounded to fp32 once (structural.hip)
   Taps taps;
-  double g[kTaps], sum = 0.0;
-  for (int t = 0; t < kTaps; ++t) {
-    g[t] = exp(-(double)((t - kRadius) * (t - kRadius)) / (2.0 * 1.5 * 1.5));
-    sum += g[t];
-  }
-  for (int t = 0; t < kTaps; ++t) taps.g[t] = (float)(g[t] / sum);
+  window::gaussian_taps(1.5, kRadius, taps.g);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(volume_ssim_kernel, dim3((unsigned)wgs), dim3(256), 0, st, reference, resampled, valid, params, d, h, w,
-                     (int)((w + kTile - 1) / kTile), (int)ssim_tiles(h, w), taps, ssim, (double*)workspace);
+                     (int)((w + kTile - 1) / kTile), (int)slice_sums::tile_workgroups(h, w), taps, ssim, (double*)workspace);
   hipLaunchKernelGGL(volume_reduce_kernel<kSsimStats>, dim3(1), dim3(256), 0, st, (const double*)workspace, (int)wgs, kSsimStats, stats);
   return (int)hipGetLastError();
 }

@@ -29,19 +29,6 @@ namespace {
 
 constexpr int kStats = 3;        // {count, min, max}
 constexpr int kChunk = 64;       // world-to-slice matrices per LDS chunk (6 KB)
-constexpr int kMaxBins = 1024;   // histogram bins
-constexpr int kHistWgs = 256;    // at most this many workgroups (and partial histograms) per histogram call
-
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // One axis of the trilinear lookup: u the continuous voxel index; i0 = floor u and the weight of i0 + 1.  false: both
 // neighbours are off the axis (also for a NaN), the value is 0.
@@ -266,7 +253,6 @@ __global__ __launch_bounds__(256) void otsu_threshold_kernel(const int64_t* __re
 bool bad_stack(int n, int h, int w) {
   return n < 1 || h < 1 || w < 1 || (int64_t)h * w > (int64_t)INT_MAX - 256 || (int64_t)n * h * w > (int64_t)INT_MAX - 256;
 }
-int hist_wgs(int64_t N) { return (int)((N + 255) / 256 < kHistWgs ? (N + 255) / 256 : kHistWgs); }
 
 }  // namespace
 

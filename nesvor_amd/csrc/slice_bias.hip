@@ -37,6 +37,7 @@
 #include <float.h>
 #include <math.h>
 #include "slice_sums.h"
+#include "window.h"  // (gaussian_taps alone)
 #include "../../include/nesvor_hip.h"
 
 namespace {
@@ -169,8 +170,6 @@ __global__ __launch_bounds__(256) void slice_bias_columns_kernel(const float* __
   if (tid < kStats) partial[((size_t)in * tiles + tile) * kStats + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
-int64_t tiles_of(int h, int w) { return (((int64_t)h + kTile - 1) / kTile) * (((int64_t)w + kTile - 1) / kTile); }
-
 // the two intermediates follow the partial sums (a multiple of 8 bytes) in the workspace
 int64_t intermediate_bytes(int n, int h, int w) { return 2 * (int64_t)sizeof(float) * n * h * w; }
 
@@ -178,7 +177,7 @@ int64_t intermediate_bytes(int n, int h, int w) { return 2 * (int64_t)sizeof(flo
 
 extern "C" int64_t nesvor_slice_bias_update_workspace_bytes(int n, int h, int w) {
   if (n < 1 || h < 1 || w < 1 || (int64_t)h * w > INT_MAX - 256) return 0;
-  return slice_sums::Plan<kStats>{n, tiles_of(h, w)}.workspace_bytes() + intermediate_bytes(n, h, w);
+  return slice_sums::Plan<kStats>{n, slice_sums::tile_workgroups(h, w)}.workspace_bytes() + intermediate_bytes(n, h, w);
 }
 
 extern "C" int nesvor_slice_bias_update(const float* sim, const float* y, const uint8_t* mask, const float* scale, const float* weight,
@@ -189,7 +188,7 @@ extern "C" int nesvor_slice_bias_update(const float* sim, const float* y, const 
   if (sim == nullptr || y == nullptr || scale == nullptr || b == nullptr || b_new == nullptr || stats == nullptr || b_new == b)
     return (int)hipErrorInvalidValue;
   if (radius < 1 || radius > kMaxRadius || !(sigma_px > 0.0 && sigma_px <= DBL_MAX)) return (int)hipErrorInvalidValue;
-  const slice_sums::Plan<kStats> plan{n, tiles_of(h, w)};  // the column pass: a workgroup per tile
+  const slice_sums::Plan<kStats> plan{n, slice_sums::tile_workgroups(h, w)};  // the column pass: a workgroup per tile
   if (!plan.accepts(h, w, plan.wgs * n, workspace, workspace_bytes)) return (int)hipErrorInvalidValue;
   if ((int64_t)workspace_bytes < plan.workspace_bytes() + intermediate_bytes(n, h, w)) return (int)hipErrorInvalidValue;
   int seg_log2 = 4;
@@ -199,14 +198,8 @@ extern "C" int nesvor_slice_bias_update(const float* sim, const float* y, const 
   if (segs * row_groups * n > INT_MAX) return (int)hipErrorInvalidValue;
   // rows of one 32-lane half (seg = 16) start 16 banks apart; otherwise the pitch is the span
   const int pitch = seg == 16 ? ((2 * radius + 31) / 32) * 32 + 16 : seg + 2 * radius;
-  // g[t] = exp(-(t - R)^2 / (2 sigma_px^2)) normalised to sum 1, in double, rounded to fp32 once
   Taps taps;
-  double g[kMaxTaps], sum = 0.0;
-  for (int t = 0; t <= 2 * radius; ++t) {
-    g[t] = exp(-(double)((t - radius) * (t - radius)) / (2.0 * sigma_px * sigma_px));
-    sum += g[t];
-  }
-  for (int t = 0; t < kMaxTaps; ++t) taps.g[t] = t <= 2 * radius ? (float)(g[t] / sum) : 0.f;
+  window::gaussian_taps(sigma_px, radius, taps.g);
   float* row_num = (float*)((char*)workspace + plan.workspace_bytes());
   float* row_den = row_num + (size_t)n * h * w;
   hipStream_t st = (hipStream_t)stream;

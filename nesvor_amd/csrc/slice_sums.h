@@ -52,6 +52,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const double* __restrict__ 
 }
 
 inline int64_t pixel_workgroups(int h, int w) { return ((int64_t)h * w + 255) / 256; }  // one per 256 pixels of a slice
+inline int64_t tile_workgroups(int h, int w) { return (((int64_t)h + 15) / 16) * (((int64_t)w + 15) / 16); }  // one per 16 x 16 tile
 
 // The host side of one call: `entries` rows of N sums, each over `wgs` workgroups.
 template <int N>

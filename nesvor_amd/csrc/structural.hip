@@ -13,15 +13,8 @@
 // Composed from torch operators one round is about 40 launches (six separable filters, twenty elementwise, eight reductions);
 // here it is one pass that reads sim, y and the mask (9 bytes per pixel) and writes the map (4 bytes), and a small reduce launch.
 //
-// Layout.  A 256-thread workgroup owns a 16 x 16 tile of one slice: thread t is pixel (t / 16, t % 16), so a 32-lane half of a
-// wave - the group whose ds_read_b32 / ds_write_b32 addresses share 32 banks - is two tile rows.
-//   halo  3 x 26 x 48 floats  I, J, v on the tile and 5 pixels around it.  Staged as 8 rows x 32 columns per sweep (26 live):
-//         a half-wave writes one row, consecutive banks.  The horizontal pass's half-wave reads columns c + t, c = 0 .. 15, of
-//         rows r and r + 1: with the row pitch = 16 mod 32 the two runs of 16 never share a bank (the pitch 26 would put them
-//         26 banks apart: 6 two-way conflicts on every read).  48 is the smallest such pitch >= 26.
-//   mom   6 x 26 x 16 floats  S_h(v, I, J, I I, J J, I J).  Pitch 16: rows r and r + 1 are 32 consecutive floats, so the horizontal
-//         pass's writes and the vertical pass's reads (rows ty + t, ty + 1 + t) are conflict-free.
-// 14976 + 9984 + 256 bytes of LDS: six workgroups per CU before LDS limits occupancy.  Two barriers.
+// Layout.  A 256-thread workgroup owns a 16 x 16 tile of one slice; the window's passes and their LDS layout are window.h's
+// (24960 bytes, and 256 for the sums).
 //
 // The per-pixel arithmetic is that of the torch expression in fp32, operation for operation (the build has -ffp-contract=off; the
 // divisions are correctly rounded); the taps are the host's doubles rounded to fp32, as gaussian_taps(torch.float32) gives them.
@@ -34,26 +27,24 @@
 #include <float.h>
 #include <math.h>
 #include "slice_sums.h"
+#include "window.h"
 #include "../../include/nesvor_hip.h"
 
 namespace {
 
-constexpr int kStats = 8;
-constexpr int kTile = 16;                      // the tile's edge: 256 threads
-constexpr int kRadius = 5, kTaps = 2 * kRadius + 1;
-constexpr int kHalo = kTile + 2 * kRadius;     // 26
-constexpr int kHaloPitch = 48;                 // = 16 mod 32, >= kHalo
-constexpr int kRows = kHalo * kTile;           // 416 horizontally filtered values per moment
+using window::kHaloPitch;
+using window::kRadius;
+using window::kTile;
 
-struct Taps { float g[kTaps]; };
+constexpr int kStats = 8;
 
 // grid: n * tiles workgroups, tiles = tiles_y * tiles_x per slice.  partial: (n, tiles, 8) doubles.
 __global__ __launch_bounds__(256) void structural_ssim_kernel(const float* __restrict__ sim, const float* __restrict__ y,
                                                               const uint8_t* __restrict__ mask, const float* __restrict__ scale,
-                                                              int h, int w, int tiles_x, int tiles, Taps taps, float c1, float c2,
-                                                              float threshold, float* __restrict__ ssim, double* __restrict__ partial) {
-  __shared__ float halo[3][kHalo * kHaloPitch];
-  __shared__ float mom[6][kRows];
+                                                              int h, int w, int tiles_x, int tiles, window::Taps taps, float c1,
+                                                              float c2, float threshold, float* __restrict__ ssim,
+                                                              double* __restrict__ partial) {
+  __shared__ window::Lds lds;
   __shared__ double red[4][kStats];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int in = blockIdx.x / tiles, tile = blockIdx.x - in * tiles;
@@ -62,74 +53,28 @@ __global__ __launch_bounds__(256) void structural_ssim_kernel(const float* __res
   const size_t base = (size_t)in * h * w;  // the host checked h w <= INT_MAX - 256
   const float s = scale[in];               // workgroup-uniform: the scalar path
 
-  // the halo: I, J, v; 0 off the mask and outside the image (the window's zero padding)
-  {
-    const int c = tid & 31;
-    if (c < kHalo) {
-      const int gx = x0 + c - kRadius;
-      for (int r = tid >> 5; r < kHalo; r += 8) {
-        const int gy = y0 + r - kRadius;
-        float iv = 0.f, jv = 0.f, vv = 0.f;
-        if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
-          const size_t idx = base + (size_t)gy * w + gx;
-          if (mask == nullptr || mask[idx]) {
-            iv = s * y[idx];
-            jv = sim[idx];
-            vv = 1.f;
-          }
-        }
-        halo[0][r * kHaloPitch + c] = iv;
-        halo[1][r * kHaloPitch + c] = jv;
-        halo[2][r * kHaloPitch + c] = vv;
-      }
-    }
-  }
+  // the halo: I = scale_k y, J = sim on the mask
+  window::stage_halo(lds, y0, x0, h, w, [&](int gy, int gx, float& iv, float& jv) {
+    const size_t idx = base + (size_t)gy * w + gx;
+    if (mask != nullptr && !mask[idx]) return false;
+    iv = s * y[idx];
+    jv = sim[idx];
+    return true;
+  });
   __syncthreads();
-
-  // along x: the six moments of the 26 rows on the tile's 16 columns
-  for (int i = tid; i < kRows; i += 256) {
-    const int o = (i >> 4) * kHaloPitch + (i & 15);
-    float av = 0.f, ai = 0.f, aj = 0.f, aii = 0.f, ajj = 0.f, aij = 0.f;
-#pragma unroll
-    for (int t = 0; t < kTaps; ++t) {
-      const float g = taps.g[t], iv = halo[0][o + t], jv = halo[1][o + t], vv = halo[2][o + t];
-      av = av + g * vv;
-      ai = ai + g * iv;
-      aj = aj + g * jv;
-      aii = aii + g * (iv * iv);
-      ajj = ajj + g * (jv * jv);
-      aij = aij + g * (iv * jv);
-    }
-    mom[0][i] = av; mom[1][i] = ai; mom[2][i] = aj; mom[3][i] = aii; mom[4][i] = ajj; mom[5][i] = aij;
-  }
+  window::row_pass(lds, taps);
   __syncthreads();
 
   // along y, and the SSIM arithmetic of this thread's pixel
   const int ty = tid >> 4, tx = tid & 15;
   const int gy = y0 + ty, gx = x0 + tx;
   const bool inside = gy < h && gx < w;
-  const float iv = halo[0][(ty + kRadius) * kHaloPitch + tx + kRadius], jv = halo[1][(ty + kRadius) * kHaloPitch + tx + kRadius];
-  const bool on = halo[2][(ty + kRadius) * kHaloPitch + tx + kRadius] != 0.f;  // (false outside the image)
-  float sv = 0.f, si = 0.f, sj = 0.f, sii = 0.f, sjj = 0.f, sij = 0.f;
-#pragma unroll
-  for (int t = 0; t < kTaps; ++t) {
-    const float g = taps.g[t];
-    const int o = (ty + t) * kTile + tx;
-    sv = sv + g * mom[0][o];
-    si = si + g * mom[1][o];
-    sj = sj + g * mom[2][o];
-    sii = sii + g * mom[3][o];
-    sjj = sjj + g * mom[4][o];
-    sij = sij + g * mom[5][o];
-  }
-  float value = 0.f;
-  if (on) {
-    const float mu_i = si / sv, mu_j = sj / sv;
-    const float var_i = sii / sv - mu_i * mu_i, var_j = sjj / sv - mu_j * mu_j, cov = sij / sv - mu_i * mu_j;
-    const float num = (2.f * mu_i * mu_j + c1) * (2.f * cov + c2);
-    const float den = (mu_i * mu_i + mu_j * mu_j + c1) * (var_i + var_j + c2);
-    value = num / den;
-  }
+  const int centre = (ty + kRadius) * kHaloPitch + tx + kRadius;
+  const float iv = lds.halo[0][centre], jv = lds.halo[1][centre];
+  const bool on = lds.halo[2][centre] != 0.f;  // (false outside the image)
+  float m[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  window::column_pass(lds, taps, ty, tx, m);
+  const float value = on ? window::ssim_value(m, c1, c2) : 0.f;
   if (inside) ssim[base + (size_t)gy * w + gx] = value;
 
   // (the products are the expression's fp32 ones; off the mask iv = jv = value = 0)
@@ -137,7 +82,7 @@ __global__ __launch_bounds__(256) void structural_ssim_kernel(const float* __res
   const double s1 = wave_sum_f64(value), s3 = wave_sum_f64(iv), s4 = wave_sum_f64(jv), s5 = wave_sum_f64(iv * iv),
                s6 = wave_sum_f64(jv * jv), s7 = wave_sum_f64(iv * jv);
   // Step 2 of slice_sums.h, written out: through slice_sums::store_workgroup_sums (or any other spelling tried) the compiler's
-  // SLP vectoriser repacks the tap loops above into v_pk_add_f32 / v_pk_mul_f32 - the same values, but the kernel then measured
+  // SLP vectoriser repacks the window's tap loops into v_pk_add_f32 / v_pk_mul_f32 - the same values, but the kernel then measured
   // 1 to 4 % slower on 128 x 128 slices in five of five alternating runs.
   if (lane == 0) {
     red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; red[wave][3] = s3;
@@ -147,15 +92,13 @@ __global__ __launch_bounds__(256) void structural_ssim_kernel(const float* __res
   if (tid < kStats) partial[((size_t)in * tiles + tile) * kStats + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
-int64_t tiles_of(int h, int w) { return (((int64_t)h + kTile - 1) / kTile) * (((int64_t)w + kTile - 1) / kTile); }
-
 bool usable(float v) { return v >= 0.f && v <= FLT_MAX; }  // false for a negative, an infinity and a NaN
 
 }  // namespace
 
 extern "C" int64_t nesvor_structural_ssim_workspace_bytes(int n, int h, int w) {
   if (n < 1 || h < 1 || w < 1) return 0;
-  return slice_sums::Plan<kStats>{n, tiles_of(h, w)}.workspace_bytes();
+  return slice_sums::Plan<kStats>{n, slice_sums::tile_workgroups(h, w)}.workspace_bytes();
 }
 
 extern "C" int nesvor_structural_ssim(const float* sim, const float* y, const uint8_t* mask, const float* scale, int n, int h, int w,
@@ -165,16 +108,10 @@ extern "C" int nesvor_structural_ssim(const float* sim, const float* y, const ui
   if (n < 0 || h < 1 || w < 1) return (int)hipErrorInvalidValue;
   if (sim == nullptr || y == nullptr || scale == nullptr || ssim == nullptr || stats == nullptr) return (int)hipErrorInvalidValue;
   if (!usable(c1) || !usable(c2) || !usable(threshold)) return (int)hipErrorInvalidValue;
-  const slice_sums::Plan<kStats> plan{n, tiles_of(h, w)};  // a workgroup per tile
+  const slice_sums::Plan<kStats> plan{n, slice_sums::tile_workgroups(h, w)};  // a workgroup per tile
   if (!plan.accepts(h, w, plan.wgs * n, workspace, workspace_bytes)) return (int)hipErrorInvalidValue;
-  // g[t] = exp(-(t - 5)^2 / (2 1.5^2)) normalised to sum 1, in double, rounded to fp32 once
-  Taps taps;
-  double g[kTaps], sum = 0.0;
-  for (int t = 0; t < kTaps; ++t) {
-    g[t] = exp(-(double)((t - kRadius) * (t - kRadius)) / (2.0 * 1.5 * 1.5));
-    sum += g[t];
-  }
-  for (int t = 0; t < kTaps; ++t) taps.g[t] = (float)(g[t] / sum);
+  window::Taps taps;
+  window::gaussian_taps(1.5, kRadius, taps.g);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(structural_ssim_kernel, dim3((unsigned)(plan.wgs * n)), dim3(256), 0, st, sim, y, mask, scale, h, w,
                      (int)((w + kTile - 1) / kTile), (int)plan.wgs, taps, c1, c2, threshold, ssim, (double*)workspace);

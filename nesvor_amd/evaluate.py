@@ -51,9 +51,9 @@ import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
-import torch.nn.functional as F
 
-from .structural import MIN_VAR_PRODUCT, RADIUS, gaussian_taps
+from . import window as _w
+from .structural import MIN_VAR_PRODUCT, gaussian_taps
 
 EPS = 2.0 ** -20  # voxels: the slack of the inside test
 FITS = ("none", "scale", "affine")
@@ -146,21 +146,7 @@ def resample_composed(reference: torch.Tensor, reference_mask: Optional[torch.Te
 
 
 def _window3(a: torch.Tensor, taps) -> torch.Tensor:
-    """S(a) over a (D,H,W) array: explicit shifted slices in tap order along x, then y, then z (``structural._window`` plus z)."""
-    d, h, w = a.shape
-    padded = F.pad(a, (RADIUS, RADIUS))
-    acc = torch.zeros_like(a)
-    for t, g in enumerate(taps):
-        acc = acc + g * padded[:, :, t:t + w]
-    padded = F.pad(acc, (0, 0, RADIUS, RADIUS))
-    acc = torch.zeros_like(a)
-    for t, g in enumerate(taps):
-        acc = acc + g * padded[:, t:t + h, :]
-    padded = F.pad(acc, (0, 0, 0, 0, RADIUS, RADIUS))
-    out = torch.zeros_like(a)
-    for t, g in enumerate(taps):
-        out = out + g * padded[t:t + d]
-    return out
+    return _w.window(a, taps, 3)
 
 
 def ssim3d_composed(reference: torch.Tensor, resampled: torch.Tensor, valid: torch.Tensor,
@@ -170,17 +156,10 @@ def ssim3d_composed(reference: torch.Tensor, resampled: torch.Tensor, valid: tor
     v = valid != 0
     a, b, c1, c2 = params.to(reference.dtype).unbind(0)
     taps = gaussian_taps(reference.dtype).tolist()  # host numbers: exactly the dtype's values
-    zero, one = torch.zeros_like(reference), torch.ones_like(reference)
+    zero = torch.zeros_like(reference)
     i = torch.where(v, reference, zero)
     j = torch.where(v, a * resampled + b, zero)
-    wt = torch.where(v, _window3(v.to(reference.dtype), taps), one)
-    mu_i, mu_j = _window3(i, taps) / wt, _window3(j, taps) / wt
-    var_i = _window3(i * i, taps) / wt - mu_i * mu_i
-    var_j = _window3(j * j, taps) / wt - mu_j * mu_j
-    cov = _window3(i * j, taps) / wt - mu_i * mu_j
-    num = (2 * mu_i * mu_j + c1) * (2 * cov + c2)
-    den = (mu_i * mu_i + mu_j * mu_j + c1) * (var_i + var_j + c2)
-    ssim = torch.where(v, num / den, zero)
+    ssim = _w.ssim_map(i, j, v, taps, c1, c2, 3)
     e = i - j
     stats = torch.stack([t.double().sum() for t in (v, ssim, e * e, e.abs())])
     return ssim, stats

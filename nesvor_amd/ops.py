@@ -61,6 +61,22 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
 
 
+def _launch(name: str, device, sizes, *args) -> None:
+    """``nesvor_<name>(*args, workspace, nbytes, stream)`` on ``device`` with the scratch ``nesvor_<name>_workspace_bytes(*sizes)``
+    asks for.  A size of 0 (a shape the library refuses) still reaches the library: the refusal is its own."""
+    lib = _lib.load()
+    nbytes = int(getattr(lib, f"nesvor_{name}_workspace_bytes")(*sizes))
+    workspace = _workspace(nbytes, device)
+    with torch.cuda.device(device):
+        err = getattr(lib, f"nesvor_{name}")(*args, _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, name.replace("_", " "))
+
+
+def _n_bins(what: str, n_bins: int) -> None:
+    if not 2 <= n_bins <= 1024:
+        raise RuntimeError(f"{what}: 2 <= n_bins <= 1024 expected, got {n_bins}")
+
+
 def _byte_mask(what: str, mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     """The optional validity mask of the classical-pipeline ops: bool or uint8 (any set byte counts), empty means none."""
     if mask is None or mask.numel() == 0:
@@ -334,14 +350,9 @@ def _svr_similarity(vol, psf, transforms, slices, slices_mask, res_slice):
     if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
         raise RuntimeError("svr_similarity: one volume expected")
     sums = torch.empty((n, K, 6), dtype=torch.float64, device=vol.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_svr_similarity_workspace_bytes(n, K, h, w))
-    workspace = _workspace(nbytes, vol.device)
-    with torch.cuda.device(vol.device):
-        err = lib.nesvor_svr_similarity(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), _lib.ptr(psf), *(int(s) for s in psf.shape),
-                                        _lib.ptr(transforms), _lib.ptr(slices), _lib.ptr(sm), n, K, h, w, float(res_slice),
-                                        _lib.ptr(sums), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "svr similarity")
+    _launch("svr_similarity", vol.device, (n, K, h, w), _lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), _lib.ptr(psf),
+            *(int(s) for s in psf.shape), _lib.ptr(transforms), _lib.ptr(slices), _lib.ptr(sm), n, K, h, w, float(res_slice),
+            _lib.ptr(sums))
     return sums
 
 
@@ -393,13 +404,8 @@ def _robust_estep(sim, y, mask, scale, model):
         raise RuntimeError("robust_estep: scale (n) and model {sigma2, c, m} (3) expected")
     p = torch.empty_like(sim)
     stats = torch.empty((n, 7), dtype=torch.float64, device=sim.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_robust_estep_workspace_bytes(n, h, w))
-    workspace = _workspace(nbytes, sim.device)
-    with torch.cuda.device(sim.device):
-        err = lib.nesvor_robust_estep(_lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), _lib.ptr(model), n, h, w, _lib.ptr(p),
-                                      _lib.ptr(stats), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "robust estep")
+    _launch("robust_estep", sim.device, (n, h, w), _lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), _lib.ptr(model), n, h, w,
+            _lib.ptr(p), _lib.ptr(stats))
     return p, stats
 
 
@@ -418,14 +424,9 @@ def _structural_ssim(sim, y, mask, scale, threshold, dynamic_range):
         raise RuntimeError("structural_ssim: scale (n) expected")
     ssim = torch.empty_like(sim)
     stats = torch.empty((n, 8), dtype=torch.float64, device=sim.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_structural_ssim_workspace_bytes(n, h, w))
-    workspace = _workspace(nbytes, sim.device)
     c1, c2 = (0.01 * dynamic_range) ** 2, (0.03 * dynamic_range) ** 2
-    with torch.cuda.device(sim.device):
-        err = lib.nesvor_structural_ssim(_lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), n, h, w, c1, c2, float(threshold),
-                                         _lib.ptr(ssim), _lib.ptr(stats), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "structural ssim")
+    _launch("structural_ssim", sim.device, (n, h, w), _lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), n, h, w, c1, c2,
+            float(threshold), _lib.ptr(ssim), _lib.ptr(stats))
     return ssim, stats
 
 
@@ -463,15 +464,9 @@ def _volume_resample(reference, reference_mask, volume, volume_mask, index_map):
     resampled = torch.empty_like(reference)
     valid = torch.empty(reference.shape, dtype=torch.bool, device=reference.device)
     stats = torch.empty(8, dtype=torch.float64, device=reference.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_volume_resample_workspace_bytes(d, h, w))
-    workspace = _workspace(nbytes, reference.device)
     M = (ctypes.c_double * 12)(*[float(v) for v in index_map])
-    with torch.cuda.device(reference.device):
-        err = lib.nesvor_volume_resample(_lib.ptr(reference), _lib.ptr(mr), d, h, w, _lib.ptr(volume), _lib.ptr(mx), vd, vh, vw, M,
-                                         _lib.ptr(resampled), _lib.ptr(valid), _lib.ptr(stats), _lib.ptr(workspace), nbytes,
-                                         _lib.stream_ptr())
-    _lib.check(err, "volume resample")
+    _launch("volume_resample", reference.device, (d, h, w), _lib.ptr(reference), _lib.ptr(mr), d, h, w, _lib.ptr(volume), _lib.ptr(mx),
+            vd, vh, vw, M, _lib.ptr(resampled), _lib.ptr(valid), _lib.ptr(stats))
     return resampled, valid, stats
 
 
@@ -485,13 +480,8 @@ def _volume_ssim(reference, resampled, valid, params):
         raise RuntimeError("volume_ssim: params, four floats {a, b, c1, c2}, and resampled on the device of reference expected")
     ssim = torch.empty_like(reference)
     stats = torch.empty(4, dtype=torch.float64, device=reference.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_volume_ssim_workspace_bytes(d, h, w))
-    workspace = _workspace(nbytes, reference.device)
-    with torch.cuda.device(reference.device):
-        err = lib.nesvor_volume_ssim(_lib.ptr(reference), _lib.ptr(resampled), _lib.ptr(m), _lib.ptr(params), d, h, w, _lib.ptr(ssim),
-                                     _lib.ptr(stats), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "volume ssim")
+    _launch("volume_ssim", reference.device, (d, h, w), _lib.ptr(reference), _lib.ptr(resampled), _lib.ptr(m), _lib.ptr(params), d, h, w,
+            _lib.ptr(ssim), _lib.ptr(stats))
     return ssim, stats
 
 
@@ -523,14 +513,8 @@ def _slice_bias_update(sim, y, mask, scale, weight, b, sigma_px, min_intensity):
     radius = window_radius(sigma_px)  # (raises for a sigma_px that is not positive and finite)
     b_new = torch.empty_like(sim)
     stats = torch.empty((n, 5), dtype=torch.float64, device=sim.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_slice_bias_update_workspace_bytes(n, h, w))
-    workspace = _workspace(nbytes, sim.device)
-    with torch.cuda.device(sim.device):
-        err = lib.nesvor_slice_bias_update(_lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), _lib.ptr(weight), _lib.ptr(b), n, h, w,
-                                           float(sigma_px), radius, float(min_intensity), _lib.ptr(b_new), _lib.ptr(stats),
-                                           _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "slice bias update")
+    _launch("slice_bias_update", sim.device, (n, h, w), _lib.ptr(sim), _lib.ptr(y), _lib.ptr(m), _lib.ptr(scale), _lib.ptr(weight),
+            _lib.ptr(b), n, h, w, float(sigma_px), radius, float(min_intensity), _lib.ptr(b_new), _lib.ptr(stats))
     return b_new, stats
 
 
@@ -554,13 +538,7 @@ def _pair_moments(slices, mask, pairs):
     m, n, h, w = _slice_stack("pair_moments", {"slices": slices}, mask, {"pairs": pairs})
     P = int(pairs.shape[0])
     moments = torch.empty((P, 6), dtype=torch.float64, device=slices.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_pair_moments_workspace_bytes(P, h, w))
-    workspace = _workspace(nbytes, slices.device)
-    with torch.cuda.device(slices.device):
-        err = lib.nesvor_pair_moments(_lib.ptr(slices), _lib.ptr(m), n, h, w, _lib.ptr(pairs), P, _lib.ptr(moments),
-                                      _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "pair moments")
+    _launch("pair_moments", slices.device, (P, h, w), _lib.ptr(slices), _lib.ptr(m), n, h, w, _lib.ptr(pairs), P, _lib.ptr(moments))
     return moments
 
 
@@ -601,21 +579,15 @@ def _n4_range(what, v, rng, n_bins):
     _lib.require_device(rng, dtype=torch.float32, name=f"{what} range")
     if rng.numel() != 2 or rng.device != v.device:
         raise RuntimeError(f"{what}: range, two floats {{lo, hi}} on the device of v, expected")
-    if not 2 <= n_bins <= 1024:
-        raise RuntimeError(f"{what}: 2 <= n_bins <= 1024 expected, got {n_bins}")
+    _n_bins(what, n_bins)
 
 
 def _n4_histogram(v, f, mask, rng, n_bins):
     m, D, H, W = _n4_volume("n4_histogram", v, f, mask)
     _n4_range("n4_histogram", v, rng, n_bins)
     hist = torch.empty(n_bins, dtype=torch.float64, device=v.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_n4_histogram_workspace_bytes(D, H, W, n_bins))
-    workspace = _workspace(nbytes, v.device)
-    with torch.cuda.device(v.device):
-        err = lib.nesvor_n4_histogram(_lib.ptr(v), _lib.ptr(f), _lib.ptr(m), D, H, W, _lib.ptr(rng), n_bins, _lib.ptr(hist),
-                                      _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "n4 histogram")
+    _launch("n4_histogram", v.device, (D, H, W, n_bins), _lib.ptr(v), _lib.ptr(f), _lib.ptr(m), D, H, W, _lib.ptr(rng), n_bins,
+            _lib.ptr(hist))
     return hist
 
 
@@ -630,14 +602,8 @@ def _n4_fit(v, f, mask, rng, lut, tz, ty, tx, sz, sy, sx, S):
     C = S + 3
     lattice = torch.empty((C, C, C), dtype=torch.float64, device=v.device)
     weight = torch.empty((C, C, C), dtype=torch.float64, device=v.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_n4_fit_workspace_bytes(D, H, W, S))
-    workspace = _workspace(nbytes, v.device)
-    with torch.cuda.device(v.device):
-        err = lib.nesvor_n4_fit(_lib.ptr(v), _lib.ptr(f), _lib.ptr(m), _lib.ptr(rng), _lib.ptr(lut), n_bins, _lib.ptr(tz), _lib.ptr(ty),
-                                _lib.ptr(tx), _lib.ptr(sz), _lib.ptr(sy), _lib.ptr(sx), D, H, W, S, _lib.ptr(lattice), _lib.ptr(weight),
-                                _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "n4 fit")
+    _launch("n4_fit", v.device, (D, H, W, S), _lib.ptr(v), _lib.ptr(f), _lib.ptr(m), _lib.ptr(rng), _lib.ptr(lut), n_bins, _lib.ptr(tz),
+            _lib.ptr(ty), _lib.ptr(tx), _lib.ptr(sz), _lib.ptr(sy), _lib.ptr(sx), D, H, W, S, _lib.ptr(lattice), _lib.ptr(weight))
     return lattice, weight
 
 
@@ -648,14 +614,8 @@ def _n4_update(lattice, tz, ty, tx, sz, sy, sx, S, f, v, mask):
     if tuple(lattice.shape) != (S + 3,) * 3 or lattice.device != v.device:
         raise RuntimeError("n4_update_: lattice (C, C, C) with C = S + 3 on the device of v expected")
     stats = torch.empty(5, dtype=torch.float64, device=v.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_n4_update_workspace_bytes(D, H, W))
-    workspace = _workspace(nbytes, v.device)
-    with torch.cuda.device(v.device):
-        err = lib.nesvor_n4_update(_lib.ptr(lattice), _lib.ptr(tz), _lib.ptr(ty), _lib.ptr(tx), _lib.ptr(sz), _lib.ptr(sy), _lib.ptr(sx), S,
-                                   _lib.ptr(f), _lib.ptr(v), _lib.ptr(m), D, H, W, _lib.ptr(stats), _lib.ptr(workspace), nbytes,
-                                   _lib.stream_ptr())
-    _lib.check(err, "n4 update")
+    _launch("n4_update", v.device, (D, H, W), _lib.ptr(lattice), _lib.ptr(tz), _lib.ptr(ty), _lib.ptr(tx), _lib.ptr(sz), _lib.ptr(sy),
+            _lib.ptr(sx), S, _lib.ptr(f), _lib.ptr(v), _lib.ptr(m), D, H, W, _lib.ptr(stats))
     return stats
 
 
@@ -712,23 +672,17 @@ def _stack_mask(slices, mask, transforms, resolution_x, resolution_y, threshold=
         _f64("stack_mask slab_extents", slab_extents, 3 * n_others, slices)
     out = torch.empty(slices.shape, dtype=torch.uint8, device=slices.device)
     stats = torch.empty((n, 3), dtype=torch.float64, device=slices.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_stack_mask_workspace_bytes(n, h, w))
-    workspace = _workspace(nbytes, slices.device)
-    with torch.cuda.device(slices.device):
-        err = lib.nesvor_stack_mask(_lib.ptr(slices), _lib.ptr(m), _lib.ptr(transforms), n, h, w, float(resolution_x), float(resolution_y),
-                                    _lib.ptr(threshold), _lib.ptr(volume), vd, vh, vw, _lib.ptr(volume_geometry if volume is not None else None),
-                                    _lib.ptr(slabs if n_others else None), _lib.ptr(slab_extents if n_others else None),
-                                    _lib.ptr(slab_offsets if n_others else None), n_others, n_slabs, _lib.ptr(out), _lib.ptr(stats),
-                                    _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "stack mask")
+    _launch("stack_mask", slices.device, (n, h, w), _lib.ptr(slices), _lib.ptr(m), _lib.ptr(transforms), n, h, w, float(resolution_x),
+            float(resolution_y), _lib.ptr(threshold), _lib.ptr(volume), vd, vh, vw,
+            _lib.ptr(volume_geometry if volume is not None else None), _lib.ptr(slabs if n_others else None),
+            _lib.ptr(slab_extents if n_others else None), _lib.ptr(slab_offsets if n_others else None), n_others, n_slabs, _lib.ptr(out),
+            _lib.ptr(stats))
     return out, stats
 
 
 def _otsu_range(what, slices, rng, n_bins):
     _f64(f"{what} range", rng, 2, slices)
-    if not 2 <= n_bins <= 1024:
-        raise RuntimeError(f"{what}: 2 <= n_bins <= 1024 expected, got {n_bins}")
+    _n_bins(what, n_bins)
 
 
 def _otsu_histogram(slices, mask, rng, n_bins):
@@ -736,13 +690,8 @@ def _otsu_histogram(slices, mask, rng, n_bins):
     m, n, h, w = _slice_stack("otsu_histogram", {"slices": slices}, mask, {"range": rng})
     _otsu_range("otsu_histogram", slices, rng, n_bins)
     hist = torch.empty(n_bins, dtype=torch.int64, device=slices.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_otsu_histogram_workspace_bytes(n, h, w, n_bins))
-    workspace = _workspace(nbytes, slices.device)
-    with torch.cuda.device(slices.device):
-        err = lib.nesvor_otsu_histogram(_lib.ptr(slices), _lib.ptr(m), n, h, w, _lib.ptr(rng), n_bins, _lib.ptr(hist), _lib.ptr(workspace),
-                                        nbytes, _lib.stream_ptr())
-    _lib.check(err, "otsu histogram")
+    _launch("otsu_histogram", slices.device, (n, h, w, n_bins), _lib.ptr(slices), _lib.ptr(m), n, h, w, _lib.ptr(rng), n_bins,
+            _lib.ptr(hist))
     return hist
 
 

@@ -16,7 +16,7 @@ first) and sigma_px = sigma_mm / res_s:
     u = weight                                   on eligible pixels, 0 elsewhere
 S(a) is the separable Gaussian window of radius R = max(1, ceil(3 sigma_px)) with zero padding: taps
 exp(-(t - R)^2 / (2 sigma_px^2)), t = 0 .. 2 R, normalised to sum 1 in double and rounded to the dtype once (``gaussian_taps``);
-along x first; each pass is acc = 0; acc = acc + g[t] a[. + t - R] in ascending t (``structural._window`` with a variable radius).
+along x first; each pass is acc = 0; acc = acc + g[t] a[. + t - R] in ascending t (``window.window``, which ``structural.py`` shares).
     num = S(u r),  den = S(u),  d = num / den where den > DEN_MIN = 1e-3, else 0,   b_new = b + d    on every pixel of the frame
 (off the mask the field is the smooth continuation of what the eligible pixels say).  Five sums per slice in fp64 follow,
 {n_eligible, sum u, sum u b_new, sum u r, sum (u r) r}.  After the sums, on fp64 n-vectors with ``torch.where``: a slice with
@@ -33,7 +33,8 @@ import os
 from typing import Optional, Tuple
 
 import torch
-import torch.nn.functional as F
+
+from . import window as _w
 
 MIN_INTENSITY = 0.05
 CLAMP = math.log(2.0)
@@ -51,14 +52,7 @@ def window_radius(sigma_px: float) -> int:
 
 
 def gaussian_taps(sigma_px: float, dtype: torch.dtype = torch.float64, device=None) -> torch.Tensor:
-    """g[t] = exp(-(t - R)^2 / (2 sigma_px^2)), t = 0 .. 2 R, normalised to sum 1 in double and rounded to ``dtype`` once (what the
-    kernel's host code does)."""
-    radius = window_radius(sigma_px)
-    g = [math.exp(-float((t - radius) * (t - radius)) / (2.0 * sigma_px * sigma_px)) for t in range(2 * radius + 1)]
-    total = 0.0
-    for v in g:
-        total += v
-    return torch.tensor([v / total for v in g], dtype=torch.float64).to(dtype=dtype, device=device)
+    return _w.gaussian_taps(sigma_px, window_radius(sigma_px), dtype, device)
 
 
 def _rounded(value: float, dtype: torch.dtype) -> float:
@@ -67,19 +61,7 @@ def _rounded(value: float, dtype: torch.dtype) -> float:
 
 
 def _window(a: torch.Tensor, taps) -> torch.Tensor:
-    """S(a) over the last two dimensions: explicit shifted slices in tap order, so that the kernel can follow it operation for
-    operation."""
-    radius = (len(taps) - 1) // 2
-    h, w = a.shape[-2], a.shape[-1]
-    padded = F.pad(a, (radius, radius))
-    acc = torch.zeros_like(a)
-    for t, g in enumerate(taps):
-        acc = acc + g * padded[..., t:t + w]
-    padded = F.pad(acc, (0, 0, radius, radius))
-    out = torch.zeros_like(a)
-    for t, g in enumerate(taps):
-        out = out + g * padded[..., t:t + h, :]
-    return out
+    return _w.window(a, taps, 2)
 
 
 def eligible(sim: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor], min_intensity: float = MIN_INTENSITY) -> torch.Tensor:

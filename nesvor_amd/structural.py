@@ -23,12 +23,12 @@ One round (``StructuralExclusion.update``) needs the map and the sums (``ssim_st
 the same formulas as a torch expression (``ssim_composed``, the fp64 yardstick of tests/test_structural.py).  What follows
 the sums is a few operations on n-vectors in fp64, written with ``torch.where``: a round reads nothing back to the host.
 """
-import math
 import os
 from typing import Optional, Tuple
 
 import torch
-import torch.nn.functional as F
+
+from . import window as _w
 
 RADIUS = 5
 SIGMA = 1.5
@@ -37,13 +37,7 @@ MIN_VAR_PRODUCT = 1e-12  # below it a slice (or its simulation) is flat: r = 0
 
 
 def gaussian_taps(dtype: torch.dtype = torch.float64, device=None) -> torch.Tensor:
-    """g[t] = exp(-(t - 5)^2 / (2 1.5^2)), t = 0 .. 10, normalised to sum 1 in double and rounded to ``dtype`` once (what the
-    kernel's host code does)."""
-    g = [math.exp(-float((t - RADIUS) ** 2) / (2.0 * SIGMA * SIGMA)) for t in range(2 * RADIUS + 1)]
-    total = 0.0
-    for v in g:
-        total += v
-    return torch.tensor([v / total for v in g], dtype=torch.float64).to(dtype=dtype, device=device)
+    return _w.gaussian_taps(SIGMA, RADIUS, dtype, device)
 
 
 def _fused(sim: torch.Tensor) -> bool:
@@ -51,18 +45,7 @@ def _fused(sim: torch.Tensor) -> bool:
 
 
 def _window(a: torch.Tensor, taps) -> torch.Tensor:
-    """S(a) over the last two dimensions: explicit shifted slices in tap order, so that the kernel can follow it operation for
-    operation."""
-    h, w = a.shape[-2], a.shape[-1]
-    padded = F.pad(a, (RADIUS, RADIUS))
-    acc = torch.zeros_like(a)
-    for t, g in enumerate(taps):
-        acc = acc + g * padded[..., t:t + w]
-    padded = F.pad(acc, (0, 0, RADIUS, RADIUS))
-    out = torch.zeros_like(a)
-    for t, g in enumerate(taps):
-        out = out + g * padded[..., t:t + h, :]
-    return out
+    return _w.window(a, taps, 2)
 
 
 def ssim_composed(sim: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor], scale: torch.Tensor, threshold: float = 0.4,
@@ -73,18 +56,11 @@ def ssim_composed(sim: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tenso
     valid = torch.ones_like(sim, dtype=torch.bool) if mask is None else mask.reshape(sim.shape).bool()
     c1, c2 = (0.01 * dynamic_range) ** 2, (0.03 * dynamic_range) ** 2
     taps = gaussian_taps(sim.dtype).tolist()  # host numbers: exactly the dtype's values
-    zero, one = torch.zeros_like(sim), torch.ones_like(sim)
+    zero = torch.zeros_like(sim)
     i = torch.where(valid, scale.view(n, *([1] * (sim.ndim - 1))) * y, zero)
     j = torch.where(valid, sim, zero)
     v = valid.to(sim.dtype)
-    wt = torch.where(valid, _window(v, taps), one)
-    mu_i, mu_j = _window(i, taps) / wt, _window(j, taps) / wt
-    var_i = _window(i * i, taps) / wt - mu_i * mu_i
-    var_j = _window(j * j, taps) / wt - mu_j * mu_j
-    cov = _window(i * j, taps) / wt - mu_i * mu_j
-    num = (2 * mu_i * mu_j + c1) * (2 * cov + c2)
-    den = (mu_i * mu_i + mu_j * mu_j + c1) * (var_i + var_j + c2)
-    ssim = torch.where(valid, num / den, zero)
+    ssim = _w.ssim_map(i, j, valid, taps, c1, c2, 2)
     below = (valid & (ssim < threshold)).to(sim.dtype)
     terms = (v, ssim, below, i, j, i * i, j * j, i * j)
     stats = torch.stack([t.double().flatten(1).sum(1) for t in terms], dim=1)
