@@ -208,7 +208,9 @@ int nesvor_hashgrid_forward_bounded(const nesvor_grid_t* grid, const float* u, c
  * runs on workgroups of neighbouring points (lattice boxes in LDS up to the middle levels instead of 8 gathers per point and
  * level), and - feature-major output - the encoded rows are re-ordered into columns by one more launch.  Results are identical to
  * nesvor_hashgrid_forward's (same arithmetic per point).  `workspace`: nesvor_hashgrid_forward_workspace_bytes(grid, N, layout)
- * bytes of scratch (0 without the hint); N < 2^32. */
+ * bytes of scratch (0 without the hint); N < 2^32.  The rows -> columns launch keeps 256 rows of n_levels * n_features + 1 floats
+ * in LDS: where that (plus 1 KiB) exceeds the device's LDS per workgroup (n_levels * n_features >= 159 on gfx950) the size query
+ * returns -1 for feature-major output and the launch is refused with hipErrorInvalidValue: call nesvor_hashgrid_forward. */
 int64_t nesvor_hashgrid_forward_workspace_bytes(const nesvor_grid_t* grid, int64_t N, int layout);
 int nesvor_hashgrid_forward_unclustered(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N,
                                         int layout, float* pe_absmax, void* workspace, int64_t workspace_bytes, void* stream);
@@ -217,7 +219,13 @@ int nesvor_hashgrid_forward_unclustered(const nesvor_grid_t* grid, const float* 
  * Owner-computes scatter (LDS aggregation per 256 samples -> per-chunk queues ->
  * one owner workgroup per table chunk); `workspace` is scratch device memory of
  * nesvor_hashgrid_backward_workspace_bytes(grid, N, queue_scale) bytes (-1: grid outside the
- * plan's limits, use the _atomic variant).  `stages`: 3 = whole backward;
+ * plan's limits, use the _atomic variant).  The limits: at most 32 levels; at most 256 chunks per
+ * level (a chunk is the largest power of two of entries with chunk * n_features <= 8192 floats);
+ * at most 4064 chunks over all levels (one queue counter each, in front of the 32 overflow
+ * counters); a level's queues below 2^32 bytes and all queues together below 2^32 records (a
+ * matter of N: 8 N records per level at queue_scale 1).  Every backward entry point that takes a
+ * workspace, and nesvor_hashgrid_forward_plan with a cloud_plan, return hipErrorInvalidValue for
+ * a grid outside them.  `stages`: 3 = whole backward;
  * 1 = aggregation launch only, 2 = owner launch only (so a caller can bracket
  * each launch with its own events; 1 then 2 on one stream == 3).
  * `queue_scale`: HOST array of one float per level in (0, 1], or NULL (= 1 everywhere): the fraction of the worst-case
@@ -228,7 +236,9 @@ int nesvor_hashgrid_forward_unclustered(const nesvor_grid_t* grid, const float* 
  * overflow.  The same `queue_scale` must be passed to the size query and to every launch on that workspace. */
 int64_t nesvor_hashgrid_backward_workspace_bytes(const nesvor_grid_t* grid, int64_t N, const float* queue_scale);
 /* The same for a backward that will be called with this `layout` (hints included): larger than the above only for
- * NESVOR_LAYOUT_FEATURE_MAJOR | NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH. */
+ * NESVOR_LAYOUT_FEATURE_MAJOR | NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH (room for dpe as rows in the points'
+ * order; not where such rows exceed the copy kernel's LDS - see nesvor_hashgrid_forward_workspace_bytes - the backward then
+ * reads dpe in place). */
 int64_t nesvor_hashgrid_backward_workspace_bytes_ex(const nesvor_grid_t* grid, int64_t N, const float* queue_scale, int layout);
 /* The first nesvor_hashgrid_backward_workspace_zero_bytes() bytes of a workspace (its two queue-tail regions) must be
  * zero-filled ONCE after the workspace is allocated; the backward keeps them consistent afterwards (every aggregation

@@ -771,7 +771,9 @@ __global__ __launch_bounds__(256) void hashgrid_bwd(const nesvor_grid_t g, const
 
 // ------------------------------------------- backward, owner-computes version
 constexpr int kSubQueues = 8;                 // every queue is split by the XCC the producing workgroup runs on (see below); plan.n_sub <= 8 are used
-constexpr uint32_t kTailStride = 4096;        // counters per sub-queue set (>= kMaxChunks * NESVOR_MAX_LEVELS)
+constexpr uint32_t kTailStride = 4096;        // counters per sub-queue set: one per bucket (chunk of a level), then the overflow counters.
+                                              // NOT kMaxChunks * NESVOR_MAX_LEVELS = 8192: make_plan refuses a grid with more than
+                                              // kOverflowBase = 4064 buckets (the size query then returns -1: the atomic kernel)
 constexpr uint32_t kOverflowBase = kTailStride - NESVOR_MAX_LEVELS;  // last words of counter set 0: records per level that found their queue full
 constexpr int kOwnerLdsFloats = 8192;         // 32 KiB accumulator per owner workgroup: 4096-entry chunks (measured: 16 / 64 / 128 KiB are slower -
                                               // fewer, hotter queue counters on one side, more reservations per workgroup on the other)
@@ -1957,6 +1959,7 @@ inline bool make_plan(const nesvor_grid_t* g, int64_t N, BwdPlan* plan, uint64_t
     plan->shift[l] = shift0;
     plan->n_chunks[l] = 0; plan->bucket_base[l] = nb; plan->cap[l] = 0; plan->slice[l] = kOwnerSlice; plan->rec_off[l] = off;
   }
+  if (nb > kOverflowBase) return false;  // bucket ids beyond that would be the overflow counters (and the next counter set)
   plan->n_buckets = nb;
   plan->level_begin = 0; plan->level_end = g->n_levels; plan->accumulate_u = 0;
   if (off > 0xFFFFFFFFull) return false;  // records are addressed by 32-bit record numbers
@@ -2133,6 +2136,19 @@ __global__ __launch_bounds__(256) void sort_compact_kernel(SortPlan p, SortBufs 
 // the backward against 0.89 ms on row-major input.  Here the columns are READ in their own order (256 consecutive floats per row
 // and workgroup) and every point's E values are WRITTEN as one row of 4 E bytes at its place in the order: both sides whole lines.
 constexpr int kGatherPts = 256;
+// Both re-ordering kernels keep [kGatherPts][E + 1] floats of dynamic LDS next to kGatherPts ranks of static LDS: whether that fits
+// a workgroup's LDS on this device (160 KiB on gfx950: E <= 158).  Wider rows do without the re-ordered copy: the backward reads
+// feature-major dpe through perm, the forward is refused (nesvor_hashgrid_forward_workspace_bytes returns -1: the per-level kernel).
+inline size_t reorder_lds_bytes(int E) { return sizeof(float) * kGatherPts * (size_t)(E + 1); }
+inline bool reorder_fits_lds(int E) {
+  static const size_t limit = []() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
+      return (size_t)64 * 1024;  // (no device: a size query on the host - what every device has)
+    return (size_t)v;
+  }();
+  return reorder_lds_bytes(E) + sizeof(uint32_t) * kGatherPts <= limit;
+}
 __global__ __launch_bounds__(256) void gather_dy_rows_kernel(const float* __restrict__ dpe, SortBufs s, float* __restrict__ rows, int64_t N, int E) {
   extern __shared__ float tile[];  // [kGatherPts][E + 1]
   __shared__ uint32_t rank[kGatherPts];
@@ -2228,7 +2244,8 @@ int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table,
   if constexpr (LAYOUT == NESVOR_LAYOUT_FEATURE_MAJOR) {
     // unclustered feature-major dpe with room for its re-ordered copy (NESVOR_LAYOUT_DY_SCRATCH: the workspace was sized by
     // nesvor_hashgrid_backward_workspace_bytes_ex with the same layout): the aggregation pass runs in its row-major form on the copy
-    if (unclustered && (hints & NESVOR_LAYOUT_DY_SCRATCH) && (stages & 1))
+    // (rows too wide for the copy kernel's LDS: this instantiation reads dpe through perm, and the size query left the copy out)
+    if (unclustered && (hints & NESVOR_LAYOUT_DY_SCRATCH) && (stages & 1) && reorder_fits_lds(g->n_levels * F))
       return launch_bwd_owner<F, NESVOR_LAYOUT_ROW_MAJOR>(g, u, table, dpe, gt, gu, N, workspace, stages, level_begin, level_end, queue_scale,
                                                           dy_bound, adam, st, hints | 0x10000, fwd_order, cloud_plan);
   }
@@ -2262,7 +2279,7 @@ int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table,
     float* rows = reinterpret_cast<float*>(reinterpret_cast<char*>(perm_buf) + ((sort_bytes(N) + 255) & ~(uint64_t)255));
     // (a later launch of a split backward finds the first launch's copy in place)
     if (!(stages & 4)) {
-      const size_t lds = sizeof(float) * kGatherPts * (E + 1);
+      const size_t lds = reorder_lds_bytes(E);
       if (lds > 48 * 1024) {
         static std::mutex mu;
         static size_t raised = 0;
@@ -2342,7 +2359,7 @@ int launch_fwd_unclustered(const nesvor_grid_t* g, const float* u, const float* 
   hipLaunchKernelGGL((hashgrid_fwd_cloud<F, LAYOUT>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, *g, u, table, pe, N, pe_absmax,
                      (const uint32_t*)perm_buf, rows);
   if constexpr (LAYOUT == NESVOR_LAYOUT_FEATURE_MAJOR) {
-    const size_t lds = sizeof(float) * kGatherPts * (E + 1);
+    const size_t lds = reorder_lds_bytes(E);
     if (lds > 48 * 1024) {
       static std::mutex mu;
       static size_t raised = 0;
@@ -2447,6 +2464,7 @@ extern "C" int nesvor_hashgrid_forward(const nesvor_grid_t* grid, const float* u
 extern "C" int64_t nesvor_hashgrid_forward_workspace_bytes(const nesvor_grid_t* grid, int64_t N, int layout) {
   if (grid == nullptr || N <= 0) return 0;
   if (!(layout & NESVOR_LAYOUT_UNCLUSTERED)) return 0;
+  if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR && !reorder_fits_lds(grid->n_levels * grid->n_features)) return -1;
   return (int64_t)fwd_ws_bytes(grid, N, layout);
 }
 
@@ -2456,6 +2474,8 @@ extern "C" int nesvor_hashgrid_forward_unclustered(const nesvor_grid_t* grid, co
   if (N <= 0) return 0;
   if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
   if (N >= ((int64_t)1 << 32)) return (int)hipErrorInvalidValue;  // (32-bit point indices in the order)
+  if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR && !reorder_fits_lds(grid->n_levels * grid->n_features))
+    return (int)hipErrorInvalidValue;  // (the rows -> columns kernel's LDS: nesvor_hashgrid_forward_workspace_bytes said -1)
   if (workspace == nullptr || workspace_bytes < (int64_t)fwd_ws_bytes(grid, N, layout)) return (int)hipErrorInvalidValue;
   layout &= NESVOR_LAYOUT_MASK;
   DISPATCH_F_LAYOUT(launch_fwd_unclustered, grid, u, table, pe, N, pe_absmax, workspace, (hipStream_t)stream);
@@ -2476,7 +2496,8 @@ extern "C" int64_t nesvor_hashgrid_backward_workspace_bytes_ex(const nesvor_grid
   // (round-5 advisor) the order's scratch - ~26 MB at N = 2^20 - only for callers that will pass NESVOR_LAYOUT_UNCLUSTERED; the
   // plain query above keeps it (its callers may pass any hint later)
   if (!(layout & NESVOR_LAYOUT_UNCLUSTERED)) base -= (int64_t)((sort_bytes(N) + 255) & ~(uint64_t)255);
-  if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR && (layout & NESVOR_LAYOUT_UNCLUSTERED) && (layout & NESVOR_LAYOUT_DY_SCRATCH))
+  if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR && (layout & NESVOR_LAYOUT_UNCLUSTERED) && (layout & NESVOR_LAYOUT_DY_SCRATCH) &&
+      reorder_fits_lds(grid->n_levels * grid->n_features))
     return base + 256 + (int64_t)((N + 255) / 256) * 256 * grid->n_levels * grid->n_features * (int64_t)sizeof(float);
   return base;
 }
@@ -2487,7 +2508,6 @@ extern "C" int64_t nesvor_hashgrid_backward_workspace_bytes(const nesvor_grid_t*
   uint64_t n_rec;
   if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return -1;
   if (!make_plan(grid, N, &plan, &n_rec, queue_scale)) return -1;
-  if (plan.n_buckets > kOverflowBase) return -1;
   return (int64_t)(kHeadBytes + n_rec * (1 + grid->n_features) * sizeof(uint32_t) + (uint64_t)((N + 255) / 256) * 256 + 256 + ((sort_bytes(N) + 255) & ~(uint64_t)255));
 }
 

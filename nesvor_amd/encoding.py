@@ -61,6 +61,8 @@ def hashgrid_forward(spec: HashGridSpec, u: torch.Tensor, table: torch.Tensor, l
         if ordered:
             lay = layout | _lib.LAYOUT_UNCLUSTERED
             nbytes = lib.nesvor_hashgrid_forward_workspace_bytes(ctypes.byref(spec.c_struct), N, lay)
+            ordered = nbytes >= 0  # (-1: feature-major rows too wide for the re-ordering kernel's LDS - the per-level kernel)
+        if ordered:
             ws = _FWD_WS.get(u.device)
             if ws is None or ws.numel() < nbytes:
                 ws = _FWD_WS[u.device] = torch.empty(nbytes, dtype=torch.uint8, device=u.device)

@@ -158,6 +158,43 @@ def test_grid_spec_and_inr_hyperparameters(golden):
         assert np.float32(a_.scale) == np.float32(b_.scale)
 
 
+def test_hashgrid_plan_limits_on_the_tested_grids():
+    """The grids of tests/test_gpu_hashgrid_grids.py sit where their table says - chunks per level and buckets (chunks over all
+    levels) under the plan's chunking rule - and the size query of the owner method (host code: the library loads without a GPU)
+    draws the line there: 256 chunks per level and 3968 of 4064 buckets are inside, 512 chunks and 4096 buckets are not."""
+    import ctypes
+
+    import hashgrid_reference as R
+    from nesvor_amd import _lib
+    from nesvor_amd.grid import HashGridSpec
+
+    lib = _lib.load()
+    for name, (spec_tuple, most, buckets, inside) in R.GRIDS.items():
+        assert R.chunk_counts(spec_tuple) == (most, buckets), name
+        assert inside == (most <= R.MAX_CHUNKS and buckets <= R.MAX_BUCKETS), name
+        spec = HashGridSpec(*spec_tuple)
+        for N in (1000, 1024):
+            nbytes = lib.nesvor_hashgrid_backward_workspace_bytes(ctypes.byref(spec.c_struct), N, None)
+            assert (nbytes > 0) if inside else (nbytes == -1), (name, nbytes)
+            for layout in (0, 1, 1 | _lib.LAYOUT_UNCLUSTERED | _lib.LAYOUT_DY_SCRATCH):
+                ex = lib.nesvor_hashgrid_backward_workspace_bytes_ex(ctypes.byref(spec.c_struct), N, None, layout)
+                assert (0 < ex <= nbytes + 256 + 1024 * 4 * spec.n_output_dims) if inside else (ex == -1), (name, layout, ex)
+            assert (lib.nesvor_hashgrid_backward_order_offset(ctypes.byref(spec.c_struct), N, None) > 0) == inside, name
+    for name in ("near_bucket_limit", "T20_256chunks"):
+        assert R.GRIDS[name][3]
+    for name in ("T21_512chunks", "many_buckets"):
+        assert not R.GRIDS[name][3]
+    # the re-ordered copy of a feature-major dpe exists only where its rows fit the copy kernel's LDS: E = 256 never does,
+    # E = 24 does whatever the device (without one the query assumes 64 KiB)
+    wide, narrow = HashGridSpec(*R.GRIDS["L32_F8"][0]), HashGridSpec(*R.GRIDS["cli_130mm"][0])
+    hinted = 1 | _lib.LAYOUT_UNCLUSTERED | _lib.LAYOUT_DY_SCRATCH
+    q = lambda s, lay: lib.nesvor_hashgrid_backward_workspace_bytes_ex(ctypes.byref(s.c_struct), 1000, None, lay)
+    assert q(wide, hinted) == q(wide, 1 | _lib.LAYOUT_UNCLUSTERED)
+    assert q(narrow, hinted) == q(narrow, 1 | _lib.LAYOUT_UNCLUSTERED) + 256 + 1024 * 4 * narrow.n_output_dims
+    fq = lambda s, lay: lib.nesvor_hashgrid_forward_workspace_bytes(ctypes.byref(s.c_struct), 1000, lay | _lib.LAYOUT_UNCLUSTERED)
+    assert fq(wide, 1) == -1 and fq(wide, 0) > 0 and fq(narrow, 1) > fq(narrow, 0) > 0
+
+
 def test_state_dict_layout_matches_reference(golden):
     """INR.state_dict() keys/shapes (checkpoint contract, cli/io.py:24-46) without touching the GPU."""
     from nesvor_amd.models import INR
