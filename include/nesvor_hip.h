@@ -1077,6 +1077,33 @@ int nesvor_volume_ssim(const float* reference, const float* resampled, const uin
                        int w, float* ssim, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 int64_t nesvor_volume_ssim_workspace_bytes(int d, int h, int w);
 
+/* ----------------------------------------------------------------------
+ * Moment sums of K candidate poses in one pass over the reference (nesvor_amd/align.py, `evaluate --align`).
+ *
+ * nesvor_volume_pose_moments.  The volumes and masks are nesvor_volume_resample's.  index_maps: K x 12 HOST doubles, K index
+ * maps (3,4) row-major, 1 <= K <= 16 (they travel as kernel arguments).  For every map the per-voxel arithmetic and the
+ * validity rule v are nesvor_volume_resample's, operation for operation (one device routine serves both), and
+ *   sums[k] = { n = #v, sum I, sum J, sum I^2, sum J^2, sum I J }     over v, I = I0, J = J0
+ * are entries 0, 2, 3, 4, 5, 6 of that call's stats.  sums (K,6) fp64 is fully written.  n is exact, products are fp32, the
+ * sums double from the first add.  No atomics: a workgroup owns 1024 consecutive voxels (EVALUATE_POSE_CHUNK of
+ * nesvor_amd/ops.py), thread t of it the voxels t, t + 256, t + 512, t + 768, whatever K is; per-workgroup partials go to the
+ * workspace and a second launch adds them in a fixed order.  Which thread owns a voxel and the order of every add depend on
+ * (d, h, w) alone: the six sums of a pose are bit-identical whatever else is in the call, and from run to run.
+ * The reference value and mask byte of a voxel are read once for the K poses; a voxel off the reference mask or outside the
+ * volume under a pose gathers nothing for it; 8 gathers per pose without a volume mask, 16 with one.
+ *
+ * workspace: at least nesvor_volume_pose_moments_workspace_bytes(d, h, w, K) = 48 K ceil(d h w / 1024) bytes of device memory
+ * (0 for sizes and K the call refuses, and for K = 0).
+ * K = 0 returns 0 without a launch.  hipErrorInvalidValue, without a launch: K < 0 or K > 16, a null pointer other than the
+ * two masks, a dimension (of either volume) below 1, more than INT_MAX - 256 voxels (in either volume), a non-finite map
+ * entry, a workspace that is missing or too small.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_volume_pose_moments(const float* reference, const uint8_t* reference_mask, int d, int h, int w, const float* volume,
+                               const uint8_t* volume_mask, int vd, int vh, int vw, const double* index_maps, int K, double* sums,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_volume_pose_moments_workspace_bytes(int d, int h, int w, int K);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,9 @@ _SIGNATURES = {
     "nesvor_volume_resample_workspace_bytes": ([c_int, c_int, c_int], c_int64),
     "nesvor_volume_ssim": ([_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P], c_int),
     "nesvor_volume_ssim_workspace_bytes": ([c_int, c_int, c_int], c_int64),
+    "nesvor_volume_pose_moments": ([_P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, POINTER(c_double), c_int, _P, _P, c_size_t, _P],
+                                   c_int),
+    "nesvor_volume_pose_moments_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
 }
 
 

@@ -77,8 +77,13 @@ and ``sample-volume`` samples the model on that mask volume instead of the store
 Also not in the reference: ``evaluate`` compares volumes with a reference volume (nesvor_amd/evaluate.py, csrc/evaluate.hip): every
 input volume is put onto the reference's lattice through the two files' poses (trilinear; ``svr`` writes a world-aligned lattice,
 ``reconstruct`` the model's own) and PSNR, NRMSE, MAE, correlation and the mean of a 3-D SSIM are taken over the voxels both
-volumes cover, after the ``--intensity-fit`` of the volume to the reference.  The volumes must share a world frame - the
-reconstructions of one set of registered slices, or of one ``--input-slices`` folder, do; rigid alignment is out of scope.  It logs
+volumes cover, after the ``--intensity-fit`` of the volume to the reference.  Without ``--align`` the volumes must
+share a world frame - the reconstructions of one set of registered slices, or of one ``--input-slices`` folder, do.
+``--align translation|rigid``
+(nesvor_amd/align.py) first finds the rigid correction of each input volume's pose that maximises its correlation with the
+reference - a coarse-to-fine descent over ``--align-levels`` pyramid levels whose dozen candidate poses per step are one fused
+pass over the reference - for a ground truth, another tool's output or a run with another ``--template-stack``; every report then
+carries an ``alignment`` entry, and ``--output-aligned`` writes each input's own voxels with the corrected pose.  It logs
 a table, ``--output-json`` writes the reports (a non-finite value as null), ``--output-ssim-maps`` / ``--output-resampled`` the maps
 on the reference's lattice.  A volume that shares no voxel with the reference is reported with a warning.
 ``--device cpu``, which this command alone takes, runs the same definition as torch expressions on the host.
@@ -332,22 +337,30 @@ def build_parser() -> argparse.ArgumentParser:
     _common_flags(p)
 
     p = sub.add_parser("evaluate")
-    g = p.add_argument_group("input (the volumes must share a world frame: nothing is aligned)")
+    g = p.add_argument_group("input (without --align the volumes must share a world frame: nothing is aligned)")
     g.add_argument("--reference-volume", type=str, required=True, help="the volume the others are compared with, on its lattice")
     g.add_argument("--reference-mask", type=str, help="a mask on the reference's lattice instead of its positive voxels")
     g.add_argument("--input-volumes", nargs="+", type=str, required=True,
                    help="the volumes under test, on any lattice of the reference's world frame (the reconstructions of one set of "
-                        "registered slices, or of one --input-slices folder, share it); rigid alignment is out of scope")
+                        "registered slices, or of one --input-slices folder, share it), or any rigid motion away from it with --align")
     g.add_argument("--input-masks", nargs="+", type=str, help="one mask per input volume instead of its positive voxels")
     g = p.add_argument_group("comparison (nesvor_amd/evaluate.py)")
     g.add_argument("--intensity-fit", default="scale", type=str, choices=["none", "scale", "affine"],
                    help="fitted to the reference before the errors are taken: nothing, a gain, or a gain and an offset")
     g.add_argument("--dynamic-range", type=float, metavar="L", help="the peak value of PSNR, NRMSE and SSIM (default: the reference's "
                                                                     "largest intensity on the compared voxels)")
+    g.add_argument("--align", default="none", type=str, choices=["none", "translation", "rigid"],
+                   help="before the comparison, correct each input volume's pose by the translation or rigid motion that maximises its "
+                        "correlation with the reference (nesvor_amd/align.py); none: the files' poses are taken as they are")
+    g.add_argument("--align-levels", default=3, type=int, metavar="N",
+                   help="with --align: at most N pyramid levels (a level needs 12 samples on every axis of both volumes)")
     g = p.add_argument_group("output")
     g.add_argument("--output-json", type=str, help="JSON file for the list of per-volume reports")
     g.add_argument("--output-ssim-maps", nargs="+", type=str, help="the SSIM map of every input volume, on the reference's lattice")
     g.add_argument("--output-resampled", nargs="+", type=str, help="every input volume on the reference's lattice")
+    g.add_argument("--output-aligned", nargs="+", type=str,
+                   help="with --align: every input volume's own voxels with the corrected pose (nothing is resampled); `evaluate` "
+                        "without --align reproduces the aligned comparison from such a file")
     _common_flags(p, host=True)
 
     p = sub.add_parser("sample-volume")

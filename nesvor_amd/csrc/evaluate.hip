@@ -14,6 +14,10 @@
 //     along x, then y, then z, taps added in ascending order from 0; Wt = S(v), the moments and the SSIM formula are
 //     structural.hip's (window::ssim_value).  ssim = 0 off v.  stats = { n, sum ssim, sum e^2, sum |e| } over v.
 //
+//   nesvor_volume_pose_moments (nesvor_amd/align.py, `evaluate --align`).  Up to 16 maps at once: for each the resampler's v
+//     and { n, sum I, sum J, sum I^2, sum J^2, sum I J } over it - its stats 0, 2, 3, 4, 5, 6 - without its two volume-sized
+//     outputs, R read once.  sample_voxel is the one definition of the per-voxel arithmetic for both kernels.
+//
 // Composed from torch operators the two are the gathers of sixteen corners with a dozen volume-sized temporaries and 3 x 11
 // shifted adds over six moment volumes: a few hundred launches.  Here each is one pass and a small reduce launch.
 //
@@ -60,6 +64,11 @@ constexpr double kEps = 1.0 / 1048576.0;       // 2^-20 voxels
 
 struct Map { double m[12]; };
 
+constexpr int kPoseStats = 6, kMaxPoses = 16;
+constexpr int kPoseVoxels = 4;                     // voxels a thread of the multi-pose pass keeps in registers
+constexpr int kPoseChunk = 256 * kPoseVoxels;      // voxels per workgroup (EVALUATE_POSE_CHUNK of nesvor_amd/ops.py)
+struct Maps { double m[kMaxPoses][12]; };
+
 // One axis: the inside test on u, then the clamped taps.  i0, i1 in [0, n - 1] whatever u is.
 __device__ __forceinline__ bool axis_taps(double u, int n, int& i0, int& i1, float& f) {
   const double top = (double)(n - 1);
@@ -74,21 +83,12 @@ __device__ __forceinline__ bool axis_taps(double u, int n, int& i0, int& i1, flo
 
 __device__ __forceinline__ float lerp(float a, float b, float f) { return a + f * (b - a); }
 
-// grid: ceil(N / 256) workgroups, N = d h w.  partial: (wgs, 8) doubles.
-__global__ __launch_bounds__(256) void volume_resample_kernel(const float* __restrict__ ref, const uint8_t* __restrict__ mask_r,
-                                                              const float* __restrict__ vol, const uint8_t* __restrict__ mask_x,
-                                                              int h, int w, int N, int xd, int xh, int xw, Map map,
-                                                              float* __restrict__ out, uint8_t* __restrict__ valid,
-                                                              double* __restrict__ partial) {
-  __shared__ double red[4][kResampleStats];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int idx = blockIdx.x * 256 + tid;  // the host checked N <= INT_MAX - 256
-  const bool here = idx < N;
-  const int p = here ? idx : 0;
-  const int z = p / (h * w), rem = p - z * (h * w), y = rem / w, x = rem - y * w;
-  const bool in_ref = here && (mask_r == nullptr || mask_r[p]);
+// One R voxel (x, y, z) under one map m (12 doubles): the inside test first, then the gathers - 8 of the mask (none without
+// one) and, where mX >= 0.5, 8 of the volume.  -> v (false at once off the reference mask); jv = J0 where v, untouched elsewhere.
+// The resampling pass and the multi-pose moments pass both call it: one definition of the per-voxel arithmetic.
+__device__ __forceinline__ bool sample_voxel(const double* m, int x, int y, int z, bool in_ref, const float* __restrict__ vol,
+                                             const uint8_t* __restrict__ mask_x, int xd, int xh, int xw, float& jv) {
   const double dx = (double)x, dy = (double)y, dz = (double)z;
-  const double* m = map.m;
   const double ux = ((m[0] * dx + m[1] * dy) + m[2] * dz) + m[3];
   const double uy = ((m[4] * dx + m[5] * dy) + m[6] * dz) + m[7];
   const double uz = ((m[8] * dx + m[9] * dy) + m[10] * dz) + m[11];
@@ -96,7 +96,6 @@ __global__ __launch_bounds__(256) void volume_resample_kernel(const float* __res
   float fx, fy, fz;
   const bool inx = axis_taps(ux, xw, x0, x1, fx), iny = axis_taps(uy, xh, y0, y1, fy), inz = axis_taps(uz, xd, z0, z1, fz);
   bool on = in_ref && inx && iny && inz;
-  float iv = 0.f, jv = 0.f;
   if (on) {
     const size_t r00 = ((size_t)z0 * xh + y0) * xw, r01 = ((size_t)z0 * xh + y1) * xw;
     const size_t r10 = ((size_t)z1 * xh + y0) * xw, r11 = ((size_t)z1 * xh + y1) * xw;
@@ -111,9 +110,27 @@ __global__ __launch_bounds__(256) void volume_resample_kernel(const float* __res
       const float c00 = lerp(vol[r00 + x0], vol[r00 + x1], fx), c01 = lerp(vol[r01 + x0], vol[r01 + x1], fx);
       const float c10 = lerp(vol[r10 + x0], vol[r10 + x1], fx), c11 = lerp(vol[r11 + x0], vol[r11 + x1], fx);
       jv = lerp(lerp(c00, c01, fy), lerp(c10, c11, fy), fz);
-      iv = ref[p];
     }
   }
+  return on;
+}
+
+// grid: ceil(N / 256) workgroups, N = d h w.  partial: (wgs, 8) doubles.
+__global__ __launch_bounds__(256) void volume_resample_kernel(const float* __restrict__ ref, const uint8_t* __restrict__ mask_r,
+                                                              const float* __restrict__ vol, const uint8_t* __restrict__ mask_x,
+                                                              int h, int w, int N, int xd, int xh, int xw, Map map,
+                                                              float* __restrict__ out, uint8_t* __restrict__ valid,
+                                                              double* __restrict__ partial) {
+  __shared__ double red[4][kResampleStats];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int idx = blockIdx.x * 256 + tid;  // the host checked N <= INT_MAX - 256
+  const bool here = idx < N;
+  const int p = here ? idx : 0;
+  const int z = p / (h * w), rem = p - z * (h * w), y = rem / w, x = rem - y * w;
+  const bool in_ref = here && (mask_r == nullptr || mask_r[p]);
+  float iv = 0.f, jv = 0.f;
+  const bool on = sample_voxel(map.m, x, y, z, in_ref, vol, mask_x, xd, xh, xw, jv);
+  if (on) iv = ref[p];
   if (here) {
     out[p] = jv;
     valid[p] = on ? 1 : 0;
@@ -133,13 +150,73 @@ __global__ __launch_bounds__(256) void volume_resample_kernel(const float* __res
     partial[(size_t)blockIdx.x * kResampleStats + tid] = fmax(fmax(red[0][tid], red[1][tid]), fmax(red[2][tid], red[3][tid]));
 }
 
-// One workgroup.  stats[j] = the wgs rows of column j: thread t combines rows t, t + 256, .. in ascending order, then the 256
-// threads are combined pairwise (stride 128, 64, .. 1).  Columns >= first_max are maxima, the others sums.
+// The moments of K poses in one pass over R (nesvor_amd/align.py).  grid: wgs = ceil(N / kPoseChunk) workgroups; a workgroup owns
+// kPoseChunk consecutive voxels and thread t the voxels base + t + 256 j, j = 0 .. kPoseVoxels - 1, whatever K is.  The
+// reference value, its mask byte and (x, y, z) of the thread's voxels are read and worked out once and stay in registers; the
+// pose loop runs OUTSIDE them, so only one pose's six double accumulators are live at a time (16 x 6 would be 192 VGPRs).  Per
+// pose: the thread adds its voxels in ascending order in double from the first add, wave_sum_f64, the four waves as
+// (0 + 1) + (2 + 3), one row of partial (K, wgs, 6).  The maps are kernel arguments: maps.m[k] with the uniform k is scalar loads.
+// The LDS rows alternate with k, so one barrier per pose is enough (row k & 1 is written again only behind barrier k + 1).
+__global__ __launch_bounds__(256) void volume_pose_moments_kernel(const float* __restrict__ ref, const uint8_t* __restrict__ mask_r,
+                                                                  const float* __restrict__ vol, const uint8_t* __restrict__ mask_x,
+                                                                  int h, int w, int N, int xd, int xh, int xw, Maps maps, int K,
+                                                                  double* __restrict__ partial) {
+  __shared__ double red[2][4][kPoseStats];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t base = (int64_t)blockIdx.x * kPoseChunk + tid;  // (N <= INT_MAX - 256, but the last chunk may reach past INT_MAX)
+  int vx[kPoseVoxels], vy[kPoseVoxels], vz[kPoseVoxels];
+  float iv[kPoseVoxels];
+  bool in_ref[kPoseVoxels];
+#pragma unroll
+  for (int j = 0; j < kPoseVoxels; ++j) {
+    const int64_t idx = base + 256 * j;
+    const bool here = idx < N;
+    const int p = here ? (int)idx : 0;
+    const int z = p / (h * w), rem = p - z * (h * w), y = rem / w;
+    vx[j] = rem - y * w; vy[j] = y; vz[j] = z;
+    in_ref[j] = here && (mask_r == nullptr || mask_r[p]);
+    iv[j] = in_ref[j] ? ref[p] : 0.f;
+  }
+  const size_t wgs = gridDim.x;
+  for (int k = 0; k < K; ++k) {
+    const double* m = maps.m[k];
+    int count = 0;
+    double si = 0.0, sj = 0.0, sii = 0.0, sjj = 0.0, sij = 0.0;
+#pragma unroll
+    for (int j = 0; j < kPoseVoxels; ++j) {
+      float jv = 0.f;
+      if (sample_voxel(m, vx[j], vy[j], vz[j], in_ref[j], vol, mask_x, xd, xh, xw, jv)) {
+        const float i = iv[j];
+        count += 1;
+        si += (double)i;
+        sj += (double)jv;
+        sii += (double)(i * i);
+        sjj += (double)(jv * jv);
+        sij += (double)(i * jv);
+      }
+    }
+    const double s[kPoseStats] = {wave_sum_f64((double)count), wave_sum_f64(si), wave_sum_f64(sj), wave_sum_f64(sii), wave_sum_f64(sjj),
+                                  wave_sum_f64(sij)};
+    double (&row)[4][kPoseStats] = red[k & 1];
+    if (lane == 0) {
+#pragma unroll
+      for (int c = 0; c < kPoseStats; ++c) row[wave][c] = s[c];
+    }
+    __syncthreads();
+    if (tid < kPoseStats) partial[((size_t)k * wgs + blockIdx.x) * kPoseStats + tid] = (row[0][tid] + row[1][tid]) + (row[2][tid] + row[3][tid]);
+  }
+}
+
+// One workgroup per entry (the two passes of a comparison have one entry, the multi-pose moments one per pose): partial is
+// (entries, wgs, N), stats (entries, N).  stats[j] = the wgs rows of column j: thread t combines rows t, t + 256, .. in ascending
+// order, then the 256 threads are combined pairwise (stride 128, 64, .. 1).  Columns >= first_max are maxima, the others sums.
 template <int N>
 __global__ __launch_bounds__(256) void volume_reduce_kernel(const double* __restrict__ partial, int wgs, int first_max,
                                                             double* __restrict__ stats) {
   __shared__ double buf[N][256];
   const int tid = threadIdx.x;
+  partial += (size_t)blockIdx.x * wgs * N;
+  stats += (size_t)blockIdx.x * N;
   double acc[N];
 #pragma unroll
   for (int j = 0; j < N; ++j) acc[j] = j >= first_max ? -INFINITY : 0.0;
@@ -284,6 +361,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
 
 int64_t resample_wgs(int d, int h, int w) { return ((int64_t)d * h * w + 255) / 256; }
 
+int64_t pose_wgs(int d, int h, int w) { return ((int64_t)d * h * w + kPoseChunk - 1) / kPoseChunk; }
+
 int64_t ssim_wgs(int d, int h, int w) { return (((int64_t)d + kZChunk - 1) / kZChunk) * slice_sums::tile_workgroups(h, w); }
 
 }  // namespace
@@ -311,6 +390,33 @@ extern "C" int nesvor_volume_resample(const float* reference, const uint8_t* ref
                      w, d * h * w, vd, vh, vw, map, resampled, valid, (double*)workspace);
   hipLaunchKernelGGL(volume_reduce_kernel<kResampleStats>, dim3(1), dim3(256), 0, st, (const double*)workspace, (int)wgs,
                      kResampleStats - 1, stats);
+  return (int)hipGetLastError();
+}
+
+extern "C" int64_t nesvor_volume_pose_moments_workspace_bytes(int d, int h, int w, int K) {
+  if (bad_volume(d, h, w) || K < 1 || K > kMaxPoses) return 0;
+  return (int64_t)sizeof(double) * kPoseStats * K * pose_wgs(d, h, w);
+}
+
+extern "C" int nesvor_volume_pose_moments(const float* reference, const uint8_t* reference_mask, int d, int h, int w, const float* volume,
+                                          const uint8_t* volume_mask, int vd, int vh, int vw, const double* index_maps, int K,
+                                          double* sums, void* workspace, size_t workspace_bytes, void* stream) {
+  if (K < 0 || K > kMaxPoses) return (int)hipErrorInvalidValue;
+  if (reference == nullptr || volume == nullptr || (K > 0 && (index_maps == nullptr || sums == nullptr))) return (int)hipErrorInvalidValue;
+  if (bad_volume(d, h, w) || bad_volume(vd, vh, vw)) return (int)hipErrorInvalidValue;
+  if (K == 0) return 0;  // nothing to write, nothing launched
+  Maps maps = {};
+  for (int i = 0; i < 12 * K; ++i) {
+    if (!isfinite(index_maps[i])) return (int)hipErrorInvalidValue;
+    maps.m[i / 12][i % 12] = index_maps[i];
+  }
+  const int64_t wgs = pose_wgs(d, h, w);  // <= INT_MAX / 1024
+  if (workspace == nullptr || (int64_t)workspace_bytes < nesvor_volume_pose_moments_workspace_bytes(d, h, w, K)) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(volume_pose_moments_kernel, dim3((unsigned)wgs), dim3(256), 0, st, reference, reference_mask, volume, volume_mask, h,
+                     w, d * h * w, vd, vh, vw, maps, K, (double*)workspace);
+  hipLaunchKernelGGL(volume_reduce_kernel<kPoseStats>, dim3((unsigned)K), dim3(256), 0, st, (const double*)workspace, (int)wgs, kPoseStats,
+                     sums);
   return (int)hipGetLastError();
 }
 

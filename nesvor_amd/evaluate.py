@@ -1,9 +1,11 @@
 """Volume comparison (the ``evaluate`` command): which of several reconstructions of one set of slices is closer to a reference
 volume.  ``svr`` writes a world-aligned lattice and ``reconstruct`` the model's own, so a volume is first put onto the
 reference's lattice through the two NIfTI poses; PSNR, NRMSE, MAE, correlation and a 3-D SSIM are then taken over the voxels
-both volumes cover.  Rigid alignment is out of scope: the volumes must share a world frame (the reconstructions of one set of
-registered slices, or of one ``--input-slices`` folder, do).  The reference project has no counterpart: the definition is this
-module's.
+both volumes cover.  Without ``--align`` nothing is aligned: the volumes must share a world frame (the reconstructions of one set
+of registered slices, or of one ``--input-slices`` folder, do).  ``--align translation|rigid`` first finds the rigid correction of
+the volume's pose that maximises its correlation with the reference (nesvor_amd/align.py, imported only then) and compares
+through the corrected index map; everything below is unchanged by it.  The reference project has no counterpart: the definition
+is this module's.
 
 Definition.  R is the reference (image I0 (D,H,W), mask, pose, voxel sizes), X the volume under test (X0 (D',H',W'), mask,
 pose, voxel sizes); everything is evaluated on R's lattice.
@@ -235,19 +237,29 @@ def compare_tensors(reference: torch.Tensor, reference_mask: Optional[torch.Tens
     return {"resampled": resampled, "valid": valid != 0, "ssim_map": ssim_map, "packed": packed}
 
 
-def compare_volumes(reference, volume, intensity_fit: str = "scale", dynamic_range: Optional[float] = None) -> Dict:
+def compare_volumes(reference, volume, intensity_fit: str = "scale", dynamic_range: Optional[float] = None, align: str = "none",
+                    align_levels: int = 3) -> Dict:
     """The report of the module docstring for the ``Volume`` ``volume`` against the ``Volume`` ``reference`` (python numbers), plus
     the device tensors ``resampled`` (J0), ``valid`` (bool) and ``ssim_map`` on the reference's lattice and ``fused``, the path.
     The poses are read where they live (the command keeps them on the host); everything else stays on the device up to the one
-    ``tolist`` of the report."""
+    ``tolist`` of the report.  ``align`` = "translation" | "rigid": the comparison runs through M(theta*) of nesvor_amd/align.py
+    and the report has an ``alignment`` entry (``align_volumes``'s result)."""
     ref = reference.image if reference.image.is_floating_point() else reference.image.float()
     vol = volume.image.to(device=ref.device, dtype=ref.dtype)
+    M, alignment = index_map(reference, volume), None
+    if align != "none":
+        from . import align as _align
+
+        alignment = _align.align_volumes(reference, volume, dof=align, levels=align_levels)
+        M = _align.pose_maps(reference, volume, [alignment["theta"]], alignment["centre"])[0]
     out = compare_tensors(ref.contiguous(), (reference.mask != 0).contiguous(), vol.contiguous(),
-                          (volume.mask != 0).to(ref.device).contiguous(), index_map(reference, volume), intensity_fit, dynamic_range)
+                          (volume.mask != 0).to(ref.device).contiguous(), M, intensity_fit, dynamic_range)
     values = out.pop("packed").tolist()  # the one host read
     report = {"n": int(values[0]), "coverage": values[1], "ncc": values[2], "fit": [values[3], values[4]], "dynamic_range": values[5],
               "mse": values[6], "rmse": values[7], "nrmse": values[8], "mae": values[9], "psnr": values[10], "ssim": values[11]}
     report.update(out, fused=_fused(ref))
+    if alignment is not None:
+        report["alignment"] = alignment
     return report
 
 
@@ -276,16 +288,23 @@ def _finite(v):
         return v if math.isfinite(v) else None
     if isinstance(v, (list, tuple)):
         return [_finite(x) for x in v]
+    if isinstance(v, dict):  # (the ``alignment`` entry)
+        return {k: _finite(x) for k, x in v.items()}
     return v
 
 
 def format_table(rows: List[Dict]) -> str:
-    head = f"{'volume':<32} {'n':>10} {'cover':>7} {'PSNR':>8} {'NRMSE':>8} {'MAE':>10} {'NCC':>7} {'SSIM':>7}  fit"
+    aligned = any("alignment" in r for r in rows)  # (with --align: the rotation and translation of the correction)
+    head = f"{'volume':<32} {'n':>10} {'cover':>7} {'PSNR':>8} {'NRMSE':>8} {'MAE':>10} {'NCC':>7} {'SSIM':>7}"
+    head += f" {'rot deg':>8} {'shift mm':>8}  fit" if aligned else "  fit"
     lines = [head]
     for r in rows:
         name = os.path.basename(str(r["input_volume"]))
-        lines.append(f"{name[-32:]:<32} {r['n']:>10d} {r['coverage']:>7.4f} {r['psnr']:>8.3f} {r['nrmse']:>8.5f} {r['mae']:>10.4g} "
-                     f"{r['ncc']:>7.4f} {r['ssim']:>7.4f}  {r['fit'][0]:.5g} x + {r['fit'][1]:.5g}")
+        line = (f"{name[-32:]:<32} {r['n']:>10d} {r['coverage']:>7.4f} {r['psnr']:>8.3f} {r['nrmse']:>8.5f} {r['mae']:>10.4g} "
+                f"{r['ncc']:>7.4f} {r['ssim']:>7.4f}")
+        if aligned:
+            line += f" {r['alignment']['rotation_deg']:>8.3f} {r['alignment']['translation_mm']:>8.3f}"
+        lines.append(line + f"  {r['fit'][0]:.5g} x + {r['fit'][1]:.5g}")
     return "\n".join(lines)
 
 
@@ -294,15 +313,19 @@ def evaluate_command(args) -> List[Dict]:
     from .image import Volume
 
     inputs = list(args.input_volumes)
-    for name in ("input_masks", "output_ssim_maps", "output_resampled"):
+    for name in ("input_masks", "output_ssim_maps", "output_resampled", "output_aligned"):
         if getattr(args, name, None) is not None and len(getattr(args, name)) != len(inputs):
             raise SystemExit(f"The numbers of {name.replace('_', ' ')} and input volumes are different!")
+    align = getattr(args, "align", None) or "none"
+    if align == "none" and getattr(args, "output_aligned", None):
+        raise SystemExit("--output-aligned needs --align translation or --align rigid!")
     device = getattr(args, "device", None) or torch.device("cpu")
     reference = load_volume(args.reference_volume, getattr(args, "reference_mask", None), device)
     rows = []
     for k, path in enumerate(inputs):
         volume = load_volume(path, args.input_masks[k] if getattr(args, "input_masks", None) else None, device)
-        report = compare_volumes(reference, volume, getattr(args, "intensity_fit", "scale"), getattr(args, "dynamic_range", None))
+        extra = {} if align == "none" else {"align": align, "align_levels": getattr(args, "align_levels", 3)}
+        report = compare_volumes(reference, volume, getattr(args, "intensity_fit", "scale"), getattr(args, "dynamic_range", None), **extra)
         if report["n"] == 0:
             logging.warning("evaluate: %s shares no voxel with the reference (do the volumes share a world frame?)", path)
         for name, key in (("output_ssim_maps", "ssim_map"), ("output_resampled", "resampled")):
@@ -310,6 +333,14 @@ def evaluate_command(args) -> List[Dict]:
                 Volume(report[key].cpu(), report["valid"].cpu(), reference.transformation, reference.resolution_x, reference.resolution_y,
                        reference.resolution_z).save(getattr(args, name)[k], masked=False)
         rows.append({"input_volume": path, **{key: report[key] for key in METRICS}})
+        if align != "none":
+            from . import align as _align
+
+            result = report["alignment"]
+            rows[-1]["alignment"] = _align.report_entry(result)
+            if getattr(args, "output_aligned", None):  # the input's own voxels and mask with the pose G^-1 o T_X: nothing is resampled
+                Volume(volume.image.cpu(), volume.mask.cpu(), _align.aligned_pose(volume, result["theta"], result["centre"]),
+                       volume.resolution_x, volume.resolution_y, volume.resolution_z).save(args.output_aligned[k])
     logging.info("Volume comparison against %s (intensity fit: %s):\n%s", args.reference_volume, getattr(args, "intensity_fit", "scale"),
                  format_table(rows))
     if getattr(args, "output_json", None):

@@ -493,6 +493,30 @@ _op("volume_resample(Tensor reference, Tensor? reference_mask, Tensor volume, Te
 _op("volume_ssim(Tensor reference, Tensor resampled, Tensor valid, Tensor params) -> (Tensor ssim, Tensor stats)", _volume_ssim,
     fake=lambda reference, resampled, valid, params: (torch.empty_like(reference), reference.new_empty((4,), dtype=torch.float64)))
 
+EVALUATE_POSE_CHUNK = 1024  # voxels per workgroup of volume_pose_moments (kPoseChunk of csrc/evaluate.hip): four per thread
+EVALUATE_MAX_POSES = 16  # index maps per call (they travel as kernel arguments)
+
+
+def _volume_pose_moments(reference, reference_mask, volume, volume_mask, index_maps):
+    mr, d, h, w = _volume("volume_pose_moments", "reference", reference, reference_mask)
+    mx, vd, vh, vw = _volume("volume_pose_moments", "volume", volume, volume_mask)
+    if volume.device != reference.device:
+        raise RuntimeError("volume_pose_moments: reference and volume must be on one device")
+    K, rest = divmod(len(index_maps), 12)
+    if rest or K > EVALUATE_MAX_POSES:
+        raise RuntimeError(f"volume_pose_moments: index_maps, the 12 entries of up to {EVALUATE_MAX_POSES} (3, 4) matrices, expected")
+    sums = torch.empty((K, 6), dtype=torch.float64, device=reference.device)
+    M = (ctypes.c_double * max(12 * K, 1))(*[float(v) for v in index_maps])
+    _launch("volume_pose_moments", reference.device, (d, h, w, K), _lib.ptr(reference), _lib.ptr(mr), d, h, w, _lib.ptr(volume),
+            _lib.ptr(mx), vd, vh, vw, M, K, _lib.ptr(sums))
+    return sums
+
+
+_op("volume_pose_moments(Tensor reference, Tensor? reference_mask, Tensor volume, Tensor? volume_mask, float[] index_maps) -> Tensor",
+    _volume_pose_moments,
+    fake=lambda reference, reference_mask, volume, volume_mask, index_maps: reference.new_empty((len(index_maps) // 12, 6),
+                                                                                                dtype=torch.float64))
+
 
 # =====================================================================================================================
 # slice bias fields of the classical reconstruction (csrc/slice_bias.hip): one round of the smoothed log-ratio of scale_k y to

@@ -111,7 +111,7 @@ def gaussian_blur(x: torch.Tensor, sigma, truncated: float) -> torch.Tensor:
             k = gaussian_1d_kernel(s, truncated, x.device)
             shape = [1] * x.ndim
             shape[d + 2] = -1
-            k = k.reshape(shape).repeat(*([c, 1] + [1] * nd))
+            k = k.reshape(shape).repeat(*([c, 1] + [1] * nd)).to(x.dtype)  # (the fp32 taps, whatever the array's dtype)
             pad = [0] * nd
             pad[d] = (k.shape[d + 2] - 1) // 2
             x = conv(x, k, padding=pad, groups=c)
