@@ -16,71 +16,21 @@ import types
 import pytest
 import torch
 
+from acq_geometry import BIG_PSFS, GEOMETRIES, OUTSIDE, TOL32, _generic_poses, _lattice_poses, _psf
+
 pytestmark = pytest.mark.gpu
 
-# name: volume (D,H,W), slice (h,w), res_slice, PSF
-GEOMETRIES = {
-    "odd": ((5, 7, 9), (7, 9), 1.0, "psf333"),  # all sizes odd: with lattice poses every tap position is an integer
-    "tiny": ((2, 2, 2), (3, 5), 1.0, "psf333"),  # the smallest volume with an interior (x < W - 1)
-    "row": ((5, 7, 300), (1, 257), 1.0, "psf955"),  # one row, one pixel past a workgroup
-    "dense": ((9, 11, 13), (16, 16), 0.5, "psf955"),  # exactly 256 pixels; several pixels per voxel
-    "sparse": ((18, 20, 22), (17, 19), 2.5, "psf955"),  # 323 pixels: second trip of the per-slice loops; sparse pixels
-    "even": ((9, 11, 13), (6, 6), 1.0, "psf426"),  # even PSF dimensions: tap ranges -d/2 .. (d+1)/2 - 1 are asymmetric
-}
-BIG_PSFS = ["psf1688", "psf1788"]  # forward only, on the "even" volume: 1024 taps fill the LDS list exactly, 1088 walk global memory
 # generic poses: seed per (geometry, masks); checked on the CPU: the fp32 oracle agrees with the fp64 oracle within TOL32
 GENERIC_SEEDS = {(g, m): 100 + 10 * i + int(m) for i, g in enumerate(GEOMETRIES) for m in (False, True)}
 BIG_SEEDS = {"psf1688": 171, "psf1788": 172}
-OUTSIDE = 4  # index of the lattice pose 100 voxels outside the volume
 MANY = 300  # slices of (2,2) on the "odd" volume: one workgroup per slice in the per-slice kernels, three of its waves idle
 INVALID = 1  # hipErrorInvalidValue
 
-# (rtol, atol as a fraction of 1, atol as a fraction of the reference's largest magnitude), from tests/test_gpu_ops.py:
-# test_slice_acq_vs_oracle / _adjoint_vs_oracle / _backward_vs_oracle / _adjoint_backward_vs_oracle (fp32) and
-# test_slice_acq_double_precision_all_four_entry_points (fp64)
-TOL32 = {"slices": (1e-4, 1e-5, 0), "weight": (1e-4, 1e-5, 0), "adjoint": (1e-4, 1e-5, 0), "adjoint_weight": (1e-4, 1e-5, 0),
-         "grad_vol": (1e-4, 1e-5, 0), "grad_transforms": (0, 0, 2e-4), "grad_slices": (2e-4, 0, 2e-5), "adjoint_grad_transforms": (0, 0, 3e-4)}
+# TOL32: (rtol, atol as a fraction of 1, atol as a fraction of the reference's largest magnitude), from tests/test_gpu_ops.py
+# (tests/acq_geometry.py); TOL64: test_slice_acq_double_precision_all_four_entry_points (fp64)
 TOL64 = {"slices": (1e-10, 1e-12, 0), "weight": (1e-10, 1e-12, 0), "adjoint": (1e-10, 1e-12, 0), "adjoint_weight": (1e-10, 1e-12, 0),
          "grad_vol": (1e-9, 1e-11, 0), "grad_transforms": (0, 0, 1e-9), "grad_slices": (1e-9, 1e-11, 0), "adjoint_grad_transforms": (0, 0, 1e-9)}
 _DATA = {}
-
-
-def _psf(name):
-    """(9,5,5): the PSF of 1.5 x 1.5 x 3 mm slices on a 1 mm grid; (3,3,3): get_PSF((1,1,1)); the others hand-made, every tap
-    non-zero, normalised."""
-    from nesvor_amd.utils import get_PSF
-
-    if name == "psf955":
-        psf = get_PSF(res_ratio=(1.5, 1.5, 3.0))
-    elif name == "psf333":
-        psf = get_PSF(res_ratio=(1.0, 1.0, 1.0))
-    else:
-        shape = {"psf426": (4, 2, 6), "psf1688": (16, 8, 8), "psf1788": (17, 8, 8)}[name]
-        g = torch.Generator().manual_seed(sum(shape))
-        psf = 0.2 + torch.rand(shape, generator=g)
-        psf = psf / psf.sum()
-    assert tuple(psf.shape) == {"psf955": (9, 5, 5), "psf333": (3, 3, 3), "psf426": (4, 2, 6), "psf1688": (16, 8, 8),
-                                "psf1788": (17, 8, 8)}[name]
-    return psf.contiguous()
-
-
-def _lattice_poses(dims):
-    """Six poses [R | t] (x = R (p + t) + centre, t in voxels): identity, 90 degrees about z, a cyclic axis permutation, identity
-    moved by (0.5, -1, 2), identity 100 voxels outside (OUTSIDE), identity moved by (W - 1) / 2 along x (half in, half out)."""
-    eye = [[1.0, 0, 0], [0, 1.0, 0], [0, 0, 1.0]]
-    rz = [[0, -1.0, 0], [1.0, 0, 0], [0, 0, 1.0]]
-    perm = [[0, 1.0, 0], [0, 0, 1.0], [1.0, 0, 0]]
-    W = dims[2]
-    poses = [(eye, (0, 0, 0)), (rz, (0, 0, 0)), (perm, (0, 0, 0)), (eye, (0.5, -1.0, 2.0)), (eye, (0, 0, 100.0)), (eye, ((W - 1) / 2.0, 0, 0))]
-    return torch.stack([torch.cat([torch.tensor(r), torch.tensor(t, dtype=torch.float32)[:, None]], 1) for r, t in poses])
-
-
-def _generic_poses(n, g):
-    from oracle import transform_convert as tc
-
-    ax = torch.randn(n, 6, generator=g) * torch.tensor([0.6, 0.6, 0.6, 3.0, 3.0, 3.0])
-    ax[0] = 0
-    return tc.axisangle2mat_forward(ax)
 
 
 def _inputs(dims, shape, tf, psf, masks, g):

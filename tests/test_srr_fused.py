@@ -124,7 +124,9 @@ def test_composed_descent_is_the_reference_loop():
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU: the kernel against edge_prior_gradient
 # ---------------------------------------------------------------------------------------------------------------------
-SHAPES = [(3, 3, 3), (2, 7, 65), (7, 2, 9), (5, 9, 33), (4, 8, 64), (17, 8, 65), (11, 19, 70)]
+SHAPES = [(3, 3, 3), (2, 7, 65), (7, 2, 9), (5, 9, 33), (4, 8, 64), (17, 8, 65), (11, 19, 70),
+          (1, 1, 1), (1, 9, 33), (9, 1, 33), (9, 33, 1), (2, 2, 2),  # no interior along one axis, or along any
+          (16, 3, 34), (32, 9, 33), (33, 3, 3)]  # z-march seams: 16 planes per workgroup, a last workgroup of one plane, halos across
 _INPUTS = {}
 
 
