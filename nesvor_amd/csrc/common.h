@@ -6,8 +6,8 @@
 
 #define NESVOR_WAVE 64
 
-// Full-wave (64-lane) sum via butterfly shuffles; every lane gets the total.
-__device__ __forceinline__ float wave_sum(float v) {
+// Full-wave (64-lane) sum of floats or doubles via butterfly shuffles; every lane gets the total.
+template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;

@@ -8,21 +8,58 @@
 // zero-tap branches from the inner loop; the per-slice rotation is read through
 // the scalar path.  Volume reads are 8 scattered dwords per tap and stay in
 // L2/Infinity Cache for phantom-sized volumes (128^3 fp32 = 8 MB).
+// The pixel geometry, the tap walks, the inside test and the per-tap arithmetic of the kernels here are acq_taps.h's
+// (slice_acq_adjoint_gather and slice_acq_adjoint_bwd keep theirs written out and say why).
 #include <hip/hip_runtime.h>
-#include "common.h"
+#include "acq_taps.h"
 
 namespace {
-// Full-wave sum for float or double (the 12 pose sums per slice: once per workgroup, off the inner loops)
-template <typename T> __device__ __forceinline__ T wave_sum_any(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
+using namespace acq;
+
+template <typename T> struct InterpTap { int iv, xr, yr, zr; T pw, gx, gy, gz; };
+
+// One PSF tap at (x, y, z) already known to lie inside the volume.  false: the rounded voxel's offset falls outside the
+// PSF support.  GRAD: also d pw / d (x_psf, y_psf, z_psf), the corner sums of the reference (.cu:311-352).
+template <typename T, bool GRAD>
+__device__ __forceinline__ bool interp_tap(const T* __restrict__ t, const PixelGeom<T>& g, const T* __restrict__ psf, int d_p,
+                                           int h_p, int w_p, T x, T y, T z, int Sy, int Sz, InterpTap<T>& o) {
+  o.xr = (int)floor(x + (T)0.5); o.yr = (int)floor(y + (T)0.5); o.zr = (int)floor(z + (T)0.5);
+  o.iv = o.zr * Sz + o.yr * Sy + o.xr;
+  const T dx = o.xr - g.xc, dy = o.yr - g.yc, dz = o.zr - g.zc;
+  const T xp = t[0] * dx + t[4] * dy + t[8] * dz + (w_p - 1) / (T)2.0;
+  const T yp = t[1] * dx + t[5] * dy + t[9] * dz + (h_p - 1) / (T)2.0;
+  const T zp = t[2] * dx + t[6] * dy + t[10] * dz + (d_p - 1) / (T)2.0;
+  if (xp < 0 || yp < 0 || zp < 0 || xp >= w_p - 1 || yp >= h_p - 1 || zp >= d_p - 1) return false;
+  const int xf = (int)floor(xp), yf = (int)floor(yp), zf = (int)floor(zp);
+  const T wx = xp - xf, wy = yp - yf, wz = zp - zf;
+  const T* p0 = psf + (zf * h_p + yf) * w_p + xf;
+  const int py = w_p, pz = w_p * h_p;
+  const T c000 = p0[0], c100 = p0[1], c010 = p0[py], c001 = p0[pz], c110 = p0[1 + py], c101 = p0[1 + pz], c011 = p0[py + pz],
+          c111 = p0[1 + py + pz];
+  T pw = (T)0.0;  // corner order of the reference: 000, 100, 010, 001, 110, 101, 011, 111
+  pw += (1 - wx) * (1 - wy) * (1 - wz) * c000;
+  pw += wx * (1 - wy) * (1 - wz) * c100;
+  pw += (1 - wx) * wy * (1 - wz) * c010;
+  pw += (1 - wx) * (1 - wy) * wz * c001;
+  pw += wx * wy * (1 - wz) * c110;
+  pw += wx * (1 - wy) * wz * c101;
+  pw += (1 - wx) * wy * wz * c011;
+  pw += wx * wy * wz * c111;
+  o.pw = pw;
+  if constexpr (GRAD) {
+    T gx = (T)0.0, gy = (T)0.0, gz = (T)0.0;
+    gx -= (1 - wy) * (1 - wz) * c000; gy -= (1 - wx) * (1 - wz) * c000; gz -= (1 - wx) * (1 - wy) * c000;
+    gx += (1 - wy) * (1 - wz) * c100; gy -= wx * (1 - wz) * c100;       gz -= wx * (1 - wy) * c100;
+    gx -= wy * (1 - wz) * c010;       gy += (1 - wx) * (1 - wz) * c010; gz -= (1 - wx) * wy * c010;
+    gx -= (1 - wy) * wz * c001;       gy -= (1 - wx) * wz * c001;       gz += (1 - wx) * (1 - wy) * c001;
+    gx += wy * (1 - wz) * c110;       gy += wx * (1 - wz) * c110;       gz -= wx * wy * c110;
+    gx += (1 - wy) * wz * c101;       gy -= wx * wz * c101;             gz += wx * (1 - wy) * c101;
+    gx -= wy * wz * c011;             gy += (1 - wx) * wz * c011;       gz += (1 - wx) * wy * c011;
+    gx += wy * wz * c111;             gy += wx * wz * c111;             gz += wx * wy * c111;
+    o.gx = gx; o.gy = gy; o.gz = gz;
+  }
+  return true;
 }
-
-
-constexpr int kMaxTaps = 1024;
-
-template <typename T> struct Tap { T x, y, z, w; };
 
 // LDS_TAPS: the PSF's non-zero taps fit the LDS list (every PSF get_PSF builds for clinical geometries: (9,5,5) = 153
 // taps for 1.5 x 1.5 x 3 mm slices on a 1 mm grid); larger PSFs (thick slices on a fine grid, e.g. 6 mm on 0.5 mm = 1813
@@ -36,16 +73,7 @@ __global__ __launch_bounds__(256) void slice_acq_fwd(
   __shared__ Tap<T> taps[LDS_TAPS ? kMaxTaps : 1];
   __shared__ int n_taps;
   if constexpr (LDS_TAPS) {
-    if (threadIdx.x == 0) {
-      int cnt = 0, ip = 0;
-      for (int iz = -d_p / 2; iz < (d_p + 1) / 2; ++iz)
-        for (int iy = -h_p / 2; iy < (h_p + 1) / 2; ++iy)
-          for (int ix = -w_p / 2; ix < (w_p + 1) / 2; ++ix, ++ip) {
-            T pv = psf[ip];
-            if (pv != (T)0.0) taps[cnt++] = Tap<T>{(T)ix, (T)iy, (T)iz, pv};  // the host checked d_p h_p w_p <= kMaxTaps
-          }
-      n_taps = cnt;
-    }
+    if (threadIdx.x == 0) n_taps = compact_taps(psf, d_p, h_p, w_p, taps);
     __syncthreads();
   }
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -53,79 +81,22 @@ __global__ __launch_bounds__(256) void slice_acq_fwd(
   if (slices_mask != nullptr && !slices_mask[idx]) return;
   const int ix = idx % w, iy = (idx / w) % h, in = idx / ((int64_t)h * w);
   const T* t = transforms + (size_t)in * 12;
-  const T r11 = t[0], r12 = t[1], r13 = t[2], r21 = t[4], r22 = t[5], r23 = t[6], r31 = t[8], r32 = t[9], r33 = t[10];
-  // the reference evaluates this affine map in double and rounds once (.cu:46-47)
-  const T px = (T)((ix - (w - 1) / 2.) * (double)res_slice + (double)t[3]);
-  const T py = (T)((iy - (h - 1) / 2.) * (double)res_slice + (double)t[7]);
-  const T pz = t[11];
-  const T xc = r11 * px + r12 * py + r13 * pz + (W - 1) / (T)2.0;
-  const T yc = r21 * px + r22 * py + r23 * pz + (H - 1) / (T)2.0;
-  const T zc = r31 * px + r32 * py + r33 * pz + (D - 1) / (T)2.0;
-  const int Sy = W, Sz = H * W;
+  const PixelGeom<T> g = pixel_geom(t, ix, iy, h, w, res_slice, D, H, W);
   T val = (T)0.0, wsum = (T)0.0;
-  const int nt = LDS_TAPS ? n_taps : d_p * h_p * w_p;
-  const int tx0 = -w_p / 2, ty0 = -h_p / 2, tz0 = -d_p / 2;
-  for (int k = 0; k < nt; ++k) {
-    Tap<T> tp;
-    if constexpr (LDS_TAPS) {
-      tp = taps[k];
-    } else {
-      const T pv = psf[k];
-      if (pv == (T)0.0) continue;
-      const int kz = k / (h_p * w_p), kr = k - kz * (h_p * w_p), ky = kr / w_p;
-      tp = Tap<T>{(T)(tx0 + kr - ky * w_p), (T)(ty0 + ky), (T)(tz0 + kz), pv};
-    }
-    const T x = xc + r11 * tp.x + r12 * tp.y + r13 * tp.z;
-    const T y = yc + r21 * tp.x + r22 * tp.y + r23 * tp.z;
-    const T z = zc + r31 * tp.x + r32 * tp.y + r33 * tp.z;
-    if (x < 0 || y < 0 || z < 0 || x >= W - 1 || y >= H - 1 || z >= D - 1) continue;
-    if (INTERP_PSF) {
+  auto tap = [&](T, T, T, T pv, T x, T y, T z) {
+    if constexpr (INTERP_PSF) {
       // nearest voxel, PSF re-interpolated at the voxel's offset from the centre
-      const int xr = (int)floor(x + (T)0.5), yr = (int)floor(y + (T)0.5), zr = (int)floor(z + (T)0.5);
-      const int iv = zr * Sz + yr * Sy + xr;
-      if (vol_mask != nullptr && !vol_mask[iv]) continue;
-      const T dx = xr - xc, dy = yr - yc, dz = zr - zc;
-      const T xp = r11 * dx + r21 * dy + r31 * dz + (w_p - 1) / (T)2.0;
-      const T yp = r12 * dx + r22 * dy + r32 * dz + (h_p - 1) / (T)2.0;
-      const T zp = r13 * dx + r23 * dy + r33 * dz + (d_p - 1) / (T)2.0;
-      if (xp < 0 || yp < 0 || zp < 0 || xp >= w_p - 1 || yp >= h_p - 1 || zp >= d_p - 1) continue;
-      const int xf = (int)floor(xp), yf = (int)floor(yp), zf = (int)floor(zp);
-      const T wx = xp - xf, wy = yp - yf, wz = zp - zf;
-      const T* p0 = psf + (zf * h_p + yf) * w_p + xf;
-      const int py_ = w_p, pz_ = w_p * h_p;
-      T pw = (T)0.0;
-      pw += (1 - wx) * (1 - wy) * (1 - wz) * p0[0];
-      pw += wx * (1 - wy) * (1 - wz) * p0[1];
-      pw += (1 - wx) * wy * (1 - wz) * p0[py_];
-      pw += (1 - wx) * (1 - wy) * wz * p0[pz_];
-      pw += wx * wy * (1 - wz) * p0[1 + py_];
-      pw += wx * (1 - wy) * wz * p0[1 + pz_];
-      pw += (1 - wx) * wy * wz * p0[py_ + pz_];
-      pw += wx * wy * wz * p0[1 + py_ + pz_];
-      val += pw * vol[iv];
-      wsum += pw;
+      InterpTap<T> o;
+      if (!interp_tap<T, false>(t, g, psf, d_p, h_p, w_p, x, y, z, W, H * W, o)) return;
+      if (vol_mask != nullptr && !vol_mask[o.iv]) return;
+      val += o.pw * vol[o.iv];
+      wsum += o.pw;
     } else {
-      const int xf = (int)floor(x), yf = (int)floor(y), zf = (int)floor(z);
-      const T wx = x - xf, wy = y - yf, wz = z - zf;
-      const int iv = zf * Sz + yf * Sy + xf;
-      // corner order as the reference accumulates: 000,100,010,001,110,101,011,111
-      const int off[8] = {0, 1, Sy, Sz, 1 + Sy, 1 + Sz, Sy + Sz, 1 + Sy + Sz};
-      const T cw[8] = {(1 - wx) * (1 - wy) * (1 - wz), wx * (1 - wy) * (1 - wz), (1 - wx) * wy * (1 - wz),
-                           (1 - wx) * (1 - wy) * wz,       wx * wy * (1 - wz),       wx * (1 - wy) * wz,
-                           (1 - wx) * wy * wz,             wx * wy * wz};
-      T v8[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) v8[c] = vol[iv + off[c]];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        if (vol_mask == nullptr || vol_mask[iv + off[c]]) {
-          const T pw = cw[c] * tp.w;
-          val += pw * v8[c];
-          wsum += pw;
-        }
-      }
+      linear_tap(vol, vol_mask, trilinear_cell(x, y, z, H, W), pv, val, wsum);
     }
-  }
+  };
+  if constexpr (LDS_TAPS) for_lds_taps(t, g, taps, n_taps, D, H, W, tap);
+  else for_psf_taps(t, g, psf, d_p, h_p, w_p, D, H, W, tap);
   if (wsum > 0) {
     slices[idx] = val / wsum;
     if (slices_weight != nullptr) slices_weight[idx] = wsum;
@@ -146,20 +117,6 @@ __global__ __launch_bounds__(256) void slice_acq_fwd(
 //   backward only     : grad_transforms by one workgroup per slice (block reduction, no atomics)
 template <typename T> __device__ __forceinline__ constexpr T sqrt3() { return (T)1.7320508075688772; }
 
-template <typename T> struct PixelGeom { T qx, qy, qz, xc, yc, zc; };
-
-template <typename T>
-__device__ __forceinline__ PixelGeom<T> pixel_geom(const T* t, int ix, int iy, int h, int w, T res_slice, int D, int H, int W) {
-  PixelGeom<T> g;
-  g.qx = (T)((ix - (w - 1) / 2.) * (double)res_slice + (double)t[3]);
-  g.qy = (T)((iy - (h - 1) / 2.) * (double)res_slice + (double)t[7]);
-  g.qz = t[11];
-  g.xc = t[0] * g.qx + t[1] * g.qy + t[2] * g.qz + (W - 1) / (T)2.0;
-  g.yc = t[4] * g.qx + t[5] * g.qy + t[6] * g.qz + (H - 1) / (T)2.0;
-  g.zc = t[8] * g.qx + t[9] * g.qy + t[10] * g.qz + (D - 1) / (T)2.0;
-  return g;
-}
-
 // mode 0: adjoint (value = slices, active iff weight >= 0.5); mode 1: backward (value = grad_slices,
 // active iff value != 0 and weight != 0).  coef[idx] = value / weight, cw[idx] = 1 / weight (0 if inactive).
 template <typename T>
@@ -177,18 +134,7 @@ __global__ __launch_bounds__(256) void slice_acq_pixel_coef(const T* __restrict_
     const T* t = transforms + (size_t)in * 12;
     const PixelGeom<T> g = pixel_geom(t, ix, iy, h, w, res_slice, D, H, W);
     T weight = (T)0.0;
-    int ip = 0;
-    for (int iz = -d_p / 2; iz < (d_p + 1) / 2; ++iz)
-      for (int iyp = -h_p / 2; iyp < (h_p + 1) / 2; ++iyp)
-        for (int ixp = -w_p / 2; ixp < (w_p + 1) / 2; ++ixp, ++ip) {
-          const T pv = psf[ip];
-          if (pv == (T)0.0) continue;
-          const T x = g.xc + t[0] * ixp + t[1] * iyp + t[2] * iz;
-          const T y = g.yc + t[4] * ixp + t[5] * iyp + t[6] * iz;
-          const T z = g.zc + t[8] * ixp + t[9] * iyp + t[10] * iz;
-          if (x < 0 || y < 0 || z < 0 || x >= W - 1 || y >= H - 1 || z >= D - 1) continue;
-          weight += pv;
-        }
+    for_psf_taps(t, g, psf, d_p, h_p, w_p, D, H, W, [&](T, T, T, T pv, T, T, T) { weight += pv; });
     const bool active = mode == 0 ? weight >= (T)0.5 : weight != (T)0.0;
     if (active) { c = val / weight; iw = (T)1.0 / weight; }
   }
@@ -236,6 +182,8 @@ __global__ __launch_bounds__(256) void slice_acq_adjoint_gather(const T* __restr
               for (int jx = jxlo; jx <= jxhi; ++jx) {
                 const T pv = psf[((iz - tz0) * h_p + (jy - ty0)) * w_p + (jx - tx0)];
                 if (pv == (T)0.0) continue;
+                // (position and test written out, not tap_position: a position only weighs a sum here, it indexes nothing, and
+                //  the NaN-safe form of the test costs this innermost loop 6 % of the adjoint's time)
                 const T x = g.xc + t[0] * jx + t[1] * jy + t[2] * iz;
                 const T y = g.yc + t[4] * jx + t[5] * jy + t[6] * iz;
                 const T z = g.zc + t[8] * jx + t[9] * jy + t[10] * iz;
@@ -263,10 +211,8 @@ __global__ __launch_bounds__(256) void slice_acq_bwd_transforms(const T* __restr
                                                                 const T* __restrict__ coef, T* __restrict__ grad_transforms,
                                                                 int D, int H, int W, int d_p, int h_p, int w_p, int h, int w,
                                                                 T res_slice) {
-  __shared__ T red[4][12];
   const int k = blockIdx.x;
   const T* t = transforms + (size_t)k * 12;
-  const int Sy = W, Sz = H * W;
   T g[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) g[i] = (T)0.0;
@@ -275,49 +221,20 @@ __global__ __launch_bounds__(256) void slice_acq_bwd_transforms(const T* __restr
     if (gs == (T)0.0) continue;
     const int ix = pix % w, iy = pix / w;
     const PixelGeom<T> pg = pixel_geom(t, ix, iy, h, w, res_slice, D, H, W);
-    int ip = 0;
-    for (int iz = -d_p / 2; iz < (d_p + 1) / 2; ++iz)
-      for (int iyp = -h_p / 2; iyp < (h_p + 1) / 2; ++iyp)
-        for (int ixp = -w_p / 2; ixp < (w_p + 1) / 2; ++ixp, ++ip) {
-          const T pv = psf[ip];
-          if (pv == (T)0.0) continue;
-          const T x = pg.xc + t[0] * ixp + t[1] * iyp + t[2] * iz;
-          const T y = pg.yc + t[4] * ixp + t[5] * iyp + t[6] * iz;
-          const T z = pg.zc + t[8] * ixp + t[9] * iyp + t[10] * iz;
-          if (x < 0 || y < 0 || z < 0 || x >= W - 1 || y >= H - 1 || z >= D - 1) continue;
-          const int xf = (int)floor(x), yf = (int)floor(y), zf = (int)floor(z);
-          const T wx = x - xf, wy = y - yf, wz = z - zf;
-          const int i0 = zf * Sz + yf * Sy + xf;
-          const T pgs = pv * gs;
-          T dx = (T)0.0, dy = (T)0.0, dz = (T)0.0;
+    for_psf_taps(t, pg, psf, d_p, h_p, w_p, D, H, W, [&](T tx, T ty, T tz, T pv, T x, T y, T z) {
+      const T pgs = pv * gs;
+      const Cell<T> cell = trilinear_cell(x, y, z, H, W);
+      T dx = (T)0.0, dy = (T)0.0, dz = (T)0.0;
 #pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            const int cx = c & 1, cy = (c >> 1) & 1, cz = c >> 2;
-            const int ic = i0 + cx + cy * Sy + cz * Sz;
-            if (vol_mask != nullptr && !vol_mask[ic]) continue;
-            const T val = pgs * vol[ic];
-            const T ax = cx ? wx : (T)1.0 - wx, ay = cy ? wy : (T)1.0 - wy, az = cz ? wz : (T)1.0 - wz;
-            dx += (cx ? val : -val) * ay * az;
-            dy += (cy ? val : -val) * ax * az;
-            dz += (cz ? val : -val) * ax * ay;
-          }
-          const T ox = pg.qx + ixp, oy = pg.qy + iyp, oz = pg.qz + iz;
-          g[0] += dx * ox; g[1] += dx * oy; g[2] += dx * oz;
-          g[4] += dy * ox; g[5] += dy * oy; g[6] += dy * oz;
-          g[8] += dz * ox; g[9] += dz * oy; g[10] += dz * oz;
-          g[3] += dx * t[0] + dy * t[4] + dz * t[8];
-          g[7] += dx * t[1] + dy * t[5] + dz * t[9];
-          g[11] += dx * t[2] + dy * t[6] + dz * t[10];
-        }
+      for (int c = 0; c < 8; ++c) {
+        const Corner<T> cn = cell_corner(cell, c);
+        if (vol_mask != nullptr && !vol_mask[cn.ic]) continue;
+        add_corner_gradient(cn, pgs * vol[cn.ic], dx, dy, dz);
+      }
+      accumulate_pose_grad(g, t, pg, tx, ty, tz, dx, dy, dz);
+    });
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const T s = wave_sum_any(g[i]);
-    if (lane == 0) red[wave][i] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 12) grad_transforms[(size_t)k * 12 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  reduce_pose_grad(g, grad_transforms + (size_t)k * 12);
 }
 
 // in-place "equalise a gradient" step of adjoint_backward (slice_acq_cuda_kernel.cu:672-693 with is_grad = true)
@@ -334,6 +251,9 @@ __global__ void slice_acq_equalize_grad(T* __restrict__ grad_vol, const T* __res
 //   grad_transforms[k] += d/dT of the same expression with the corner values weighted by
 //                         (slices[p] - vol[corner]) (equalised adjoint) or slices[p].
 // One workgroup per slice; the 12 pose sums are block-reduced (the reference adds them with atomics).
+// The tap walk, the corner loop and the pose accumulation stay written out here (the twins of for_psf_taps, cell_corner /
+// add_corner_gradient and accumulate_pose_grad in acq_taps.h, with that header's NaN rule in its hoisted form): routed through the helpers this
+// kernel's fp32 allocation came out at 82 registers, one occupancy step down, and held at 78 by launch bounds it ran 5 % slower.
 template <typename T>
 __global__ __launch_bounds__(256) void slice_acq_adjoint_bwd(const T* __restrict__ transforms, const T* __restrict__ grad_vol,
                                                              const T* __restrict__ psf, const T* __restrict__ slices,
@@ -341,14 +261,14 @@ __global__ __launch_bounds__(256) void slice_acq_adjoint_bwd(const T* __restrict
                                                              const uint8_t* __restrict__ vol_mask, T* __restrict__ grad_slices,
                                                              T* __restrict__ grad_transforms, int D, int H, int W, int d_p,
                                                              int h_p, int w_p, int h, int w, T res_slice) {
-  __shared__ T red[4][12];
   const int k = blockIdx.x;
   const T* t = transforms + (size_t)k * 12;
   const int Sy = W, Sz = H * W;
+  const int n_pix = pose_is_bounded(t, res_slice) ? h * w : 0;  // a non-finite pose: no pixel walks its taps, so that the plain test below suffices
   T g[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) g[i] = (T)0.0;
-  for (int pix = threadIdx.x; pix < h * w; pix += blockDim.x) {
+  for (int pix = threadIdx.x; pix < n_pix; pix += blockDim.x) {
     const size_t idx = (size_t)k * h * w + pix;
     if (slices_mask != nullptr && !slices_mask[idx]) continue;
     const int ix = pix % w, iy = pix / w;
@@ -402,15 +322,7 @@ __global__ __launch_bounds__(256) void slice_acq_adjoint_bwd(const T* __restrict
       for (int i = 0; i < 12; ++i) g[i] += gp[i] / weight;
     }
   }
-  if (grad_transforms == nullptr) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const T s = wave_sum_any(g[i]);
-    if (lane == 0) red[wave][i] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 12) grad_transforms[(size_t)k * 12 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (grad_transforms != nullptr) reduce_pose_grad(g, grad_transforms + (size_t)k * 12);
 }
 
 // The kernels above index voxels with int (zf * Sz + yf * Sy + xf): every entry point refuses a larger volume before a launch.
@@ -511,71 +423,17 @@ int slice_acq_backward_impl(const T* transforms, const T* vol, const uint8_t* vo
 // adjoint, :754-836 adjoint backward), and no caller of the reference ever switches it on.  It is built here for
 // completeness of the module, one thread per slice pixel exactly as the reference formulates it; the scatters are
 // global atomics (memory-side on MI355X, ~16 G/s: fine for a mode nothing iterates on - the linear mode above is the
-// one that was re-formulated as a gather).
-template <typename T> struct InterpTap { int iv, xr, yr, zr; T pw, gx, gy, gz; };
-
-// One PSF tap at (x, y, z) already known to lie inside the volume.  false: the rounded voxel's offset falls outside the
-// PSF support.  GRAD: also d pw / d (x_psf, y_psf, z_psf), the corner sums of the reference (.cu:311-352).
-template <typename T, bool GRAD>
-__device__ __forceinline__ bool interp_tap(const T* __restrict__ t, const PixelGeom<T>& g, const T* __restrict__ psf, int d_p,
-                                           int h_p, int w_p, T x, T y, T z, int Sy, int Sz, InterpTap<T>& o) {
-  o.xr = (int)floor(x + (T)0.5); o.yr = (int)floor(y + (T)0.5); o.zr = (int)floor(z + (T)0.5);
-  o.iv = o.zr * Sz + o.yr * Sy + o.xr;
-  const T dx = o.xr - g.xc, dy = o.yr - g.yc, dz = o.zr - g.zc;
-  const T xp = t[0] * dx + t[4] * dy + t[8] * dz + (w_p - 1) / (T)2.0;
-  const T yp = t[1] * dx + t[5] * dy + t[9] * dz + (h_p - 1) / (T)2.0;
-  const T zp = t[2] * dx + t[6] * dy + t[10] * dz + (d_p - 1) / (T)2.0;
-  if (xp < 0 || yp < 0 || zp < 0 || xp >= w_p - 1 || yp >= h_p - 1 || zp >= d_p - 1) return false;
-  const int xf = (int)floor(xp), yf = (int)floor(yp), zf = (int)floor(zp);
-  const T wx = xp - xf, wy = yp - yf, wz = zp - zf;
-  const T* p0 = psf + (zf * h_p + yf) * w_p + xf;
-  const int py = w_p, pz = w_p * h_p;
-  const T c000 = p0[0], c100 = p0[1], c010 = p0[py], c001 = p0[pz], c110 = p0[1 + py], c101 = p0[1 + pz], c011 = p0[py + pz],
-          c111 = p0[1 + py + pz];
-  T pw = (T)0.0;  // corner order of the reference: 000, 100, 010, 001, 110, 101, 011, 111
-  pw += (1 - wx) * (1 - wy) * (1 - wz) * c000;
-  pw += wx * (1 - wy) * (1 - wz) * c100;
-  pw += (1 - wx) * wy * (1 - wz) * c010;
-  pw += (1 - wx) * (1 - wy) * wz * c001;
-  pw += wx * wy * (1 - wz) * c110;
-  pw += wx * (1 - wy) * wz * c101;
-  pw += (1 - wx) * wy * wz * c011;
-  pw += wx * wy * wz * c111;
-  o.pw = pw;
-  if constexpr (GRAD) {
-    T gx = (T)0.0, gy = (T)0.0, gz = (T)0.0;
-    gx -= (1 - wy) * (1 - wz) * c000; gy -= (1 - wx) * (1 - wz) * c000; gz -= (1 - wx) * (1 - wy) * c000;
-    gx += (1 - wy) * (1 - wz) * c100; gy -= wx * (1 - wz) * c100;       gz -= wx * (1 - wy) * c100;
-    gx -= wy * (1 - wz) * c010;       gy += (1 - wx) * (1 - wz) * c010; gz -= (1 - wx) * wy * c010;
-    gx -= (1 - wy) * wz * c001;       gy -= (1 - wx) * wz * c001;       gz += (1 - wx) * (1 - wy) * c001;
-    gx += wy * (1 - wz) * c110;       gy += wx * (1 - wz) * c110;       gz -= wx * wy * c110;
-    gx += (1 - wy) * wz * c101;       gy -= wx * wz * c101;             gz += wx * (1 - wy) * c101;
-    gx -= wy * wz * c011;             gy += (1 - wx) * wz * c011;       gz += (1 - wx) * wy * c011;
-    gx += wy * wz * c111;             gy += wx * wz * c111;             gz += wx * wy * c111;
-    o.gx = gx; o.gy = gy; o.gz = gz;
-  }
-  return true;
-}
+// one that was re-formulated as a gather).  interp_tap stands above the forward kernel, which takes it too.
 
 // the taps of a pixel: body(tap) for every non-zero PSF tap whose position lies inside the volume and whose rounded voxel
 // lies inside the PSF support
 template <typename T, bool GRAD, typename Body>
 __device__ __forceinline__ void for_interp_taps(const T* __restrict__ t, const PixelGeom<T>& g, const T* __restrict__ psf, int d_p,
                                                 int h_p, int w_p, int D, int H, int W, Body body) {
-  const int Sy = W, Sz = H * W;
-  int ip = 0;
-  for (int iz = -d_p / 2; iz < (d_p + 1) / 2; ++iz)
-    for (int iyp = -h_p / 2; iyp < (h_p + 1) / 2; ++iyp)
-      for (int ixp = -w_p / 2; ixp < (w_p + 1) / 2; ++ixp, ++ip) {
-        if (psf[ip] == (T)0.0) continue;
-        const T x = g.xc + t[0] * ixp + t[1] * iyp + t[2] * iz;
-        const T y = g.yc + t[4] * ixp + t[5] * iyp + t[6] * iz;
-        const T z = g.zc + t[8] * ixp + t[9] * iyp + t[10] * iz;
-        if (x < 0 || y < 0 || z < 0 || x >= W - 1 || y >= H - 1 || z >= D - 1) continue;
-        InterpTap<T> tap;
-        if (!interp_tap<T, GRAD>(t, g, psf, d_p, h_p, w_p, x, y, z, Sy, Sz, tap)) continue;
-        body(tap);
-      }
+  for_psf_taps(t, g, psf, d_p, h_p, w_p, D, H, W, [&](T, T, T, T, T x, T y, T z) {
+    InterpTap<T> tap;
+    if (interp_tap<T, GRAD>(t, g, psf, d_p, h_p, w_p, x, y, z, W, H * W, tap)) body(tap);
+  });
 }
 
 // the 12 pose sums of a pixel -> grad_transforms of its slice (wave reduction, one atomic per wave and entry)
@@ -584,7 +442,7 @@ __device__ __forceinline__ void add_pose_grad(T* __restrict__ grad_transforms, i
   if (uniform_slice) {
 #pragma unroll
     for (int k = 0; k < 12; ++k) {
-      const T s = wave_sum_any(gt[k]);
+      const T s = wave_sum(gt[k]);
       if ((threadIdx.x & 63) == 0 && s != (T)0.0) atomicAdd(grad_transforms + (size_t)in * 12 + k, s);
     }
   } else {

@@ -8,23 +8,21 @@
 //   { count, sum I, sum I^2, sum I J, sum J, sum J^2 },   I = simulated, J = acquired,
 // from which NCC and MSE follow.
 //
-// The per-pixel arithmetic is that of slice_acq_fwd<float, false, true> (slice_acq.hip; INTERP_PSF off, no volume mask):
-// the same affine map in double rounded once, the same tap skip rule, corner order and val / wsum, so the valid set is
-// the one that operator produces.  (The skip test is written in its negated form: a NaN coordinate skips the tap instead
-// of indexing the volume.)
+// A pixel's value under a pose comes from the functions slice_acq_fwd<float, false, true> calls (acq_taps.h: pixel_geom, the LDS
+// tap list, the inside test, linear_tap without a volume mask) and the same val / wsum, so value and valid set are that
+// operator's bit for bit.
 //
 // The sums are added in the reproducible order of slice_sums.h.  A workgroup serves all poses of its 256 pixels, so it parks
 // the wave sums per pose inside the pose loop and combines them after one barrier at the end, in that header's order.
 #include <hip/hip_runtime.h>
+#include "acq_taps.h"
 #include "slice_sums.h"
 #include "../../include/nesvor_hip.h"
 
 namespace {
+using namespace acq;
 
-constexpr int kMaxTaps = 1024;
 constexpr int kSums = 6;
-
-struct Tap { float x, y, z, w; };
 
 // grid: n * wgs workgroups of 256 pixels, wgs = ceil(h w / 256) per slice.  transforms: (n, K, 3, 4), this pass covers poses
 // k0 .. k0 + KT - 1.  partial: (n, K, wgs, 6) doubles.
@@ -34,19 +32,10 @@ __global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __rest
                                                              const float* __restrict__ transforms, const float* __restrict__ slices,
                                                              const uint8_t* __restrict__ slices_mask, int K, int k0, int h, int w,
                                                              int wgs, float res_slice, double* __restrict__ partial) {
-  __shared__ Tap taps[kMaxTaps];
+  __shared__ Tap<float> taps[kMaxTaps];
   __shared__ int n_taps;
   __shared__ float red[4][KT][kSums];
-  if (threadIdx.x == 0) {
-    int cnt = 0, ip = 0;
-    for (int iz = -d_p / 2; iz < (d_p + 1) / 2; ++iz)
-      for (int iy = -h_p / 2; iy < (h_p + 1) / 2; ++iy)
-        for (int ix = -w_p / 2; ix < (w_p + 1) / 2; ++ix, ++ip) {
-          const float pv = psf[ip];
-          if (pv != 0.f) taps[cnt++] = Tap{(float)ix, (float)iy, (float)iz, pv};  // the host checked d_p h_p w_p <= kMaxTaps
-        }
-    n_taps = cnt;
-  }
+  if (threadIdx.x == 0) n_taps = compact_taps(psf, d_p, h_p, w_p, taps);
   __syncthreads();
   const int in = blockIdx.x / wgs, wg = blockIdx.x - in * wgs;
   const int pix = wg * 256 + (int)threadIdx.x;
@@ -56,7 +45,6 @@ __global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __rest
   const bool on = inside && (slices_mask == nullptr || slices_mask[idx]);
   const float J = on ? slices[idx] : 0.f;
   const int ix = pix % w, iy = pix / w;
-  const int Sy = W, Sz = H * W;
   const int nt = n_taps;
 #pragma unroll 1
   for (int k = 0; k < KT; ++k) {
@@ -64,38 +52,11 @@ __global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __rest
     bool valid = false;
     if (on) {  // (a wave without a masked-in pixel branches over its tap loops: its exec mask is empty)
       const float* t = transforms + ((size_t)in * K + k0 + k) * 12;  // wave-uniform: the scalar path
-      const float r11 = t[0], r12 = t[1], r13 = t[2], r21 = t[4], r22 = t[5], r23 = t[6], r31 = t[8], r32 = t[9], r33 = t[10];
-      const float px = (float)((ix - (w - 1) / 2.) * (double)res_slice + (double)t[3]);
-      const float py = (float)((iy - (h - 1) / 2.) * (double)res_slice + (double)t[7]);
-      const float pz = t[11];
-      const float xc = r11 * px + r12 * py + r13 * pz + (W - 1) / 2.0f;
-      const float yc = r21 * px + r22 * py + r23 * pz + (H - 1) / 2.0f;
-      const float zc = r31 * px + r32 * py + r33 * pz + (D - 1) / 2.0f;
+      const PixelGeom<float> g = pixel_geom(t, ix, iy, h, w, res_slice, D, H, W);
       float val = 0.f, wsum = 0.f;
-      for (int j = 0; j < nt; ++j) {
-        const Tap tp = taps[j];
-        const float x = xc + r11 * tp.x + r12 * tp.y + r13 * tp.z;
-        const float y = yc + r21 * tp.x + r22 * tp.y + r23 * tp.z;
-        const float z = zc + r31 * tp.x + r32 * tp.y + r33 * tp.z;
-        if (!(x >= 0 && y >= 0 && z >= 0 && x < W - 1 && y < H - 1 && z < D - 1)) continue;
-        const int xf = (int)floorf(x), yf = (int)floorf(y), zf = (int)floorf(z);
-        const float wx = x - xf, wy = y - yf, wz = z - zf;
-        const int iv = zf * Sz + yf * Sy + xf;
-        // corner order as the operator accumulates: 000,100,010,001,110,101,011,111
-        const int off[8] = {0, 1, Sy, Sz, 1 + Sy, 1 + Sz, Sy + Sz, 1 + Sy + Sz};
-        const float cw[8] = {(1 - wx) * (1 - wy) * (1 - wz), wx * (1 - wy) * (1 - wz), (1 - wx) * wy * (1 - wz),
-                             (1 - wx) * (1 - wy) * wz,       wx * wy * (1 - wz),       wx * (1 - wy) * wz,
-                             (1 - wx) * wy * wz,             wx * wy * wz};
-        float v8[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) v8[c] = vol[iv + off[c]];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const float pw = cw[c] * tp.w;
-          val += pw * v8[c];
-          wsum += pw;
-        }
-      }
+      for_lds_taps(t, g, taps, nt, D, H, W, [&](float, float, float, float pv, float x, float y, float z) {
+        linear_tap(vol, (const uint8_t*)nullptr, trilinear_cell(x, y, z, H, W), pv, val, wsum);
+      });
       if (wsum > 0) { I = val / wsum; valid = true; }
     }
     // this pose's six values leave the registers at once: wave sums, parked in LDS per (wave, pose)

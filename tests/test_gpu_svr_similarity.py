@@ -101,17 +101,26 @@ def test_every_pixel_under_every_pose(device, geom, psf):
 
 @pytest.mark.parametrize("geom,psf", PIXEL_CASES, ids=PIXEL_IDS)
 def test_valid_set_is_the_acquisition_kernels(device, geom, psf):
-    """The header's design claim: the valid set is the one slice_acq_fwd produces - generic poses too.  All pixels unmasked: the
-    count of every pose equals the number of weight > 0 of ``slice_acq_cuda.forward``; and pixel by pixel from the one-hot run."""
+    """The header's design claim: valid set and value are the ones slice_acq_fwd produces (both kernels call csrc/acq_taps.h) -
+    generic poses too.  All pixels unmasked: the count of every pose equals the number of weight > 0 of
+    ``slice_acq_cuda.forward``; and pixel by pixel from the one-hot run, where a single non-zero term enters the wave sum and every
+    later add is in double: the validity, and on every valid pixel sum I equal to the operator's ``slices`` BIT FOR BIT under the
+    same pose and sum I^2 equal to its fp32 square."""
     from nesvor_amd import slice_acq_cuda as A
 
     c = R.case(geom, psf)
     e = torch.empty(0, device=device)
-    _, wgt = A.forward(c.poses.to(device), c.vol[None, None].to(device), e, e, c.psf.to(device), c.shape, c.res, True, False)
+    sim, wgt = A.forward(c.poses.to(device), c.vol[None, None].to(device), e, e, c.psf.to(device), c.shape, c.res, True, False)
     valid = (wgt[:, 0] > 0).cpu()
     got = _svr(device, c, c.poses[None], c.J[:1], None)
     assert torch.equal(got[0, :, 0], valid.flatten(1).sum(1).double())
-    assert torch.equal(_by_pose(c, _one_hot(device, c))[..., 0], valid.flatten(1).double())
+    own = _by_pose(c, _one_hot(device, c))  # (27, h w, 6)
+    assert torch.equal(own[..., 0], valid.flatten(1).double())
+    I, v = sim[:, 0].cpu().flatten(1), valid.flatten(1)
+    assert I.dtype == torch.float32
+    for col, want in ((1, I), (2, I * I)):
+        differs = (own[..., col] != want.double()) & v
+        assert not bool(differs.any()), (col, "first (pose, pixel) that differs", differs.nonzero()[0].tolist(), int(differs.sum()))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
