@@ -193,6 +193,13 @@ typedef struct {
                                          re-ordered into rows (4 L F bytes per point): the aggregation pass then reads whole rows
                                          instead of 4-byte words at scattered columns (1.80 -> 0.9 ms at N = 2^20 uniform points) */
 #define NESVOR_LAYOUT_MASK 3          /* the layout proper; the other bits are hints */
+/* `stages` of the owner-computes backward, OR-ed */
+#define NESVOR_HG_STAGE_AGGREGATE 1    /* the aggregation launch */
+#define NESVOR_HG_STAGE_OWNER 2        /* the owner launch (AGGREGATE then OWNER on one stream == both at once, NESVOR_HG_STAGE_ALL) */
+#define NESVOR_HG_STAGE_ALL 3
+#define NESVOR_HG_STAGE_KEEP 4         /* a later launch of a split backward (same u, N, workspace): the first launch's queue tails,
+                                          sample order and re-ordered dpe are kept */
+#define NESVOR_HG_STAGE_ACCUMULATE_U 8 /* the input gradient of this launch's levels is added to grad_u, not written over it */
 
 /* u (N,3) in [0,1]; table flat fp32; pe out. */
 int nesvor_hashgrid_forward(const nesvor_grid_t* grid, const float* u, const float* table, float* pe,
@@ -214,80 +221,72 @@ int nesvor_hashgrid_forward_bounded(const nesvor_grid_t* grid, const float* u, c
 int64_t nesvor_hashgrid_forward_workspace_bytes(const nesvor_grid_t* grid, int64_t N, int layout);
 int nesvor_hashgrid_forward_unclustered(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N,
                                         int layout, float* pe_absmax, void* workspace, int64_t workspace_bytes, void* stream);
-/* grad_table is ACCUMULATED into (caller zero-fills when needed);
- * grad_u (N,3) is OVERWRITTEN, or NULL to skip the input gradient.
- * Owner-computes scatter (LDS aggregation per 256 samples -> per-chunk queues ->
- * one owner workgroup per table chunk); `workspace` is scratch device memory of
- * nesvor_hashgrid_backward_workspace_bytes(grid, N, queue_scale) bytes (-1: grid outside the
- * plan's limits, use the _atomic variant).  The limits: at most 32 levels; at most 256 chunks per
- * level (a chunk is the largest power of two of entries with chunk * n_features <= 8192 floats);
- * at most 4064 chunks over all levels (one queue counter each, in front of the 32 overflow
- * counters); a level's queues below 2^32 bytes and all queues together below 2^32 records (a
- * matter of N: 8 N records per level at queue_scale 1).  Every backward entry point that takes a
- * workspace, and nesvor_hashgrid_forward_plan with a cloud_plan, return hipErrorInvalidValue for
- * a grid outside them.  `stages`: 3 = whole backward;
- * 1 = aggregation launch only, 2 = owner launch only (so a caller can bracket
- * each launch with its own events; 1 then 2 on one stream == 3).
- * `queue_scale`: HOST array of one float per level in (0, 1], or NULL (= 1 everywhere): the fraction of the worst-case
- * queue capacity (8 records per point and level) to provide for each level.  A record that finds its queue full is added
- * with a global atomic instead - the result is exact for any scale - and counted: 32 uint32 counters (one per level) of
- * the latest backward sit at byte nesvor_hashgrid_backward_overflow_offset(workspace) of the workspace, so that a caller
- * can start small (a PSF-cloud batch fills a few percent of the worst case at most levels) and grow the levels that
- * overflow.  The same `queue_scale` must be passed to the size query and to every launch on that workspace. */
+/* The backward: grad_table is ACCUMULATED into (the caller zero-fills when needed); grad_u (N,3) is OVERWRITTEN, or NULL to skip
+ * the input gradient.  Owner-computes scatter: LDS aggregation per 256 samples -> per-chunk queues -> one owner workgroup per
+ * table chunk.  It is ONE call with five entry points; each names the fields it sets, the others keep their defaults:
+ *   nesvor_hashgrid_backward           the common arguments; `stages` bits other than AGGREGATE and OWNER are ignored
+ *   nesvor_hashgrid_backward_levels    + level_begin, level_end
+ *   nesvor_hashgrid_backward_bounded   + level_begin, level_end, dy_bound
+ *   nesvor_hashgrid_backward_plan      + level_begin, level_end, dy_bound, order, cloud_plan
+ *   nesvor_hashgrid_backward_adamw     + dy_bound, exp_avg, exp_avg_sq, adam (declared below); KEEP, ACCUMULATE_U and N <= 0 are refused
+ * The fields:
+ *   workspace    scratch device memory of nesvor_hashgrid_backward_workspace_bytes(grid, N, queue_scale) bytes, shared by the
+ *                launches of one backward.  _ex: the same for launches with this `layout` (hints included) - without the point
+ *                order's scratch unless NESVOR_LAYOUT_UNCLUSTERED, with room for dpe as rows for NESVOR_LAYOUT_FEATURE_MAJOR |
+ *                _UNCLUSTERED | _DY_SCRATCH (not where such rows exceed the copy kernel's LDS, see the forward's query: dpe is then
+ *                read in place).  Its first nesvor_hashgrid_backward_workspace_zero_bytes() bytes are zero-filled ONCE after
+ *                allocation; the backward keeps them consistent (every aggregation pass zero-fills the next backward's queue tails).
+ *   stages       NESVOR_HG_STAGE_*: ALL, or AGGREGATE and OWNER in two calls (to bracket each launch with events, or on two streams).
+ *   level_begin, level_end   only these levels (default: all): a data-parallel step runs the fine levels first, starts their
+ *                all-reduce and overlaps it with the rest - every launch after the first with KEEP | ACCUMULATE_U.
+ *   queue_scale  HOST array of one float per level in (0, 1], or NULL (= 1): the fraction of the worst-case queue capacity (8
+ *                records per point and level) to provide.  A record that finds its queue full is added with a global atomic -
+ *                exact for any scale - and counted: 32 uint32 counters (one per level) of the latest backward sit at byte
+ *                nesvor_hashgrid_backward_overflow_offset(workspace) of the workspace, so a caller can start small (a PSF-cloud batch
+ *                fills a few percent) and grow the levels that overflow.  The same array goes to the size query and every launch.
+ *   dy_bound     device scalar >= max |dpe| over the batch (any upper bound within ~2^20 of the true maximum keeps fp32
+ *                accuracy: the merge table sums in 64-bit fixed point scaled by it), or NULL (default): the kernel determines
+ *                each workgroup's maximum itself by reading dpe once more (134 MB at N = 2^20).
+ *   order, cloud_plan   the hand-over from the forward of the SAME points, or NULL (default).  The aggregation pass starts with
+ *                work that depends on u alone: every 256-point cloud's order by the Morton code of its finest-level cells, its
+ *                bounding box, lattice boxes, window bits and box-round schedule.  nesvor_hashgrid_forward_plan is
+ *                nesvor_hashgrid_forward_bounded on clustered points (always the per-cloud kernel; pe, pe_absmax bit-identical)
+ *                that also writes `order` - nesvor_hashgrid_cloud_order_bytes(N) bytes, exactly those the aggregation pass finds
+ *                for itself and keeps at byte nesvor_hashgrid_backward_order_offset() of its workspace - and, unless NULL,
+ *                `cloud_plan`: nesvor_hashgrid_cloud_plan_bytes(grid, N) bytes, 16-byte aligned (n_features <= 2; 0 = no plan
+ *                for this grid), with the chunking of `queue_scale`.  With `order` no launch sorts, any level range; with
+ *                `cloud_plan` too (needs `order`, all levels) the set-up is read from the records.  Both hold for the u, N, grid
+ *                and queue_scale they were written for; not with NESVOR_LAYOUT_UNCLUSTERED.
+ * N <= 0 returns 0 at once.  hipErrorInvalidValue: n_levels outside 1..32, n_features not 1, 2, 4 or 8, an unknown layout, a NULL
+ * workspace, `stages` without a launch, an empty or outside level range, a hand-over against the rules above, and a grid
+ * outside the plan's limits (the size queries return -1: use nesvor_hashgrid_backward_atomic) - at most 256 chunks per level (a
+ * chunk is the largest power of two of entries with chunk * n_features <= 8192 floats), at most 4064 chunks over all levels, a
+ * level's queues below 2^32 bytes and all queues below 2^32 records (8 N records per level at queue_scale 1);
+ * nesvor_hashgrid_forward_plan with a cloud_plan refuses such a grid too. */
 int64_t nesvor_hashgrid_backward_workspace_bytes(const nesvor_grid_t* grid, int64_t N, const float* queue_scale);
-/* The same for a backward that will be called with this `layout` (hints included): larger than the above only for
- * NESVOR_LAYOUT_FEATURE_MAJOR | NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH (room for dpe as rows in the points'
- * order; not where such rows exceed the copy kernel's LDS - see nesvor_hashgrid_forward_workspace_bytes - the backward then
- * reads dpe in place). */
 int64_t nesvor_hashgrid_backward_workspace_bytes_ex(const nesvor_grid_t* grid, int64_t N, const float* queue_scale, int layout);
-/* The first nesvor_hashgrid_backward_workspace_zero_bytes() bytes of a workspace (its two queue-tail regions) must be
- * zero-filled ONCE after the workspace is allocated; the backward keeps them consistent afterwards (every aggregation
- * pass zero-fills the region the next backward will use, so no memset launch is needed per call). */
 int64_t nesvor_hashgrid_backward_workspace_zero_bytes(void);
 int64_t nesvor_hashgrid_backward_overflow_offset(void* workspace);
+int64_t nesvor_hashgrid_backward_order_offset(const nesvor_grid_t* grid, int64_t N, const float* queue_scale);
+int64_t nesvor_hashgrid_cloud_order_bytes(int64_t N);
+int64_t nesvor_hashgrid_cloud_plan_bytes(const nesvor_grid_t* grid, int64_t N);
+int nesvor_hashgrid_forward_plan(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N, int layout,
+                                 float* pe_absmax, void* order, void* cloud_plan, const float* queue_scale, void* stream);
 int nesvor_hashgrid_backward(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
                              float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
                              const float* queue_scale, void* stream);
-
-/* The same backward restricted to levels [level_begin, level_end): a data-parallel step runs the fine levels first,
- * starts their all-reduce and overlaps it with the remaining levels.  Extra `stages` bits: 4 = do not reset the
- * queue tails and re-use the sample order the first launch sorted (every launch of one backward after the first: same
- * u, same N), 8 = add the input gradient of these levels to grad_u instead of overwriting it.  The launches of one
- * backward share `workspace`. */
 int nesvor_hashgrid_backward_levels(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
                                     float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
                                     int level_begin, int level_end, const float* queue_scale, void* stream);
-/* nesvor_hashgrid_backward_levels with a caller-supplied bound: dy_bound = device scalar >= max |dpe| over the batch (any
- * upper bound within ~2^20 of the true maximum keeps fp32 accuracy: the merge table sums in 64-bit fixed point scaled by
- * it), or NULL = the kernel determines each workgroup's maximum itself by reading dpe once more (134 MB at N = 2^20). */
 int nesvor_hashgrid_backward_bounded(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
                                      float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
                                      int level_begin, int level_end, const float* queue_scale, const float* dy_bound,
                                      void* stream);
-/* Hand-over from the forward to the backward of the SAME points.  The aggregation pass of the backward starts with work that
- * depends on u alone: the order of every 256-point cloud by the Morton code of its finest-level cells, the cloud's bounding
- * box, its lattice boxes and window bits per level and the schedule of its box rounds.  nesvor_hashgrid_forward_plan is
- * nesvor_hashgrid_forward_bounded on clustered points (always the one-workgroup-per-cloud kernel, pe and pe_absmax bit-identical)
- * that also writes
- *   order:      nesvor_hashgrid_cloud_order_bytes(N) bytes - exactly the bytes the aggregation pass finds for itself;
- *   cloud_plan: NULL, or nesvor_hashgrid_cloud_plan_bytes(grid, N) bytes, 16-byte aligned (n_features <= 2; 0 = no plan for this
- *               grid) - one record per cloud, computed with the chunking of nesvor_hashgrid_backward_*(.., queue_scale).
- * nesvor_hashgrid_backward_plan is nesvor_hashgrid_backward_bounded that takes them: with `order` (non-NULL) no launch sorts, any
- * level range; with `cloud_plan` as well (all levels only) the set-up is read from the records.  Both are valid only for the u, N,
- * grid and queue_scale levels' chunking they were written for; not with NESVOR_LAYOUT_UNCLUSTERED.  order == cloud_plan == NULL:
- * nesvor_hashgrid_backward_bounded.  nesvor_hashgrid_backward_order_offset: where in `workspace` a backward WITHOUT a hand-over
- * keeps the order it sorted (tests compare the two).
- * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.) */
-int64_t nesvor_hashgrid_cloud_order_bytes(int64_t N);
-int64_t nesvor_hashgrid_cloud_plan_bytes(const nesvor_grid_t* grid, int64_t N);
-int64_t nesvor_hashgrid_backward_order_offset(const nesvor_grid_t* grid, int64_t N, const float* queue_scale);
-int nesvor_hashgrid_forward_plan(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N, int layout,
-                                 float* pe_absmax, void* order, void* cloud_plan, const float* queue_scale, void* stream);
 int nesvor_hashgrid_backward_plan(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
                                   float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
                                   int level_begin, int level_end, const float* queue_scale, const float* dy_bound,
                                   const void* order, const void* cloud_plan, void* stream);
-/* Same contract, tcnn-style per-corner global atomics (slow on MI355X: memory-side atomics). */
+/* Same contract, tcnn-style per-corner global atomics (slow on MI355X: memory-side atomics); no workspace, no plan limits. */
 int nesvor_hashgrid_backward_atomic(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
                                     float* grad_table, float* grad_u, int64_t N, int layout, void* stream);
 
@@ -674,7 +673,7 @@ int nesvor_loss_scale_weights(const float* base, float* out, int n, const nesvor
  * never travels through HBM.  Equals nesvor_hashgrid_backward_bounded(stages) over all levels followed by
  * nesvor_adamw_step(table, grad_table, exp_avg, exp_avg_sq, <table numel>, ..., zero_grad = 1): grad_table is read (it may
  * hold an earlier backward's gradient) and is all zero afterwards, but the gradient of THIS backward is never stored in it.
- * stages: 1 = aggregation pass, 2 = owner pass + AdamW, 3 = both (as nesvor_hashgrid_backward; no level ranges).
+ * One of the entry points of the hash-grid backward's contract (above): stages AGGREGATE, OWNER (+ AdamW) or both, all levels.
  * table, exp_avg, exp_avg_sq, grad_table: (sum of level sizes, F), the layout nesvor_hashgrid_forward reads. */
 int nesvor_hashgrid_backward_adamw(const nesvor_grid_t* grid, const float* u, float* table, const float* dpe,
                                    float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,

@@ -24,6 +24,12 @@ STEP_BIAS_SUM_RESUME = 32  # ... and the rest of that phase, behind the event of
 LAYOUT_CLUSTERED = 4  # forward hint, OR-ed into the layout: 256 consecutive points are one spatial cluster
 LAYOUT_UNCLUSTERED = 8  # backward hint, OR-ed into the layout: consecutive points are not clustered - order them by cell first
 LAYOUT_DY_SCRATCH = 16  # with LAYOUT_UNCLUSTERED | LAYOUT_FEATURE_MAJOR: the workspace (sized by ..._workspace_bytes_ex) has room for dpe as rows
+# `stages` of the hash-grid backward entry points (NESVOR_HG_STAGE_*)
+HG_STAGE_AGGREGATE = 1  # the aggregation launch
+HG_STAGE_OWNER = 2  # the owner launch
+HG_STAGE_ALL = HG_STAGE_AGGREGATE | HG_STAGE_OWNER
+HG_STAGE_KEEP = 4  # a later launch of a split backward: keep the queue tails and the point order of the first
+HG_STAGE_ACCUMULATE_U = 8  # add this launch's input gradient to grad_u instead of overwriting it
 
 
 class GridT(Structure):

@@ -2232,146 +2232,226 @@ inline int sort_points(const float* u, int64_t N, uint32_t* base, hipStream_t st
   return (int)hipGetLastError();
 }
 
-template <int F, int LAYOUT>
-int launch_bwd_owner(const nesvor_grid_t* g, const float* u, const float* table, const float* dpe, float* gt,
-                     float* gu, int64_t N, void* workspace, int stages, int level_begin, int level_end, const float* queue_scale,
-                     const float* dy_bound, const OwnerAdam* adam, hipStream_t st, int hints = 0,
-                     const uint8_t* fwd_order = nullptr, const uint32_t* cloud_plan = nullptr) {  // the forward's hand-over (nesvor_hashgrid_forward_plan)
-  const bool unclustered = (hints & NESVOR_LAYOUT_UNCLUSTERED) != 0;
-  // the forward's order is the order of the points as given; its plan covers all levels at F <= 2
-  if ((fwd_order != nullptr || cloud_plan != nullptr) && unclustered) return (int)hipErrorInvalidValue;
-  if (cloud_plan != nullptr && (fwd_order == nullptr || F > 2 || level_begin != 0 || level_end != g->n_levels)) return (int)hipErrorInvalidValue;
-  if constexpr (LAYOUT == NESVOR_LAYOUT_FEATURE_MAJOR) {
-    // unclustered feature-major dpe with room for its re-ordered copy (NESVOR_LAYOUT_DY_SCRATCH: the workspace was sized by
-    // nesvor_hashgrid_backward_workspace_bytes_ex with the same layout): the aggregation pass runs in its row-major form on the copy
-    // (rows too wide for the copy kernel's LDS: this instantiation reads dpe through perm, and the size query left the copy out)
-    if (unclustered && (hints & NESVOR_LAYOUT_DY_SCRATCH) && (stages & 1) && reorder_fits_lds(g->n_levels * F))
-      return launch_bwd_owner<F, NESVOR_LAYOUT_ROW_MAJOR>(g, u, table, dpe, gt, gu, N, workspace, stages, level_begin, level_end, queue_scale,
-                                                          dy_bound, adam, st, hints | 0x10000, fwd_order, cloud_plan);
+// ---- host layer: where things live in a workspace, what a backward call asks for, and the launches ----------------------------
+constexpr int kRefused = (int)hipErrorInvalidValue, kProceed = -1;  // (kProceed: validate() below)
+constexpr uint64_t align256(uint64_t bytes) { return (bytes + 255) & ~(uint64_t)255; }
+template <typename T> T* at(void* base, uint64_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+// (the point order starts at an ABSOLUTE multiple of 256 bytes - what stands in front of it has any multiple of 4 - so 256 of slack)
+inline uint32_t* at_next_256(void* base, uint64_t off) { return reinterpret_cast<uint32_t*>(align256(reinterpret_cast<uintptr_t>(base) + off)); }
+inline bool levels_ok(const nesvor_grid_t* g) { return g->n_levels > 0 && g->n_levels <= NESVOR_MAX_LEVELS; }
+inline bool grid_ok(const nesvor_grid_t* g, int layout) {  // ... and a shape the kernels are instantiated for: every launching entry point
+  const int F = g->n_features, lay = layout & NESVOR_LAYOUT_MASK;
+  return levels_ok(g) && (F == 1 || F == 2 || F == 4 || F == 8) && (lay == NESVOR_LAYOUT_ROW_MAJOR || lay == NESVOR_LAYOUT_FEATURE_MAJOR);
+}
+// The backward's workspace, region after region (the table: DESIGN.md, "The hash-grid host layer"): what size queries and launches read.
+// The head is zero-filled once by the caller: two tails regions (tails_parity: which one a backward uses; its 32 overflow counters are
+// the last words of counter set 0) and the owner pass's tickets.
+struct BwdWorkspace {
+  struct Region { uint64_t off, bytes; };
+  static constexpr uint64_t kZeroBytes = kHeadBytes, kTicketsOff = 2 * kTailBytes;
+  static constexpr uint64_t tails_off(int parity) { return parity ? kTailBytes : 0; }
+  static constexpr uint64_t overflow_off(int parity) { return tails_off(parity) + kOverflowBase * sizeof(uint32_t); }
+  Region records;  // the plan's queues: n_records of 4 (1 + F) bytes
+  Region order;    // one byte per point, whole 256s: the sample order of every cloud
+  Region slack;    // 256 bytes for perm's alignment
+  Region sort;     // perm and the counting sort's scratch (sort_bufs), whole 256s; empty unless the launches are unclustered
+  Region rows;     // behind it dpe as rows (n_pad, E) and 256 spare bytes; empty unless the hints ask for them and the copy kernel's LDS takes one
+  BwdPlan plan;    // the chunking the records are sized for
+  // -> bytes in all for launches with this layout's hints (any_hint: whatever hints, but no rows), or -1: outside the plan's limits
+  int64_t init(const nesvor_grid_t* g, int64_t N, const float* queue_scale, int layout, bool any_hint = false) {
+    constexpr int kRowsHints = NESVOR_LAYOUT_FEATURE_MAJOR | NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH;
+    uint64_t n_rec, end = kZeroBytes;
+    if (!levels_ok(g) || !make_plan(g, N, &plan, &n_rec, queue_scale)) return -1;
+    auto put = [&end](uint64_t bytes) { const Region r{end, bytes}; end += bytes; return r; };
+    records = put(n_rec * (1 + g->n_features) * sizeof(uint32_t));
+    order = put(align256((uint64_t)N));
+    slack = put(256);
+    sort = put(any_hint || (layout & NESVOR_LAYOUT_UNCLUSTERED) ? align256(sort_bytes(N)) : 0);
+    const bool with_rows = (layout & (NESVOR_LAYOUT_MASK | kRowsHints)) == kRowsHints && reorder_fits_lds(g->n_levels * g->n_features);
+    rows = put(with_rows ? 256 + align256((uint64_t)N) * (g->n_levels * g->n_features) * sizeof(float) : 0);
+    return (int64_t)end;
   }
-  BwdPlan plan;
-  uint64_t n_rec;
-  if (!make_plan(g, N, &plan, &n_rec, queue_scale)) return (int)hipErrorInvalidValue;
-  plan.level_begin = level_begin; plan.level_end = level_end;
-  plan.accumulate_u = (stages & 8) ? 1 : 0;
-  // bit 4: a later launch of a split backward - same region, the queue tails of its levels are still zero
-  const int par = tails_parity(workspace, (stages & 1) && !(stages & 4));
-  uint32_t* tails = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + (par ? kTailBytes : 0));
-  uint32_t* tails_next = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + (par ? 0 : kTailBytes));
-  uint32_t* records = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + kHeadBytes);
-  uint8_t* const own_order = reinterpret_cast<uint8_t*>(records) + n_rec * (1 + F) * sizeof(uint32_t);  // ceil(N / 256) * 256 bytes
-  uint8_t* const order = fwd_order != nullptr ? const_cast<uint8_t*>(fwd_order) : own_order;  // (only read in mode 2)
-  const int order_mode = (fwd_order != nullptr || (stages & 4)) ? 2 : 1;
-  // unclustered input: the points in cell order (a later launch of a split backward finds the first launch's order in place)
-  // (256-byte aligned in absolute terms: the records in front have any multiple of 4 bytes; the size query leaves the slack)
-  uint32_t* const perm_buf = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(own_order) + (uintptr_t)((N + 255) / 256) * 256 + 255) & ~(uintptr_t)255);
-  const uint32_t* const perm = unclustered ? perm_buf : nullptr;
-  dim3 grid((unsigned)((N + 255) / 256)), block(256);
-  hipError_t e;
-  int dy_by_slot = 0;
-  if (!(stages & 1)) goto owner_stage;
-  if (unclustered && !(stages & 4)) {
-    const int se = sort_points(u, N, perm_buf, st);
+  uint32_t* tails_of(void* base, int parity) const { return at<uint32_t>(base, tails_off(parity)); }
+  uint32_t* tickets_of(void* base) const { return at<uint32_t>(base, kTicketsOff); }
+  uint32_t* records_of(void* base) const { return at<uint32_t>(base, records.off); }
+  uint8_t* order_of(void* base) const { return at<uint8_t>(base, order.off); }
+  uint32_t* perm_of(void* base) const { return at_next_256(base, slack.off); }
+  float* rows_of(void* base) const { return at<float>(perm_of(base), sort.bytes); }
+};
+// The unclustered forward's: slack | the point order and its scratch | for feature-major output, pe as rows (n_pad, E)
+struct FwdWorkspace {
+  uint64_t sort, rows;  // bytes
+  FwdWorkspace(const nesvor_grid_t* g, int64_t N, int layout) : sort(align256(sort_bytes(N))), rows(0) {
+    if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR) rows = align256((uint64_t)N) * (g->n_levels * g->n_features) * sizeof(float);
+  }
+  uint64_t bytes() const { return 256 + sort + rows; }
+  uint32_t* perm_of(void* base) const { return at_next_256(base, 0); }
+  float* rows_of(void* base) const { return rows ? at<float>(perm_of(base), sort) : nullptr; }
+};
+
+// One call of the owner-computes backward.  The first twelve fields are the arguments every entry point has, in their order.
+struct BwdRequest {
+  const nesvor_grid_t* g;
+  const float *u, *table, *dpe;  // dpe as `layout` says, until the launch code has re-ordered it (dpe_rows)
+  float *gt, *gu;                // gu NULL: no input gradient
+  int64_t N;
+  int layout;                    // NESVOR_LAYOUT_* of dpe with the caller's hints
+  void* workspace;
+  int stages;                    // NESVOR_HG_STAGE_*
+  const float* queue_scale;      // host array or NULL
+  void* stream;
+  bool all_levels = true;        // or [level_begin, level_end)
+  int level_begin = 0, level_end = 0;
+  const float* dy_bound = nullptr;                    // device scalar
+  const void *order = nullptr, *cloud_plan = nullptr; // the forward's hand-over (nesvor_hashgrid_forward_plan)
+  bool adamw = false;            // the owner pass takes the table's AdamW step (`table` is written) on these moments, with these coefficients
+  float *exp_avg = nullptr, *exp_avg_sq = nullptr; const nesvor_adamw_t* adam = nullptr;
+  // where the entry points' rules differ
+  int stages_ignored = 0;        // bits dropped without a word (nesvor_hashgrid_backward: all but the two launches)
+  int stages_refused = 0;        // bits that refuse the call (_adamw: those of a split backward)
+  bool refuse_empty = false;     // N <= 0 is an error, not a no-op (_adamw)
+  // set by the launch code: dpe now points at rows (N, E) in the points' order, the aggregation pass runs in its row-major form
+  bool dpe_rows = false;
+  bool unclustered() const { return (layout & NESVOR_LAYOUT_UNCLUSTERED) != 0; }
+  hipStream_t st() const { return (hipStream_t)stream; }
+};
+// Every refusal rule of the backward entry points.  -> kProceed, 0 (nothing to do) or kRefused
+inline int validate(BwdRequest& r) {
+  if (r.N <= 0) return r.refuse_empty ? kRefused : 0;
+  if (!grid_ok(r.g, r.layout) || r.workspace == nullptr) return kRefused;
+  if (r.all_levels) r.level_begin = 0, r.level_end = r.g->n_levels;
+  r.stages &= ~r.stages_ignored;
+  if ((r.stages & NESVOR_HG_STAGE_ALL) == 0 || (r.stages & r.stages_refused) != 0) return kRefused;
+  if (r.level_begin < 0 || r.level_end > r.g->n_levels || r.level_begin >= r.level_end) return kRefused;
+  if (r.adamw && (r.table == nullptr || r.gt == nullptr || r.exp_avg == nullptr || r.exp_avg_sq == nullptr || r.adam == nullptr)) return kRefused;
+  // the hand-over: records read 16 bytes at a time; an order of the points as given; a plan needs the order and covers all levels at F <= 2
+  if ((reinterpret_cast<uintptr_t>(r.cloud_plan) & 15u) != 0 || ((r.order != nullptr || r.cloud_plan != nullptr) && r.unclustered())) return kRefused;
+  if (r.cloud_plan != nullptr && (r.order == nullptr || r.g->n_features > 2 || r.level_begin != 0 || r.level_end != r.g->n_levels)) return kRefused;
+  return kProceed;
+}
+
+// Raises KERNEL's dynamic-LDS limit to `lds` bytes where that is more than every kernel may use; once per kernel and size.
+template <auto* KERNEL>
+hipError_t raise_dynamic_lds(size_t lds) {
+  static std::mutex mu;
+  static size_t raised = 48 * 1024;
+  std::lock_guard<std::mutex> lock(mu);
+  if (lds <= raised) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e == hipSuccess) raised = lds;
+  return e;
+}
+
+// In front of an aggregation launch on unclustered points: the points in cell order and - with room for it - feature-major dpe as
+// rows in that order.  A later launch of a split backward finds both in place.
+inline int bwd_order_points(BwdRequest& r, const BwdWorkspace& w) {
+  if (!r.unclustered()) return 0;
+  uint32_t* const perm = w.perm_of(r.workspace);
+  float* const rows = w.rows.bytes ? w.rows_of(r.workspace) : nullptr;  // (none: row-major dpe, no room, or rows too wide for the copy kernel's LDS)
+  if (!(r.stages & NESVOR_HG_STAGE_KEEP)) {
+    const int se = sort_points(r.u, r.N, perm, r.st());
     if (se) return se;
-  }
-  if (hints & 0x10000) {  // (re-entered from the feature-major instantiation: see the top)
-    const int E = g->n_levels * F;
-    float* rows = reinterpret_cast<float*>(reinterpret_cast<char*>(perm_buf) + ((sort_bytes(N) + 255) & ~(uint64_t)255));
-    // (a later launch of a split backward finds the first launch's copy in place)
-    if (!(stages & 4)) {
-      const size_t lds = reorder_lds_bytes(E);
-      if (lds > 48 * 1024) {
-        static std::mutex mu;
-        static size_t raised = 0;
-        std::lock_guard<std::mutex> lock(mu);
-        if (lds > raised) {
-          e = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_dy_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          if (e != hipSuccess) return (int)e;
-          raised = lds;
-        }
-      }
-      hipLaunchKernelGGL(gather_dy_rows_kernel, dim3((unsigned)((N + kGatherPts - 1) / kGatherPts)), dim3(256), lds, st, dpe,
-                         sort_bufs(perm_buf, N, sort_plan(N)), rows, N, E);
+    const int E = r.g->n_levels * r.g->n_features;
+    const size_t lds = reorder_lds_bytes(E);
+    if (rows != nullptr) {
+      const hipError_t e = raise_dynamic_lds<gather_dy_rows_kernel>(lds);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(gather_dy_rows_kernel, dim3((unsigned)((r.N + kGatherPts - 1) / kGatherPts)), dim3(256), lds, r.st(), r.dpe,
+                         sort_bufs(perm, r.N, sort_plan(r.N)), rows, r.N, E);
     }
-    dpe = rows;
-    dy_by_slot = 1;
   }
-  {
-#define NESVOR_LAUNCH_AGG(IG, BD)                                                                                         \
-    hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, IG, BD>), grid, block, 0, st, *g, plan, u, table, dpe, gt, gu, \
-                       tails, tails_next, records, N, dy_bound, order, order_mode, perm, dy_by_slot)
-#define NESVOR_LAUNCH_AGG_PLAN(IG, BD)                                                                                      \
-    hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, IG, BD, true>), grid, block, 0, st, *g, plan, u, table, dpe, gt, gu, \
-                       tails, tails_next, records, N, dy_bound, order, order_mode, perm, dy_by_slot, cloud_plan)
-    const bool bounded = dy_bound != nullptr;  // (the bound scales the merge table's fixed-point sums)
-    bool planned = false;
-    if constexpr (F <= 2) {
-      if (cloud_plan != nullptr) {
-        planned = true;
-        if (gu != nullptr) { if (bounded) NESVOR_LAUNCH_AGG_PLAN(true, true); else NESVOR_LAUNCH_AGG_PLAN(true, false); }
-        else { if (bounded) NESVOR_LAUNCH_AGG_PLAN(false, true); else NESVOR_LAUNCH_AGG_PLAN(false, false); }
-      }
-    }
-#undef NESVOR_LAUNCH_AGG_PLAN
-    if (planned) { }
-    else if (gu != nullptr) { if (bounded) NESVOR_LAUNCH_AGG(true, true); else NESVOR_LAUNCH_AGG(true, false); }
-    else { if (bounded) NESVOR_LAUNCH_AGG(false, true); else NESVOR_LAUNCH_AGG(false, false); }
-#undef NESVOR_LAUNCH_AGG
+  if (rows != nullptr) r.dpe = rows, r.dpe_rows = true;
+  return 0;
+}
+
+// The aggregation launch.  The kernel is instantiated over (input gradient, caller's bound, forward's plan - at F <= 2 only):
+// aggregate<F, LAYOUT>(r, w, parity, flags...) moves one flag at a time into the template arguments.
+template <int F, int LAYOUT, bool INPUT_GRAD, bool BOUND, bool PLAN>
+void aggregate(const BwdRequest& r, const BwdWorkspace& w, int parity) {
+  if constexpr (!PLAN || F <= 2) {
+    const bool ordered = r.order != nullptr || (r.stages & NESVOR_HG_STAGE_KEEP);  // the forward's order or the first launch's: only read
+    uint8_t* const order = r.order != nullptr ? static_cast<uint8_t*>(const_cast<void*>(r.order)) : w.order_of(r.workspace);
+    hipLaunchKernelGGL((hashgrid_bwd_aggregate<F, LAYOUT, INPUT_GRAD, BOUND, PLAN>), dim3((unsigned)((r.N + 255) / 256)), dim3(256), 0, r.st(), *r.g,
+                       w.plan, r.u, r.table, r.dpe, r.gt, r.gu, w.tails_of(r.workspace, parity), w.tails_of(r.workspace, parity ^ 1),
+                       w.records_of(r.workspace), r.N, r.dy_bound, order, ordered ? 2 : 1, r.unclustered() ? w.perm_of(r.workspace) : nullptr,
+                       r.dpe_rows ? 1 : 0, static_cast<const uint32_t*>(r.cloud_plan));
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-owner_stage:
-  if (stages & 2) {
-    OwnerAdam oa{};
-    // only the workgroups of this launch's level range (a launch over all ids, the others returning at once, cost the pipelined
-    // table update of the training step 30 us per pair of launches: gpurun_out/r06g)
-    const uint32_t wg_base = owner_grid(g, plan, 0, plan.level_begin);
-    const uint32_t og = owner_grid(g, plan, plan.level_begin, plan.level_end);
-    if (og == 0u) return (int)hipGetLastError();
-    const uint32_t id_stride = 1u;  // (kept as a kernel argument: without it the ADAM kernels at F = 4 and 8 take one more SGPR)
-    if (adam != nullptr) {
-      oa = *adam;
-      oa.done = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + 2 * kTailBytes);
-      hipLaunchKernelGGL((hashgrid_bwd_owner<F, true>), dim3(og), dim3(kOwnerThreads), 0, st, *g, plan, tails, records, gt, oa, id_stride, wg_base);
-    } else
-      hipLaunchKernelGGL((hashgrid_bwd_owner<F, false>), dim3(og), dim3(kOwnerThreads), 0, st, *g, plan, tails, records, gt, oa, id_stride, wg_base);
-  }
+}
+template <int F, int LAYOUT, bool... CHOSEN, typename... Flags>
+void aggregate(const BwdRequest& r, const BwdWorkspace& w, int parity, bool flag, Flags... flags) {
+  if (flag) aggregate<F, LAYOUT, CHOSEN..., true>(r, w, parity, flags...);
+  else aggregate<F, LAYOUT, CHOSEN..., false>(r, w, parity, flags...);
+}
+
+template <int F>
+int bwd_aggregate(const BwdRequest& r, const BwdWorkspace& w, int parity) {
+  const bool bounded = r.dy_bound != nullptr;  // (the bound scales the merge table's fixed-point sums)
+  if (r.dpe_rows || (r.layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_ROW_MAJOR)
+    aggregate<F, NESVOR_LAYOUT_ROW_MAJOR>(r, w, parity, r.gu != nullptr, bounded, r.cloud_plan != nullptr);
+  else
+    aggregate<F, NESVOR_LAYOUT_FEATURE_MAJOR>(r, w, parity, r.gu != nullptr, bounded, r.cloud_plan != nullptr);
+  return (int)hipGetLastError();
+}
+// The owner launch (with the table's AdamW step where the request asks for it)
+template <int F>
+int bwd_owner(const BwdRequest& r, const BwdWorkspace& w, int parity) {
+  // only the workgroups of this launch's level range (a launch over all ids, the others returning at once, cost the pipelined
+  // table update of the training step 30 us per pair of launches: gpurun_out/r06g)
+  const uint32_t wg_base = owner_grid(r.g, w.plan, 0, w.plan.level_begin);
+  const uint32_t og = owner_grid(r.g, w.plan, w.plan.level_begin, w.plan.level_end);
+  if (og == 0u) return (int)hipGetLastError();
+  const uint32_t id_stride = 1u;  // (kept as a kernel argument: without it the ADAM kernels at F = 4 and 8 take one more SGPR)
+  const uint32_t *const tails = w.tails_of(r.workspace, parity), *const records = w.records_of(r.workspace);
+  OwnerAdam oa{};
+  if (r.adamw) {
+    const nesvor_adamw_t* a = r.adam;
+    oa.param = const_cast<float*>(r.table); oa.exp_avg = r.exp_avg; oa.exp_avg_sq = r.exp_avg_sq; oa.done = w.tickets_of(r.workspace);
+    oa.a = make_adam_args(a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, a->bias_correction1, a->bias_correction2, a->grad_scale);
+    hipLaunchKernelGGL((hashgrid_bwd_owner<F, true>), dim3(og), dim3(kOwnerThreads), 0, r.st(), *r.g, w.plan, tails, records, r.gt, oa, id_stride, wg_base);
+  } else
+    hipLaunchKernelGGL((hashgrid_bwd_owner<F, false>), dim3(og), dim3(kOwnerThreads), 0, r.st(), *r.g, w.plan, tails, records, r.gt, oa, id_stride, wg_base);
   return (int)hipGetLastError();
 }
 
-// scratch of the unclustered forward: the order (sort_bytes) | feature-major output: rows (n_pad, E) in that order
-inline uint64_t fwd_ws_bytes(const nesvor_grid_t* g, int64_t N, int layout) {
-  const uint64_t n_pad = (uint64_t)((N + 255) / 256) * 256;
-  uint64_t b = 256 + ((sort_bytes(N) + 255) & ~(uint64_t)255);
-  if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR) b += n_pad * (uint64_t)(g->n_levels * g->n_features) * sizeof(float);
-  return b;
+template <int F>
+int launch_backward(BwdRequest& r) {
+  BwdWorkspace w;
+  if (w.init(r.g, r.N, r.queue_scale, r.layout) < 0) return kRefused;
+  w.plan.level_begin = r.level_begin; w.plan.level_end = r.level_end;
+  w.plan.accumulate_u = (r.stages & NESVOR_HG_STAGE_ACCUMULATE_U) ? 1 : 0;
+  const bool aggregate_stage = (r.stages & NESVOR_HG_STAGE_AGGREGATE) != 0;
+  const int parity = tails_parity(r.workspace, aggregate_stage && !(r.stages & NESVOR_HG_STAGE_KEEP));  // a fresh backward switches tails regions
+  if (aggregate_stage) {
+    int e = bwd_order_points(r, w);
+    if (e == 0) e = bwd_aggregate<F>(r, w, parity);
+    if (e) return e;
+  }
+  return (r.stages & NESVOR_HG_STAGE_OWNER) ? bwd_owner<F>(r, w, parity) : 0;
 }
+inline int run_backward(BwdRequest r) {
+  const int v = validate(r);
+  if (v != kProceed) return v;
+  const int F = r.g->n_features;
+  return F == 1 ? launch_backward<1>(r) : F == 2 ? launch_backward<2>(r) : F == 4 ? launch_backward<4>(r) : launch_backward<8>(r);
+}
+
 template <int F, int LAYOUT>
 int launch_fwd_unclustered(const nesvor_grid_t* g, const float* u, const float* table, float* pe, int64_t N, float* pe_absmax,
                            void* workspace, hipStream_t st) {
-  uint32_t* const perm_buf = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-  const int se = sort_points(u, N, perm_buf, st);
+  const FwdWorkspace w(g, N, LAYOUT);
+  uint32_t* const perm = w.perm_of(workspace);
+  float* const rows = w.rows_of(workspace);
+  const int se = sort_points(u, N, perm, st);
   if (se) return se;
-  float* rows = nullptr;
-  const int E = g->n_levels * F;
-  if constexpr (LAYOUT == NESVOR_LAYOUT_FEATURE_MAJOR)
-    rows = reinterpret_cast<float*>(reinterpret_cast<char*>(perm_buf) + ((sort_bytes(N) + 255) & ~(uint64_t)255));
   hipLaunchKernelGGL((hashgrid_fwd_cloud<F, LAYOUT>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, *g, u, table, pe, N, pe_absmax,
-                     (const uint32_t*)perm_buf, rows);
+                     (const uint32_t*)perm, rows);
   if constexpr (LAYOUT == NESVOR_LAYOUT_FEATURE_MAJOR) {
+    const int E = g->n_levels * F;
     const size_t lds = reorder_lds_bytes(E);
-    if (lds > 48 * 1024) {
-      static std::mutex mu;
-      static size_t raised = 0;
-      std::lock_guard<std::mutex> lock(mu);
-      if (lds > raised) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(scatter_pe_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        raised = lds;
-      }
-    }
+    const hipError_t e = raise_dynamic_lds<scatter_pe_rows_kernel>(lds);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(scatter_pe_rows_kernel, dim3((unsigned)((N + kGatherPts - 1) / kGatherPts)), dim3(256), lds, st, rows,
-                       sort_bufs(perm_buf, N, sort_plan(N)), pe, N, E);
+                       sort_bufs(perm, N, sort_plan(N)), pe, N, E);
   }
   return (int)hipGetLastError();
 }
@@ -2430,88 +2510,71 @@ int launch_bwd(const nesvor_grid_t* g, const float* u, const float* table, const
 
 }  // namespace
 
-#define DISPATCH_F_LAYOUT(FN, ...)                                                              \
-  do {                                                                                          \
-    const int F_ = grid->n_features;                                                            \
-    if (layout == NESVOR_LAYOUT_ROW_MAJOR) {                                                    \
-      if (F_ == 1) return FN<1, NESVOR_LAYOUT_ROW_MAJOR>(__VA_ARGS__);                          \
-      if (F_ == 2) return FN<2, NESVOR_LAYOUT_ROW_MAJOR>(__VA_ARGS__);                          \
-      if (F_ == 4) return FN<4, NESVOR_LAYOUT_ROW_MAJOR>(__VA_ARGS__);                          \
-      if (F_ == 8) return FN<8, NESVOR_LAYOUT_ROW_MAJOR>(__VA_ARGS__);                          \
-    } else if (layout == NESVOR_LAYOUT_FEATURE_MAJOR) {                                         \
-      if (F_ == 1) return FN<1, NESVOR_LAYOUT_FEATURE_MAJOR>(__VA_ARGS__);                      \
-      if (F_ == 2) return FN<2, NESVOR_LAYOUT_FEATURE_MAJOR>(__VA_ARGS__);                      \
-      if (F_ == 4) return FN<4, NESVOR_LAYOUT_FEATURE_MAJOR>(__VA_ARGS__);                      \
-      if (F_ == 8) return FN<8, NESVOR_LAYOUT_FEATURE_MAJOR>(__VA_ARGS__);                      \
-    }                                                                                           \
-    return (int)hipErrorInvalidValue;                                                           \
+// the forwards and the atomic backward: an empty batch is a no-op; then the grid check they share with validate()
+#define DISPATCH_F(FN, LAY, ...) \
+  return F_ == 1 ? FN<1, LAY>(__VA_ARGS__) : F_ == 2 ? FN<2, LAY>(__VA_ARGS__) : F_ == 4 ? FN<4, LAY>(__VA_ARGS__) : FN<8, LAY>(__VA_ARGS__)
+#define DISPATCH_F_LAYOUT(FN, ...)                                                                                          \
+  do {                                                                                                                      \
+    if (N <= 0) return 0;                                                                                                   \
+    if (!grid_ok(grid, layout)) return kRefused;                                                                            \
+    const int F_ = grid->n_features;                                                                                        \
+    if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_ROW_MAJOR) DISPATCH_F(FN, NESVOR_LAYOUT_ROW_MAJOR, __VA_ARGS__);     \
+    DISPATCH_F(FN, NESVOR_LAYOUT_FEATURE_MAJOR, __VA_ARGS__);                                                               \
   } while (0)
 
 extern "C" int nesvor_hashgrid_forward_bounded(const nesvor_grid_t* grid, const float* u, const float* table, float* pe,
                                                int64_t N, int layout, float* pe_absmax, void* stream) {
-  if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
   const int clustered = (layout & NESVOR_LAYOUT_CLUSTERED) ? 1 : 0;
-  layout &= NESVOR_LAYOUT_MASK;
   DISPATCH_F_LAYOUT(launch_fwd, grid, u, table, pe, N, clustered, pe_absmax, (hipStream_t)stream);
 }
-
 extern "C" int nesvor_hashgrid_forward(const nesvor_grid_t* grid, const float* u, const float* table, float* pe,
                                        int64_t N, int layout, void* stream) {
   return nesvor_hashgrid_forward_bounded(grid, u, table, pe, N, layout, nullptr, stream);
 }
-
 extern "C" int64_t nesvor_hashgrid_forward_workspace_bytes(const nesvor_grid_t* grid, int64_t N, int layout) {
-  if (grid == nullptr || N <= 0) return 0;
-  if (!(layout & NESVOR_LAYOUT_UNCLUSTERED)) return 0;
+  if (grid == nullptr || N <= 0 || !(layout & NESVOR_LAYOUT_UNCLUSTERED)) return 0;
   if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR && !reorder_fits_lds(grid->n_levels * grid->n_features)) return -1;
-  return (int64_t)fwd_ws_bytes(grid, N, layout);
+  return (int64_t)FwdWorkspace(grid, N, layout).bytes();
 }
-
-extern "C" int nesvor_hashgrid_forward_unclustered(const nesvor_grid_t* grid, const float* u, const float* table, float* pe,
-                                                   int64_t N, int layout, float* pe_absmax, void* workspace, int64_t workspace_bytes,
-                                                   void* stream) {
+extern "C" int nesvor_hashgrid_forward_unclustered(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N, int layout,
+                                                   float* pe_absmax, void* workspace, int64_t workspace_bytes, void* stream) {
   if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  if (N >= ((int64_t)1 << 32)) return (int)hipErrorInvalidValue;  // (32-bit point indices in the order)
-  if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR && !reorder_fits_lds(grid->n_levels * grid->n_features))
-    return (int)hipErrorInvalidValue;  // (the rows -> columns kernel's LDS: nesvor_hashgrid_forward_workspace_bytes said -1)
-  if (workspace == nullptr || workspace_bytes < (int64_t)fwd_ws_bytes(grid, N, layout)) return (int)hipErrorInvalidValue;
-  layout &= NESVOR_LAYOUT_MASK;
+  if (!grid_ok(grid, layout) || N >= ((int64_t)1 << 32)) return kRefused;  // (32-bit point indices in the order)
+  const int64_t need = nesvor_hashgrid_forward_workspace_bytes(grid, N, layout | NESVOR_LAYOUT_UNCLUSTERED);  // (-1: the rows -> columns kernel's LDS)
+  if (workspace == nullptr || need < 0 || workspace_bytes < need) return kRefused;
   DISPATCH_F_LAYOUT(launch_fwd_unclustered, grid, u, table, pe, N, pe_absmax, workspace, (hipStream_t)stream);
 }
-
-extern "C" int nesvor_hashgrid_backward_atomic(const nesvor_grid_t* grid, const float* u, const float* table,
-                                               const float* dpe, float* grad_table, float* grad_u, int64_t N,
-                                               int layout, void* stream) {
+extern "C" int nesvor_hashgrid_forward_plan(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N, int layout,
+                                            float* pe_absmax, void* order, void* cloud_plan, const float* queue_scale, void* stream) {
   if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  layout &= NESVOR_LAYOUT_MASK;  // (hints of the other kernels)
+  if (order == nullptr || (reinterpret_cast<uintptr_t>(cloud_plan) & 15u) != 0) return kRefused;
+  DISPATCH_F_LAYOUT(launch_fwd_plan, grid, u, table, pe, N, pe_absmax, static_cast<uint8_t*>(order), static_cast<uint32_t*>(cloud_plan),
+                    queue_scale, (hipStream_t)stream);
+}
+extern "C" int nesvor_hashgrid_backward_atomic(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe, float* grad_table,
+                                               float* grad_u, int64_t N, int layout, void* stream) {
   DISPATCH_F_LAYOUT(launch_bwd, grid, u, table, dpe, grad_table, grad_u, N, (hipStream_t)stream);
 }
 
-extern "C" int64_t nesvor_hashgrid_backward_workspace_bytes_ex(const nesvor_grid_t* grid, int64_t N, const float* queue_scale, int layout) {
-  int64_t base = nesvor_hashgrid_backward_workspace_bytes(grid, N, queue_scale);
-  if (base <= 0) return base;
-  // (round-5 advisor) the order's scratch - ~26 MB at N = 2^20 - only for callers that will pass NESVOR_LAYOUT_UNCLUSTERED; the
-  // plain query above keeps it (its callers may pass any hint later)
-  if (!(layout & NESVOR_LAYOUT_UNCLUSTERED)) base -= (int64_t)((sort_bytes(N) + 255) & ~(uint64_t)255);
-  if ((layout & NESVOR_LAYOUT_MASK) == NESVOR_LAYOUT_FEATURE_MAJOR && (layout & NESVOR_LAYOUT_UNCLUSTERED) && (layout & NESVOR_LAYOUT_DY_SCRATCH) &&
-      reorder_fits_lds(grid->n_levels * grid->n_features))
-    return base + 256 + (int64_t)((N + 255) / 256) * 256 * grid->n_levels * grid->n_features * (int64_t)sizeof(float);
-  return base;
-}
-
+// ---- size and offset queries of the backward's workspace: 0 for an empty batch, -1 for a grid outside the plan's limits
+// (callers of the plain query may pass any hint later: it keeps the order's scratch, ~26 MB at N = 2^20)
 extern "C" int64_t nesvor_hashgrid_backward_workspace_bytes(const nesvor_grid_t* grid, int64_t N, const float* queue_scale) {
-  if (N <= 0) return 0;
-  BwdPlan plan;
-  uint64_t n_rec;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return -1;
-  if (!make_plan(grid, N, &plan, &n_rec, queue_scale)) return -1;
-  return (int64_t)(kHeadBytes + n_rec * (1 + grid->n_features) * sizeof(uint32_t) + (uint64_t)((N + 255) / 256) * 256 + 256 + ((sort_bytes(N) + 255) & ~(uint64_t)255));
+  return N <= 0 ? 0 : BwdWorkspace().init(grid, N, queue_scale, 0, true);
 }
-
-extern "C" int64_t nesvor_hashgrid_backward_workspace_zero_bytes(void) { return (int64_t)kHeadBytes; }
+extern "C" int64_t nesvor_hashgrid_backward_workspace_bytes_ex(const nesvor_grid_t* grid, int64_t N, const float* queue_scale, int layout) {
+  return N <= 0 ? 0 : BwdWorkspace().init(grid, N, queue_scale, layout);
+}
+extern "C" int64_t nesvor_hashgrid_backward_order_offset(const nesvor_grid_t* grid, int64_t N, const float* queue_scale) {
+  BwdWorkspace w;
+  return grid != nullptr && N > 0 && w.init(grid, N, queue_scale, 0) > 0 ? (int64_t)w.order.off : -1;
+}
+extern "C" int64_t nesvor_hashgrid_backward_workspace_zero_bytes(void) { return (int64_t)BwdWorkspace::kZeroBytes; }
+extern "C" int64_t nesvor_hashgrid_backward_overflow_offset(void* workspace) { return (int64_t)BwdWorkspace::overflow_off(tails_parity(workspace, false)); }
+extern "C" int64_t nesvor_hashgrid_cloud_order_bytes(int64_t N) { return N <= 0 ? 0 : (int64_t)align256((uint64_t)N); }
+extern "C" int64_t nesvor_hashgrid_cloud_plan_bytes(const nesvor_grid_t* grid, int64_t N) {
+  if (grid == nullptr || N <= 0 || !levels_ok(grid) || grid->n_features > 2) return 0;
+  return (N + 255) / 256 * (int64_t)plan_words(grid->n_levels) * (int64_t)sizeof(uint32_t);
+}
 
 #if NESVOR_HG_TIMELINE
 // (debug builds only; not part of include/nesvor_hip.h)  64 workgroups x 96 marks of (site << 56 | 100 MHz time)
@@ -2520,104 +2583,39 @@ extern "C" int nesvor_debug_hg_timeline(unsigned long long* dst_host) {
 }
 #endif
 
-extern "C" int64_t nesvor_hashgrid_backward_overflow_offset(void* workspace) {
-  return (int64_t)(tails_parity(workspace, false) ? kTailBytes : 0) + (int64_t)kOverflowBase * (int64_t)sizeof(uint32_t);
+// ---- the owner-computes backward: every entry point names what it adds to the common request (the table: include/nesvor_hip.h)
+extern "C" int nesvor_hashgrid_backward(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe, float* grad_table,
+                                        float* grad_u, int64_t N, int layout, void* workspace, int stages, const float* queue_scale, void* stream) {
+  BwdRequest r{grid, u, table, dpe, grad_table, grad_u, N, layout, workspace, stages, queue_scale, stream};
+  r.stages_ignored = ~NESVOR_HG_STAGE_ALL;
+  return run_backward(r);
 }
-
-extern "C" int nesvor_hashgrid_backward(const nesvor_grid_t* grid, const float* u, const float* table,
-                                        const float* dpe, float* grad_table, float* grad_u, int64_t N, int layout,
-                                        void* workspace, int stages, const float* queue_scale, void* stream) {
-  if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  if (workspace == nullptr || (stages & 3) == 0) return (int)hipErrorInvalidValue;
-  const int hints = layout & (NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH);
-  layout &= NESVOR_LAYOUT_MASK;
-  DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages & 3, 0, grid->n_levels,
-                    queue_scale, nullptr, nullptr, (hipStream_t)stream, hints);
-}
-
-extern "C" int nesvor_hashgrid_backward_levels(const nesvor_grid_t* grid, const float* u, const float* table,
-                                               const float* dpe, float* grad_table, float* grad_u, int64_t N, int layout,
-                                               void* workspace, int stages, int level_begin, int level_end,
+extern "C" int nesvor_hashgrid_backward_levels(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe, float* grad_table,
+                                               float* grad_u, int64_t N, int layout, void* workspace, int stages, int level_begin, int level_end,
                                                const float* queue_scale, void* stream) {
-  if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  if (workspace == nullptr || (stages & 3) == 0) return (int)hipErrorInvalidValue;
-  if (level_begin < 0 || level_end > grid->n_levels || level_begin >= level_end) return (int)hipErrorInvalidValue;
-  const int hints = layout & (NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH);
-  layout &= NESVOR_LAYOUT_MASK;
-  DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages, level_begin, level_end,
-                    queue_scale, nullptr, nullptr, (hipStream_t)stream, hints);
+  BwdRequest r{grid, u, table, dpe, grad_table, grad_u, N, layout, workspace, stages, queue_scale, stream};
+  r.all_levels = false; r.level_begin = level_begin; r.level_end = level_end;
+  return run_backward(r);
 }
-
-extern "C" int nesvor_hashgrid_backward_bounded(const nesvor_grid_t* grid, const float* u, const float* table,
-                                                const float* dpe, float* grad_table, float* grad_u, int64_t N, int layout,
-                                                void* workspace, int stages, int level_begin, int level_end,
+extern "C" int nesvor_hashgrid_backward_bounded(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe, float* grad_table,
+                                                float* grad_u, int64_t N, int layout, void* workspace, int stages, int level_begin, int level_end,
                                                 const float* queue_scale, const float* dy_bound, void* stream) {
-  if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  if (workspace == nullptr || (stages & 3) == 0) return (int)hipErrorInvalidValue;
-  if (level_begin < 0 || level_end > grid->n_levels || level_begin >= level_end) return (int)hipErrorInvalidValue;
-  const int hints = layout & (NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH);
-  layout &= NESVOR_LAYOUT_MASK;
-  DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages, level_begin, level_end,
-                    queue_scale, dy_bound, nullptr, (hipStream_t)stream, hints);
+  BwdRequest r{grid, u, table, dpe, grad_table, grad_u, N, layout, workspace, stages, queue_scale, stream};
+  r.all_levels = false; r.level_begin = level_begin; r.level_end = level_end; r.dy_bound = dy_bound;
+  return run_backward(r);
 }
-
-extern "C" int64_t nesvor_hashgrid_cloud_order_bytes(int64_t N) { return N <= 0 ? 0 : (N + 255) / 256 * 256; }
-
-extern "C" int64_t nesvor_hashgrid_cloud_plan_bytes(const nesvor_grid_t* grid, int64_t N) {
-  if (grid == nullptr || N <= 0 || grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS || grid->n_features > 2) return 0;
-  return (N + 255) / 256 * (int64_t)plan_words(grid->n_levels) * (int64_t)sizeof(uint32_t);
+extern "C" int nesvor_hashgrid_backward_plan(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe, float* grad_table,
+                                             float* grad_u, int64_t N, int layout, void* workspace, int stages, int level_begin, int level_end,
+                                             const float* queue_scale, const float* dy_bound, const void* order, const void* cloud_plan, void* stream) {
+  BwdRequest r{grid, u, table, dpe, grad_table, grad_u, N, layout, workspace, stages, queue_scale, stream};
+  r.all_levels = false; r.level_begin = level_begin; r.level_end = level_end; r.dy_bound = dy_bound; r.order = order; r.cloud_plan = cloud_plan;
+  return run_backward(r);
 }
-
-extern "C" int64_t nesvor_hashgrid_backward_order_offset(const nesvor_grid_t* grid, int64_t N, const float* queue_scale) {
-  BwdPlan plan;
-  uint64_t n_rec;
-  if (grid == nullptr || N <= 0 || grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return -1;
-  if (!make_plan(grid, N, &plan, &n_rec, queue_scale)) return -1;
-  return (int64_t)(kHeadBytes + n_rec * (1 + grid->n_features) * sizeof(uint32_t));
-}
-
-extern "C" int nesvor_hashgrid_forward_plan(const nesvor_grid_t* grid, const float* u, const float* table, float* pe, int64_t N, int layout,
-                                            float* pe_absmax, void* order, void* cloud_plan, const float* queue_scale, void* stream) {
-  if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  if (order == nullptr || (reinterpret_cast<uintptr_t>(cloud_plan) & 15u) != 0) return (int)hipErrorInvalidValue;
-  layout &= NESVOR_LAYOUT_MASK;
-  DISPATCH_F_LAYOUT(launch_fwd_plan, grid, u, table, pe, N, pe_absmax, static_cast<uint8_t*>(order), static_cast<uint32_t*>(cloud_plan),
-                    queue_scale, (hipStream_t)stream);
-}
-
-extern "C" int nesvor_hashgrid_backward_plan(const nesvor_grid_t* grid, const float* u, const float* table, const float* dpe,
-                                             float* grad_table, float* grad_u, int64_t N, int layout, void* workspace, int stages,
-                                             int level_begin, int level_end, const float* queue_scale, const float* dy_bound,
-                                             const void* order, const void* cloud_plan, void* stream) {
-  if (N <= 0) return 0;
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  if (workspace == nullptr || (stages & 3) == 0) return (int)hipErrorInvalidValue;
-  if (level_begin < 0 || level_end > grid->n_levels || level_begin >= level_end) return (int)hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(cloud_plan) & 15u) != 0) return (int)hipErrorInvalidValue;
-  const int hints = layout & (NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH);
-  layout &= NESVOR_LAYOUT_MASK;
-  DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages, level_begin, level_end,
-                    queue_scale, dy_bound, nullptr, (hipStream_t)stream, hints, static_cast<const uint8_t*>(order),
-                    static_cast<const uint32_t*>(cloud_plan));
-}
-
-extern "C" int nesvor_hashgrid_backward_adamw(const nesvor_grid_t* grid, const float* u, float* table, const float* dpe,
-                                              float* grad_table, float* grad_u, int64_t N, int layout, void* workspace,
-                                              int stages, const float* queue_scale, const float* dy_bound, float* exp_avg,
-                                              float* exp_avg_sq, const nesvor_adamw_t* adam, void* stream) {
-  if (grid->n_levels <= 0 || grid->n_levels > NESVOR_MAX_LEVELS) return (int)hipErrorInvalidValue;
-  if (N <= 0 || workspace == nullptr || (stages & ~3) != 0 || (stages & 3) == 0) return (int)hipErrorInvalidValue;
-  if (table == nullptr || grad_table == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || adam == nullptr) return (int)hipErrorInvalidValue;
-  OwnerAdam oa;
-  oa.param = table; oa.exp_avg = exp_avg; oa.exp_avg_sq = exp_avg_sq; oa.done = nullptr;
-  oa.a = make_adam_args(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->weight_decay, adam->bias_correction1,
-                        adam->bias_correction2, adam->grad_scale);
-  const int hints = layout & (NESVOR_LAYOUT_UNCLUSTERED | NESVOR_LAYOUT_DY_SCRATCH);
-  layout &= NESVOR_LAYOUT_MASK;
-  DISPATCH_F_LAYOUT(launch_bwd_owner, grid, u, table, dpe, grad_table, grad_u, N, workspace, stages, 0, grid->n_levels, queue_scale,
-                    dy_bound, &oa, (hipStream_t)stream, hints);
+extern "C" int nesvor_hashgrid_backward_adamw(const nesvor_grid_t* grid, const float* u, float* table, const float* dpe, float* grad_table,
+                                              float* grad_u, int64_t N, int layout, void* workspace, int stages, const float* queue_scale,
+                                              const float* dy_bound, float* exp_avg, float* exp_avg_sq, const nesvor_adamw_t* adam, void* stream) {
+  BwdRequest r{grid, u, table, dpe, grad_table, grad_u, N, layout, workspace, stages, queue_scale, stream};
+  r.dy_bound = dy_bound; r.adamw = true; r.exp_avg = exp_avg; r.exp_avg_sq = exp_avg_sq; r.adam = adam;
+  r.stages_refused = ~NESVOR_HG_STAGE_ALL; r.refuse_empty = true;
+  return run_backward(r);
 }

@@ -516,7 +516,7 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
       //  set-up, 36 + 50 us side by side against 63 us, and the cross-stream hand-overs ate the rest: 0.285 -> 0.294 ms at 2^17
       //  points.  Not kept.)
       Span t(ctx, NESVOR_STEP_SPAN_HASHGRID_BWD_AGGREGATE, main);
-      NESVOR_TRY(nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 1, 0, L,
+      NESVOR_TRY(nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, NESVOR_HG_STAGE_AGGREGATE, 0, L,
                                                d.queue_scale, dpe_bound, hg_order, hg_plan, main));
     }
     // the owner pass only finishes grad_table (or, fused, takes the table's AdamW step): it runs under the sampler backward
@@ -531,29 +531,31 @@ extern "C" int nesvor_step_run(void* handle, const float* xyz, const float* v, c
     {
       Span t(ctx, NESVOR_STEP_SPAN_HASHGRID_BWD_OWNER, owner_stream);  // (with fuse_adamw: the owner pass AND the table's AdamW step)
       if (fuse_adamw)
-        NESVOR_TRY(nesvor_hashgrid_backward_adamw(&d.grid, d.u, d.flat_param + table_off, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 2,
-                                                  d.queue_scale, dpe_bound, d.flat_exp_avg + table_off, d.flat_exp_avg_sq + table_off, adam,
-                                                  owner_stream));
+        NESVOR_TRY(nesvor_hashgrid_backward_adamw(&d.grid, d.u, d.flat_param + table_off, d.dpe, d.g_table, du, N, layout, d.hg_workspace,
+                                                  NESVOR_HG_STAGE_OWNER, d.queue_scale, dpe_bound, d.flat_exp_avg + table_off,
+                                                  d.flat_exp_avg_sq + table_off, adam, owner_stream));
       else
-        NESVOR_TRY(nesvor_hashgrid_backward_levels(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 2, 0, L,
+        NESVOR_TRY(nesvor_hashgrid_backward_levels(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, NESVOR_HG_STAGE_OWNER, 0, L,
                                                    d.queue_scale, owner_stream));
     }
     if (overlap_owner && hipEventRecord(ctx->ev_owner, side) != hipSuccess) return (int)hipGetLastError();
   } else if (phase == 1) {
     // fine levels first (the end of the flat gradient): the host starts their all-reduce when this call returns
-    return nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 3, split_level, L,
+    return nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, NESVOR_HG_STAGE_ALL, split_level, L,
                                          d.queue_scale, dpe_bound, hg_order, nullptr, main);
   } else {
     // the coarse levels: aggregation on the main stream, their owner pass again under the rest of the step (the caller joins
     // the side stream before it reduces / applies the rest of the gradient)
-    NESVOR_TRY(nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 1 | 4 | 8, 0,
+    NESVOR_TRY(nesvor_hashgrid_backward_plan(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace,
+                                             NESVOR_HG_STAGE_AGGREGATE | NESVOR_HG_STAGE_KEEP | NESVOR_HG_STAGE_ACCUMULATE_U, 0,
                                              split_level, d.queue_scale, dpe_bound, hg_order, nullptr, main));
     hipStream_t owner_stream = main;
     if (overlap_owner) {
       if (hipEventRecord(ctx->ev_agg, main) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_agg, 0) != hipSuccess) return (int)hipGetLastError();
       owner_stream = side;
     }
-    NESVOR_TRY(nesvor_hashgrid_backward_bounded(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace, 2 | 4 | 8, 0,
+    NESVOR_TRY(nesvor_hashgrid_backward_bounded(&d.grid, d.u, d.table, d.dpe, d.g_table, du, N, layout, d.hg_workspace,
+                                                NESVOR_HG_STAGE_OWNER | NESVOR_HG_STAGE_KEEP | NESVOR_HG_STAGE_ACCUMULATE_U, 0,
                                                 split_level, d.queue_scale, dpe_bound, owner_stream));
     if (overlap_owner && hipEventRecord(ctx->ev_owner, side) != hipSuccess) return (int)hipGetLastError();
   }

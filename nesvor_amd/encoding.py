@@ -263,7 +263,7 @@ def hashgrid_backward(spec, u, table, dpe, grad_table=None, need_input_grad=True
             args = (ctypes.byref(spec.c_struct), _lib.ptr(u), _lib.ptr(table), _lib.ptr(dpe), _lib.ptr(grad_table),
                     _lib.ptr(grad_u), N, layout, _lib.ptr(ws))
             l0, l1 = (0, spec.n_levels) if levels is None else levels
-            extra = 0 if first else (4 | 8)  # keep the queue tails, add to grad_u
+            extra = 0 if first else (_lib.HG_STAGE_KEEP | _lib.HG_STAGE_ACCUMULATE_U)  # keep the queue tails, add to grad_u
             if plan is not None and not (clustered and plan.fits(spec, u)):
                 plan = None
             p_order = _lib.ptr(plan.order) if plan is not None else None
@@ -272,17 +272,17 @@ def hashgrid_backward(spec, u, table, dpe, grad_table=None, need_input_grad=True
                                                                             p_order, p_rec, st or _lib.stream_ptr())
             if _lib.kernel_timer.enabled:  # bracket each of the two launches with its own events
                 with _lib.kernel_timer.span("hashgrid_bwd_aggregate"):
-                    err = call(1)
+                    err = call(_lib.HG_STAGE_AGGREGATE)
                 if err == 0:
                     with _lib.kernel_timer.span("hashgrid_bwd_owner"):
-                        err = call(2)
+                        err = call(_lib.HG_STAGE_OWNER)
             elif owner_stream is not None:
-                err = call(1)
+                err = call(_lib.HG_STAGE_AGGREGATE)
                 if err == 0:
                     owner_stream.wait_stream(torch.cuda.current_stream(u.device))
-                    err = call(2, ctypes.c_void_p(owner_stream.cuda_stream))
+                    err = call(_lib.HG_STAGE_OWNER, ctypes.c_void_p(owner_stream.cuda_stream))
             else:
-                err = call(3)
+                err = call(_lib.HG_STAGE_ALL)
         else:
             err = lib.nesvor_hashgrid_backward_atomic(
                 ctypes.byref(spec.c_struct), _lib.ptr(u), _lib.ptr(table), _lib.ptr(dpe), _lib.ptr(grad_table),
@@ -313,7 +313,7 @@ def hashgrid_backward_adamw(spec, u, table, dpe, grad_table, exp_avg, exp_avg_sq
         raise RuntimeError("the grid does not fit the owner method's plan")
     with torch.cuda.device(u.device):
         err = lib.nesvor_hashgrid_backward_adamw(ctypes.byref(spec.c_struct), _lib.ptr(u), _lib.ptr(table), _lib.ptr(dpe), _lib.ptr(grad_table),
-                                                 _lib.ptr(grad_u), N, layout, _lib.ptr(ws), 3, sizer.scale, _lib.ptr(dy_bound),
+                                                 _lib.ptr(grad_u), N, layout, _lib.ptr(ws), _lib.HG_STAGE_ALL, sizer.scale, _lib.ptr(dy_bound),
                                                  _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), ctypes.byref(adam), _lib.stream_ptr())
     _lib.check(err, "hashgrid backward + AdamW")
     sizer.snapshot(ws)

@@ -108,6 +108,7 @@ def _compute(spec_name, kind, N):
     dy = dy_cpu.t().contiguous().to(device)  # feature-major (E, N)
     bound = dy.abs().max().reshape(1).clone()
     layout = _lib.LAYOUT_FEATURE_MAJOR
+    ALL, LATER = _lib.HG_STAGE_ALL, _lib.HG_STAGE_KEEP | _lib.HG_STAGE_ACCUMULATE_U
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     out = {"spec": spec, "N": N, "name": f"{spec_name} {kind} N={N}"}
     with torch.cuda.device(device):
@@ -129,23 +130,23 @@ def _compute(spec_name, kind, N):
 
         # the backward that sorts and plans for itself ...
         gt0, gu0 = torch.zeros_like(table), torch.full_like(u, float("nan"))
-        backward(3, 0, L, gt0, gu0, None, None)
+        backward(ALL, 0, L, gt0, gu0, None, None)
         off = lib.nesvor_hashgrid_backward_order_offset(g, N, None)
         out.update(gt0=gt0.cpu(), gu0=gu0.cpu(), order_bwd=ws[off : off + n_order].cpu(), overflow0=_overflow(lib, spec, ws))
         # ... the one that takes the forward's order and plan ...
         gt1, gu1 = torch.zeros_like(table), torch.full_like(u, float("nan"))
-        backward(3, 0, L, gt1, gu1, order, plan)
+        backward(ALL, 0, L, gt1, gu1, order, plan)
         out.update(gt1=gt1.cpu(), gu1=gu1.cpu(), overflow1=_overflow(lib, spec, ws))
         # ... and the split one: fine levels, then the coarse ones adding to grad_u, both with the forward's order, no plan
         s = SPLIT[spec_name]
         gt2, gu2 = torch.zeros_like(table), torch.full_like(u, float("nan"))
-        backward(3, s, L, gt2, gu2, order, None)
-        backward(3 | 4 | 8, 0, s, gt2, gu2, order, None)
+        backward(ALL, s, L, gt2, gu2, order, None)
+        backward(ALL | LATER, 0, s, gt2, gu2, order, None)
         out.update(gt2=gt2.cpu(), gu2=gu2.cpu(), overflow2=_overflow(lib, spec, ws))
         # (the same split where the first launch sorts and the second re-uses its order)
         gt3, gu3 = torch.zeros_like(table), torch.full_like(u, float("nan"))
-        backward(3, s, L, gt3, gu3, None, None)
-        backward(3 | 4 | 8, 0, s, gt3, gu3, None, None)
+        backward(ALL, s, L, gt3, gu3, None, None)
+        backward(ALL | LATER, 0, s, gt3, gu3, None, None)
         out.update(gt3=gt3.cpu(), gu3=gu3.cpu())
         torch.cuda.synchronize(device)
     lv = O.make_levels(*SPECS[spec_name][:1], *SPECS[spec_name][2:])
@@ -217,7 +218,7 @@ def test_plan_is_refused_where_it_does_not_hold(device):
     g = ctypes.byref(spec.c_struct)
     one = ctypes.c_void_p(16)  # never dereferenced: the calls are refused on the host
     for layout, l0, l1 in ((_lib.LAYOUT_FEATURE_MAJOR, 0, 3), (_lib.LAYOUT_FEATURE_MAJOR | _lib.LAYOUT_UNCLUSTERED, 0, spec.n_levels)):
-        assert lib.nesvor_hashgrid_backward_plan(g, one, one, one, one, None, N, layout, one, 1, l0, l1, None, None, one, one, None) != 0
+        assert lib.nesvor_hashgrid_backward_plan(g, one, one, one, one, None, N, layout, one, _lib.HG_STAGE_AGGREGATE, l0, l1, None, None, one, one, None) != 0
 
 
 def test_one_call_step_hands_over_and_follows_the_python_issued_step(device, golden):

@@ -195,6 +195,158 @@ def test_hashgrid_plan_limits_on_the_tested_grids():
     assert fq(wide, 1) == -1 and fq(wide, 0) > 0 and fq(narrow, 1) > fq(narrow, 0) > 0
 
 
+def _hg_sort_bytes(N):
+    """csrc/hashgrid.hip's sort_bytes(N) from its sort_plan rule: 2^b cells per axis with b = (floor(log2 N) - 5) / 3 clamped to
+    [1, 6], strips of twice the mean occupancy rounded up to a power of two (at least 2) - the formula of
+    tests/test_cabi.py::test_backward_workspace_size_queries_follow_the_layout_hints for any N."""
+    n_pad = (N + 255) // 256 * 256
+    b = min(max((N.bit_length() - 1 - 5) // 3, 1), 6)
+    n_cells = 1 << (3 * b)
+    mean, cap = -(-N // n_cells), 2
+    while cap < 2 * mean:
+        cap *= 2
+    return (n_pad * 2 + 2 * ((1 << 18) + 2)) * 4 + n_pad * 8 + n_cells * cap * 4
+
+
+def test_hashgrid_workspace_layout_identities():
+    """What the size and offset queries of the hash-grid launches say about one workspace, as identities between them (host code:
+    no GPU), on every tested grid inside the plan's limits, at point counts around the 256-point padding, with and without
+    queue scales: two zero-filled tail regions and the tickets | records of 4 (1 + F) bytes | cloud order (n_pad) | 256 bytes of
+    alignment slack | the point order's scratch (whole 256s) | optionally dpe as rows."""
+    import ctypes
+
+    import hashgrid_reference as R
+    from nesvor_amd import _lib
+    from nesvor_amd.grid import HashGridSpec
+
+    lib = _lib.load()
+    U, S = _lib.LAYOUT_UNCLUSTERED, _lib.LAYOUT_DY_SCRATCH
+    zero = lib.nesvor_hashgrid_backward_workspace_zero_bytes()
+    assert zero == (2 * 8 + 1) * 4096 * 4  # two regions of 8 sub-queue counter sets, one set of tickets
+    assert lib.nesvor_hashgrid_backward_overflow_offset(ctypes.c_void_p(0x7000)) == (4096 - 32) * 4  # (a workspace not seen before)
+    assert lib.nesvor_hashgrid_cloud_order_bytes(0) == 0
+    checked = 0
+    for name, (spec_tuple, _, _, inside) in R.GRIDS.items():
+        if not inside:
+            continue
+        spec = HashGridSpec(*spec_tuple)
+        g, L, F = ctypes.byref(spec.c_struct), spec.n_levels, spec.n_features
+        E = L * F
+        for N in (1, 255, 256, 257, 1000, (1 << 20) - 77):
+            n_pad = (N + 255) // 256 * 256
+            sort = (_hg_sort_bytes(N) + 255) // 256 * 256
+            # the rows -> columns kernels' LDS decides whether the re-ordered copies exist; the forward's query says so
+            fwd_fm = lib.nesvor_hashgrid_forward_workspace_bytes(g, N, 1 | U)
+            fits = fwd_fm != -1
+            assert fits or E > 62, (name, N)  # 256 rows of E + 1 floats + 1 KiB <= 64 KiB, what every device has
+            assert not fits or E < 159, (name, N)
+            for scale in (None, (ctypes.c_float * L)(*([1.0 / 16] * L))):
+                tag = (name, N, scale is not None)
+                base = lib.nesvor_hashgrid_backward_workspace_bytes(g, N, scale)
+                order = lib.nesvor_hashgrid_backward_order_offset(g, N, scale)
+                assert base > 0 and order > zero, tag
+                assert base - order == n_pad + 256 + sort, tag
+                assert (order - zero) % (4 * (1 + F)) == 0, tag
+                for lay in (0, 1):
+                    for u in (0, U):
+                        for s in (0, S):
+                            want = base - (0 if u else sort) + (256 + n_pad * E * 4 if (lay == 1 and u and s and fits) else 0)
+                            assert lib.nesvor_hashgrid_backward_workspace_bytes_ex(g, N, scale, lay | u | s) == want, tag + (lay, u, s)
+                checked += 1
+            assert lib.nesvor_hashgrid_cloud_order_bytes(N) == n_pad
+            plan_words = 8 + 14 * ((L + 4) & ~3)
+            assert lib.nesvor_hashgrid_cloud_plan_bytes(g, N) == (n_pad // 256 * plan_words * 4 if F <= 2 else 0), (name, N)
+            for hint in (0, _lib.LAYOUT_CLUSTERED, S):
+                assert lib.nesvor_hashgrid_forward_workspace_bytes(g, N, hint) == lib.nesvor_hashgrid_forward_workspace_bytes(g, N, 1 | hint) == 0
+            assert lib.nesvor_hashgrid_forward_workspace_bytes(g, N, 0 | U) == 256 + sort, (name, N)
+            assert fwd_fm == (256 + sort + n_pad * E * 4 if fits else -1), (name, N)
+        assert lib.nesvor_hashgrid_forward_workspace_bytes(g, 0, 1 | U) == 0 == lib.nesvor_hashgrid_backward_workspace_bytes(g, 0, None)
+        assert lib.nesvor_hashgrid_backward_workspace_bytes_ex(g, 0, None, 1 | U | S) == 0
+        assert lib.nesvor_hashgrid_backward_order_offset(g, 0, None) == -1
+    assert checked == 2 * 6 * sum(1 for v in R.GRIDS.values() if v[3])
+
+
+def test_hashgrid_entry_points_refuse_before_any_launch():
+    """The refusal rules of the hash-grid entry points, row by row (ctypes calls that return before anything is launched: the
+    grid is real, the other pointers are dummies).  An empty batch is a no-op - except for the backward with the AdamW step,
+    which refuses it; every other row is hipErrorInvalidValue."""
+    import ctypes
+
+    from nesvor_amd import _lib
+    from nesvor_amd.grid import HashGridSpec
+
+    lib = _lib.load()
+    INVALID, P, Q, NULL = 1, ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1008), ctypes.c_void_p(0)  # (Q: not 16-byte aligned)
+    AGG, OWN, KEEP, ACC = _lib.HG_STAGE_AGGREGATE, _lib.HG_STAGE_OWNER, _lib.HG_STAGE_KEEP, _lib.HG_STAGE_ACCUMULATE_U
+    BOTH = AGG | OWN
+    U = _lib.LAYOUT_UNCLUSTERED
+    spec = HashGridSpec(6, 2, 10, 4, 1.5)
+    L = spec.n_levels
+    adam = _lib.AdamwT()
+
+    def grid(**kw):
+        c = type(spec.c_struct)()
+        ctypes.memmove(ctypes.byref(c), ctypes.byref(spec.c_struct), ctypes.sizeof(c))
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+    # every entry point as f(grid struct, **overrides) over one set of named defaults
+    base = dict(N=1000, layout=0, ws=P, stages=BOTH, l0=0, l1=L, dy_bound=NULL, order=NULL, plan=NULL, fwd_order=P, table=P, gt=P,
+                m=P, v=P, adam=ctypes.byref(adam))
+
+    def entry(fn):
+        def call(g, **kw):
+            a = dict(base, **kw)
+            return fn(ctypes.byref(g), a)
+        return call
+
+    E = {
+        "backward": entry(lambda g, a: lib.nesvor_hashgrid_backward(g, P, P, P, P, P, a["N"], a["layout"], a["ws"], a["stages"], None, NULL)),
+        "levels": entry(lambda g, a: lib.nesvor_hashgrid_backward_levels(g, P, P, P, P, P, a["N"], a["layout"], a["ws"], a["stages"],
+                                                                          a["l0"], a["l1"], None, NULL)),
+        "bounded": entry(lambda g, a: lib.nesvor_hashgrid_backward_bounded(g, P, P, P, P, P, a["N"], a["layout"], a["ws"], a["stages"],
+                                                                            a["l0"], a["l1"], None, a["dy_bound"], NULL)),
+        "plan": entry(lambda g, a: lib.nesvor_hashgrid_backward_plan(g, P, P, P, P, P, a["N"], a["layout"], a["ws"], a["stages"],
+                                                                      a["l0"], a["l1"], None, a["dy_bound"], a["order"], a["plan"], NULL)),
+        "adamw": entry(lambda g, a: lib.nesvor_hashgrid_backward_adamw(g, P, a["table"], P, a["gt"], P, a["N"], a["layout"], a["ws"],
+                                                                        a["stages"], None, a["dy_bound"], a["m"], a["v"], a["adam"], NULL)),
+        "atomic": entry(lambda g, a: lib.nesvor_hashgrid_backward_atomic(g, P, P, P, P, P, a["N"], a["layout"], NULL)),
+        "forward": entry(lambda g, a: lib.nesvor_hashgrid_forward(g, P, P, P, a["N"], a["layout"], NULL)),
+        "forward_bounded": entry(lambda g, a: lib.nesvor_hashgrid_forward_bounded(g, P, P, P, a["N"], a["layout"], NULL, NULL)),
+        "forward_unclustered": entry(lambda g, a: lib.nesvor_hashgrid_forward_unclustered(g, P, P, P, a["N"], a["layout"] | U, NULL, a["ws"],
+                                                                                          1 << 40, NULL)),
+        "forward_plan": entry(lambda g, a: lib.nesvor_hashgrid_forward_plan(g, P, P, P, a["N"], a["layout"], NULL,
+                                                                            a["fwd_order"], a["plan"], None, NULL)),
+    }
+    owner, ranged = ("backward", "levels", "bounded", "plan"), ("levels", "bounded", "plan")
+    rows = []  # (entry, grid overrides, argument overrides, expected)
+    for e in E:
+        rows.append((e, {}, dict(N=0), INVALID if e == "adamw" else 0))
+        rows += [(e, dict(n_levels=0), {}, INVALID), (e, dict(n_levels=33), {}, INVALID), (e, dict(n_features=3), {}, INVALID),
+                 (e, {}, dict(layout=2), INVALID)]
+    for e in owner + ("adamw", "forward_unclustered"):
+        rows.append((e, {}, dict(ws=NULL), INVALID))
+    for e in owner + ("adamw",):
+        rows += [(e, {}, dict(stages=0), INVALID), (e, {}, dict(stages=KEEP | ACC), INVALID)]
+    for e in ranged:
+        rows += [(e, {}, dict(l0=-1), INVALID), (e, {}, dict(l1=L + 1), INVALID), (e, {}, dict(l0=3, l1=3), INVALID),
+                 (e, {}, dict(l0=4, l1=2), INVALID)]
+    rows += [("plan", {}, dict(order=P, plan=Q), INVALID), ("forward_plan", {}, dict(plan=Q), INVALID)]
+    rows.append(("forward_plan", {}, dict(fwd_order=NULL), INVALID))
+    rows += [("plan", {}, dict(order=P, layout=U), INVALID), ("plan", {}, dict(order=P, plan=P, layout=U), INVALID),
+             ("plan", {}, dict(plan=P, layout=U), INVALID),
+             ("plan", {}, dict(plan=P), INVALID),  # a plan without the order
+             ("plan", dict(n_features=4), dict(order=P, plan=P), INVALID),
+             ("plan", {}, dict(order=P, plan=P, l0=1), INVALID), ("plan", {}, dict(order=P, plan=P, l1=L - 1), INVALID)]
+    rows += [("adamw", {}, dict(stages=BOTH | KEEP), INVALID), ("adamw", {}, dict(stages=BOTH | ACC), INVALID),
+             ("adamw", {}, dict(stages=AGG | KEEP | ACC), INVALID)]
+    rows += [("adamw", {}, {k: NULL}, INVALID) for k in ("table", "gt", "m", "v")] + [("adamw", {}, dict(adam=None), INVALID)]
+    for e, gkw, akw, want in rows:
+        assert E[e](grid(**gkw), **akw) == want, (e, gkw, {k: getattr(v, "value", v) for k, v in akw.items()})
+    assert len(rows) == 10 * 5 + 6 + 10 + 12 + 3 + 7 + 3 + 5
+
+
 def test_state_dict_layout_matches_reference(golden):
     """INR.state_dict() keys/shapes (checkpoint contract, cli/io.py:24-46) without touching the GPU."""
     from nesvor_amd.models import INR

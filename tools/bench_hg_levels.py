@@ -25,7 +25,7 @@ HINTS = (_lib.LAYOUT_UNCLUSTERED | _lib.LAYOUT_DY_SCRATCH) if UNIFORM else 0
 ws = _workspace(spec, N, dev, None, LAYOUT | HINTS)
 _SCALE = __import__('nesvor_amd.encoding', fromlist=['queue_sizer']).queue_sizer(spec, N, dev).scale
 lib = _lib.load()
-def run(l0, l1, stage=1):
+def run(l0, l1, stage=_lib.HG_STAGE_AGGREGATE):
     return lib.nesvor_hashgrid_backward_levels(ctypes.byref(spec.c_struct), _lib.ptr(u), _lib.ptr(table), _lib.ptr(dy), _lib.ptr(gt), _lib.ptr(gu), N, LAYOUT | HINTS, _lib.ptr(ws), stage, l0, l1, _SCALE, _lib.stream_ptr())
 def timeit(fn, n=20):
     for _ in range(3): fn()

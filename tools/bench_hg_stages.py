@@ -30,11 +30,11 @@ def timeit(fn, n=20):
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / n
 for name, u in (("P", uP), ("U", uU)):
-    run(u, 1); torch.cuda.synchronize()
+    run(u, _lib.HG_STAGE_AGGREGATE); torch.cuda.synchronize()
     nb = 0
     tails = ws[:8 * 4096 * 4].view(torch.int32).cpu()  # kSubQueues x kTailStride counters
     tot = int(tails.sum())
-    tn = timeit(lambda: run(u, 1, False))
+    tn = timeit(lambda: run(u, _lib.HG_STAGE_AGGREGATE, False))
     print(f"{name}: aggregate without input grad {tn:.3f} ms")
-    ta = timeit(lambda: run(u, 1)); to = timeit(lambda: run(u, 2)); t3 = timeit(lambda: run(u, 3))
+    ta = timeit(lambda: run(u, _lib.HG_STAGE_AGGREGATE)); to = timeit(lambda: run(u, _lib.HG_STAGE_OWNER)); t3 = timeit(lambda: run(u, _lib.HG_STAGE_ALL))
     print(f"{name}: records {tot/1e6:.2f} M  aggregate {ta:.3f} ms  owner {to:.3f} ms  both {t3:.3f} ms", flush=True)

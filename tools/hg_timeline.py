@@ -47,7 +47,7 @@ else:
     sizer = queue_sizer(spec, N, dev); ws = _workspace(spec, N, dev, sizer)
     lib = _lib.load()
     run = lambda: lib.nesvor_hashgrid_backward_bounded(ctypes.byref(spec.c_struct), _lib.ptr(u), _lib.ptr(table), _lib.ptr(dy), _lib.ptr(gt), _lib.ptr(gu), N, 1,
-                                                       _lib.ptr(ws), 1, 0, 16, sizer.scale, _lib.ptr(bound), _lib.stream_ptr())
+                                                       _lib.ptr(ws), _lib.HG_STAGE_AGGREGATE, 0, 16, sizer.scale, _lib.ptr(bound), _lib.stream_ptr())
     for _ in range(3): assert run() == 0
     torch.cuda.synchronize()
     s, e = torch.cuda.Event(True), torch.cuda.Event(True)

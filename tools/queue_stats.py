@@ -23,7 +23,7 @@ table = torch.zeros(spec.n_params, device=dev); dy = torch.randn((32, N) if LAYO
 sizer = queue_sizer(spec, N, dev, not UNIFORM)
 ws = _workspace(spec, N, dev, sizer, LAYOUT | hints)
 lib = _lib.load()
-err = lib.nesvor_hashgrid_backward(ctypes.byref(spec.c_struct), _lib.ptr(u), _lib.ptr(table), _lib.ptr(dy), _lib.ptr(gt), None, N, LAYOUT | hints, _lib.ptr(ws), 1, sizer.scale, _lib.stream_ptr())
+err = lib.nesvor_hashgrid_backward(ctypes.byref(spec.c_struct), _lib.ptr(u), _lib.ptr(table), _lib.ptr(dy), _lib.ptr(gt), None, N, LAYOUT | hints, _lib.ptr(ws), _lib.HG_STAGE_AGGREGATE, sizer.scale, _lib.stream_ptr())
 torch.cuda.synchronize()
 assert err == 0
 STRIDE, SUBS = 4096, 8
