@@ -1035,6 +1035,34 @@ int nesvor_slice_bias_update(const float* sim, const float* y, const uint8_t* ma
 int64_t nesvor_slice_bias_update_workspace_bytes(int n, int h, int w);
 
 /* ----------------------------------------------------------------------
+ * Stack denoising (nesvor_amd/denoise.py): 2-D non-local means of every slice of a stack, slice by slice.
+ * y (n,h,w) fp32 the slices, mask (n,h,w) bytes or NULL (all valid), sigma (n) DEVICE fp32 the noise standard deviation of
+ * every slice, P = patch_radius in 1 .. 3, S = search_radius in 1 .. 10, beta = strength.  With m the validity as 0 / 1 (0
+ * outside the image), y0 = y on valid pixels and 0 elsewhere, and for a valid pixel p of slice k with sigma_k positive and finite:
+ *   candidates   q = p + t, t in [-S,S]^2 \ {0} with m(q) = 1, taken in ascending (t_y, t_x);
+ *   c_o = m(p+o) m(q+o),  e_o = c_o (y0(p+o) - y0(q+o))^2,  o in [-P,P]^2;  num = sum_o e_o and den = sum_o c_o, each added
+ *                along x first and then along y, in ascending order from the first term;
+ *   d2 = num / max(den, 1),   w(p,q) = exp(-(max(d2 - 2 sigma_k^2, 0) / (beta sigma_k)^2));
+ *   w_c = the largest w(p,q), or 1 without a candidate;  W = w_c + sum_q w(p,q),  V = w_c y(p) + sum_q w(p,q) y(q);
+ *   out(p) = V / W, or y(p) where W is 0 (every weight underflowed),
+ * all in fp32 without contraction, expf the library's, the sums over q from 0 in candidate order.  An invalid pixel and every
+ * pixel of a slice whose sigma_k is not positive and finite keep y bit for bit.  out (n,h,w) fp32 and stats (n,2) fp64 are
+ * fully written (no memset needed):  stats[k] = { number of valid pixels, sum over them of (out - y)^2 }, the count exact, the
+ * squares fp32, their sum double from the first add and reproducible (no atomics: per-workgroup partials in the workspace,
+ * added in workgroup order by a second launch).  One workgroup per 16 x 16 tile of a slice; y is read once per tile (with its
+ * S + P halo) into LDS and nothing else is read.  workspace: device memory of at least
+ * nesvor_nlm_denoise_workspace_bytes(n, h, w) bytes (0 for sizes the call treats as a no-op or refuses).
+ * n == 0: no-op, returns 0.  hipErrorInvalidValue, without a launch: n < 0, h or w below 1, h w > INT_MAX - 256, more than
+ * INT_MAX workgroups, a null pointer other than mask, out == y (a tile reads its neighbours' y), patch_radius outside 1 .. 3,
+ * search_radius outside 1 .. 10, a strength that is not positive and finite, a workspace that is missing or too small.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_nlm_denoise(const float* y, const uint8_t* mask, const float* sigma, int n, int h, int w, int patch_radius,
+                       int search_radius, float strength, float* out, double* stats, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int64_t nesvor_nlm_denoise_workspace_bytes(int n, int h, int w);
+
+/* ----------------------------------------------------------------------
  * Volume comparison (nesvor_amd/evaluate.py, the `evaluate` command): a volume X on the lattice of a reference volume R, and
  * the 3-D SSIM map of the two with the sums of the error measures.
  *

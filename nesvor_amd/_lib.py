@@ -251,6 +251,8 @@ _SIGNATURES = {
     "nesvor_otsu_threshold_workspace_bytes": ([c_int], c_int64),
     "nesvor_slice_bias_update": ([_P] * 6 + [c_int, c_int, c_int, c_double, c_int, c_float, _P, _P, _P, c_size_t, _P], c_int),
     "nesvor_slice_bias_update_workspace_bytes": ([c_int, c_int, c_int], c_int64),
+    "nesvor_nlm_denoise": ([_P] * 3 + [c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P], c_int),
+    "nesvor_nlm_denoise_workspace_bytes": ([c_int, c_int, c_int], c_int64),
     "nesvor_volume_resample": ([_P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, POINTER(c_double), _P, _P, _P, _P, c_size_t, _P],
                                c_int),
     "nesvor_volume_resample_workspace_bytes": ([c_int, c_int, c_int], c_int64),

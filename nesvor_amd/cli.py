@@ -18,6 +18,8 @@ nesvor/cli/commands.py:64-146) for the commands that sit on the built path (SURV
                                            [--metric ncc|matrix-rank|volume] [--output-json FILE.json]
     python -m nesvor_amd.cli correct-bias-field --input-stacks a.nii.gz b.nii.gz [--stack-masks ...]
                                            --output-corrected-stacks ca.nii.gz cb.nii.gz [--output-bias-fields fa.nii.gz fb.nii.gz]
+    python -m nesvor_amd.cli denoise       --input-stacks a.nii.gz b.nii.gz [--stack-masks ...] --output-stacks da.nii.gz db.nii.gz
+                                           [--output-json FILE.json]
     python -m nesvor_amd.cli evaluate      --reference-volume r.nii.gz [--reference-mask ...] --input-volumes a.nii.gz b.nii.gz
                                            [--input-masks ...] [--intensity-fit none|scale|affine] [--dynamic-range L]
                                            [--output-json FILE.json] [--output-ssim-maps ...] [--output-resampled ...]
@@ -73,6 +75,15 @@ other stack contains the voxel (ignored with a warning beside ``--volume-mask`` 
 threshold of the voxels kept so far.  ``--output-stack-masks`` writes the final masks, one file per stack.  A stack left without
 a voxel ends the command; with ``--input-slices`` the flags are ignored with a warning.  ``--sample-mask FILE`` on ``reconstruct``
 and ``sample-volume`` samples the model on that mask volume instead of the stored one.
+
+Also not in the reference (SVRTK denoises every stack by default): on the five commands that read stacks
+
+    [--denoise [--denoise-patch-radius 1] [--denoise-search-radius 3] [--denoise-strength 1.0] [--denoise-sigma X]]
+
+denoises every stack as it is loaded, after the masking switches and before ``--bias-field-correction``: 2-D non-local means,
+slice by slice (nesvor_amd/denoise.py, csrc/denoise.hip), with the noise level estimated per stack or given by ``--denoise-sigma``
+in the intensities of the stacks as loaded; the log shows sigma and the rms of what was removed.  ``denoise`` writes the denoised
+stacks and, with ``--output-json``, the per-stack report.  With ``--input-slices`` the flags are ignored with a warning.
 
 Also not in the reference: ``evaluate`` compares volumes with a reference volume (nesvor_amd/evaluate.py, csrc/evaluate.hip): every
 input volume is put onto the reference's lattice through the two files' poses (trilinear; ``svr`` writes a world-aligned lattice,
@@ -205,6 +216,30 @@ def _mask_flags(p: argparse.ArgumentParser) -> None:
     g.add_argument("--output-stack-masks", nargs="+", type=str, help="write the final mask of every input stack, one file per stack")
 
 
+def _denoise_flags(p: argparse.ArgumentParser, switch: bool = True) -> None:
+    g = p.add_argument_group("stack denoising (not in the reference; nesvor_amd/denoise.py)")
+    if switch:
+        g.add_argument("--denoise", action="store_true",
+                       help="denoise every input stack as it is loaded: 2-D non-local means, slice by slice, after the masking "
+                            "switches and before --bias-field-correction")
+    g.add_argument("--denoise-patch-radius", default=1, type=int, help="patches of (2 r + 1)^2 pixels are compared")
+    g.add_argument("--denoise-search-radius", default=3, type=int, help="every pixel is compared with those at most this far away")
+    g.add_argument("--denoise-strength", default=1.0, type=float, help="the filter parameter h in units of sigma: h = strength x sigma")
+    g.add_argument("--denoise-sigma", type=float, metavar="X",
+                   help="the noise standard deviation, in the intensities of the stacks as loaded, instead of the per-stack estimate")
+
+
+def denoise_options(args: Namespace) -> Dict:
+    """The keyword arguments of ``denoise.denoise_stacks`` from the ``--denoise-*`` flags (defaults where a Namespace lacks them)."""
+    return {"patch_radius": getattr(args, "denoise_patch_radius", 1), "search_radius": getattr(args, "denoise_search_radius", 3),
+            "strength": getattr(args, "denoise_strength", 1.0), "sigma": getattr(args, "denoise_sigma", None)}
+
+
+def warn_denoise_ignored(args: Namespace, why: str) -> None:
+    if getattr(args, "denoise", False):
+        logging.warning("--denoise and the --denoise-* flags are ignored with %s: no stack is loaded", why)
+
+
 MASK_FLAGS = ("volume_mask", "stacks_intersection", "background_threshold", "otsu_thresholding", "output_stack_masks")
 
 
@@ -252,6 +287,7 @@ def build_parser() -> argparse.ArgumentParser:
     _training_flags(p)
     _bias_flags(p)
     _mask_flags(p)
+    _denoise_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("register")
@@ -267,6 +303,7 @@ def build_parser() -> argparse.ArgumentParser:
     _template_flags(g)
     _bias_flags(p)
     _mask_flags(p)
+    _denoise_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("svr")
@@ -310,6 +347,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="folder for the slices divided by their fields (with --slice-bias-fields)")
     _bias_flags(p)
     _mask_flags(p)
+    _denoise_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("assess")
@@ -323,6 +361,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--output-json", type=str, help="JSON file for the list of per-stack results")
     _bias_flags(p)
     _mask_flags(p)
+    _denoise_flags(p)
     _common_flags(p)
 
     p = sub.add_parser("correct-bias-field")
@@ -334,6 +373,17 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--output-bias-fields", nargs="+", type=str, help="the estimated fields exp(f), one file per input stack")
     _bias_flags(p, switch=False)
     _mask_flags(p)
+    _denoise_flags(p)
+    _common_flags(p)
+
+    p = sub.add_parser("denoise")
+    g = p.add_argument_group("input")
+    g.add_argument("--input-stacks", nargs="+", type=str, required=True)
+    g.add_argument("--stack-masks", nargs="+", type=str)
+    g = p.add_argument_group("output")
+    g.add_argument("--output-stacks", nargs="+", type=str, required=True, help="the denoised stacks, one file per input stack")
+    g.add_argument("--output-json", type=str, help="JSON file for the list of per-stack reports (sigma, method noise)")
+    _denoise_flags(p, switch=False)
     _common_flags(p)
 
     p = sub.add_parser("evaluate")
@@ -484,6 +534,8 @@ def _load_stacks(args: Namespace) -> List:
         stacks.append(st)
     if masking_requested(args):
         _mask_stacks(args, stacks)
+    if getattr(args, "denoise", False):
+        _denoise_stacks(args, stacks)
     if getattr(args, "bias_field_correction", False):
         from . import bias
 
@@ -511,6 +563,17 @@ def _mask_stacks(args: Namespace, stacks: List) -> None:
     if out is not None:
         for path, st in zip(out, stacks):
             save_stack(path, st, st.mask.to(st.slices.dtype))
+
+
+def _denoise_stacks(args: Namespace, stacks: List) -> List[Dict]:
+    """``--denoise`` on the loaded stacks (nesvor_amd/denoise.py); returns the per-stack reports as host numbers."""
+    from . import denoise
+
+    t0 = time.time()
+    reports = denoise.denoise_stacks(stacks, names=[f"stack {i} ({f})" for i, f in enumerate(args.input_stacks)], **denoise_options(args))
+    rows = [denoise.report_row(r) for r in reports]  # (reads the sums: the device has finished when the time is taken)
+    logging.info("Denoising of %d stacks finished in %.1f s", len(stacks), time.time() - t0)
+    return rows
 
 
 def _sample_mask(args: Namespace, mask):
@@ -594,6 +657,26 @@ def correct_bias_field_cmd(args: Namespace) -> None:
             save_stack(args.output_bias_fields[i], st, torch.exp(field).to(st.slices.dtype))
 
 
+def denoise_cmd(args: Namespace) -> None:
+    import json
+
+    from .image_io import save_stack
+
+    for name in ("output_stacks", "stack_masks"):
+        if getattr(args, name, None) is not None and len(getattr(args, name)) != len(args.input_stacks):
+            raise SystemExit(f"The numbers of {name.replace('_', ' ')} and input stacks are different!")
+    args.thicknesses = None
+    args.denoise = False  # (the stacks are denoised below, where the reports are at hand)
+    stacks = _load_stacks(args)
+    rows = _denoise_stacks(args, stacks)
+    for path, st, row, source in zip(args.output_stacks, stacks, rows, args.input_stacks):
+        save_stack(path, st)
+        row["input_stack"], row["output_stack"] = source, path
+    if args.output_json:
+        with open(args.output_json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def evaluate_cmd(args: Namespace) -> None:
     from .evaluate import evaluate_command
 
@@ -613,6 +696,7 @@ def reconstruct(args: Namespace) -> None:
     if args.input_slices is not None:
         warn_template_ignored(args, "--input-slices")
         warn_masking_ignored(args, "--input-slices")
+        warn_denoise_ignored(args, "--input-slices")
     for name in ("stack_masks", "thicknesses"):
         if getattr(args, name) is not None and len(getattr(args, name)) != len(args.input_stacks):
             raise SystemExit(f"The numbers of {name.replace('_', ' ')} and input stacks are different!")
@@ -693,7 +777,7 @@ def main(argv=None) -> None:
     _setup(args)
     t0 = time.time()
     {"reconstruct": reconstruct, "register": register_cmd, "svr": svr_cmd, "assess": assess_cmd,
-     "correct-bias-field": correct_bias_field_cmd, "evaluate": evaluate_cmd, "sample-volume": sample_volume_cmd,
+     "correct-bias-field": correct_bias_field_cmd, "denoise": denoise_cmd, "evaluate": evaluate_cmd, "sample-volume": sample_volume_cmd,
      "sample-slices": sample_slices_cmd}[args.command](args)
     logging.info("Command 'nesvor %s' finished, overall time: %.1f s", args.command, time.time() - t0)
 

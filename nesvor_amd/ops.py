@@ -550,6 +550,28 @@ _op("slice_bias_update(Tensor sim, Tensor y, Tensor? mask, Tensor scale, Tensor?
 
 
 # =====================================================================================================================
+# stack denoising (csrc/denoise.hip): 2-D non-local means of every slice of a stack and the two per-slice sums in one pass;
+# the definition, the noise estimate and the choice of the path are nesvor_amd/denoise.py
+# =====================================================================================================================
+def _nlm_denoise(y, mask, sigma, patch_radius, search_radius, strength):
+    _lib.require_device(y, sigma, dtype=torch.float32, name="nlm_denoise y/sigma")
+    m, n, h, w = _slice_stack("nlm_denoise", {"y": y}, mask, {"sigma": sigma})
+    if sigma.numel() != n:
+        raise RuntimeError("nlm_denoise: sigma (n) expected")
+    out = torch.empty_like(y)
+    stats = torch.empty((n, 2), dtype=torch.float64, device=y.device)
+    _launch("nlm_denoise", y.device, (n, h, w), _lib.ptr(y), _lib.ptr(m), _lib.ptr(sigma), n, h, w, int(patch_radius), int(search_radius),
+            float(strength), _lib.ptr(out), _lib.ptr(stats))
+    return out, stats
+
+
+_op("nlm_denoise(Tensor y, Tensor? mask, Tensor sigma, int patch_radius, int search_radius, float strength) -> (Tensor out, Tensor stats)",
+    _nlm_denoise,
+    fake=lambda y, mask, sigma, patch_radius, search_radius, strength: (torch.empty_like(y),
+                                                                        y.new_empty((y.shape[0], 2), dtype=torch.float64)))
+
+
+# =====================================================================================================================
 # masked moments of slice pairs for the stack quality assessment (csrc/assess.hip): {count, sum a, sum b, sum a^2, sum b^2,
 # sum a b} per pair over the pixels valid in both slices; the host logic (and the range check of the pair indices, which the
 # kernel does not repeat) is nesvor_amd/assess.py
