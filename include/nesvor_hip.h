@@ -839,6 +839,46 @@ int nesvor_svr_similarity(const float* vol, int D, int H, int W, const float* ps
 int64_t nesvor_svr_similarity_workspace_bytes(int n, int K, int h, int w);
 
 /* ----------------------------------------------------------------------
+ * Per-slice PSFs: a PSF BANK in A, A^T and the similarity sums (fp32, linear mode; interp_psf, both backwards and fp64 keep
+ * one PSF).  A bank is
+ *   psf_bank  : P dense PSFs of their own sizes, concatenated into one float array           (device memory)
+ *   psf_table : (P,4) int32, row p = { offset of member p in psf_bank in floats, d_p, h_p, w_p }   (HOST memory: the entry
+ *               point checks it and hands it to the kernels as an argument; it may be freed when the call returns)
+ *   psf_id    : (n) int32, the member of every slice                                           (device memory)
+ * Slice k takes member psf_id[k] everywhere: its taps in the order of its dense array with zero taps skipped, its extents
+ * in the box bounds of A^T's voxel gather, its weight sum.  The slices are walked in the order k = 0 .. n-1, never grouped
+ * by member.  A slice whose id lies outside [0, P) has no taps: it is simulated as empty (no pixel written, no valid pixel
+ * in the sums) and contributes nothing to A^T; nothing is indexed by such an id.  With P = 1 and every id 0 the results
+ * are those of the one-PSF entry points bit for bit, and so are a member's slices in any bank; a member padded with zero
+ * taps gives the same bits as the member itself.
+ *
+ * Apart from the bank, the arguments, the outputs and the scratch / workspace rules are those of the one-PSF twins:
+ *   nesvor_slice_acq_forward_bank          nesvor_slice_acq_forward (interp_psf = 0): writes the pixels of weight > 0 only -
+ *                                          the caller zero-fills slices / slices_weight; members of more than 1024 elements
+ *                                          are walked from global memory, per slice, in the same launch
+ *   nesvor_slice_acq_adjoint_forward_bank  nesvor_slice_acq_adjoint_forward: scratch of 2 n h w floats; vol (and vol_weight, if
+ *                                          not NULL) fully written
+ *   nesvor_svr_similarity_bank             nesvor_svr_similarity: workspace of nesvor_svr_similarity_workspace_bytes(n, K, h, w);
+ *                                          refuses a bank in which ANY member has more than 1024 elements
+ * An empty stack (n h w = 0) launches nothing (A^T of it is the zero volume, by clears).
+ * hipErrorInvalidValue, before anything is launched or written: P < 1 or P > 32, a NULL bank or table, psf_id NULL with n > 0,
+ * a member with a negative offset or a dimension below 1, D H W > INT_MAX, and what the twin refuses.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_slice_acq_forward_bank(const float* transforms, const float* vol, const uint8_t* vol_mask,
+                                  const uint8_t* slices_mask, const float* psf_bank, const int32_t* psf_table, int P,
+                                  const int32_t* psf_id, float* slices, float* slices_weight, int D, int H, int W, int n,
+                                  int h, int w, float res_slice, void* stream);
+int nesvor_slice_acq_adjoint_forward_bank(const float* transforms, const float* psf_bank, const int32_t* psf_table, int P,
+                                          const int32_t* psf_id, const float* slices, const uint8_t* slices_mask,
+                                          const uint8_t* vol_mask, float* vol, float* vol_weight, float* scratch, int D,
+                                          int H, int W, int n, int h, int w, float res_slice, int equalize, void* stream);
+int nesvor_svr_similarity_bank(const float* vol, int D, int H, int W, const float* psf_bank, const int32_t* psf_table, int P,
+                               const int32_t* psf_id, const float* transforms, const float* slices,
+                               const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, double* sums,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* ----------------------------------------------------------------------
  * One descent step of the classical super-resolution reconstruction with the edge-preserving prior, in one launch
  * (the loop body of the reference's SRR, svort/srr.py:117-131, whose prior gradient dR is :139-160):
  *   out[a] = x[a] - alpha * (grad[a] + beta * dR(x)[a])

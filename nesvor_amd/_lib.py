@@ -229,6 +229,11 @@ _SIGNATURES = {
     "nesvor_svr_similarity": ([_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P,
                                c_size_t, _P], c_int),
     "nesvor_svr_similarity_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
+    # the PSF bank's twins: (psf_bank, psf_table (host), P, psf_id) in the place of (psf, d_p, h_p, w_p)
+    "nesvor_slice_acq_forward_bank": ([_P] * 6 + [c_int, _P, _P, _P] + [c_int] * 6 + [c_float, _P], c_int),
+    "nesvor_slice_acq_adjoint_forward_bank": ([_P] * 3 + [c_int] + [_P] * 7 + [c_int] * 6 + [c_float, c_int, _P], c_int),
+    "nesvor_svr_similarity_bank": ([_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P,
+                                    c_size_t, _P], c_int),
     "nesvor_srr_step": ([_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_int, _P], c_int),
     "nesvor_robust_estep": ([_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P], c_int),
     "nesvor_robust_estep_workspace_bytes": ([c_int, c_int, c_int], c_int64),

@@ -56,6 +56,13 @@ data matrix, ``volume`` of the mask; higher is better) and ranks them; ``--templ
 (default 0, the first file, as before) or ``auto`` = the best stack under ``--template-metric``.  The output slices keep the
 input order.  With ``--registration none`` or ``--input-slices`` the two flags are ignored with a warning.
 
+Also not in the reference: ``--per-stack-thickness`` on ``svr``, ``register`` and ``reconstruct`` (there for the registration stage
+only) lets stacks of unequal slice thickness keep their own (``--thicknesses``, or the files' z spacing): ``--registration stack``
+registers every stack on the template's slice spacing and spaces its slices by its own gap, and ``svr`` / ``--registration svr``
+simulate every slice with the PSF of its own thickness (a PSF bank, nesvor_amd/psf_bank.py, looked up per slice inside one
+launch of A and A^T); ``svr --input-slices`` then accepts a folder of mixed thickness (not of mixed pixel size).  Without the flag
+the mean thickness serves all stacks, with a warning, as before; with it and equal thicknesses nothing changes either.
+
 Also not in the reference (upstream added both in later releases, on SimpleITK's N4): ``correct-bias-field`` estimates the smooth
 multiplicative coil bias of every input stack (nesvor_amd/bias.py, csrc/bias.hip: histogram sharpening and a multilevel
 B-spline fit of the log field, this project's own definition) and writes the corrected stacks and, with
@@ -262,6 +269,13 @@ def bias_options(args: Namespace) -> Dict:
             "fwhm": getattr(args, "fwhm_n4", 0.15), "noise": getattr(args, "noise_n4", 0.01)}
 
 
+def _thickness_flags(g) -> None:
+    g.add_argument("--per-stack-thickness", action="store_true",
+                   help="stacks of unequal slice thickness keep their own: the stack registration spaces every stack by its own gap, "
+                        "and svr / --registration svr simulate every slice with the PSF of its own thickness (nesvor_amd/psf_bank.py); "
+                        "without the flag the mean thickness is used for all stacks")
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="nesvor_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = parser.add_subparsers(dest="command", required=True)
@@ -284,6 +298,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--registration", default="none", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
+    _thickness_flags(g)
     _training_flags(p)
     _bias_flags(p)
     _mask_flags(p)
@@ -301,6 +316,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--registration", default="stack", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
+    _thickness_flags(g)
     _bias_flags(p)
     _mask_flags(p)
     _denoise_flags(p)
@@ -322,6 +338,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--registration", default="svr", type=str, choices=["svort", "svort-stack", "stack", "svr", "none"])
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
+    _thickness_flags(g)
     g = p.add_argument_group("super-resolution reconstruction")
     g.add_argument("--n-iter-srr", default=30, type=int, help="descent steps")
     g.add_argument("--srr-beta", default=0.02, type=float, help="weight of the edge-preserving prior")
@@ -601,17 +618,18 @@ def register(args: Namespace, stacks: List) -> List:
 
     # the template only names the registration's target: the stacks, and stack_idx / slice_idx of the slices, stay in input order
     template = choose_template(stacks, getattr(args, "template_stack", "0"), getattr(args, "template_metric", "ncc"))
+    per_stack = bool(getattr(args, "per_stack_thickness", False))
     if args.registration == "stack":
         from .registration import register_stacks
 
         t1 = time.time()
-        stacks = register_stacks(stacks, template=template)
+        stacks = register_stacks(stacks, template=template, per_stack_thickness=per_stack)
         logging.info("Stack registration finished in %.1f s", time.time() - t1)
     elif args.registration == "svr":
         from .registration import register_slices
 
         t1 = time.time()
-        stacks = register_slices(stacks, template=template)
+        stacks = register_slices(stacks, template=template, per_stack_thickness=per_stack)
         logging.info("Slice-to-volume registration finished in %.1f s", time.time() - t1)
     return stacks_to_slices(stacks)
 

@@ -44,6 +44,55 @@ __device__ __forceinline__ int compact_taps(const T* __restrict__ psf, int d_p, 
   return cnt;
 }
 
+// Which PSF a slice takes.  A kernel is written once over a source S with `S::at(k)`, the PSF of slice k as a view; k is uniform
+// over a workgroup (the forward, svr) or over the launch (the k loop of the voxel gather), so the id and the table row stay in
+// scalar registers: read once per slice, never per tap.
+template <typename T> struct PsfView { const T* psf; int d, h, w; };
+
+// One PSF for every slice (the kernels' first form; at() is loop-invariant and costs nothing).
+template <typename T> struct OnePsf {
+  const T* psf; int d, h, w;
+  __device__ __forceinline__ PsfView<T> at(int) const { return PsfView<T>{psf, d, h, w}; }
+};
+
+// A PSF bank: P dense PSFs of their own sizes concatenated in `data`, row p of the table {offset in elements, d_p, h_p, w_p}, one
+// id per slice in device memory.  The table travels by value as a kernel argument (the host checked it: P <= kMaxBankMembers,
+// positive sizes); an id outside [0, P) gives the empty view - no taps (compact_taps and for_psf_taps walk nothing of a 0 x 0 x 0
+// PSF, the gather's tap range iz = 0 .. -1 is empty), nothing indexed.
+constexpr int kMaxBankMembers = 32;
+template <typename T> struct BankPsf {
+  const T* data;
+  const int* ids;
+  int P;
+  int table[kMaxBankMembers][4];
+  __device__ __forceinline__ PsfView<T> at(int k) const {
+    const int id = ids[k];
+    if (id < 0 || id >= P) return PsfView<T>{data, 0, 0, 0};
+    return PsfView<T>{data + table[id][0], table[id][1], table[id][2], table[id][3]};
+  }
+};
+
+// The host's side of a bank: the checks every bank entry point makes before a launch, and the kernel argument.  `table` is HOST
+// memory, (P,4) ints.  false: P outside 1 .. kMaxBankMembers, no data or table, ids missing for n > 0 slices, a negative offset or a
+// member with a size below 1.
+// max_elements: the largest member's d_p h_p w_p.
+template <typename T>
+inline bool make_bank(const T* data, const int* table, int P, const int* ids, int n, BankPsf<T>& out, int64_t& max_elements) {
+  if (P < 1 || P > kMaxBankMembers || data == nullptr || table == nullptr || (ids == nullptr && n > 0)) return false;
+  out.data = data;
+  out.ids = ids;
+  out.P = P;
+  max_elements = 0;
+  for (int p = 0; p < kMaxBankMembers; ++p)
+    for (int j = 0; j < 4; ++j) out.table[p][j] = p < P ? table[4 * p + j] : 0;
+  for (int p = 0; p < P; ++p) {
+    if (out.table[p][0] < 0 || out.table[p][1] < 1 || out.table[p][2] < 1 || out.table[p][3] < 1) return false;
+    const int64_t e = (int64_t)out.table[p][1] * out.table[p][2] * out.table[p][3];
+    if (e > max_elements) max_elements = e;
+  }
+  return true;
+}
+
 template <typename T> struct PixelGeom { T qx, qy, qz, xc, yc, zc; };
 
 template <typename T>

@@ -103,6 +103,42 @@ __global__ __launch_bounds__(256) void slice_acq_fwd(
   }
 }
 
+// A with a PSF bank (fp32, linear mode): slice k is blurred by PSF ids[k].  One workgroup serves pixels of ONE slice (grid:
+// n * wgs, wgs = ceil(h w / 256), as svr_similarity_kernel), so the PSF, its sizes and the choice between the LDS list and the
+// dense walk (a member of more than kMaxTaps elements) are uniform over the workgroup.  Per pixel the arithmetic is slice_acq_fwd's.
+__global__ __launch_bounds__(256) void slice_acq_fwd_bank(const float* __restrict__ transforms, const float* __restrict__ vol,
+                                                          const uint8_t* __restrict__ vol_mask, const uint8_t* __restrict__ slices_mask,
+                                                          const BankPsf<float> psfs, float* __restrict__ slices,
+                                                          float* __restrict__ slices_weight, int D, int H, int W, int h, int w, int wgs,
+                                                          float res_slice) {
+  __shared__ Tap<float> taps[kMaxTaps];
+  __shared__ int n_taps;
+  const int in = blockIdx.x / wgs, wg = blockIdx.x - in * wgs;
+  const PsfView<float> pk = psfs.at(in);
+  const bool lds = (int64_t)pk.d * pk.h * pk.w <= kMaxTaps;
+  if (lds) {
+    if (threadIdx.x == 0) n_taps = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
+    __syncthreads();
+  }
+  const int pix = wg * 256 + (int)threadIdx.x;
+  if (pix >= h * w) return;
+  const size_t idx = (size_t)in * h * w + pix;
+  if (slices_mask != nullptr && !slices_mask[idx]) return;
+  const int ix = pix % w, iy = pix / w;
+  const float* t = transforms + (size_t)in * 12;
+  const PixelGeom<float> g = pixel_geom(t, ix, iy, h, w, res_slice, D, H, W);
+  float val = 0.f, wsum = 0.f;
+  auto tap = [&](float, float, float, float pv, float x, float y, float z) {
+    linear_tap(vol, vol_mask, trilinear_cell(x, y, z, H, W), pv, val, wsum);
+  };
+  if (lds) for_lds_taps(t, g, taps, n_taps, D, H, W, tap);
+  else for_psf_taps(t, g, pk.psf, pk.d, pk.h, pk.w, D, H, W, tap);
+  if (wsum > 0) {
+    slices[idx] = val / wsum;
+    if (slices_weight != nullptr) slices_weight[idx] = wsum;
+  }
+}
+
 // ------------------------------------------------------------------ adjoint A^T and backward of A
 // The reference scatters every (pixel, PSF tap) into 8 voxels with atomicAdd
 // (slice_acq_cuda_kernel.cu:173-470 backward, :472-670 adjoint).  On MI355X global atomics execute
@@ -142,21 +178,47 @@ __global__ __launch_bounds__(256) void slice_acq_pixel_coef(const T* __restrict_
   if (cw != nullptr) cw[idx] = iw;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void slice_acq_adjoint_gather(const T* __restrict__ transforms, const T* __restrict__ psf,
+// Pass 1 of A^T with a PSF bank (mode 0 of slice_acq_pixel_coef): the weight sum of a pixel runs over its slice's PSF.  Grid as
+// slice_acq_fwd_bank: the workgroup's slice, hence its PSF, is uniform.
+__global__ __launch_bounds__(256) void slice_acq_pixel_coef_bank(const float* __restrict__ transforms, const BankPsf<float> psfs,
+                                                                 const float* __restrict__ value, const uint8_t* __restrict__ slices_mask,
+                                                                 float* __restrict__ coef, float* __restrict__ cw, int D, int H, int W,
+                                                                 int h, int w, int wgs, float res_slice) {
+  const int in = blockIdx.x / wgs, wg = blockIdx.x - in * wgs;
+  const int pix = wg * 256 + (int)threadIdx.x;
+  if (pix >= h * w) return;
+  const PsfView<float> pk = psfs.at(in);
+  const size_t idx = (size_t)in * h * w + pix;
+  float c = 0.f, iw = 0.f;
+  if (slices_mask == nullptr || slices_mask[idx]) {
+    const float* t = transforms + (size_t)in * 12;
+    const PixelGeom<float> g = pixel_geom(t, pix % w, pix / w, h, w, res_slice, D, H, W);
+    float weight = 0.f;
+    for_psf_taps(t, g, pk.psf, pk.d, pk.h, pk.w, D, H, W, [&](float, float, float, float pv, float, float, float) { weight += pv; });
+    if (weight >= 0.5f) { c = value[idx] / weight; iw = 1.f / weight; }
+  }
+  coef[idx] = c;
+  cw[idx] = iw;
+}
+
+// PSF: OnePsf<T>, or BankPsf<T> - slice k then takes its own PSF and, with it, its own tap ranges tz0 .. tx1 in the box bounds.
+template <typename T, typename PSF>
+__global__ __launch_bounds__(256) void slice_acq_adjoint_gather(const T* __restrict__ transforms, const PSF psfs,
                                                                 const T* __restrict__ coef, const T* __restrict__ cw,
                                                                 const uint8_t* __restrict__ vol_mask, T* __restrict__ vol,
-                                                                T* __restrict__ vol_weight, int D, int H, int W, int d_p,
-                                                                int h_p, int w_p, int n, int h, int w, T res_slice,
-                                                                int equalize, int accumulate) {
+                                                                T* __restrict__ vol_weight, int D, int H, int W, int n, int h, int w,
+                                                                T res_slice, int equalize, int accumulate) {
   const int64_t iv = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (iv >= (int64_t)D * H * W) return;
   const int vx = iv % W, vy = (iv / W) % H, vz = iv / ((int64_t)H * W);
   T acc = (T)0.0, accw = (T)0.0;
   if (vol_mask == nullptr || vol_mask[iv]) {
     const T d0 = vx - (W - 1) / (T)2.0, d1 = vy - (H - 1) / (T)2.0, d2 = vz - (D - 1) / (T)2.0;
-    const int tz0 = -d_p / 2, tz1 = (d_p + 1) / 2 - 1, ty0 = -h_p / 2, ty1 = (h_p + 1) / 2 - 1, tx0 = -w_p / 2, tx1 = (w_p + 1) / 2 - 1;
     for (int k = 0; k < n; ++k) {
+      const PsfView<T> pk = psfs.at(k);  // (uniform over the launch; loop-invariant for OnePsf)
+      const T* __restrict__ psf = pk.psf;
+      const int d_p = pk.d, h_p = pk.h, w_p = pk.w;
+      const int tz0 = -d_p / 2, tz1 = (d_p + 1) / 2 - 1, ty0 = -h_p / 2, ty1 = (h_p + 1) / 2 - 1, tx0 = -w_p / 2, tx1 = (w_p + 1) / 2 - 1;
       const T* t = transforms + (size_t)k * 12;
       // voxel in the slice frame: r = R^T (v - c0)
       const T rz = t[2] * d0 + t[6] * d1 + t[10] * d2;
@@ -387,9 +449,55 @@ int slice_acq_adjoint_forward_impl(const T* transforms, const T* psf, const T* s
   if (np > 0)
     hipLaunchKernelGGL(slice_acq_pixel_coef<T>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, transforms, psf, slices,
                        slices_mask, coef, cw, D, H, W, d_p, h_p, w_p, n, h, w, res_slice, 0);
-  hipLaunchKernelGGL(slice_acq_adjoint_gather<T>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, transforms, psf, coef,
-                     (equalize || vol_weight != nullptr) ? cw : (const T*)nullptr, vol_mask, vol, vol_weight, D, H, W, d_p, h_p,
-                     w_p, n, h, w, res_slice, equalize, 0);
+  hipLaunchKernelGGL((slice_acq_adjoint_gather<T, OnePsf<T>>), dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, transforms,
+                     OnePsf<T>{psf, d_p, h_p, w_p}, coef, (equalize || vol_weight != nullptr) ? cw : (const T*)nullptr, vol_mask, vol,
+                     vol_weight, D, H, W, n, h, w, res_slice, equalize, 0);
+  return (int)hipGetLastError();
+}
+
+// The bank entry points' common checks -> the kernel argument and the per-slice grid (n * wgs workgroups of 256 pixels).
+bool bank_request(const float* psf_bank, const int* psf_table, int P, const int* psf_id, int D, int H, int W, int n, int h, int w,
+                  BankPsf<float>& bank, int64_t& wgs) {
+  int64_t max_elements;
+  if (!make_bank(psf_bank, psf_table, P, psf_id, n, bank, max_elements) || volume_too_large(D, H, W)) return false;
+  if (n < 0 || h < 0 || w < 0 || (int64_t)h * w > (int64_t)INT_MAX) return false;
+  wgs = ((int64_t)h * w + 255) / 256;
+  return wgs * n <= (int64_t)INT_MAX;
+}
+
+int slice_acq_forward_bank_impl(const float* transforms, const float* vol, const uint8_t* vol_mask, const uint8_t* slices_mask,
+                                const float* psf_bank, const int* psf_table, int P, const int* psf_id, float* slices,
+                                float* slices_weight, int D, int H, int W, int n, int h, int w, float res_slice, void* stream) {
+  BankPsf<float> bank;
+  int64_t wgs;
+  if (!bank_request(psf_bank, psf_table, P, psf_id, D, H, W, n, h, w, bank, wgs)) return (int)hipErrorInvalidValue;
+  if (wgs * n <= 0) return 0;
+  hipLaunchKernelGGL(slice_acq_fwd_bank, dim3((unsigned)(wgs * n)), dim3(256), 0, (hipStream_t)stream, transforms, vol, vol_mask,
+                     slices_mask, bank, slices, slices_weight, D, H, W, h, w, (int)wgs, res_slice);
+  return (int)hipGetLastError();
+}
+
+int slice_acq_adjoint_forward_bank_impl(const float* transforms, const float* psf_bank, const int* psf_table, int P, const int* psf_id,
+                                        const float* slices, const uint8_t* slices_mask, const uint8_t* vol_mask, float* vol,
+                                        float* vol_weight, float* scratch, int D, int H, int W, int n, int h, int w, float res_slice,
+                                        int equalize, void* stream) {
+  BankPsf<float> bank;
+  int64_t wgs;
+  if (!bank_request(psf_bank, psf_table, P, psf_id, D, H, W, n, h, w, bank, wgs)) return (int)hipErrorInvalidValue;
+  const int64_t np = (int64_t)n * h * w, nv = (int64_t)D * H * W;
+  if (nv <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (np <= 0) {  // an empty stack launches nothing: A^T of it is the zero volume, by two clears
+    const int e = zero_fill(vol, nv, st);
+    return e != 0 ? e : zero_fill(vol_weight, nv, st);
+  }
+  float* coef = scratch;
+  float* cw = scratch + np;
+  hipLaunchKernelGGL(slice_acq_pixel_coef_bank, dim3((unsigned)(wgs * n)), dim3(256), 0, st, transforms, bank, slices, slices_mask,
+                     coef, cw, D, H, W, h, w, (int)wgs, res_slice);
+  hipLaunchKernelGGL((slice_acq_adjoint_gather<float, BankPsf<float>>), dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, transforms,
+                     bank, (const float*)coef, (equalize || vol_weight != nullptr) ? (const float*)cw : (const float*)nullptr, vol_mask,
+                     vol, vol_weight, D, H, W, n, h, w, res_slice, equalize, 0);
   return (int)hipGetLastError();
 }
 
@@ -409,8 +517,9 @@ int slice_acq_backward_impl(const T* transforms, const T* vol, const uint8_t* vo
   hipLaunchKernelGGL(slice_acq_pixel_coef<T>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, transforms, psf, grad_slices,
                      slices_mask, coef, (T*)nullptr, D, H, W, d_p, h_p, w_p, n, h, w, res_slice, 1);
   if (grad_vol != nullptr)
-    hipLaunchKernelGGL(slice_acq_adjoint_gather<T>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, transforms, psf, coef,
-                       (const T*)nullptr, vol_mask, grad_vol, (T*)nullptr, D, H, W, d_p, h_p, w_p, n, h, w, res_slice, 0, 0);
+    hipLaunchKernelGGL((slice_acq_adjoint_gather<T, OnePsf<T>>), dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, transforms,
+                       OnePsf<T>{psf, d_p, h_p, w_p}, coef, (const T*)nullptr, vol_mask, grad_vol, (T*)nullptr, D, H, W, n, h, w,
+                       res_slice, 0, 0);
   if (grad_transforms != nullptr)
     hipLaunchKernelGGL(slice_acq_bwd_transforms<T>, dim3((unsigned)n), dim3(256), 0, st, transforms, vol, vol_mask, psf, coef,
                        grad_transforms, D, H, W, d_p, h_p, w_p, h, w, res_slice);
@@ -693,3 +802,19 @@ int slice_acq_adjoint_backward_interp_impl(const T* transforms, T* grad_vol, con
 NESVOR_SLICE_ACQ_ENTRY(, float)
 NESVOR_SLICE_ACQ_ENTRY(_f64, double)
 #undef NESVOR_SLICE_ACQ_ENTRY
+
+// ---- A and A^T with a PSF bank (fp32, linear mode): slice k takes PSF psf_id[k]
+extern "C" int nesvor_slice_acq_forward_bank(const float* transforms, const float* vol, const uint8_t* vol_mask,
+                                             const uint8_t* slices_mask, const float* psf_bank, const int32_t* psf_table, int P,
+                                             const int32_t* psf_id, float* slices, float* slices_weight, int D, int H, int W, int n,
+                                             int h, int w, float res_slice, void* stream) {
+  return slice_acq_forward_bank_impl(transforms, vol, vol_mask, slices_mask, psf_bank, psf_table, P, psf_id, slices, slices_weight, D, H,
+                                     W, n, h, w, res_slice, stream);
+}
+extern "C" int nesvor_slice_acq_adjoint_forward_bank(const float* transforms, const float* psf_bank, const int32_t* psf_table, int P,
+                                                     const int32_t* psf_id, const float* slices, const uint8_t* slices_mask,
+                                                     const uint8_t* vol_mask, float* vol, float* vol_weight, float* scratch, int D,
+                                                     int H, int W, int n, int h, int w, float res_slice, int equalize, void* stream) {
+  return slice_acq_adjoint_forward_bank_impl(transforms, psf_bank, psf_table, P, psf_id, slices, slices_mask, vol_mask, vol, vol_weight,
+                                             scratch, D, H, W, n, h, w, res_slice, equalize, stream);
+}

@@ -25,19 +25,22 @@ using namespace acq;
 constexpr int kSums = 6;
 
 // grid: n * wgs workgroups of 256 pixels, wgs = ceil(h w / 256) per slice.  transforms: (n, K, 3, 4), this pass covers poses
-// k0 .. k0 + KT - 1.  partial: (n, K, wgs, 6) doubles.
-template <int KT>
-__global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __restrict__ vol, int D, int H, int W,
-                                                             const float* __restrict__ psf, int d_p, int h_p, int w_p,
+// k0 .. k0 + KT - 1.  partial: (n, K, wgs, 6) doubles.  PSF: OnePsf<float>, or BankPsf<float> - the workgroup's slice then compacts
+// its own PSF (acq_taps.h).
+template <int KT, typename PSF>
+__global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __restrict__ vol, int D, int H, int W, const PSF psfs,
                                                              const float* __restrict__ transforms, const float* __restrict__ slices,
                                                              const uint8_t* __restrict__ slices_mask, int K, int k0, int h, int w,
                                                              int wgs, float res_slice, double* __restrict__ partial) {
   __shared__ Tap<float> taps[kMaxTaps];
   __shared__ int n_taps;
   __shared__ float red[4][KT][kSums];
-  if (threadIdx.x == 0) n_taps = compact_taps(psf, d_p, h_p, w_p, taps);
-  __syncthreads();
   const int in = blockIdx.x / wgs, wg = blockIdx.x - in * wgs;
+  if (threadIdx.x == 0) {
+    const PsfView<float> pk = psfs.at(in);
+    n_taps = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
+  }
+  __syncthreads();
   const int pix = wg * 256 + (int)threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool inside = pix < h * w;
@@ -83,13 +86,13 @@ extern "C" int64_t nesvor_svr_similarity_workspace_bytes(int n, int K, int h, in
   return slice_sums::Plan<kSums>{(int64_t)n * K, slice_sums::pixel_workgroups(h, w)}.workspace_bytes();
 }
 
-extern "C" int nesvor_svr_similarity(const float* vol, int D, int H, int W, const float* psf, int d_p, int h_p, int w_p,
-                                     const float* transforms, const float* slices, const uint8_t* slices_mask, int n, int K,
-                                     int h, int w, float res_slice, double* sums, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-  if (K <= 0 || n == 0) return 0;
-  if (D < 1 || H < 1 || W < 1 || h < 1 || w < 1 || n < 1 || d_p < 1 || h_p < 1 || w_p < 1) return (int)hipErrorInvalidValue;
-  if ((int64_t)d_p * h_p * w_p > kMaxTaps) return (int)hipErrorInvalidValue;
+namespace {
+// The launches of both entry points, behind their checks of the PSF source.
+template <typename PSF>
+int svr_similarity_launch(const float* vol, int D, int H, int W, const PSF& psfs, const float* transforms, const float* slices,
+                          const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, double* sums, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (D < 1 || H < 1 || W < 1 || h < 1 || w < 1 || n < 1) return (int)hipErrorInvalidValue;
   // voxel indices are ints; an entry is a (slice, pose), a workgroup serves all poses of its 256 pixels
   if ((int64_t)D * H * W > INT_MAX || (int64_t)n * K > INT_MAX) return (int)hipErrorInvalidValue;
   const slice_sums::Plan<kSums> plan{(int64_t)n * K, slice_sums::pixel_workgroups(h, w)};
@@ -101,15 +104,40 @@ extern "C" int nesvor_svr_similarity(const float* vol, int D, int H, int W, cons
   int k = 0;
   while (k < K) {  // 13 poses per pass (one finite-difference gradient), single poses otherwise
     if (K - k >= 13) {
-      hipLaunchKernelGGL((svr_similarity_kernel<13>), grid, block, 0, st, vol, D, H, W, psf, d_p, h_p, w_p, transforms, slices,
-                         slices_mask, K, k, h, w, (int)wgs, res_slice, partial);
+      hipLaunchKernelGGL((svr_similarity_kernel<13, PSF>), grid, block, 0, st, vol, D, H, W, psfs, transforms, slices, slices_mask, K,
+                         k, h, w, (int)wgs, res_slice, partial);
       k += 13;
     } else {
-      hipLaunchKernelGGL((svr_similarity_kernel<1>), grid, block, 0, st, vol, D, H, W, psf, d_p, h_p, w_p, transforms, slices,
-                         slices_mask, K, k, h, w, (int)wgs, res_slice, partial);
+      hipLaunchKernelGGL((svr_similarity_kernel<1, PSF>), grid, block, 0, st, vol, D, H, W, psfs, transforms, slices, slices_mask, K,
+                         k, h, w, (int)wgs, res_slice, partial);
       k += 1;
     }
   }
   plan.reduce(workspace, sums, st);
   return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int nesvor_svr_similarity(const float* vol, int D, int H, int W, const float* psf, int d_p, int h_p, int w_p,
+                                     const float* transforms, const float* slices, const uint8_t* slices_mask, int n, int K,
+                                     int h, int w, float res_slice, double* sums, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  if (K <= 0 || n == 0) return 0;
+  if (d_p < 1 || h_p < 1 || w_p < 1 || (int64_t)d_p * h_p * w_p > kMaxTaps) return (int)hipErrorInvalidValue;
+  return svr_similarity_launch(vol, D, H, W, OnePsf<float>{psf, d_p, h_p, w_p}, transforms, slices, slices_mask, n, K, h, w, res_slice,
+                               sums, workspace, workspace_bytes, stream);
+}
+
+// The same sums with a PSF bank: slice i is simulated with PSF psf_id[i].  Refused if ANY member has more than kMaxTaps elements.
+extern "C" int nesvor_svr_similarity_bank(const float* vol, int D, int H, int W, const float* psf_bank, const int32_t* psf_table,
+                                          int P, const int32_t* psf_id, const float* transforms, const float* slices,
+                                          const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, double* sums,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  BankPsf<float> bank;
+  int64_t max_elements;
+  if (!make_bank(psf_bank, psf_table, P, psf_id, n, bank, max_elements) || max_elements > kMaxTaps) return (int)hipErrorInvalidValue;
+  if ((int64_t)D * H * W > INT_MAX) return (int)hipErrorInvalidValue;
+  if (K <= 0 || n == 0) return 0;
+  return svr_similarity_launch(vol, D, H, W, bank, transforms, slices, slices_mask, n, K, h, w, res_slice, sums, workspace,
+                               workspace_bytes, stream);
 }

@@ -361,6 +361,92 @@ _op("svr_similarity(Tensor vol, Tensor psf, Tensor transforms, Tensor slices, Te
 
 
 # =====================================================================================================================
+# per-slice PSFs (nesvor_amd/psf_bank.py): A, A^T and the similarity sums with a PSF bank - psf_bank the members concatenated,
+# psf_table (P,4) int32 on the HOST {offset, d_p, h_p, w_p}, psf_id (n) int32 on the device.  fp32, linear mode, no autograd
+# formula (slice_acquisition.py raises when a gradient is asked for)
+# =====================================================================================================================
+def _bank(what, psf_bank, psf_table, psf_id, n):
+    _lib.require_device(psf_bank, dtype=torch.float32, name=f"{what} psf_bank")
+    _lib.require_device(psf_id, dtype=torch.int32, name=f"{what} psf_id")
+    if psf_table.is_cuda or psf_table.dtype != torch.int32 or psf_table.ndim != 2 or psf_table.shape[1] != 4 or not psf_table.is_contiguous():
+        raise RuntimeError(f"{what}: psf_table, (P, 4) int32 in host memory, expected")
+    if psf_id.numel() != n:
+        raise RuntimeError(f"{what}: psf_id must hold one id per slice ({n}), got {psf_id.numel()}")
+    P = int(psf_table.shape[0])
+    if P > 0 and int((psf_table[:, 0] + psf_table[:, 1:].prod(1)).max()) > psf_bank.numel():
+        raise RuntimeError(f"{what}: a row of psf_table reaches past the end of psf_bank")
+    return _lib.ptr(psf_bank), ctypes.c_void_p(psf_table.data_ptr()), P, _lib.ptr(psf_id)
+
+
+def _sa_forward_bank(transforms, vol, vol_mask, slices_mask, psf_bank, psf_table, psf_id, slice_shape, res_slice, need_weight):
+    _lib.require_device(transforms, vol, dtype=torch.float32, name="slice_acq_forward_bank transforms/vol")
+    vm, sm = _mask(vol_mask), _mask(slices_mask)
+    n, (h, w) = transforms.shape[0], (int(slice_shape[0]), int(slice_shape[1]))
+    bank = _bank("slice_acq_forward_bank", psf_bank, psf_table, psf_id, n)
+    slices = torch.zeros((n, 1, h, w), dtype=vol.dtype, device=vol.device)
+    weight = torch.zeros((n, 1, h, w), dtype=vol.dtype, device=vol.device) if need_weight else None
+    with torch.cuda.device(vol.device):
+        err = _lib.load().nesvor_slice_acq_forward_bank(
+            _lib.ptr(transforms), _lib.ptr(vol), _lib.ptr(vm), _lib.ptr(sm), *bank, _lib.ptr(slices), _lib.ptr(weight),
+            *(int(s) for s in vol.shape[-3:]), n, h, w, float(res_slice), _lib.stream_ptr())
+    _lib.check(err, "slice_acq forward_bank")
+    return [slices, weight] if need_weight else [slices]
+
+
+def _sa_adjoint_forward_bank(transforms, psf_bank, psf_table, psf_id, slices, slices_mask, vol_mask, vol_shape, res_slice, equalize):
+    _lib.require_device(transforms, slices, dtype=torch.float32, name="slice_acq_adjoint_forward_bank transforms/slices")
+    vm, sm = _mask(vol_mask), _mask(slices_mask)
+    n, h, w = slices.shape[0], slices.shape[-2], slices.shape[-1]
+    bank = _bank("slice_acq_adjoint_forward_bank", psf_bank, psf_table, psf_id, n)
+    D, H, W = (int(s) for s in vol_shape)
+    vol = torch.empty((1, 1, D, H, W), dtype=slices.dtype, device=slices.device)
+    vol_weight = torch.empty((1, 1, D, H, W), dtype=slices.dtype, device=slices.device) if equalize else None
+    scratch = torch.empty(max(2 * n * h * w, 1), dtype=slices.dtype, device=slices.device)
+    with torch.cuda.device(slices.device):
+        err = _lib.load().nesvor_slice_acq_adjoint_forward_bank(
+            _lib.ptr(transforms), *bank, _lib.ptr(slices), _lib.ptr(sm), _lib.ptr(vm), _lib.ptr(vol), _lib.ptr(vol_weight),
+            _lib.ptr(scratch), D, H, W, n, h, w, float(res_slice), int(bool(equalize)), _lib.stream_ptr())
+    _lib.check(err, "slice_acq adjoint_forward_bank")
+    return [vol, vol_weight if equalize else _empty(slices)]
+
+
+def _svr_similarity_bank(vol, psf_bank, psf_table, psf_id, transforms, slices, slices_mask, res_slice):
+    _lib.require_device(vol, transforms, slices, dtype=torch.float32, name="svr_similarity_bank vol/transforms/slices")
+    sm = _mask(slices_mask)
+    if vol.ndim < 3 or transforms.ndim != 4 or tuple(transforms.shape[2:]) != (3, 4) or slices.ndim < 3:
+        raise RuntimeError("svr_similarity_bank: vol (..., D, H, W), transforms (n, K, 3, 4), slices (n, ..., h, w)")
+    n, K = int(transforms.shape[0]), int(transforms.shape[1])
+    h, w = int(slices.shape[-2]), int(slices.shape[-1])
+    if slices.numel() != n * h * w or (sm is not None and sm.numel() != n * h * w):
+        raise RuntimeError("svr_similarity_bank: slices / slices_mask must hold n x h x w elements")
+    if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
+        raise RuntimeError("svr_similarity_bank: one volume expected")
+    bank = _bank("svr_similarity_bank", psf_bank, psf_table, psf_id, n)
+    sums = torch.empty((n, K, 6), dtype=torch.float64, device=vol.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_svr_similarity_workspace_bytes(n, K, h, w))  # (the one-PSF twin's: the size does not differ)
+    workspace = _workspace(nbytes, vol.device)
+    with torch.cuda.device(vol.device):
+        err = lib.nesvor_svr_similarity_bank(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), *bank, _lib.ptr(transforms),
+                                             _lib.ptr(slices), _lib.ptr(sm), n, K, h, w, float(res_slice), _lib.ptr(sums),
+                                             _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, "svr similarity bank")
+    return sums
+
+
+_op("slice_acq_forward_bank(Tensor transforms, Tensor vol, Tensor vol_mask, Tensor slices_mask, Tensor psf_bank, Tensor psf_table, "
+    "Tensor psf_id, int[] slice_shape, float res_slice, bool need_weight) -> Tensor[]", _sa_forward_bank,
+    fake=lambda tf, vol, vm, sm, pb, pt, pi, shape, r, nw: _fake_slices(tf, vol, vm, sm, pb, shape, r, nw, False))
+_op("slice_acq_adjoint_forward_bank(Tensor transforms, Tensor psf_bank, Tensor psf_table, Tensor psf_id, Tensor slices, "
+    "Tensor slices_mask, Tensor vol_mask, int[] vol_shape, float res_slice, bool equalize) -> Tensor[]", _sa_adjoint_forward_bank,
+    fake=lambda tf, pb, pt, pi, s, sm, vm, shape, r, e: [s.new_empty((1, 1) + tuple(int(v) for v in shape)),
+                                                         s.new_empty((1, 1) + tuple(int(v) for v in shape)) if e else s.new_empty(0)])
+_op("svr_similarity_bank(Tensor vol, Tensor psf_bank, Tensor psf_table, Tensor psf_id, Tensor transforms, Tensor slices, "
+    "Tensor? slices_mask, float res_slice) -> Tensor", _svr_similarity_bank,
+    fake=lambda vol, pb, pt, pi, tf, s, sm, r: vol.new_empty((tf.shape[0], tf.shape[1], 6), dtype=torch.float64))
+
+
+# =====================================================================================================================
 # one descent step of the classical reconstruction with the edge-preserving prior (csrc/srr.hip):
 # out = x - alpha (grad + beta dR(x)), dR = srr.edge_prior_gradient, in one launch
 # =====================================================================================================================

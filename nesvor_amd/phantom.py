@@ -123,7 +123,7 @@ def simulate_stacks(
     n_stacks: int = 3,
     res: float = 1.0,
     res_s: float = 1.5,
-    s_thick: float = 3.0,
+    s_thick=3.0,  # a float, or one thickness per stack
     gap: Optional[float] = None,
     motion_deg: float = 0.0,
     motion_mm: float = 0.0,
@@ -132,18 +132,24 @@ def simulate_stacks(
 ) -> Tuple[List[Slice], RigidTransform]:
     """Simulate `n_stacks` orthogonal/oblique stacks.  Returns (slices with the NOMINAL
     poses, true poses).  With motion_* > 0 each slice is acquired at a perturbed pose
-    (rotvec ~ N(0, motion_deg^2), t ~ N(0, motion_mm^2)) — BASELINE config 4."""
+    (rotvec ~ N(0, motion_deg^2), t ~ N(0, motion_mm^2)) — BASELINE config 4.
+    ``s_thick`` may be a sequence, one thickness per stack: every stack then has its own PSF, slice spacing (its thickness, unless
+    ``gap`` is given) and number of slices."""
     device = volume.device
-    gap = s_thick if gap is None else gap
+    thick = [s_thick] * n_stacks if isinstance(s_thick, (int, float)) else [float(t) for t in s_thick]
+    if len(thick) != n_stacks:
+        raise ValueError(f"one thickness per stack expected: {n_stacks} stacks, {len(thick)} thicknesses")
     vs = volume.shape[-1]
-    n_slice, ss = stack_geometry(vs, res, res_s, gap)
-    psf = get_PSF(res_ratio=(res_s / res, res_s / res, s_thick / res), device=device)
     g = torch.Generator().manual_seed(seed)
     slices: List[Slice] = []
     true_tf = []
     vol5 = volume[None, None].contiguous()
     for si in range(n_stacks):
-        nominal = stack_transforms(STACK_ANGLES[si], n_slice, gap, device)
+        s_thick = thick[si]
+        stack_gap = s_thick if gap is None else gap
+        n_slice, ss = stack_geometry(vs, res, res_s, stack_gap)
+        psf = get_PSF(res_ratio=(res_s / res, res_s / res, s_thick / res), device=device)
+        nominal = stack_transforms(STACK_ANGLES[si], n_slice, stack_gap, device)
         actual = nominal
         if motion_deg > 0 or motion_mm > 0:
             d = torch.cat(
@@ -163,3 +169,4 @@ def simulate_stacks(
         for s in slices:
             s.image = s.image / q
     return slices, RigidTransform.cat(true_tf)
+

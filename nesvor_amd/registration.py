@@ -38,7 +38,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .slice_acquisition import slice_acquisition
+from .psf_bank import SAME_THICKNESS, PsfBank, bank_for
+from .slice_acquisition import bank_fused, slice_acquisition, slice_acquisition_bank
 from .transform import RigidTransform, mat_transform_points, mat_update_resolution
 from .utils import gaussian_blur, get_PSF, meshgrid, ncc_loss
 
@@ -257,9 +258,9 @@ class VVR:
 # ---------------------------------------------------------------------------------------------------------------------
 class _SliceLevel:
     """One pyramid level of ``SVR``: the volume on the level's grid, the slices and their masks at the level's pixel size,
-    the PSF of a slice in the level's voxels."""
+    the PSF of a slice in the level's voxels (a ``PsfBank`` for slices of unequal thickness)."""
 
-    def __init__(self, volume: torch.Tensor, slices: torch.Tensor, mask: torch.Tensor, psf: torch.Tensor, res_slice: float,
+    def __init__(self, volume: torch.Tensor, slices: torch.Tensor, mask: torch.Tensor, psf, res_slice: float,
                  voxel: float):
         self.volume, self.slices, self.mask, self.psf = volume, slices, mask, psf  # (D,H,W), (n,h,w), (n,h,w) bool, (d,h,w)
         self.res_slice, self.voxel = res_slice, voxel  # pixel size in voxels; voxel size in mm
@@ -309,7 +310,10 @@ class SVR(VVR):
         vol = resample(gaussian_blur(volume, sigma, truncated=4.0), [1.0] * 3, [f] * 3)
         sl = resample(gaussian_blur(slices, sigma, truncated=4.0), [1.0] * 2, [f] * 2)
         mask = resample(slices_mask.to(slices.dtype), [1.0] * 2, [f] * 2) > 0.5
-        psf = get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / (res_r * f)), device=volume.device)
+        if isinstance(s_thick, (int, float)):
+            psf = get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / (res_r * f)), device=volume.device)
+        else:  # one thickness per slice: a PSF bank on the level's grid (a plain PSF if they all agree)
+            psf = bank_for(s_thick, res_s, res_r, volume.device, scale=f)
         return _SliceLevel(vol[0, 0].contiguous(), sl[:, 0].contiguous(), mask[:, 0].contiguous(), psf, res_s / res_r, res_r * f)
 
     # ---- objective -------------------------------------------------------------------------------------------
@@ -317,6 +321,8 @@ class SVR(VVR):
     def _fused_path(lv: _SliceLevel) -> bool:
         from .ops import SVR_MAX_PSF_ELEMENTS
 
+        if isinstance(lv.psf, PsfBank):
+            return os.environ.get("NESVOR_SVR", "") != "composed" and bank_fused() and lv.psf.max_elements() <= SVR_MAX_PSF_ELEMENTS
         return os.environ.get("NESVOR_SVR", "") != "composed" and lv.psf.numel() <= SVR_MAX_PSF_ELEMENTS
 
     def _sums(self, thetas_deg: torch.Tensor, lv: _SliceLevel, ids: Optional[torch.Tensor]) -> torch.Tensor:
@@ -326,13 +332,19 @@ class SVR(VVR):
         mats = mat_update_resolution(pose.matrix(), 1, lv.voxel).view(m, K, 3, 4).contiguous()
         slices = lv.slices if ids is None else lv.slices[ids]
         mask = lv.mask if ids is None else lv.mask[ids]
+        bank = isinstance(lv.psf, PsfBank)
         if self._fused_path(lv):
+            if bank:  # (the subset's ids on the device; members without a slice in it do no harm)
+                return torch.ops.nesvor.svr_similarity_bank(lv.volume, lv.psf.flat, lv.psf.table, lv.psf.ids if ids is None else
+                                                            lv.psf.ids[ids].contiguous(), mats, slices, mask, lv.res_slice)
             return torch.ops.nesvor.svr_similarity(lv.volume, lv.psf, mats, slices, mask, lv.res_slice)
         out = torch.empty((m, K, 6), dtype=torch.float64, device=mats.device)
         J = slices.double()
+        psf = lv.psf.subset(ids) if bank and ids is not None else lv.psf
+        acquire = slice_acquisition_bank if bank else slice_acquisition
         for k in range(K):
-            sim, weight = slice_acquisition(mats[:, k], lv.volume[None, None], None, mask[:, None], lv.psf, slices.shape[-2:],
-                                            lv.res_slice, True, False)
+            sim, weight = acquire(mats[:, k], lv.volume[None, None], None, mask[:, None], psf, slices.shape[-2:],
+                                  lv.res_slice, True, False)
             valid = (mask & (weight[:, 0] > 0)).double()
             Ik, Jk = sim[:, 0].double() * valid, J * valid
             out[:, k] = torch.stack([t.sum((1, 2)) for t in (valid, Ik, Ik * Ik, Ik * Jk, Jk, Jk * Jk)], -1)
@@ -411,11 +423,15 @@ def _mean_pose(t: RigidTransform) -> RigidTransform:
 
 
 def stack_registration(transforms_list: List[List[RigidTransform]], transform_target: RigidTransform,
-                       stacks: List[torch.Tensor], res_s: float, s_thick: float) -> List[RigidTransform]:
+                       stacks: List[torch.Tensor], res_s: float, s_thick: float,
+                       gaps: Optional[Sequence[float]] = None) -> List[RigidTransform]:
     """Register every stack (as a volume of its slices) to stack 0 and return per-slice poses
     (svort/inference.py:308-367): stack j starts from each candidate in ``transforms_list`` (mean pose of its
     slices, expressed relative to the target's), the best final NCC wins; the output poses put the slices of stack
-    j at  centre o registered_j o (0,0,(i - (n-1)/2) * s_thick)."""
+    j at  centre o registered_j o (0,0,(i - (n-1)/2) * s_thick).
+
+    ``gaps`` (per-stack slice profiles), one slice spacing per stack: every other stack is resampled along z from its own gap to
+    stack 0's before it is registered (``s_thick`` is then that gap), and the output poses of stack j are ``gaps[j]`` apart."""
     device = transform_target.device
     t_target = _mean_pose(transform_target)
     candidates = [[_mean_pose(t) for t in ts] for ts in transforms_list]
@@ -427,6 +443,8 @@ def stack_registration(transforms_list: List[List[RigidTransform]], transform_ta
     target = stacks[0].squeeze(1)[None, None]
     for j in range(1, len(stacks)):
         source = stacks[j].squeeze(1)[None, None]
+        if gaps is not None and abs(gaps[j] - gaps[0]) > SAME_THICKNESS:
+            source = resample(source, (1.0, 1.0, gaps[j]), (1.0, 1.0, gaps[0]))
         best, best_ax = float("inf"), None
         for cand in candidates:
             ax = t_target.compose(cand[0].inv()).compose(cand[j]).axisangle(trans_first=trans_first)
@@ -442,29 +460,42 @@ def stack_registration(transforms_list: List[List[RigidTransform]], transform_ta
     for j, stack in enumerate(stacks):
         n = stack.shape[0]
         t = torch.zeros((n, 6), dtype=torch.float32, device=device)
-        t[:, -1] = (torch.arange(n, dtype=torch.float32, device=device) - (n - 1) / 2) * s_thick
+        t[:, -1] = (torch.arange(n, dtype=torch.float32, device=device) - (n - 1) / 2) * (s_thick if gaps is None else gaps[j])
         out.append(centre.compose(registered[j]).compose(RigidTransform(t)))
     return out
 
 
-def register_stacks(dataset: List, res_s: float = 1.0, template: int = 0) -> List:
+def _unequal(values: Sequence[float]) -> bool:
+    return max(values) - min(values) > SAME_THICKNESS
+
+
+def register_stacks(dataset: List, res_s: float = 1.0, template: int = 0, per_stack_thickness: bool = False) -> List:
     """``--registration stack``: in-plane resampling of the masked stacks to ``res_s`` mm (parse_data), stack
     registration to the first stack, new per-slice poses written into the stacks (run_svort with svort=False, vvr=True).
     As in the reference, the slice spacing of the output poses is the MEAN thickness of the input stacks.
 
     ``template`` (not in the reference; ``--template-stack``, nesvor_amd/assess.py) names the stack the others are registered
     to and the world frame is centred on: that stack is moved to the front for the registration, the poses land in the stacks
-    themselves, and the list comes back in input order.  ``template=0`` is the reference's behaviour."""
+    themselves, and the list comes back in input order.  ``template=0`` is the reference's behaviour.
+
+    ``per_stack_thickness`` (``--per-stack-thickness``) and stacks whose thicknesses or gaps differ by more than 1e-3 mm: every
+    stack is registered on the template's slice spacing (resampled along z from its own gap) and its output poses are its own
+    gap apart.  Stacks that agree take the path above, bit for bit."""
     if template != 0:
         if not 0 <= template < len(dataset):
             raise ValueError(f"template stack {template} out of range: {len(dataset)} stacks")
-        register_stacks([dataset[template]] + [s for j, s in enumerate(dataset) if j != template], res_s)
+        register_stacks([dataset[template]] + [s for j, s in enumerate(dataset) if j != template], res_s,
+                        per_stack_thickness=per_stack_thickness)
         return dataset
     t0 = time.time()
     stacks = [resample(s.slices * s.mask, (s.resolution_x, s.resolution_y), (res_s, res_s)) for s in dataset]
     transforms = [s.transformation for s in dataset]
     s_thick = float(sum(s.thickness for s in dataset) / len(dataset))
-    out = stack_registration([transforms], transforms[0], stacks, res_s, s_thick)
+    gaps = [float(s.gap) for s in dataset]
+    if per_stack_thickness and (_unequal(gaps) or _unequal([float(s.thickness) for s in dataset])):
+        out = stack_registration([transforms], transforms[0], stacks, res_s, gaps[0], gaps)
+    else:
+        out = stack_registration([transforms], transforms[0], stacks, res_s, s_thick)
     logging.debug("time for stack registration: %f s", time.time() - t0)
     for s, t in zip(dataset, out):
         s.transformation = t
@@ -502,22 +533,28 @@ def _common_frame(stacks: List[torch.Tensor], transforms: List[RigidTransform], 
     return torch.cat(padded).contiguous(), poses, to_frame
 
 
-def reconstruct_from_slices(mats: torch.Tensor, slices: torch.Tensor, res_s: float, s_thick: float, res_r: float,
+def reconstruct_from_slices(mats: torch.Tensor, slices: torch.Tensor, res_s: float, s_thick, res_r: float,
                             volume_shape: Sequence[int]) -> torch.Tensor:
     """The volume the slice registration aligns to (svort/inference.py:370-406): equalised back-projection, then one CG
-    step on the normal equations over the non-zero pixels.  mats (n,3,4) in voxels of ``res_r``, slices (n,1,h,w)."""
+    step on the normal equations over the non-zero pixels.  mats (n,3,4) in voxels of ``res_r``, slices (n,1,h,w); ``s_thick``: a
+    float, or one thickness per slice (a PSF bank)."""
     from .srr import SRR, PSFreconstruction
 
-    params = {"psf": get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / res_r), device=slices.device),
-              "slice_shape": slices.shape[-2:], "interp_psf": False, "res_s": res_s, "res_r": res_r, "s_thick": s_thick,
+    if isinstance(s_thick, (int, float)):
+        psf = get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / res_r), device=slices.device)
+    else:  # one thickness per slice
+        psf = bank_for(s_thick, res_s, res_r, slices.device)
+    params = {"psf": psf, "slice_shape": slices.shape[-2:], "interp_psf": False, "res_s": res_s, "res_r": res_r, "s_thick": s_thick,
               "volume_shape": tuple(int(s) for s in volume_shape)}
     volume = PSFreconstruction(mats, slices, None, None, params)
     return SRR(n_iter=1, use_CG=True)(mats, slices, volume, params, slices_mask=slices > 0)
 
 
-def _cover_shape(poses: RigidTransform, mask: torch.Tensor, res_s: float, s_thick: float, res_r: float) -> Tuple[int, int, int]:
+def _cover_shape(poses: RigidTransform, mask: torch.Tensor, res_s: float, s_thick, res_r: float) -> Tuple[int, int, int]:
     """(D,H,W) of a volume of ``res_r`` voxels, centred at the origin, that holds every masked pixel of the posed slices
-    (mask (n,1,h,w)) with the slice thickness and a few voxels to spare."""
+    (mask (n,1,h,w)) with the slice thickness (the largest, for one thickness per slice) and a few voxels to spare."""
+    if not isinstance(s_thick, (int, float)):
+        s_thick = max(float(t) for t in s_thick)
     h, w = mask.shape[-2:]
     grid = meshgrid((w, h), (res_s, res_s), device=mask.device)  # (h,w,2), centred
     pts = torch.cat([grid, torch.zeros_like(grid[..., :1])], -1)[None].expand(mask.shape[0], -1, -1, -1)
@@ -527,12 +564,14 @@ def _cover_shape(poses: RigidTransform, mask: torch.Tensor, res_s: float, s_thic
     return size[2], size[1], size[0]
 
 
-def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = None, n_outer: int = 3, template: int = 0) -> List:
+def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = None, n_outer: int = 3, template: int = 0,
+                    per_stack_thickness: bool = False) -> List:
     """``--registration svr``: stack registration (``register_stacks``, to the stack ``template``), then ``n_outer`` rounds of
     reconstruct a volume from all slices at their current poses  /  register every non-empty slice rigidly to it (``SVR``,
     global NCC); the per-slice poses are written back into the stacks.  ``res_r``: voxel size of the intermediate volume
-    (default ``res_s``)."""
-    dataset = register_stacks(dataset, res_s, template)
+    (default ``res_s``).  ``per_stack_thickness`` and stacks of unequal thickness: the stack registration above runs under the
+    switch, and the volume and the slice registration take every slice's own thickness (a PSF bank)."""
+    dataset = register_stacks(dataset, res_s, template, per_stack_thickness)
     t0 = time.time()
     res_r = res_s if res_r is None else res_r
     s_thick = float(sum(s.thickness for s in dataset) / len(dataset))
@@ -541,6 +580,9 @@ def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = 
     mask = slices > 0
     keep = torch.nonzero(mask.flatten(1).any(1)).flatten()
     slices, mask = slices[keep].contiguous(), mask[keep].contiguous()
+    if per_stack_thickness and _unequal([float(s.thickness) for s in dataset]):
+        per_slice = [float(s.thickness) for s in dataset for _ in range(s.slices.shape[0])]
+        s_thick = [per_slice[k] for k in keep.tolist()]
     theta = poses.axisangle()[keep].clone()
     svr = SVR(num_levels=3, num_steps=4, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1}, loss={"name": "ncc"})
     params = {"res_s": res_s, "s_thick": s_thick, "res_r": res_r}

@@ -17,12 +17,14 @@ from typing import Callable, Optional
 import torch
 import torch.nn as nn
 
-from .slice_acquisition import slice_acquisition, slice_acquisition_adjoint
+from .psf_bank import PsfBank
+from .slice_acquisition import slice_acquisition, slice_acquisition_adjoint, slice_acquisition_adjoint_bank, slice_acquisition_bank
 from .transform import axisangle2mat
 
 
 class AcquisitionOperator:
-    """y = A x for one set of slice poses: ``forward`` (A), ``adjoint`` (A^T), ``normal`` (A^T W A + mu I)."""
+    """y = A x for one set of slice poses: ``forward`` (A), ``adjoint`` (A^T), ``normal`` (A^T W A + mu I).
+    ``params["psf"]``: one PSF for every slice, or a ``PsfBank`` (one id per slice: per-stack slice profiles; fp32, no autograd)."""
 
     def __init__(self, transforms: torch.Tensor, params: dict, vol_mask=None, slices_mask=None) -> None:
         self.transforms = transforms
@@ -34,10 +36,16 @@ class AcquisitionOperator:
         self.vol_mask, self.slices_mask = vol_mask, slices_mask
 
     def forward(self, volume: torch.Tensor) -> torch.Tensor:
+        if isinstance(self.psf, PsfBank):
+            return slice_acquisition_bank(self.transforms, volume, self.vol_mask, self.slices_mask, self.psf, self.slice_shape,
+                                          self.ratio, False, self.interp_psf)
         return slice_acquisition(self.transforms, volume, self.vol_mask, self.slices_mask, self.psf, self.slice_shape,
                                  self.ratio, False, self.interp_psf)
 
     def adjoint(self, slices: torch.Tensor, equalize: bool = False) -> torch.Tensor:
+        if isinstance(self.psf, PsfBank):
+            return slice_acquisition_adjoint_bank(self.transforms, self.psf, slices, self.slices_mask, self.vol_mask,
+                                                  self.volume_shape, self.ratio, self.interp_psf, equalize)
         return slice_acquisition_adjoint(self.transforms, self.psf, slices, self.slices_mask, self.vol_mask,
                                          self.volume_shape, self.ratio, self.interp_psf, equalize)
 

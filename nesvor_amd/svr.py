@@ -19,8 +19,12 @@ every round estimates a smooth multiplicative field per slice from the log-ratio
 round and the structural step, if any, and the descent runs on the corrected slices.  Two passes of a fused HIP kernel per
 round (csrc/slice_bias.hip).  Without the flag nothing changes.
 
-Out of scope here: a gauge for the robust scales, robust weights and bias fields inside the ``--registration svr`` rounds,
-per-stack PSFs for unequal thicknesses (the mean thickness is used, as the registration does).  A volume mask, the stacks' intersection and intensity
+Optional per-stack slice profiles (``--per-stack-thickness``; ``s_thick`` as one value per slice, nesvor_amd/psf_bank.py): every
+slice is simulated with the PSF of its own thickness - a PSF bank, looked up per slice inside the one launch of A and of A^T
+(csrc/slice_acq.hip, csrc/svr.hip) - in the descent, the statistics above and the registration.  Without the flag the mean
+thickness is used for every stack, and nothing changes.
+
+Out of scope here: a gauge for the robust scales, robust weights and bias fields inside the ``--registration svr`` rounds.  A volume mask, the stacks' intersection and intensity
 thresholds narrow the stacks' masks as they are loaded (``--volume-mask`` and the other stack masking flags, nesvor_amd/masking.py).
 """
 import json
@@ -32,6 +36,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from .image import Slice, Volume
+from .psf_bank import SAME_THICKNESS, as_thickness_list, bank_for, group_thicknesses
 from .registration import _common_frame, _cover_shape, resample
 from .robust import RobustStatistics
 from .slice_bias import MIN_WEIGHT, SliceBias, eligible
@@ -66,16 +71,31 @@ def _frame(slices, mask, poses, res_s: float) -> Tuple[torch.Tensor, torch.Tenso
     return _frame_keep(slices, mask, poses, res_s)[:3]
 
 
-def _operator(images: torch.Tensor, m: torch.Tensor, frame_poses: RigidTransform, res_s: float, s_thick: float, res_r: float,
+def _kept_thickness(s_thick, slices, keep: torch.Tensor):
+    """``s_thick`` of the kept slices: the float as it is, or the entries of the list - one per slice of the concatenated input
+    ``slices`` (stacks, or their number of slices) - at ``keep``."""
+    if isinstance(s_thick, (int, float)):
+        return s_thick
+    n_input = slices if isinstance(slices, int) else sum(s.shape[0] for s in _as_list(slices))
+    per_slice = as_thickness_list(s_thick, n_input)
+    return [per_slice[k] for k in keep.tolist()]
+
+
+def _operator(images: torch.Tensor, m: torch.Tensor, frame_poses: RigidTransform, res_s: float, s_thick, res_r: float,
               volume_shape: Sequence[int]) -> Tuple[AcquisitionOperator, Dict]:
-    params = {"psf": get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / res_r), device=images.device),
+    """``s_thick``: a float (one PSF), or one thickness per slice of ``images`` (a PSF bank; one PSF if they all agree)."""
+    if isinstance(s_thick, (int, float)):
+        psf = get_PSF(res_ratio=(res_s / res_r, res_s / res_r, s_thick / res_r), device=images.device)
+    else:
+        psf = bank_for(s_thick, res_s, res_r, images.device)
+    params = {"psf": psf,
               "slice_shape": images.shape[-2:], "interp_psf": False, "res_s": res_s, "res_r": res_r, "s_thick": s_thick,
               "volume_shape": tuple(int(s) for s in volume_shape)}
     mats = mat_update_resolution(frame_poses.matrix(), 1, res_r).contiguous()
     return AcquisitionOperator(mats, params, None, m), params
 
 
-def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r: float, n_iter: int = 30, beta: float = 0.02,
+def reconstruct_volume(slices, mask, poses, res_s: float, s_thick, res_r: float, n_iter: int = 30, beta: float = 0.02,
                        delta: float = 0.1, robust_rounds: int = 0, robust_out: Optional[Dict] = None,
                        structural: Optional[StructuralExclusion] = None, structural_out: Optional[Dict] = None,
                        slice_bias: Optional[SliceBias] = None, slice_bias_out: Optional[Dict] = None) -> Volume:
@@ -83,7 +103,9 @@ def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r:
     ``res_r``, large enough for every masked pixel; its mask is the set of voxels a masked pixel's PSF reaches (A^T 1 > 0).
 
     slices: a stack (n,1,h,w) of ``res_s`` pixels or a list of stacks; mask: the same of bool, or None (the non-zero pixels);
-    poses: a ``RigidTransform`` per stack (one pose per slice).  ``beta`` / ``delta``: the prior's weight and edge scale as the
+    poses: a ``RigidTransform`` per stack (one pose per slice).  ``s_thick``: the slice thickness, a float - or one value per slice
+    of the concatenated input (per-stack slice profiles: every slice takes the PSF of its own thickness, the volume covers the
+    largest).  ``beta`` / ``delta``: the prior's weight and edge scale as the
     reference's ``SRR`` takes them; ``n_iter`` descent steps of length 1 / L (``srr.descent_step_bound``) from the equalised
     back-projection.
 
@@ -113,6 +135,7 @@ def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r:
     images, m, frame_poses, keep = _frame_keep(slices, mask, poses, res_s)
     if images.shape[0] == 0:
         raise ValueError("reconstruct_volume: every slice is empty")
+    s_thick = _kept_thickness(s_thick, slices, keep)
     shape = _cover_shape(frame_poses, m, res_s, s_thick, res_r)
     op, params = _operator(images, m, frame_poses, res_s, s_thick, res_r, shape)
     start = PSFreconstruction(op.transforms, images, m, None, params)
@@ -174,22 +197,35 @@ def reconstruct_volume(slices, mask, poses, res_s: float, s_thick: float, res_r:
     return Volume(x[0, 0], cover[0, 0], None, res_r, res_r, res_r)
 
 
-def simulate_slices(volume: Volume, slices, mask, poses, res_s: float, s_thick: float) -> List[Slice]:
+def _thickness_of(s_thick, k: int) -> float:
+    return s_thick if isinstance(s_thick, (int, float)) else s_thick[k]
+
+
+def simulate_slices(volume: Volume, slices, mask, poses, res_s: float, s_thick) -> List[Slice]:
     """A x at the slices' poses through the acquisition operator: one ``Slice`` (on the padded frame, with the frame's pose and
-    the acquired slice's mask) per non-empty input slice."""
-    images, m, frame_poses = _frame(slices, mask, poses, res_s)
+    the acquired slice's mask) per non-empty input slice.  ``s_thick`` as ``reconstruct_volume`` takes it: with one value per
+    slice every written slice carries its own."""
+    if isinstance(s_thick, (int, float)):
+        images, m, frame_poses = _frame(slices, mask, poses, res_s)
+    else:
+        images, m, frame_poses, keep = _frame_keep(slices, mask, poses, res_s)
+        s_thick = _kept_thickness(s_thick, slices, keep)
     res_r = float(volume.resolution_x)
     op, _ = _operator(images, m, frame_poses, res_s, s_thick, res_r, volume.image.shape)
     sim = op.forward(volume.image[None, None].contiguous())
-    return [Slice(sim[k], m[k], frame_poses[k], res_s, res_s, s_thick) for k in range(sim.shape[0])]
+    return [Slice(sim[k], m[k], frame_poses[k], res_s, res_s, _thickness_of(s_thick, k)) for k in range(sim.shape[0])]
 
 
-def corrected_slices(b: torch.Tensor, slices, mask, poses, res_s: float, s_thick: float) -> List[Slice]:
+def corrected_slices(b: torch.Tensor, slices, mask, poses, res_s: float, s_thick) -> List[Slice]:
     """y exp(-b) for the log-fields ``b`` that ``reconstruct_volume(slice_bias_out=...)`` returned: one ``Slice`` (on the padded
     frame, with the frame's pose and the acquired slice's mask) per non-empty input slice."""
-    images, m, frame_poses = _frame(slices, mask, poses, res_s)
+    if isinstance(s_thick, (int, float)):
+        images, m, frame_poses = _frame(slices, mask, poses, res_s)
+    else:
+        images, m, frame_poses, keep = _frame_keep(slices, mask, poses, res_s)
+        s_thick = _kept_thickness(s_thick, slices, keep)
     corrected = images * torch.exp(-b)
-    return [Slice(corrected[k], m[k], frame_poses[k], res_s, res_s, s_thick) for k in range(corrected.shape[0])]
+    return [Slice(corrected[k], m[k], frame_poses[k], res_s, res_s, _thickness_of(s_thick, k)) for k in range(corrected.shape[0])]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -228,6 +264,7 @@ def svr_command(args: Namespace) -> Dict:
         raise SystemExit("No image data provided! Use --input-slices or --input-stacks to input data.")
     use_structural = bool(getattr(args, "structural_exclusion", False))
     use_bias = bool(getattr(args, "slice_bias_fields", False))
+    per_stack = bool(getattr(args, "per_stack_thickness", False))
     if getattr(args, "slice_weights", None) and not getattr(args, "outlier_rejection", False) and not use_structural and not use_bias:
         raise SystemExit("--slice-weights needs --outlier-rejection: without it no slice weights are estimated")
     if getattr(args, "output_corrected_slices", None) and not use_bias:
@@ -247,19 +284,27 @@ def svr_command(args: Namespace) -> Dict:
             raise SystemExit("No non-empty slice found in --input-slices")
         sizes = [(float(s.resolution_x), float(s.resolution_y), float(s.resolution_z)) for s in slices]
         res_s, s_thick = sizes[0][0], sizes[0][2]
-        if any(abs(rx - res_s) > 1e-3 or abs(ry - res_s) > 1e-3 or abs(rz - s_thick) > 1e-3 for rx, ry, rz in sizes):
+        mixed_thickness = any(abs(rz - s_thick) > SAME_THICKNESS for _, _, rz in sizes)
+        if any(abs(rx - res_s) > 1e-3 or abs(ry - res_s) > 1e-3 for rx, ry, _ in sizes) or (mixed_thickness and not per_stack):
             raise SystemExit(MIXED_SLICES_MESSAGE)
         stacks, masks, poses, res_s = _group(slices, res_s)
     else:
         loaded = cli._load_stacks(args)
         thick = [float(s.thickness) for s in loaded]
         s_thick = sum(thick) / len(thick)
-        if max(thick) - min(thick) > 0.01 * s_thick:
+        if max(thick) - min(thick) > 0.01 * s_thick and not per_stack:
             logging.warning("The stacks' thicknesses differ (%s): the mean, %.3f mm, is used for all of them", thick, s_thick)
         slices = cli.register(args, loaded)  # non-empty slices, each stack normalised by its 0.99 quantile
         stacks, masks, poses, res_s = _group(slices, None)
     logging.info("Data loading and registration finished in %.1f s (%d slices, pixel size %.3f mm, thickness %.3f mm)",
                  time.time() - t0, len(slices), res_s, s_thick)
+    if per_stack:
+        # every slice carries its stack's thickness (Slice.resolution_z); slices that agree within 1e-3 mm keep today's path
+        per_slice = [float(s.resolution_z) for s in slices]
+        members, ids = group_thicknesses(per_slice)
+        logging.info("Per-stack slice profiles: %s", ", ".join(f"{t:.3f} mm x {ids.count(g)} slices" for g, t in enumerate(members)))
+        if len(members) > 1:
+            s_thick = per_slice
     t0 = time.time()
     robust: Dict = {}
     structural: Dict = {}

@@ -1,0 +1,186 @@
+"""CPU: the host side of per-stack slice profiles - ``nesvor_amd/psf_bank.py`` (members, table, ids, subsets, id validation), the
+``--per-stack-thickness`` switch of the parser and of ``svr_command``'s ``--input-slices`` checks, and the refusal of gradients
+through a bank.  Nothing here launches a kernel."""
+import logging
+import os
+from argparse import Namespace
+
+import pytest
+import torch
+
+
+def test_bank_for_merges_orders_and_lays_out_members():
+    from nesvor_amd.psf_bank import PsfBank, bank_for
+    from nesvor_amd.utils import get_PSF
+
+    # 3.0 and 3.0005 share a member (within 1e-3 mm), 6.0 comes second (order of first appearance), 3.002 is a third
+    thick = [3.0, 6.0, 3.0005, 6.0, 3.002, 3.0]
+    bank = bank_for(thick, 1.5, 1.0, torch.device("cpu"))
+    assert isinstance(bank, PsfBank) and bank.n_members == 3 and len(bank) == 6
+    assert bank.host_ids == [0, 1, 0, 1, 2, 0] and bank.ids.dtype == torch.int32 and bank.ids.tolist() == bank.host_ids
+    for g, t in enumerate((3.0, 6.0, 3.002)):
+        assert torch.equal(bank.psfs[g], get_PSF(res_ratio=(1.5, 1.5, t)))
+    assert bank.psfs[0].shape != bank.psfs[1].shape  # (9,5,5) and (13,5,5): members keep their own sizes
+    # the table against the members' shapes; the flat array holds them back to back
+    assert bank.table.dtype == torch.int32 and not bank.table.is_cuda and tuple(bank.table.shape) == (3, 4)
+    at = 0
+    for g, p in enumerate(bank.psfs):
+        assert bank.table[g].tolist() == [at, *p.shape]
+        assert torch.equal(bank.flat[at:at + p.numel()], p.flatten())
+        at += p.numel()
+    assert bank.flat.numel() == at and bank.max_elements() == max(p.numel() for p in bank.psfs)
+    # a pyramid level's factor scales the through-plane ratio only, as SVR._level builds its PSF
+    lvl = bank_for(thick, 1.5, 1.0, torch.device("cpu"), scale=2.0)
+    assert torch.equal(lvl.psfs[1], get_PSF(res_ratio=(1.5, 1.5, 6.0 / 2.0)))
+    # one thickness (within 1e-3 mm): a plain tensor, the PSF of the first value - no bank
+    one = bank_for([3.0, 3.0004, 3.0], 1.5, 0.8, torch.device("cpu"))
+    assert torch.is_tensor(one) and torch.equal(one, get_PSF(res_ratio=(1.5 / 0.8, 1.5 / 0.8, 3.0 / 0.8)))
+    with pytest.raises(ValueError):
+        bank_for([], 1.5, 1.0, torch.device("cpu"))
+
+
+def test_subset_remaps_ids_and_drops_unused_members():
+    from nesvor_amd.psf_bank import PsfBank
+
+    psfs = [torch.full((1, 1, 1), 1.0), torch.full((2, 1, 1), 0.5), torch.full((3, 1, 1), 1 / 3)]
+    bank = PsfBank(psfs, [0, 1, 0, 2, 1, 2])
+    sub = bank.subset(torch.tensor([3, 5, 0]))  # members 2, 2, 0 -> members 2 and 0, in that order; member 1 dropped
+    assert sub.n_members == 2 and sub.host_ids == [0, 0, 1]
+    assert torch.equal(sub.psfs[0], psfs[2]) and torch.equal(sub.psfs[1], psfs[0])
+    assert sub.table.tolist() == [[0, 3, 1, 1], [3, 1, 1, 1]]
+    same = bank.subset(range(6))
+    assert same.host_ids == bank.host_ids and same.table.tolist() == bank.table.tolist()
+    assert [g for g, _, _ in bank.members()] == [0, 1, 2] and [idx.tolist() for _, _, idx in bank.members()] == [[0, 2], [1, 4], [3, 5]]
+
+
+def test_ids_outside_the_bank_are_refused_on_the_host():
+    from nesvor_amd.psf_bank import MAX_MEMBERS, PsfBank
+
+    psfs = [torch.ones(1, 1, 1), torch.ones(2, 1, 1) / 2]
+    for bad in ([0, 2], [-1, 0], torch.tensor([0, 1, 5])):
+        with pytest.raises(ValueError, match=r"slice ids must lie in \[0, 2\)"):
+            PsfBank(psfs, bad)
+    with pytest.raises(ValueError):
+        PsfBank([], [])
+    with pytest.raises(ValueError):
+        PsfBank([torch.ones(1, 1, 1)] * (MAX_MEMBERS + 1), [0])
+    with pytest.raises(ValueError):
+        PsfBank([torch.ones(2, 2)], [0])
+
+
+def test_gradient_through_a_bank_raises():
+    """The backward kernels keep one PSF: asking for a gradient through a bank is an error, raised before anything is launched
+    (so on host tensors too)."""
+    from nesvor_amd.psf_bank import PsfBank
+    from nesvor_amd.slice_acquisition import slice_acquisition_adjoint_bank, slice_acquisition_bank
+    from nesvor_amd.srr import AcquisitionOperator
+
+    bank = PsfBank([torch.ones(1, 1, 1), torch.ones(3, 1, 1) / 3], [0, 1])
+    tf = torch.eye(3, 4).repeat(2, 1, 1)
+    vol = torch.rand(1, 1, 4, 4, 4, requires_grad=True)
+    with pytest.raises(RuntimeError, match="no gradient flows through a PSF bank"):
+        slice_acquisition_bank(tf, vol, None, None, bank, (3, 3), 1.0, False)
+    y = torch.rand(2, 1, 3, 3, requires_grad=True)
+    with pytest.raises(RuntimeError, match="no gradient flows through a PSF bank"):
+        slice_acquisition_adjoint_bank(tf, bank, y, None, None, (4, 4, 4), 1.0)
+    params = {"psf": bank, "slice_shape": (3, 3), "volume_shape": (4, 4, 4), "res_s": 1.0, "res_r": 1.0, "interp_psf": False}
+    with pytest.raises(RuntimeError, match="no gradient flows through a PSF bank"):
+        AcquisitionOperator(tf.clone().requires_grad_(True), params).forward(vol.detach())
+    with torch.no_grad():  # (without a gradient the call goes on to the dispatcher, which has no CPU kernel)
+        with pytest.raises(NotImplementedError, match="Could not run 'nesvor::slice_acq_forward_bank'"):
+            slice_acquisition_bank(tf, vol, None, None, bank, (3, 3), 1.0, False)
+    with pytest.raises(ValueError, match="ids for 2 slices"):
+        slice_acquisition_bank(tf[:1], vol.detach(), None, None, bank, (3, 3), 1.0, False)
+
+
+def test_bank_ops_are_registered_with_fake_kernels():
+    import nesvor_amd.ops as ops
+
+    m = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device="meta")
+    for name in ("slice_acq_forward_bank", "slice_acq_adjoint_forward_bank", "svr_similarity_bank"):
+        assert name in ops.op_names()
+        assert torch._C._dispatch_has_kernel_for_dispatch_key(f"nesvor::{name}", "CUDA")
+        assert not torch._C._dispatch_has_kernel_for_dispatch_key(f"nesvor::{name}", "CPU")
+    bank = (m(100), m(2, 4, dtype=torch.int32), m(7, dtype=torch.int32))
+    out = torch.ops.nesvor.slice_acq_forward_bank(m(7, 3, 4), m(1, 1, 8, 9, 10), m(0), m(0), *bank, [11, 12], 1.5, True)
+    assert [tuple(t.shape) for t in out] == [(7, 1, 11, 12)] * 2
+    vol, wgt = torch.ops.nesvor.slice_acq_adjoint_forward_bank(m(7, 3, 4), *bank, m(7, 1, 11, 12), m(0), m(0), [8, 9, 10], 1.5, True)
+    assert tuple(vol.shape) == tuple(wgt.shape) == (1, 1, 8, 9, 10)
+    sums = torch.ops.nesvor.svr_similarity_bank(m(8, 9, 10), *bank, m(7, 13, 3, 4), m(7, 11, 12), None, 1.5)
+    assert tuple(sums.shape) == (7, 13, 6) and sums.dtype == torch.float64
+
+
+def test_parser_takes_the_switch_on_three_commands():
+    from nesvor_amd.cli import build_parser
+
+    p = build_parser()
+    base = {"svr": ["svr", "--input-stacks", "a.nii.gz", "--output-volume", "v.nii.gz"],
+            "register": ["register", "--input-stacks", "a.nii.gz", "--output-slices", "out"],
+            "reconstruct": ["reconstruct", "--input-stacks", "a.nii.gz", "--output-volume", "v.nii.gz"]}
+    for name, argv in base.items():
+        assert p.parse_args(argv).per_stack_thickness is False, name
+        assert p.parse_args(argv + ["--per-stack-thickness"]).per_stack_thickness is True, name
+    with pytest.raises(SystemExit):
+        p.parse_args(["assess", "--input-stacks", "a.nii.gz", "--per-stack-thickness"])
+
+
+def test_input_slices_of_mixed_thickness_pass_with_the_switch(tmp_path, monkeypatch, caplog):
+    """A folder of 3 mm and 4 mm slices: refused without the switch (as before), accepted with it - ``reconstruct_volume`` is
+    reached with one thickness per slice, and the distinct thicknesses are logged.  A folder of mixed PIXEL sizes is refused
+    with the same message, switch or not."""
+    import nesvor_amd.svr as svr
+    from nesvor_amd.image import Slice
+    from nesvor_amd.image_io import save_slices
+    from nesvor_amd.transform import RigidTransform
+
+    g = torch.Generator().manual_seed(0)
+    pose = lambda: RigidTransform(torch.eye(3, 4)[None].clone())  # (as a matrix: the axis-angle conversion is a HIP kernel)
+    folders = {}
+    for name, sizes in (("pixel", [(1.5, 1.5, 3.0), (1.0, 1.0, 3.0)]), ("thickness", [(1.5, 1.5, 3.0), (1.5, 1.5, 4.0), (1.5, 1.5, 3.0)])):
+        folders[name] = str(tmp_path / name)
+        os.makedirs(folders[name])
+        save_slices(folders[name], [Slice(torch.rand(1, 6, 7, generator=g) + 0.5, None, pose(), *s) for s in sizes])
+    args = lambda name, switch: Namespace(input_slices=folders[name], input_stacks=None, stack_masks=None, thicknesses=None,
+                                          device=torch.device("cpu"), output_resolution=0.8, n_iter_srr=1, srr_beta=0.02, srr_delta=0.1,
+                                          simulated_slices=None, per_stack_thickness=switch)
+
+    class Reached(Exception):
+        pass
+
+    seen = {}
+
+    def stop(stacks, masks, poses, res_s, s_thick, *a, **k):
+        seen.update(s_thick=s_thick, res_s=res_s, n=sum(s.shape[0] for s in stacks))
+        raise Reached
+
+    monkeypatch.setattr(svr, "reconstruct_volume", stop)
+    for switch in (False, True):
+        with pytest.raises(SystemExit) as e:
+            svr.svr_command(args("pixel", switch))
+        assert str(e.value) == svr.MIXED_SLICES_MESSAGE
+    with pytest.raises(SystemExit) as e:
+        svr.svr_command(args("thickness", False))
+    assert str(e.value) == svr.MIXED_SLICES_MESSAGE and not seen
+    with caplog.at_level(logging.INFO):
+        with pytest.raises(Reached):
+            svr.svr_command(args("thickness", True))
+    assert seen["n"] == 3 and seen["res_s"] == 1.5
+    assert seen["s_thick"] == pytest.approx([3.0, 4.0, 3.0], abs=1e-5)
+    assert "3.000 mm x 2 slices, 4.000 mm x 1 slices" in caplog.text and "the mean" not in caplog.text
+
+
+def test_pipeline_helpers_take_one_thickness_per_slice():
+    """``_kept_thickness`` follows the kept slices; ``_cover_shape`` covers the largest thickness; a float stays a float."""
+    from nesvor_amd.registration import _cover_shape
+    from nesvor_amd.svr import _kept_thickness
+    from nesvor_amd.transform import RigidTransform
+
+    keep = torch.tensor([0, 2, 3])
+    assert _kept_thickness(3.0, 4, keep) == 3.0
+    assert _kept_thickness([2.0, 2.0, 4.0, 4.0], 4, keep) == [2.0, 4.0, 4.0]
+    with pytest.raises(ValueError):
+        _kept_thickness([2.0, 4.0], 4, keep)
+    poses = RigidTransform(torch.eye(3, 4).repeat(2, 1, 1))
+    mask = torch.ones(2, 1, 5, 5, dtype=torch.bool)
+    assert _cover_shape(poses, mask, 1.0, [2.0, 4.0], 1.0) == _cover_shape(poses, mask, 1.0, 4.0, 1.0)
+    assert _cover_shape(poses, mask, 1.0, [2.0, 4.0], 1.0) != _cover_shape(poses, mask, 1.0, 2.0, 1.0)
