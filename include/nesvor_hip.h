@@ -879,6 +879,42 @@ int nesvor_svr_similarity_bank(const float* vol, int D, int H, int W, const floa
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* ----------------------------------------------------------------------
+ * Grouped similarity sums (package registration): the sums of nesvor_svr_similarity for GROUPS of slices that move together.
+ * Every slice keeps a base pose, every group takes K corrections, and the call returns the six sums per (group, pose).
+ *   base         (n,3,4)   fp32: the pose of every slice, in the storage nesvor_svr_similarity takes (translation first, voxels)
+ *   corrections  (G,K,3,4) fp32: same storage
+ *   group_offsets (G+1) int32, group_slices (E) int32, E = group_offsets[G]: a CSR grouping in DEVICE memory.  Entry e in
+ *                [group_offsets[g], group_offsets[g+1]) says that slice group_slices[e] belongs to group g.  Offsets start at 0
+ *                and do not decrease; a group may be empty, a slice may be listed nowhere (it takes no part) or more than once.
+ *                The CALLER guarantees this and 0 <= group_slices[e] < n (the library cannot read device memory on the host;
+ *                torch.ops.nesvor.svr_similarity_groups checks both on the host before it uploads them).  An index outside
+ *                [0, n) is never used to index anything: its entry counts no pixel.
+ * The pose of slice i of group g under pose k is  corrections[g][k] o base[i]  in the sense of RigidTransform.compose:
+ *   R'[r][c] = Rc[r][0] R[0][c] + Rc[r][1] R[1][c] + Rc[r][2] R[2][c]
+ *   t'[r]    = t[r] + (R[0][r] uc[0] + R[1][r] uc[1] + R[2][r] uc[2])
+ * in double from the fp32 inputs, every sum added left to right without contraction, rounded once to fp32; once per
+ * workgroup.  From that matrix on a pixel's value and valid set are nesvor_svr_similarity's bit for bit, and so are an
+ * entry's sums (workgroup rows added from 0).  sums (G,K,6) fp64: a group's sum adds its entries' sums one after the other
+ * from 0 in CSR order - "nesvor_svr_similarity at the composed matrices, added per group in CSR order", bit for bit; an empty
+ * group gives six zeros.  No atomics, no memset.  The grid runs over the E entries: a subset of the slices costs what it holds.
+ * workspace: nesvor_svr_similarity_groups_workspace_bytes(E, K, h, w) bytes.
+ * K <= 0 or E == 0: returns 0 without a launch and WITHOUT writing sums.  hipErrorInvalidValue: what nesvor_svr_similarity
+ * (the bank twin: nesvor_svr_similarity_bank) refuses, G < 1, E < 0, NULL group_offsets, NULL group_slices with E > 0.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_svr_similarity_groups(const float* vol, int D, int H, int W, const float* psf, int d_p, int h_p, int w_p,
+                                 const float* base, const float* corrections, const int32_t* group_offsets,
+                                 const int32_t* group_slices, int G, int E, const float* slices, const uint8_t* slices_mask,
+                                 int n, int K, int h, int w, float res_slice, double* sums, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int nesvor_svr_similarity_groups_bank(const float* vol, int D, int H, int W, const float* psf_bank, const int32_t* psf_table,
+                                      int P, const int32_t* psf_id, const float* base, const float* corrections,
+                                      const int32_t* group_offsets, const int32_t* group_slices, int G, int E,
+                                      const float* slices, const uint8_t* slices_mask, int n, int K, int h, int w,
+                                      float res_slice, double* sums, void* workspace, size_t workspace_bytes, void* stream);
+int64_t nesvor_svr_similarity_groups_workspace_bytes(int E, int K, int h, int w);
+
+/* ----------------------------------------------------------------------
  * One descent step of the classical super-resolution reconstruction with the edge-preserving prior, in one launch
  * (the loop body of the reference's SRR, svort/srr.py:117-131, whose prior gradient dR is :139-160):
  *   out[a] = x[a] - alpha * (grad[a] + beta * dR(x)[a])

@@ -234,6 +234,12 @@ _SIGNATURES = {
     "nesvor_slice_acq_adjoint_forward_bank": ([_P] * 3 + [c_int] + [_P] * 7 + [c_int] * 6 + [c_float, c_int, _P], c_int),
     "nesvor_svr_similarity_bank": ([_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P,
                                     c_size_t, _P], c_int),
+    # the grouped twins: (base, corrections, group_offsets, group_slices, G, E) in the place of (transforms)
+    "nesvor_svr_similarity_groups": ([_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int,
+                                      c_int, c_int, c_float, _P, _P, c_size_t, _P], c_int),
+    "nesvor_svr_similarity_groups_bank": ([_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int,
+                                           c_int, c_int, c_float, _P, _P, c_size_t, _P], c_int),
+    "nesvor_svr_similarity_groups_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
     "nesvor_srr_step": ([_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_int, _P], c_int),
     "nesvor_robust_estep": ([_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P], c_int),
     "nesvor_robust_estep_workspace_bytes": ([c_int, c_int, c_int], c_int64),

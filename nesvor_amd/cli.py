@@ -56,6 +56,13 @@ data matrix, ``volume`` of the mask; higher is better) and ranks them; ``--templ
 (default 0, the first file, as before) or ``auto`` = the best stack under ``--template-metric``.  The output slices keep the
 input order.  With ``--registration none`` or ``--input-slices`` the two flags are ignored with a warning.
 
+Also not in the reference: ``--packages P [P ...]`` and ``--package-rounds N`` (default 2) on ``svr``, ``register`` and
+``reconstruct``: a stack acquired in P interleaved packages (package p holds slices p, p+P, p+2P, ...) gets a stage between one
+pose per stack and one pose per slice - after the stack registration, N rounds of reconstruct a volume / register every package
+rigidly to it (``GroupSVR``, nesvor_amd/registration.py; one count per input stack, or one for all).  Only with
+``--registration svr``: with another choice, or with ``--input-slices``, the flags are ignored with a warning; a count that matches
+neither 1 nor the number of stacks, or a ``P`` below 1, ends the command.  ``--debug`` logs every package's correction per round.
+
 Also not in the reference: ``--per-stack-thickness`` on ``svr``, ``register`` and ``reconstruct`` (there for the registration stage
 only) lets stacks of unequal slice thickness keep their own (``--thicknesses``, or the files' z spacing): ``--registration stack``
 registers every stack on the template's slice spacing and spaces its slices by its own gap, and ``svr`` / ``--registration svr``
@@ -112,7 +119,7 @@ import os
 import sys
 import time
 from argparse import Namespace
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
@@ -276,6 +283,14 @@ def _thickness_flags(g) -> None:
                         "without the flag the mean thickness is used for all stacks")
 
 
+def _package_flags(g) -> None:
+    g.add_argument("--packages", nargs="+", type=int, default=None, metavar="P",
+                   help="(not in the reference) interleaved packages per stack, one count per input stack or one for all: with "
+                        "--registration svr every package (slices p, p+P, p+2P, ...) is registered rigidly to the joint volume "
+                        "between the stack registration and the slice rounds (nesvor_amd/registration.py: GroupSVR)")
+    g.add_argument("--package-rounds", type=int, default=2, metavar="N", help="reconstruct / register-packages rounds of --packages")
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog="nesvor_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = parser.add_subparsers(dest="command", required=True)
@@ -299,6 +314,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
     _thickness_flags(g)
+    _package_flags(g)
     _training_flags(p)
     _bias_flags(p)
     _mask_flags(p)
@@ -317,6 +333,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
     _thickness_flags(g)
+    _package_flags(g)
     _bias_flags(p)
     _mask_flags(p)
     _denoise_flags(p)
@@ -339,6 +356,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--svort-version", default="v1", type=str, choices=["v1", "v2"])
     _template_flags(g)
     _thickness_flags(g)
+    _package_flags(g)
     g = p.add_argument_group("super-resolution reconstruction")
     g.add_argument("--n-iter-srr", default=30, type=int, help="descent steps")
     g.add_argument("--srr-beta", default=0.02, type=float, help="weight of the edge-preserving prior")
@@ -611,6 +629,7 @@ def register(args: Namespace, stacks: List) -> List:
         raise NotImplementedError(f"--registration {args.registration}: the SVoRT transformer is out of scope of this "
                                   "build; register with the reference and pass the result through --input-slices, or use "
                                   "--registration svr / stack / none")
+    packages = package_options(args, len(stacks))  # (a bad count ends the command before any registration)
     if args.registration == "none":
         warn_template_ignored(args, "--registration none")
         return stacks_to_slices(stacks)
@@ -629,7 +648,11 @@ def register(args: Namespace, stacks: List) -> List:
         from .registration import register_slices
 
         t1 = time.time()
-        stacks = register_slices(stacks, template=template, per_stack_thickness=per_stack)
+        if packages is None:
+            stacks = register_slices(stacks, template=template, per_stack_thickness=per_stack)
+        else:
+            stacks = register_slices(stacks, template=template, per_stack_thickness=per_stack, packages=packages,
+                                     package_rounds=int(getattr(args, "package_rounds", 2)))
         logging.info("Slice-to-volume registration finished in %.1f s", time.time() - t1)
     return stacks_to_slices(stacks)
 
@@ -638,6 +661,31 @@ def warn_template_ignored(args: Namespace, why: str) -> None:
     """``--template-stack`` / ``--template-metric`` only act where stacks are registered."""
     if str(getattr(args, "template_stack", "0")) != "0" or getattr(args, "template_metric", "ncc") != "ncc":
         logging.warning("--template-stack / --template-metric are ignored with %s: no stack is registered to a template", why)
+
+
+def warn_packages_ignored(args: Namespace, why: str) -> None:
+    """``--packages`` / ``--package-rounds`` only act in the package stage of ``--registration svr``."""
+    if getattr(args, "packages", None) is not None or getattr(args, "package_rounds", 2) != 2:
+        logging.warning("--packages / --package-rounds are ignored with %s: packages are registered by --registration svr only", why)
+
+
+def package_options(args: Namespace, n_stacks: int) -> Optional[List[int]]:
+    """``--packages`` as one count per stack, or None (no package stage).  With a registration other than ``svr`` the flags are
+    ignored with a warning; a count that matches neither 1 nor the number of stacks, a ``P < 1`` or ``--package-rounds`` below 0
+    ends the command."""
+    if getattr(args, "registration", "none") != "svr":
+        warn_packages_ignored(args, f"--registration {getattr(args, 'registration', 'none')}")
+        return None
+    if int(getattr(args, "package_rounds", 2)) < 0:
+        raise SystemExit(f"--package-rounds: a number of rounds >= 0 expected, got {args.package_rounds}")
+    packages = getattr(args, "packages", None)
+    if packages is None:
+        return None
+    if len(packages) not in (1, n_stacks):
+        raise SystemExit(f"--packages: one count per input stack ({n_stacks}) or one for all expected, got {len(packages)}")
+    if min(packages) < 1:
+        raise SystemExit(f"--packages: every stack has at least 1 package, got {min(packages)}")
+    return [int(p) for p in packages] * (n_stacks if len(packages) == 1 else 1)
 
 
 def register_cmd(args: Namespace) -> None:
@@ -713,6 +761,7 @@ def reconstruct(args: Namespace) -> None:
         args.input_stacks = args.stack_masks = args.thicknesses = None
     if args.input_slices is not None:
         warn_template_ignored(args, "--input-slices")
+        warn_packages_ignored(args, "--input-slices")
         warn_masking_ignored(args, "--input-slices")
         warn_denoise_ignored(args, "--input-slices")
     for name in ("stack_masks", "thicknesses"):

@@ -14,6 +14,10 @@
 //
 // The sums are added in the reproducible order of slice_sums.h.  A workgroup serves all poses of its 256 pixels, so it parks
 // the wave sums per pose inside the pose loop and combines them after one barrier at the end, in that header's order.
+//
+// Package registration (GroupSVR) moves GROUPS of slices together: svr_similarity_groups_kernel takes one correction per (group,
+// pose) and a CSR grouping, composes the correction with each slice's base pose once per workgroup and runs the same pixel loop
+// (similarity_pixels); svr_groups_reduce_kernel adds a group's per-slice sums in CSR order.
 #include <hip/hip_runtime.h>
 #include "acq_taps.h"
 #include "slice_sums.h"
@@ -24,26 +28,19 @@ using namespace acq;
 
 constexpr int kSums = 6;
 
-// grid: n * wgs workgroups of 256 pixels, wgs = ceil(h w / 256) per slice.  transforms: (n, K, 3, 4), this pass covers poses
-// k0 .. k0 + KT - 1.  partial: (n, K, wgs, 6) doubles.  PSF: OnePsf<float>, or BankPsf<float> - the workgroup's slice then compacts
-// its own PSF (acq_taps.h).
-template <int KT, typename PSF>
-__global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __restrict__ vol, int D, int H, int W, const PSF psfs,
-                                                             const float* __restrict__ transforms, const float* __restrict__ slices,
-                                                             const uint8_t* __restrict__ slices_mask, int K, int k0, int h, int w,
-                                                             int wgs, float res_slice, double* __restrict__ partial) {
-  __shared__ Tap<float> taps[kMaxTaps];
-  __shared__ int n_taps;
-  __shared__ float red[4][KT][kSums];
-  const int in = blockIdx.x / wgs, wg = blockIdx.x - in * wgs;
-  if (threadIdx.x == 0) {
-    const PsfView<float> pk = psfs.at(in);
-    n_taps = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
-  }
-  __syncthreads();
+// The pixel loop of both kernels: the workgroup's 256 pixels of slice `in` under the KT poses pose_of(0 .. KT-1) (12 floats each,
+// wave-uniform), the six sums per pose added in slice_sums.h's steps 1-2 and stored to rows (entry K + k0 + k) wgs + wg of
+// `partial`.  `entry` is the slice itself (svr_similarity_kernel) or the slice's place in a grouping (svr_similarity_groups_kernel);
+// `live` false: no pixel of the workgroup counts and nothing is indexed by `in`.  Every thread must call (barrier).
+template <int KT, typename PoseOf>
+__device__ __forceinline__ void similarity_pixels(const float* __restrict__ vol, int D, int H, int W, const Tap<float>* taps, const int& n_taps,
+                                                  float (&red)[4][KT][kSums], PoseOf pose_of, const float* __restrict__ slices,
+                                                  const uint8_t* __restrict__ slices_mask, bool live, int in, int64_t entry, int wg,
+                                                  int K, int k0, int h, int w, int wgs, float res_slice,
+                                                  double* __restrict__ partial) {
   const int pix = wg * 256 + (int)threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool inside = pix < h * w;
+  const bool inside = live && pix < h * w;
   const size_t idx = (size_t)in * h * w + (inside ? pix : 0);
   const bool on = inside && (slices_mask == nullptr || slices_mask[idx]);
   const float J = on ? slices[idx] : 0.f;
@@ -54,7 +51,7 @@ __global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __rest
     float I = 0.f;
     bool valid = false;
     if (on) {  // (a wave without a masked-in pixel branches over its tap loops: its exec mask is empty)
-      const float* t = transforms + ((size_t)in * K + k0 + k) * 12;  // wave-uniform: the scalar path
+      const float* t = pose_of(k);  // wave-uniform
       const PixelGeom<float> g = pixel_geom(t, ix, iy, h, w, res_slice, D, H, W);
       float val = 0.f, wsum = 0.f;
       for_lds_taps(t, g, taps, nt, D, H, W, [&](float, float, float, float pv, float x, float y, float z) {
@@ -75,8 +72,106 @@ __global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __rest
   for (int e = threadIdx.x; e < KT * kSums; e += blockDim.x) {
     const int k = e / kSums, j = e - k * kSums;
     const double s = ((double)red[0][k][j] + (double)red[1][k][j]) + ((double)red[2][k][j] + (double)red[3][k][j]);
-    partial[(((size_t)in * K + k0 + k) * wgs + wg) * kSums + j] = s;
+    partial[(((size_t)entry * K + k0 + k) * wgs + wg) * kSums + j] = s;
   }
+}
+
+// grid: n * wgs workgroups of 256 pixels, wgs = ceil(h w / 256) per slice.  transforms: (n, K, 3, 4), this pass covers poses
+// k0 .. k0 + KT - 1.  partial: (n, K, wgs, 6) doubles.  PSF: OnePsf<float>, or BankPsf<float> - the workgroup's slice then compacts
+// its own PSF (acq_taps.h).
+template <int KT, typename PSF>
+__global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __restrict__ vol, int D, int H, int W, const PSF psfs,
+                                                             const float* __restrict__ transforms, const float* __restrict__ slices,
+                                                             const uint8_t* __restrict__ slices_mask, int K, int k0, int h, int w,
+                                                             int wgs, float res_slice, double* __restrict__ partial) {
+  __shared__ Tap<float> taps[kMaxTaps];
+  __shared__ int n_taps;
+  __shared__ float red[4][KT][kSums];
+  const int in = blockIdx.x / wgs, wg = blockIdx.x - in * wgs;
+  if (threadIdx.x == 0) {
+    const PsfView<float> pk = psfs.at(in);
+    n_taps = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
+  }
+  __syncthreads();
+  similarity_pixels<KT>(vol, D, H, W, taps, n_taps, red,
+                        [&](int k) { return transforms + ((size_t)in * K + k0 + k) * 12; },  // the scalar path
+                        slices, slices_mask, true, in, in, wg, K, k0, h, w, wgs, res_slice, partial);
+}
+
+// ---- grouped sums: one correction per (group, pose), composed with every slice's base pose in the kernel ----
+// Element j of  correction o base  (RigidTransform.compose: R' = Rc R, t' = t + R^T uc; both 3 x 4 row-major, translation first),
+// in double from the fp32 inputs, every sum of products added left to right (the build does not contract), rounded once.
+__device__ __forceinline__ float composed_element(const float* __restrict__ c, const float* __restrict__ b, int j) {
+  const int i = j >> 2, col = j & 3;
+  if (col < 3)
+    return (float)((double)c[4 * i] * (double)b[col] + (double)c[4 * i + 1] * (double)b[4 + col] + (double)c[4 * i + 2] * (double)b[8 + col]);
+  const double rtu = (double)b[i] * (double)c[3] + (double)b[4 + i] * (double)c[7] + (double)b[8 + i] * (double)c[11];
+  return (float)((double)b[4 * i + 3] + rtu);
+}
+
+// The group of entry e: offsets[g] <= e < offsets[g + 1] (offsets non-decreasing from 0, e < offsets[G]; empty groups are skipped).
+__device__ __forceinline__ int group_of_entry(const int* __restrict__ offsets, int G, int e) {
+  int lo = 0, hi = G;
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (offsets[mid] <= e) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// grid: E * wgs workgroups, one entry of the grouping (a slice of a group) per wgs of them.  base: (n, 3, 4), corrections: (G, K, 3, 4),
+// partial: (E, K, wgs, 6) doubles.  The KT composed poses are wave-uniform: threads < 12 KT compose one element each into LDS, once
+// per workgroup, and the pixel loop reads them there.  A slice index outside [0, n) (the caller's error: ops.py refuses it on
+// the host) indexes nothing and gives the entry six zeros.
+template <int KT, typename PSF>
+__global__ __launch_bounds__(256) void svr_similarity_groups_kernel(const float* __restrict__ vol, int D, int H, int W, const PSF psfs,
+                                                                    const float* __restrict__ base, const float* __restrict__ corrections,
+                                                                    const int* __restrict__ group_offsets, int G,
+                                                                    const int* __restrict__ group_slices, const float* __restrict__ slices,
+                                                                    const uint8_t* __restrict__ slices_mask, int n, int K, int k0, int h,
+                                                                    int w, int wgs, float res_slice, double* __restrict__ partial) {
+  __shared__ Tap<float> taps[kMaxTaps];
+  __shared__ int n_taps;
+  __shared__ float red[4][KT][kSums];
+  __shared__ float poses[KT][12];
+  const int e = blockIdx.x / wgs, wg = blockIdx.x - e * wgs;
+  const int listed = group_slices[e];
+  const bool live = listed >= 0 && listed < n;
+  const int in = live ? listed : 0;
+  if (threadIdx.x == 0) {
+    int cnt = 0;
+    if (live) {
+      const PsfView<float> pk = psfs.at(in);
+      cnt = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
+    }
+    n_taps = cnt;
+  }
+  if (live && threadIdx.x < KT * 12) {
+    const int k = threadIdx.x / 12, j = threadIdx.x - k * 12;
+    const int g = group_of_entry(group_offsets, G, e);
+    poses[k][j] = composed_element(corrections + ((size_t)g * K + k0 + k) * 12, base + (size_t)in * 12, j);
+  }
+  __syncthreads();
+  similarity_pixels<KT>(vol, D, H, W, taps, n_taps, red, [&](int k) { return (const float*)poses[k]; }, slices, slices_mask, live, in,
+                        e, wg, K, k0, h, w, wgs, res_slice, partial);
+}
+
+// sums[g][k][j] = the entries of group g one after the other from 0, in CSR order; an entry's sum is its wgs rows added from 0 in
+// workgroup order (slice_sums.h's step 3, per entry).  One thread per (g, k, j); an empty group stores 0.
+__global__ __launch_bounds__(256) void svr_groups_reduce_kernel(const double* __restrict__ partial, const int* __restrict__ group_offsets,
+                                                                int G, int K, int wgs, double* __restrict__ sums) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)G * K * kSums) return;
+  const int64_t gk = t / kSums;
+  const int j = (int)(t - gk * kSums);
+  const int g = (int)(gk / K), k = (int)(gk - (int64_t)g * K);
+  double s = 0.0;
+  for (int e = group_offsets[g]; e < group_offsets[g + 1]; ++e) {
+    double se = 0.0;
+    for (int r = 0; r < wgs; ++r) se += partial[(((size_t)e * K + k) * wgs + r) * kSums + j];
+    s += se;
+  }
+  sums[t] = s;
 }
 
 }  // namespace
@@ -140,4 +235,76 @@ extern "C" int nesvor_svr_similarity_bank(const float* vol, int D, int H, int W,
   if (K <= 0 || n == 0) return 0;
   return svr_similarity_launch(vol, D, H, W, bank, transforms, slices, slices_mask, n, K, h, w, res_slice, sums, workspace,
                                workspace_bytes, stream);
+}
+
+// ---- grouped sums (package registration): the same pixels, poses composed in the kernel, sums per (group, pose) ----
+extern "C" int64_t nesvor_svr_similarity_groups_workspace_bytes(int E, int K, int h, int w) {
+  if (E < 1 || K < 1 || h < 1 || w < 1) return 0;
+  return slice_sums::Plan<kSums>{(int64_t)E * K, slice_sums::pixel_workgroups(h, w)}.workspace_bytes();
+}
+
+namespace {
+// What both grouped entry points refuse about the grouping itself.
+inline bool grouping_accepted(const int32_t* group_offsets, const int32_t* group_slices, int G, int E) {
+  return G >= 1 && E >= 0 && group_offsets != nullptr && (E == 0 || group_slices != nullptr);
+}
+
+template <typename PSF>
+int svr_similarity_groups_launch(const float* vol, int D, int H, int W, const PSF& psfs, const float* base, const float* corrections,
+                                 const int32_t* group_offsets, const int32_t* group_slices, int G, int E, const float* slices,
+                                 const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, double* sums, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  if (D < 1 || H < 1 || W < 1 || h < 1 || w < 1 || n < 1) return (int)hipErrorInvalidValue;
+  if ((int64_t)D * H * W > INT_MAX || (int64_t)E * K > INT_MAX || (int64_t)G * K > INT_MAX / kSums) return (int)hipErrorInvalidValue;
+  const slice_sums::Plan<kSums> plan{(int64_t)E * K, slice_sums::pixel_workgroups(h, w)};
+  if (!plan.accepts(h, w, plan.wgs * E, workspace, workspace_bytes)) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  double* partial = (double*)workspace;
+  const int wgs = (int)plan.wgs;
+  const dim3 grid((unsigned)(plan.wgs * E)), block(256);  // over the entries: a subset costs what it holds
+  int k = 0;
+  while (k < K) {  // 13 poses per pass (one finite-difference gradient), single poses otherwise: nesvor_svr_similarity's split
+    if (K - k >= 13) {
+      hipLaunchKernelGGL((svr_similarity_groups_kernel<13, PSF>), grid, block, 0, st, vol, D, H, W, psfs, base, corrections, group_offsets,
+                         G, group_slices, slices, slices_mask, n, K, k, h, w, wgs, res_slice, partial);
+      k += 13;
+    } else {
+      hipLaunchKernelGGL((svr_similarity_groups_kernel<1, PSF>), grid, block, 0, st, vol, D, H, W, psfs, base, corrections, group_offsets,
+                         G, group_slices, slices, slices_mask, n, K, k, h, w, wgs, res_slice, partial);
+      k += 1;
+    }
+  }
+  const int64_t total = (int64_t)G * K * kSums;
+  hipLaunchKernelGGL(svr_groups_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)partial,
+                     group_offsets, G, K, wgs, sums);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int nesvor_svr_similarity_groups(const float* vol, int D, int H, int W, const float* psf, int d_p, int h_p, int w_p,
+                                            const float* base, const float* corrections, const int32_t* group_offsets,
+                                            const int32_t* group_slices, int G, int E, const float* slices,
+                                            const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, double* sums,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+  if (!grouping_accepted(group_offsets, group_slices, G, E)) return (int)hipErrorInvalidValue;
+  if (K <= 0 || E == 0) return 0;
+  if (d_p < 1 || h_p < 1 || w_p < 1 || (int64_t)d_p * h_p * w_p > kMaxTaps) return (int)hipErrorInvalidValue;
+  return svr_similarity_groups_launch(vol, D, H, W, OnePsf<float>{psf, d_p, h_p, w_p}, base, corrections, group_offsets, group_slices, G,
+                                      E, slices, slices_mask, n, K, h, w, res_slice, sums, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nesvor_svr_similarity_groups_bank(const float* vol, int D, int H, int W, const float* psf_bank,
+                                                 const int32_t* psf_table, int P, const int32_t* psf_id, const float* base,
+                                                 const float* corrections, const int32_t* group_offsets, const int32_t* group_slices,
+                                                 int G, int E, const float* slices, const uint8_t* slices_mask, int n, int K, int h,
+                                                 int w, float res_slice, double* sums, void* workspace, size_t workspace_bytes,
+                                                 void* stream) {
+  if (!grouping_accepted(group_offsets, group_slices, G, E)) return (int)hipErrorInvalidValue;
+  BankPsf<float> bank;
+  int64_t max_elements;
+  if (!make_bank(psf_bank, psf_table, P, psf_id, n, bank, max_elements) || max_elements > kMaxTaps) return (int)hipErrorInvalidValue;
+  if ((int64_t)D * H * W > INT_MAX) return (int)hipErrorInvalidValue;
+  if (K <= 0 || E == 0) return 0;
+  return svr_similarity_groups_launch(vol, D, H, W, bank, base, corrections, group_offsets, group_slices, G, E, slices, slices_mask, n, K,
+                                      h, w, res_slice, sums, workspace, workspace_bytes, stream);
 }

@@ -447,6 +447,86 @@ _op("svr_similarity_bank(Tensor vol, Tensor psf_bank, Tensor psf_table, Tensor p
 
 
 # =====================================================================================================================
+# grouped similarity sums (package registration, csrc/svr.hip): one correction per (group, pose), composed with every slice's
+# base pose in the kernel, sums per (group, pose) in CSR order.  The grouping arrives in HOST memory, is checked there and
+# uploaded: a bad index is a Python exception, never a device read, and no call reads the device back
+# =====================================================================================================================
+def check_grouping(what: str, group_offsets: torch.Tensor, group_slices: torch.Tensor, n: int):
+    """The CSR grouping of ``svr_similarity_groups``, checked on the host -> (offsets int32, slices int32, G, E).  Offsets
+    (G+1) start at 0, do not decrease and end at ``len(group_slices)``; every slice index lies in [0, n)."""
+    for name, t in (("group_offsets", group_offsets), ("group_slices", group_slices)):
+        if t.is_cuda or t.dtype not in (torch.int32, torch.int64) or t.ndim != 1:
+            raise RuntimeError(f"{what}: {name}, a 1-D int32 / int64 tensor in host memory, expected")
+    G, E = int(group_offsets.numel()) - 1, int(group_slices.numel())
+    if G < 1:
+        raise RuntimeError(f"{what}: group_offsets must hold G + 1 >= 2 entries, got {G + 1}")
+    if int(group_offsets[0]) != 0 or bool((group_offsets[1:] < group_offsets[:-1]).any()):
+        raise RuntimeError(f"{what}: group_offsets must start at 0 and must not decrease")
+    if int(group_offsets[-1]) != E:
+        raise RuntimeError(f"{what}: the last of group_offsets ({int(group_offsets[-1])}) must equal len(group_slices) ({E})")
+    if E > 0 and (int(group_slices.min()) < 0 or int(group_slices.max()) >= n):
+        raise RuntimeError(f"{what}: group_slices must lie in [0, {n}), got [{int(group_slices.min())}, {int(group_slices.max())}]")
+    return group_offsets.to(torch.int32).contiguous(), group_slices.to(torch.int32).contiguous(), G, E
+
+
+def _svr_groups(what, vol, psf_args, corrections, base, group_offsets, group_slices, slices, slices_mask, res_slice):
+    n = int(base.shape[0]) if base.ndim == 3 else -1
+    offsets, listed, G, E = check_grouping(what, group_offsets, group_slices, n)  # first: nothing is launched on a bad grouping
+    _lib.require_device(vol, corrections, base, slices, dtype=torch.float32, name=f"{what} vol/corrections/base/slices")
+    sm = _mask(slices_mask)
+    if (vol.ndim < 3 or corrections.ndim != 4 or tuple(corrections.shape[2:]) != (3, 4) or base.ndim != 3
+            or tuple(base.shape[1:]) != (3, 4) or slices.ndim < 3 or int(corrections.shape[0]) != G):
+        raise RuntimeError(f"{what}: vol (..., D, H, W), corrections (G, K, 3, 4), base (n, 3, 4), slices (n, ..., h, w), "
+                           "group_offsets (G + 1)")
+    K = int(corrections.shape[1])
+    h, w = int(slices.shape[-2]), int(slices.shape[-1])
+    if slices.numel() != n * h * w or (sm is not None and sm.numel() != n * h * w):
+        raise RuntimeError(f"{what}: slices / slices_mask must hold n x h x w elements")
+    if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
+        raise RuntimeError(f"{what}: one volume expected")
+    psf = psf_args(n)
+    if E == 0 or K == 0:  # (the library returns without a launch and without writing)
+        return torch.zeros((G, K, 6), dtype=torch.float64, device=vol.device)
+    sums = torch.empty((G, K, 6), dtype=torch.float64, device=vol.device)
+    offsets, listed = offsets.to(vol.device), listed.to(vol.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_svr_similarity_groups_workspace_bytes(E, K, h, w))
+    workspace = _workspace(nbytes, vol.device)
+    with torch.cuda.device(vol.device):
+        err = getattr(lib, f"nesvor_{what}")(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), *psf, _lib.ptr(base), _lib.ptr(corrections),
+                                             _lib.ptr(offsets), _lib.ptr(listed), G, E, _lib.ptr(slices), _lib.ptr(sm), n, K, h, w,
+                                             float(res_slice), _lib.ptr(sums), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, what.replace("_", " "))
+    return sums
+
+
+def _svr_similarity_groups(vol, psf, corrections, base, group_offsets, group_slices, slices, slices_mask, res_slice):
+    def psf_args(n):
+        _lib.require_device(psf, dtype=torch.float32, name="svr_similarity_groups psf")
+        if psf.ndim != 3:
+            raise RuntimeError("svr_similarity_groups: psf (d, h, w) expected")
+        return _lib.ptr(psf), *(int(s) for s in psf.shape)
+
+    return _svr_groups("svr_similarity_groups", vol, psf_args, corrections, base, group_offsets, group_slices, slices, slices_mask,
+                       res_slice)
+
+
+def _svr_similarity_groups_bank(vol, psf_bank, psf_table, psf_id, corrections, base, group_offsets, group_slices, slices,
+                                slices_mask, res_slice):
+    return _svr_groups("svr_similarity_groups_bank", vol, lambda n: _bank("svr_similarity_groups_bank", psf_bank, psf_table, psf_id, n),
+                       corrections, base, group_offsets, group_slices, slices, slices_mask, res_slice)
+
+
+_op("svr_similarity_groups(Tensor vol, Tensor psf, Tensor corrections, Tensor base, Tensor group_offsets, Tensor group_slices, "
+    "Tensor slices, Tensor? slices_mask, float res_slice) -> Tensor", _svr_similarity_groups,
+    fake=lambda vol, psf, c, b, go, gs, s, sm, r: vol.new_empty((c.shape[0], c.shape[1], 6), dtype=torch.float64))
+_op("svr_similarity_groups_bank(Tensor vol, Tensor psf_bank, Tensor psf_table, Tensor psf_id, Tensor corrections, Tensor base, "
+    "Tensor group_offsets, Tensor group_slices, Tensor slices, Tensor? slices_mask, float res_slice) -> Tensor",
+    _svr_similarity_groups_bank,
+    fake=lambda vol, pb, pt, pi, c, b, go, gs, s, sm, r: vol.new_empty((c.shape[0], c.shape[1], 6), dtype=torch.float64))
+
+
+# =====================================================================================================================
 # one descent step of the classical reconstruction with the edge-preserving prior (csrc/srr.hip):
 # out = x - alpha (grad + beta dR(x)), dR = srr.edge_prior_gradient, in one launch
 # =====================================================================================================================

@@ -26,6 +26,9 @@ returns the moment sums the loss is a function of (fp64); ``stack_registration``
 Slice-to-volume registration (``SVR``, ``register_slices`` = ``--registration svr``; no counterpart in the reference, whose
 slice-level choices need the pretrained SVoRT transformer): the same descent with one pose per slice, the objective being
 the similarity of the acquired slice and the slice simulated from the volume by the acquisition operator.
+
+Package registration (``GroupSVR``, ``register_slices(..., packages=...)`` = ``--packages``): the stage between the two - one
+rigid correction per interleaved package of a stack, the objective being the similarity over all slices of the package.
 """
 import ctypes
 import logging
@@ -329,7 +332,11 @@ class SVR(VVR):
         """Moment sums of slices ``ids`` (None: all) under K poses each: thetas_deg (m,K,6) -> (m,K,6) float64."""
         m, K = thetas_deg.shape[:2]
         pose = RigidTransform(thetas_deg.reshape(-1, 6) * self._unit(thetas_deg), trans_first=self.trans_first)
-        mats = mat_update_resolution(pose.matrix(), 1, lv.voxel).view(m, K, 3, 4).contiguous()
+        return self._sums_at(mat_update_resolution(pose.matrix(), 1, lv.voxel).view(m, K, 3, 4).contiguous(), lv, ids)
+
+    def _sums_at(self, mats: torch.Tensor, lv: _SliceLevel, ids: Optional[torch.Tensor]) -> torch.Tensor:
+        """The same sums at given matrices: mats (m,K,3,4) fp32 in the level's voxels, row j the poses of slice ``ids[j]``."""
+        m, K = mats.shape[:2]
         slices = lv.slices if ids is None else lv.slices[ids]
         mask = lv.mask if ids is None else lv.mask[ids]
         bank = isinstance(lv.psf, PsfBank)
@@ -413,6 +420,230 @@ class SVR(VVR):
             cur[lv.index] = sub
             loss[lv.index] = sub_loss
         return theta0 + (cur * unit - theta0), loss
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# package registration: groups of slices that move together (the interleaved sub-stacks of an acquisition)
+# ---------------------------------------------------------------------------------------------------------------------
+def package_groups(counts: Sequence[int], packages: Sequence[int], keep: Optional[Sequence[int]] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The CSR grouping of interleaved packages -> (group_offsets (G+1), group_slices (E)), int32 host tensors.
+
+    Stack s has ``counts[s]`` slices in file order and ``packages[s]`` packages (one value serves every stack): slice k of stack
+    s belongs to package ``k mod P_s``, and packages of different stacks are different groups, numbered stack by stack
+    (G = sum of P_s).  ``keep``: the increasing indices, into the concatenation of all stacks, of the slices that remain (the
+    empty ones are dropped AFTER the assignment); ``group_slices`` then indexes the kept slices.  A group whose slices were all
+    dropped stays, empty."""
+    packages = [int(p) for p in packages]
+    if len(packages) == 1:
+        packages = packages * len(counts)
+    if len(packages) != len(counts):
+        raise ValueError(f"packages: one count per stack ({len(counts)}) or one for all expected, got {len(packages)}")
+    for s, (c, P) in enumerate(zip(counts, packages)):
+        if P < 1:
+            raise ValueError(f"packages: stack {s} has {P} packages; at least 1 expected")
+        if P > c:
+            raise ValueError(f"packages: stack {s} has {c} slices, fewer than its {P} packages")
+    new_index = {int(k): j for j, k in enumerate(range(sum(counts)) if keep is None else keep)}
+    members: List[List[int]] = []
+    start = 0
+    for c, P in zip(counts, packages):
+        for p in range(P):
+            members.append([new_index[k] for k in range(start + p, start + c, P) if k in new_index])
+        start += c
+    offsets = [0]
+    for m in members:
+        offsets.append(offsets[-1] + len(m))
+    return torch.tensor(offsets, dtype=torch.int32), torch.tensor([k for m in members for k in m], dtype=torch.int32)
+
+
+def compose_mats(correction: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
+    """``correction o base`` of (...,3,4) translation-first matrices with the meaning of ``RigidTransform.compose``
+    (R' = Rc R, t' = t + R^T uc), written out element by element in the order csrc/svr.hip's grouped kernel uses: in float64,
+    every sum of products added left to right, so that rounding the result to fp32 gives that kernel's matrices bit for bit."""
+    c, b = correction.double(), base.double()
+    rows = []
+    for r in range(3):
+        row = [c[..., r, 0] * b[..., 0, col] + c[..., r, 1] * b[..., 1, col] + c[..., r, 2] * b[..., 2, col] for col in range(3)]
+        rtu = b[..., 0, r] * c[..., 0, 3] + b[..., 1, r] * c[..., 1, 3] + b[..., 2, r] * c[..., 2, 3]
+        row.append(b[..., r, 3] + rtu)
+        rows.append(torch.stack(row, -1))
+    return torch.stack(rows, -2)
+
+
+def centroid_corrections(x: torch.Tensor, centroid: torch.Tensor, voxel: float = 1.0) -> torch.Tensor:
+    """The rigid correction  p -> Rc (p - c) + c + d  as a (...,3,4) translation-first matrix [Rc | Rc^T (c + d) - c], float64.
+    x (...,6): rotation vector in DEGREES and d in mm; centroid c (...,3) in voxels of ``voxel`` mm (broadcast against x).
+    Rotating about the group's centroid keeps rotation and translation decoupled: the centroid moves by d alone."""
+    x, c = x.double(), centroid.double()
+    r = x[..., :3] * (math.pi / 180)
+    d = x[..., 3:] / voxel
+    t2 = (r * r).sum(-1)
+    small = t2 < 1e-16
+    t = torch.sqrt(torch.where(small, torch.ones_like(t2), t2))
+    a = torch.where(small, 1 - t2 / 6, torch.sin(t) / t)  # sin t / t
+    bq = torch.where(small, 0.5 - t2 / 24, (1 - torch.cos(t)) / (t * t))  # (1 - cos t) / t^2
+    rx, ry, rz = r.unbind(-1)
+    zero = torch.zeros_like(rx)
+    Kx = torch.stack([torch.stack([zero, -rz, ry], -1), torch.stack([rz, zero, -rx], -1), torch.stack([-ry, rx, zero], -1)], -2)
+    R = torch.eye(3, dtype=x.dtype, device=x.device) + a[..., None, None] * Kx + bq[..., None, None] * (Kx @ Kx)
+    u = (R.transpose(-2, -1) @ (c + d)[..., None])[..., 0] - c
+    return torch.cat([R, u[..., None]], -1)
+
+
+def _sub_grouping(offsets: torch.Tensor, listed: torch.Tensor, groups: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The CSR of the named groups, in that order (host tensors)."""
+    off, parts = [0], []
+    for g in groups:
+        part = listed[int(offsets[g]):int(offsets[g + 1])]
+        parts.append(part)
+        off.append(off[-1] + int(part.numel()))
+    return torch.tensor(off, dtype=torch.int32), (torch.cat(parts) if parts else listed[:0])
+
+
+class GroupSVR(SVR):
+    """``GroupSVR(...)`` (the arguments of ``SVR``) then ``theta_out, loss = gsvr(theta, groups, slices, slices_mask, volume,
+    params, trans_first)``: ``SVR`` with one rigid correction per GROUP of slices - the package stage between one pose per
+    stack and one pose per slice.  ``groups = (group_offsets, group_slices)``: a CSR grouping in host memory
+    (``package_groups``); a slice listed nowhere keeps its pose.
+
+    The unknown is one 6-vector per group (rotation vector in degrees, translation in mm): slice i of group g moves to
+    ``correction_g o pose_i``, the correction rotating about the centroid of the group's masked pixel centres at the stage's
+    starting poses (``centroid_corrections``).  Pyramid, losses and descent (``_round``: momentum, accept test) are ``SVR``'s; the
+    loss of a group is the loss of the sums over all its slices; a group whose valid count at the start of a level is below
+    ``min_valid`` sits that level out.  ``theta_out`` (n,6): the corrections folded into the slices' poses in float64.  After a
+    call ``corrections`` holds the (G,6) result and ``history`` one ``(level, loss at the level's start, loss at its end)`` per
+    level, (G,) each - the accept test keeps the end at or below the start.
+
+    Two evaluation paths with one definition.  Fused (``torch.ops.nesvor.svr_similarity_groups``, csrc/svr.hip): the corrections
+    go to the kernel, which composes them with every slice's pose and adds a group's sums in CSR order.  Composed: the same
+    composition in float64 here (``compose_mats``), rounded to fp32, then ``SVR``'s per-slice sums (fused or composed themselves:
+    ``NESVOR_SVR`` keeps its meaning) added per group in CSR order - taken for PSFs the kernel refuses and forced with
+    ``NESVOR_PACKAGES=composed``."""
+
+    def _packages_fused(self, lv: _SliceLevel) -> bool:
+        return os.environ.get("NESVOR_PACKAGES", "") != "composed" and self._fused_path(lv)
+
+    def _group_sums(self, x: torch.Tensor, lv: _SliceLevel, gids: Optional[torch.Tensor]) -> torch.Tensor:
+        """Moment sums of groups ``gids`` (None: all) under K corrections each: x (m,K,6) [deg | mm] -> (m,K,6) float64."""
+        offsets, listed = lv.groups if gids is None else _sub_grouping(*lv.groups, gids.tolist())
+        centroid = lv.centroid if gids is None else lv.centroid[gids]
+        corr = centroid_corrections(x, centroid[:, None], lv.voxel).float().contiguous()
+        m, K = corr.shape[:2]
+        if self._packages_fused(lv):
+            if isinstance(lv.psf, PsfBank):
+                return torch.ops.nesvor.svr_similarity_groups_bank(lv.volume, lv.psf.flat, lv.psf.table, lv.psf.ids, corr, lv.base,
+                                                                   offsets, listed, lv.slices, lv.mask, lv.res_slice)
+            return torch.ops.nesvor.svr_similarity_groups(lv.volume, lv.psf, corr, lv.base, offsets, listed, lv.slices, lv.mask,
+                                                          lv.res_slice)
+        out = torch.zeros((m, K, 6), dtype=torch.float64, device=corr.device)
+        if listed.numel() == 0:
+            return out
+        sizes = (offsets[1:] - offsets[:-1]).long()
+        entry_group = torch.repeat_interleave(torch.arange(m), sizes).to(corr.device)
+        ids = listed.long().to(corr.device)
+        mats = compose_mats(corr[entry_group], lv.base[ids][:, None]).float().contiguous()  # (E,K,3,4)
+        per_entry = self._sums_at(mats, lv, ids)
+        for j in range(int(sizes.max())):  # a group's entries one after the other from 0, in CSR order
+            has = torch.nonzero(sizes > j).flatten()
+            rows = (offsets[:-1].long()[has] + j).to(corr.device)
+            has = has.to(corr.device)
+            out[has] = out[has] + per_entry[rows]
+        return out
+
+    def _gids(self, idx: torch.Tensor, lv: _SliceLevel) -> Optional[torch.Tensor]:
+        gids = lv.index[idx]
+        return None if gids.shape[0] == lv.centroid.shape[0] else gids
+
+    def _trial_at(self, idx: torch.Tensor, theta: torch.Tensor, lv: _SliceLevel) -> torch.Tensor:
+        return self._loss_of(self._group_sums(theta[:, None], lv, self._gids(idx, lv)))[:, 0]
+
+    def _gradient_at(self, idx: torch.Tensor, cur: torch.Tensor, lv: _SliceLevel, step: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        e = torch.zeros((13, 6), dtype=cur.dtype, device=cur.device)  # the correction and its 12 perturbations
+        j = torch.arange(6, device=cur.device)
+        e[1 + 2 * j, j] = step
+        e[2 + 2 * j, j] = -step
+        l = self._loss_of(self._group_sums(cur[:, None] + e[None], lv, self._gids(idx, lv)))
+        return l[:, 0], l[:, 1::2] - l[:, 2::2]
+
+    @staticmethod
+    def group_centroids(base_mm: torch.Tensor, slices_mask: torch.Tensor, res_s: float, groups) -> torch.Tensor:
+        """(G,3) float64, mm: the mean world position of the masked pixel centres of every group's slices at poses ``base_mm``
+        (n,3,4); the origin for a group without a masked pixel.  The per-group adds run on the host, in CSR order."""
+        offsets, listed = groups
+        m = slices_mask.reshape(slices_mask.shape[0], slices_mask.shape[-2], slices_mask.shape[-1]).double()
+        h, w = m.shape[-2:]
+        qx = (torch.arange(w, dtype=torch.float64, device=m.device) - (w - 1) / 2) * res_s
+        qy = (torch.arange(h, dtype=torch.float64, device=m.device) - (h - 1) / 2) * res_s
+        cnt = m.sum((1, 2))
+        sq = torch.stack([(m * qx).sum((1, 2)), (m * qy[:, None]).sum((1, 2)), torch.zeros_like(cnt)], -1)  # sum of q per slice
+        R, t = base_mm[..., :3].double(), base_mm[..., 3].double()
+        world = (R @ (sq + cnt[:, None] * t)[..., None])[..., 0]  # sum over the slice's masked pixels of R (q + t)
+        per = torch.cat([world, cnt[:, None]], -1).cpu()
+        G = offsets.numel() - 1
+        acc = torch.zeros((G, 4), dtype=torch.float64)
+        for g in range(G):
+            for k in listed[int(offsets[g]):int(offsets[g + 1])].tolist():
+                acc[g] += per[k]
+        return (acc[:, :3] / acc[:, 3:].clamp(min=1)).to(base_mm.device)
+
+    def _prepare(self, lv: _SliceLevel, base_mm: torch.Tensor, centroid_mm: torch.Tensor, groups) -> None:
+        lv.base = mat_update_resolution(base_mm, 1, lv.voxel).contiguous()  # (n,3,4) fp32, the level's voxels
+        lv.centroid = centroid_mm / lv.voxel
+        lv.groups = groups
+
+    @torch.no_grad()
+    def evaluate(self, theta: torch.Tensor, groups, slices: torch.Tensor, slices_mask: torch.Tensor, volume: torch.Tensor,
+                 params: Dict, trans_first: bool = True, level: int = 0) -> torch.Tensor:
+        """The loss of every group at the slice poses ``theta`` (n,6) [rad | mm] on pyramid level ``level`` -> (G,)."""
+        base_mm = RigidTransform(theta, trans_first=trans_first).matrix()
+        lv = self._level(level, slices, slices_mask, volume, params)
+        self._prepare(lv, base_mm, self.group_centroids(base_mm, slices_mask, params["res_s"], groups), groups)
+        x = torch.zeros((groups[0].numel() - 1, 1, 6), dtype=theta.dtype, device=theta.device)
+        return self._loss_of(self._group_sums(x, lv, None))[:, 0]
+
+    @torch.no_grad()
+    def __call__(self, theta: torch.Tensor, groups, slices: torch.Tensor, slices_mask: torch.Tensor, volume: torch.Tensor,
+                 params: Dict, trans_first: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+        G = groups[0].numel() - 1
+        base_mm = RigidTransform(theta, trans_first=trans_first).matrix()
+        centroid_mm = self.group_centroids(base_mm, slices_mask, params["res_s"], groups)
+        cur = torch.zeros((G, 6), dtype=theta.dtype, device=theta.device)
+        loss = torch.zeros(G, dtype=theta.dtype, device=theta.device)
+        self.history: List[Tuple[int, torch.Tensor, torch.Tensor]] = []
+        for level in range(self.num_levels - 1, -1, -1):
+            self.current_level = level
+            lv = self._level(level, slices, slices_mask, volume, params)
+            self._prepare(lv, base_mm, centroid_mm, groups)
+            sums = self._group_sums(cur[:, None], lv, None)[:, 0]
+            start = self._loss_of(sums)
+            lv.index = torch.nonzero(sums[:, 0] >= self.min_valid).flatten()
+            loss = torch.zeros(G, dtype=theta.dtype, device=theta.device)
+            if lv.index.numel() > 0:
+                sub = cur[lv.index]
+                step = self.step_size * 2**level
+                state: Dict = {}  # the momentum buffer lives for one level
+                for _ in range(self.num_steps):
+                    sub, _ = self._round(sub, lv, step, state)
+                    step /= 2
+                cur[lv.index] = sub
+                loss[lv.index] = self._loss_of(self._group_sums(cur[:, None], lv, None))[lv.index, 0]
+            self.history.append((level, start, torch.where(sums[:, 0] >= self.min_valid, loss, start)))
+        self.corrections = cur
+        # fold: every listed slice's pose becomes correction_g o pose, in float64 (mm), then back to the input's form
+        offsets, listed = groups
+        corr = centroid_corrections(cur, centroid_mm, 1.0)
+        mats = base_mm.double().clone()
+        sizes = (offsets[1:] - offsets[:-1]).long()
+        if listed.numel() > 0:
+            entry_group = torch.repeat_interleave(torch.arange(G), sizes).to(theta.device)
+            ids = listed.long().to(theta.device)
+            mats[ids] = compose_mats(corr[entry_group], mats[ids])
+        out = RigidTransform(mats.to(theta.dtype)).axisangle(trans_first=trans_first)
+        moved = torch.zeros(theta.shape[0], dtype=torch.bool, device=theta.device)
+        if listed.numel() > 0:
+            moved[ids] = True
+        return torch.where(moved[:, None], out, theta), loss
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -565,12 +796,19 @@ def _cover_shape(poses: RigidTransform, mask: torch.Tensor, res_s: float, s_thic
 
 
 def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = None, n_outer: int = 3, template: int = 0,
-                    per_stack_thickness: bool = False) -> List:
+                    per_stack_thickness: bool = False, packages: Optional[Sequence[int]] = None, package_rounds: int = 2) -> List:
     """``--registration svr``: stack registration (``register_stacks``, to the stack ``template``), then ``n_outer`` rounds of
     reconstruct a volume from all slices at their current poses  /  register every non-empty slice rigidly to it (``SVR``,
     global NCC); the per-slice poses are written back into the stacks.  ``res_r``: voxel size of the intermediate volume
     (default ``res_s``).  ``per_stack_thickness`` and stacks of unequal thickness: the stack registration above runs under the
-    switch, and the volume and the slice registration take every slice's own thickness (a PSF bank)."""
+    switch, and the volume and the slice registration take every slice's own thickness (a PSF bank).
+
+    ``packages`` (``--packages``; one count per stack, or one for all): between the stack registration and the slice rounds,
+    ``package_rounds`` rounds of reconstruct a volume from all slices  /  register every interleaved package rigidly to it
+    (``GroupSVR``).  Slice k of stack s belongs to package ``k mod P_s``, counted in file order before the empty slices are
+    dropped; ``P_s = 1`` registers the whole stack against the joint volume.  ``None``: no package stage, as before."""
+    if packages is not None:  # (refusals before any work)
+        package_groups([s.slices.shape[0] for s in dataset], packages)
     dataset = register_stacks(dataset, res_s, template, per_stack_thickness)
     t0 = time.time()
     res_r = res_s if res_r is None else res_r
@@ -586,6 +824,19 @@ def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = 
     theta = poses.axisangle()[keep].clone()
     svr = SVR(num_levels=3, num_steps=4, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1}, loss={"name": "ncc"})
     params = {"res_s": res_s, "s_thick": s_thick, "res_r": res_r}
+    if packages is not None:
+        groups = package_groups([s.slices.shape[0] for s in dataset], packages, keep.tolist())
+        gsvr = GroupSVR(num_levels=3, num_steps=4, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1},
+                        loss={"name": "ncc"})
+        for it in range(package_rounds):
+            current = RigidTransform(theta)
+            shape = _cover_shape(current, mask, res_s, s_thick, res_r)
+            volume = reconstruct_from_slices(mat_update_resolution(current.matrix(), 1, res_r), slices, res_s, s_thick, res_r, shape)
+            theta, loss = gsvr(theta, groups, slices, mask, volume, params, True)
+            logging.debug("package registration round %d: volume %s, mean NCC %f", it, shape, -float(loss.mean()))
+            if logging.getLogger().isEnabledFor(logging.DEBUG):
+                for g, c in enumerate(gsvr.corrections.tolist()):
+                    logging.debug("  package %d: rotation (%.3f, %.3f, %.3f) deg, translation (%.3f, %.3f, %.3f) mm", g, *c)
     for it in range(n_outer):
         current = RigidTransform(theta)
         shape = _cover_shape(current, mask, res_s, s_thick, res_r)

@@ -274,6 +274,7 @@ def svr_command(args: Namespace) -> Dict:
         if args.input_stacks or args.stack_masks or args.thicknesses:
             logging.warning("Since <input-slices> is provided, <input-stacks>, <stack_masks> and <thicknesses> would be ignored.")
         cli.warn_template_ignored(args, "--input-slices")
+        cli.warn_packages_ignored(args, "--input-slices")
         cli.warn_masking_ignored(args, "--input-slices")
         cli.warn_denoise_ignored(args, "--input-slices")
         loaded = load_slices(args.input_slices, args.device)
