@@ -915,6 +915,41 @@ int nesvor_svr_similarity_groups_bank(const float* vol, int D, int H, int W, con
 int64_t nesvor_svr_similarity_groups_workspace_bytes(int E, int K, int h, int w);
 
 /* ----------------------------------------------------------------------
+ * Joint histograms of the slice-to-volume registration (the statistic of its mutual-information similarity): what
+ * nesvor_svr_similarity sums into six moments, binned.  vol, psf, transforms (n,K,3,4), slices, slices_mask, res_slice and the
+ * valid set (mask byte set or mask NULL, PSF weight > 0) are nesvor_svr_similarity's; I = A's value, J = the acquired value.
+ *   i_lo, i_scale        the affine map of I to bin coordinates, one for the call
+ *   j_map   (n,2) fp32   { lo, scale } of J per slice (device memory)
+ *   bins    B, 2 <= B <= 64
+ * Position of a value v on an axis, in fp32 with every operation rounded on its own:
+ *   u = clamp((v - lo) * scale, 0, B-1),  b0 = min((int)u, B-2),  f = u - b0,  q = (int)(f * 256 + 0.5)   in [0, 256]
+ * v gives weight 256 - q to bin b0 and q to bin b0 + 1.  A valid pixel adds the four integer products of its I weights and its
+ * J weights to cells (bI, bJ): 65536 units per pixel.
+ *   hist[i][k][bI][bJ]   int64, (n,K,B,B), row = I bin; fully written (no memset needed); its total is 65536 * count, a
+ * (slice, pose) without a valid pixel yields zeros.  Integer adds only: the result does not depend on the order of addition and
+ * is the same from run to run.  A slice's pixels are cut into segments of 1024 to 16384 pixels (whole slices when n K reaches 1024
+ * workgroups, shorter segments for smaller calls); a segment's histogram is built in LDS in 32-bit cells (16384 pixels of 65536
+ * units stay below 2^32), stored to the workspace, and a second launch adds the segments in 64 bits: no cell overflows at any
+ * slice size.  workspace: device memory of at least
+ * nesvor_svr_joint_histogram_workspace_bytes(n, K, h, w, bins) bytes (0 for sizes the call refuses or treats as a no-op).
+ * K <= 0 or n == 0: no-op, returns 0.  hipErrorInvalidValue, without a launch: what nesvor_svr_similarity refuses (the bank
+ * twin: nesvor_svr_similarity_bank), bins outside [2, 64], NULL j_map, a workspace that is NULL or too small.
+ * nesvor_svr_joint_histogram_bank: the PSF-bank twin ((psf_bank, psf_table (host), P, psf_id) in the place of (psf, d_p, h_p,
+ * w_p)); the workspace size does not differ.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_svr_joint_histogram(const float* vol, int D, int H, int W, const float* psf, int d_p, int h_p, int w_p,
+                               const float* transforms, const float* slices, const uint8_t* slices_mask, int n, int K, int h,
+                               int w, float res_slice, float i_lo, float i_scale, const float* j_map, int bins, int64_t* hist,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int nesvor_svr_joint_histogram_bank(const float* vol, int D, int H, int W, const float* psf_bank, const int32_t* psf_table,
+                                    int P, const int32_t* psf_id, const float* transforms, const float* slices,
+                                    const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, float i_lo,
+                                    float i_scale, const float* j_map, int bins, int64_t* hist, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int64_t nesvor_svr_joint_histogram_workspace_bytes(int n, int K, int h, int w, int bins);
+
+/* ----------------------------------------------------------------------
  * One descent step of the classical super-resolution reconstruction with the edge-preserving prior, in one launch
  * (the loop body of the reference's SRR, svort/srr.py:117-131, whose prior gradient dR is :139-160):
  *   out[a] = x[a] - alpha * (grad[a] + beta * dR(x)[a])

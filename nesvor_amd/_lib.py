@@ -240,6 +240,12 @@ _SIGNATURES = {
     "nesvor_svr_similarity_groups_bank": ([_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int,
                                            c_int, c_int, c_float, _P, _P, c_size_t, _P], c_int),
     "nesvor_svr_similarity_groups_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),
+    # the joint histograms: (i_lo, i_scale, j_map, bins) behind res_slice, int64 cells in the place of the sums
+    "nesvor_svr_joint_histogram": ([_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float,
+                                    c_float, c_float, _P, c_int, _P, _P, c_size_t, _P], c_int),
+    "nesvor_svr_joint_histogram_bank": ([_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float,
+                                         c_float, c_float, _P, c_int, _P, _P, c_size_t, _P], c_int),
+    "nesvor_svr_joint_histogram_workspace_bytes": ([c_int, c_int, c_int, c_int, c_int], c_int64),
     "nesvor_srr_step": ([_P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_int, _P], c_int),
     "nesvor_robust_estep": ([_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P], c_int),
     "nesvor_robust_estep_workspace_bytes": ([c_int, c_int, c_int], c_int64),

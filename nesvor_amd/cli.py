@@ -63,6 +63,13 @@ rigidly to it (``GroupSVR``, nesvor_amd/registration.py; one count per input sta
 ``--registration svr``: with another choice, or with ``--input-slices``, the flags are ignored with a warning; a count that matches
 neither 1 nor the number of stacks, or a ``P`` below 1, ends the command.  ``--debug`` logs every package's correction per round.
 
+Also not in the reference: ``--svr-similarity ncc|nmi`` (default ``ncc``) and ``--nmi-bins B`` (default 32, 2 <= B <= 64) on
+``svr``, ``register`` and ``reconstruct`` choose the metric ``--registration svr`` steers its package and slice stages on: the global
+NCC of a slice and its simulation, or their normalised mutual information on a joint histogram of B bins per axis
+(nesvor_amd/nmi.py, csrc/svr_nmi.hip) - for stacks of different contrast, of different coil bias, or with saturated slices, where
+the linear intensity relation NCC assumes fails.  With another registration, or with ``--input-slices``, the flags are ignored
+with a warning; a ``B`` outside [2, 64] ends the command.
+
 Also not in the reference: ``--per-stack-thickness`` on ``svr``, ``register`` and ``reconstruct`` (there for the registration stage
 only) lets stacks of unequal slice thickness keep their own (``--thicknesses``, or the files' z spacing): ``--registration stack``
 registers every stack on the template's slice spacing and spaces its slices by its own gap, and ``svr`` / ``--registration svr``
@@ -289,6 +296,10 @@ def _package_flags(g) -> None:
                         "--registration svr every package (slices p, p+P, p+2P, ...) is registered rigidly to the joint volume "
                         "between the stack registration and the slice rounds (nesvor_amd/registration.py: GroupSVR)")
     g.add_argument("--package-rounds", type=int, default=2, metavar="N", help="reconstruct / register-packages rounds of --packages")
+    g.add_argument("--svr-similarity", choices=["ncc", "nmi"], default="ncc",
+                   help="(not in the reference) the metric of --registration svr's package and slice stages: global NCC, or normalised "
+                        "mutual information on a joint histogram (nesvor_amd/nmi.py) for stacks whose intensities are not linearly related")
+    g.add_argument("--nmi-bins", type=int, default=32, metavar="B", help="bins per axis of --svr-similarity nmi, 2 <= B <= 64")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -630,6 +641,7 @@ def register(args: Namespace, stacks: List) -> List:
                                   "build; register with the reference and pass the result through --input-slices, or use "
                                   "--registration svr / stack / none")
     packages = package_options(args, len(stacks))  # (a bad count ends the command before any registration)
+    similarity = similarity_options(args)
     if args.registration == "none":
         warn_template_ignored(args, "--registration none")
         return stacks_to_slices(stacks)
@@ -649,10 +661,10 @@ def register(args: Namespace, stacks: List) -> List:
 
         t1 = time.time()
         if packages is None:
-            stacks = register_slices(stacks, template=template, per_stack_thickness=per_stack)
+            stacks = register_slices(stacks, template=template, per_stack_thickness=per_stack, **similarity)
         else:
             stacks = register_slices(stacks, template=template, per_stack_thickness=per_stack, packages=packages,
-                                     package_rounds=int(getattr(args, "package_rounds", 2)))
+                                     package_rounds=int(getattr(args, "package_rounds", 2)), **similarity)
         logging.info("Slice-to-volume registration finished in %.1f s", time.time() - t1)
     return stacks_to_slices(stacks)
 
@@ -667,6 +679,26 @@ def warn_packages_ignored(args: Namespace, why: str) -> None:
     """``--packages`` / ``--package-rounds`` only act in the package stage of ``--registration svr``."""
     if getattr(args, "packages", None) is not None or getattr(args, "package_rounds", 2) != 2:
         logging.warning("--packages / --package-rounds are ignored with %s: packages are registered by --registration svr only", why)
+
+
+def warn_similarity_ignored(args: Namespace, why: str) -> None:
+    """``--svr-similarity`` / ``--nmi-bins`` only act in the package and slice stages of ``--registration svr``."""
+    if getattr(args, "svr_similarity", "ncc") != "ncc" or getattr(args, "nmi_bins", 32) != 32:
+        logging.warning("--svr-similarity / --nmi-bins are ignored with %s: the metric is that of --registration svr only", why)
+
+
+def similarity_options(args: Namespace) -> Dict:
+    """``--svr-similarity`` / ``--nmi-bins`` as keyword arguments of ``register_slices`` (none for the default, NCC).  With a
+    registration other than ``svr`` the flags are ignored with a warning; ``--nmi-bins`` outside [2, 64] ends the command."""
+    if getattr(args, "registration", "none") != "svr":
+        warn_similarity_ignored(args, f"--registration {getattr(args, 'registration', 'none')}")
+        return {}
+    bins = getattr(args, "nmi_bins", 32)
+    if not 2 <= int(bins) <= 64:
+        raise SystemExit(f"--nmi-bins: a number of bins in [2, 64] expected, got {bins}")
+    if getattr(args, "svr_similarity", "ncc") == "ncc":
+        return {}
+    return {"similarity": "nmi", "nmi_bins": int(bins)}
 
 
 def package_options(args: Namespace, n_stacks: int) -> Optional[List[int]]:
@@ -762,6 +794,7 @@ def reconstruct(args: Namespace) -> None:
     if args.input_slices is not None:
         warn_template_ignored(args, "--input-slices")
         warn_packages_ignored(args, "--input-slices")
+        warn_similarity_ignored(args, "--input-slices")
         warn_masking_ignored(args, "--input-slices")
         warn_denoise_ignored(args, "--input-slices")
     for name in ("stack_masks", "thicknesses"):

@@ -1,0 +1,174 @@
+// Joint histograms for the mutual-information similarity of the slice-to-volume registration (gfx950): the sibling of svr.hip
+// whose statistic per (slice, pose) is not six moments but a B x B histogram of (simulated, acquired) intensities.
+//
+// The definition (nesvor_amd/nmi.py states it once; the composed path and the tests use that statement).  Each axis maps a value
+// to bin coordinates with an affine map (lo, scale) the host computed in fp32:
+//   u = clamp((v - lo) * scale, 0, B - 1),  b0 = min((int)u, B - 2),  f = u - b0,  q = (int)(f * 256 + 0.5)  in [0, 256]
+// (fp32, every operation rounded on its own: the build does not contract); the value gives weight 256 - q to bin b0 and q to bin
+// b0 + 1.  A valid pixel (mask set and PSF weight > 0: svr_similarity's valid set) adds the four integer products of its I weights
+// and its J weights to the cells (bI, bJ), 65536 units in all, zero products skipped.  Integer adds: the histogram does not depend
+// on the order of addition, so LDS atomics are reproducible here and no float atomic is used.
+//
+// A pixel's value under a pose comes from the functions slice_acq_fwd<float, false, true> and svr_similarity_kernel call (acq_taps.h:
+// pixel_geom, the LDS tap list, the inside test, linear_tap without a volume mask) and the same val / wsum, so I and the valid set
+// are that operator's bit for bit.
+//
+// Shape.  A slice's pixels are cut into segments; one workgroup serves one (slice, pose, segment): it keeps the histogram in LDS
+// (B B 32-bit cells, at most 16 KB, next to the 16 KB tap list), walks its pixels 256 at a time, adds with integer LDS atomics and
+// stores the cells to its own rows of the workspace with plain stores; a second launch adds the segments of a (slice, pose) in
+// 64 bits.  The segment length is the launch's (segment_pixels): a call with many (slice, pose) entries - the 13 poses of a
+// gradient - takes whole slices, one workgroup per entry, which pays the tap list and the histogram's clear and store once per
+// entry; a call with few entries - the K = 1 accept test - cuts its slices until about kTargetWorkgroups workgroups fill the chip
+// ("Mutual-information similarity", has the measurements behind both).  No cell can overflow: a segment holds at most
+// kMaxSegmentPixels <= 65535 pixels of at most 65536 units each, below 2^32; the result in memory is 64-bit.  No global atomics, no
+// memset: every row of the workspace is written by exactly one workgroup before the second launch reads it.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include "acq_taps.h"
+#include "../../include/nesvor_hip.h"
+
+namespace {
+using namespace acq;
+
+constexpr int kMaxNmiBins = 64;
+constexpr int kMinSegmentPixels = 1024, kMaxSegmentPixels = 16384;  // multiples of the workgroup's 256 pixels
+constexpr int kTargetWorkgroups = 1024;                             // four per CU: what a launch is cut for
+static_assert(kMinSegmentPixels % 256 == 0 && kMaxSegmentPixels % 256 == 0 && kMaxSegmentPixels <= 65535,
+              "a 32-bit cell holds at most 65535 pixels of 65536 units");
+
+// A value's place on an axis: the lower bin and the weight (of 256) of the upper one.
+struct AxisPlace { int b0, q; };
+
+__device__ __forceinline__ AxisPlace axis_place(float v, float lo, float scale, int B) {
+  const float u = fminf(fmaxf((v - lo) * scale, 0.f), (float)(B - 1));  // (a NaN becomes 0: nothing is indexed by it)
+  const int b0 = min((int)u, B - 2);
+  const float f = u - (float)b0;
+  return AxisPlace{b0, (int)(f * 256.f + 0.5f)};
+}
+
+// grid: n K S workgroups, S = ceil(h w / seg) segments of `seg` pixels per (slice, pose); block e S + s serves segment s of entry
+// e = slice K + pose.  partial: (n K, S, B, B) 32-bit cells, row = I bin.
+template <typename PSF>
+__global__ __launch_bounds__(256) void svr_joint_histogram_kernel(const float* __restrict__ vol, int D, int H, int W, const PSF psfs,
+                                                                  const float* __restrict__ transforms, const float* __restrict__ slices,
+                                                                  const uint8_t* __restrict__ slices_mask, int K, int h, int w, int S,
+                                                                  int seg, float res_slice, float i_lo, float i_scale,
+                                                                  const float* __restrict__ j_map, int B, uint32_t* __restrict__ partial) {
+  __shared__ Tap<float> taps[kMaxTaps];
+  __shared__ int n_taps;
+  __shared__ uint32_t hist[kMaxNmiBins * kMaxNmiBins];
+  const int e = blockIdx.x / S, s = blockIdx.x - e * S;
+  const int in = e / K;
+  const int cells = B * B;
+  for (int c = threadIdx.x; c < cells; c += 256) hist[c] = 0u;
+  if (threadIdx.x == 0) {
+    const PsfView<float> pk = psfs.at(in);
+    n_taps = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
+  }
+  __syncthreads();
+  const float* t = transforms + (size_t)e * 12;  // wave-uniform: the scalar path
+  const float j_lo = j_map[2 * in], j_scale = j_map[2 * in + 1];
+  const int nt = n_taps;
+  const int first = s * seg;  // (below h w: S = ceil(h w / seg))
+  const int last = (int)min((int64_t)first + seg, (int64_t)h * w);
+  for (int pix = first + (int)threadIdx.x; pix < last; pix += 256) {
+    const size_t idx = (size_t)in * h * w + pix;
+    if (slices_mask != nullptr && !slices_mask[idx]) continue;
+    const PixelGeom<float> g = pixel_geom(t, pix % w, pix / w, h, w, res_slice, D, H, W);
+    float val = 0.f, wsum = 0.f;
+    for_lds_taps(t, g, taps, nt, D, H, W, [&](float, float, float, float pv, float x, float y, float z) {
+      linear_tap(vol, (const uint8_t*)nullptr, trilinear_cell(x, y, z, H, W), pv, val, wsum);
+    });
+    if (!(wsum > 0)) continue;
+    const AxisPlace a = axis_place(val / wsum, i_lo, i_scale, B), b = axis_place(slices[idx], j_lo, j_scale, B);
+    const int c00 = a.b0 * B + b.b0;  // at most (B - 2) B + B - 2: the four cells stay below B B
+    const uint32_t ai[2] = {(uint32_t)(256 - a.q), (uint32_t)a.q}, bj[2] = {(uint32_t)(256 - b.q), (uint32_t)b.q};
+#pragma unroll
+    for (int di = 0; di < 2; ++di)
+#pragma unroll
+      for (int dj = 0; dj < 2; ++dj) {
+        const uint32_t p = ai[di] * bj[dj];
+        if (p != 0u) atomicAdd(&hist[c00 + di * B + dj], p);
+      }
+  }
+  __syncthreads();
+  uint32_t* row = partial + (size_t)blockIdx.x * cells;
+  for (int c = threadIdx.x; c < cells; c += 256) row[c] = hist[c];
+}
+
+// out[e][c] = the S segments of entry e added in 64 bits; one thread per (entry, cell), total = entries * cells.
+__global__ __launch_bounds__(256) void svr_joint_histogram_reduce_kernel(const uint32_t* __restrict__ partial, int64_t total, int cells, int S,
+                                                                         int64_t* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int64_t e = t / cells;
+  const int c = (int)(t - e * cells);
+  int64_t sum = 0;
+  for (int s = 0; s < S; ++s) sum += (int64_t)partial[((size_t)e * S + s) * cells + c];
+  out[t] = sum;
+}
+
+// The segment length of a launch of `entries` (slice, pose) pairs of h w pixels: the slice cut into as many segments as it takes to
+// reach kTargetWorkgroups workgroups, in whole trips of 256 pixels, between kMinSegmentPixels and kMaxSegmentPixels.
+inline int segment_pixels(int64_t entries, int64_t hw) {
+  const int64_t want = (kTargetWorkgroups + entries - 1) / entries;
+  const int64_t seg = ((hw + want - 1) / want + 255) / 256 * 256;
+  return (int)(seg < kMinSegmentPixels ? kMinSegmentPixels : seg > kMaxSegmentPixels ? kMaxSegmentPixels : seg);
+}
+inline int64_t segments(int64_t entries, int h, int w) {
+  const int64_t hw = (int64_t)h * w, seg = segment_pixels(entries, hw);
+  return (hw + seg - 1) / seg;
+}
+
+// The launches of both entry points, behind their checks of the PSF source.
+template <typename PSF>
+int svr_joint_histogram_launch(const float* vol, int D, int H, int W, const PSF& psfs, const float* transforms, const float* slices,
+                               const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, float i_lo, float i_scale,
+                               const float* j_map, int bins, int64_t* hist, void* workspace, size_t workspace_bytes, void* stream) {
+  if (D < 1 || H < 1 || W < 1 || h < 1 || w < 1 || n < 1) return (int)hipErrorInvalidValue;
+  if (bins < 2 || bins > kMaxNmiBins || j_map == nullptr) return (int)hipErrorInvalidValue;
+  // voxel and pixel indices are ints (a workgroup's last trip may index 255 past a slice's end), an entry is a (slice, pose)
+  if ((int64_t)D * H * W > INT_MAX || (int64_t)n * K > INT_MAX || (int64_t)h * w > INT_MAX - 256) return (int)hipErrorInvalidValue;
+  const int64_t entries = (int64_t)n * K, S = segments(entries, h, w), cells = (int64_t)bins * bins;
+  if (entries * S > INT_MAX || entries * cells / 256 >= INT_MAX) return (int)hipErrorInvalidValue;  // both grids fit an int
+  if (workspace == nullptr || (int64_t)workspace_bytes < (int64_t)sizeof(uint32_t) * entries * S * cells) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* partial = (uint32_t*)workspace;
+  hipLaunchKernelGGL((svr_joint_histogram_kernel<PSF>), dim3((unsigned)(entries * S)), dim3(256), 0, st, vol, D, H, W, psfs, transforms,
+                     slices, slices_mask, K, h, w, (int)S, segment_pixels(entries, (int64_t)h * w), res_slice, i_lo, i_scale, j_map, bins, partial);
+  const int64_t total = entries * cells;
+  hipLaunchKernelGGL(svr_joint_histogram_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint32_t*)partial,
+                     total, (int)cells, (int)S, hist);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int64_t nesvor_svr_joint_histogram_workspace_bytes(int n, int K, int h, int w, int bins) {
+  if (n < 1 || K < 1 || h < 1 || w < 1 || bins < 2 || bins > kMaxNmiBins) return 0;
+  return (int64_t)sizeof(uint32_t) * n * K * segments((int64_t)n * K, h, w) * bins * bins;
+}
+
+extern "C" int nesvor_svr_joint_histogram(const float* vol, int D, int H, int W, const float* psf, int d_p, int h_p, int w_p,
+                                          const float* transforms, const float* slices, const uint8_t* slices_mask, int n, int K,
+                                          int h, int w, float res_slice, float i_lo, float i_scale, const float* j_map, int bins,
+                                          int64_t* hist, void* workspace, size_t workspace_bytes, void* stream) {
+  if (K <= 0 || n == 0) return 0;
+  if (d_p < 1 || h_p < 1 || w_p < 1 || (int64_t)d_p * h_p * w_p > kMaxTaps) return (int)hipErrorInvalidValue;
+  return svr_joint_histogram_launch(vol, D, H, W, OnePsf<float>{psf, d_p, h_p, w_p}, transforms, slices, slices_mask, n, K, h, w,
+                                    res_slice, i_lo, i_scale, j_map, bins, hist, workspace, workspace_bytes, stream);
+}
+
+// The same histograms with a PSF bank: slice i is simulated with PSF psf_id[i].  Refused if ANY member has more than kMaxTaps elements.
+extern "C" int nesvor_svr_joint_histogram_bank(const float* vol, int D, int H, int W, const float* psf_bank, const int32_t* psf_table,
+                                               int P, const int32_t* psf_id, const float* transforms, const float* slices,
+                                               const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, float i_lo,
+                                               float i_scale, const float* j_map, int bins, int64_t* hist, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+  BankPsf<float> bank;
+  int64_t max_elements;
+  if (!make_bank(psf_bank, psf_table, P, psf_id, n, bank, max_elements) || max_elements > kMaxTaps) return (int)hipErrorInvalidValue;
+  if ((int64_t)D * H * W > INT_MAX) return (int)hipErrorInvalidValue;
+  if (K <= 0 || n == 0) return 0;
+  return svr_joint_histogram_launch(vol, D, H, W, bank, transforms, slices, slices_mask, n, K, h, w, res_slice, i_lo, i_scale, j_map,
+                                    bins, hist, workspace, workspace_bytes, stream);
+}

@@ -447,6 +447,66 @@ _op("svr_similarity_bank(Tensor vol, Tensor psf_bank, Tensor psf_table, Tensor p
 
 
 # =====================================================================================================================
+# joint histograms of the slice-to-volume registration (csrc/svr_nmi.hip; the definition: nesvor_amd/nmi.py): what svr_similarity
+# sums into moments, binned - (n, K, B, B) int64, row = bin of the simulated value.  i_lo / i_scale: floats fp32 holds exactly
+# =====================================================================================================================
+def _svr_histogram(what, vol, psf_args, transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins):
+    _lib.require_device(vol, transforms, slices, j_map, dtype=torch.float32, name=f"{what} vol/transforms/slices/j_map")
+    sm = _mask(slices_mask)
+    if vol.ndim < 3 or transforms.ndim != 4 or tuple(transforms.shape[2:]) != (3, 4) or slices.ndim < 3:
+        raise RuntimeError(f"{what}: vol (..., D, H, W), transforms (n, K, 3, 4), slices (n, ..., h, w)")
+    n, K = int(transforms.shape[0]), int(transforms.shape[1])
+    h, w = int(slices.shape[-2]), int(slices.shape[-1])
+    if slices.numel() != n * h * w or (sm is not None and sm.numel() != n * h * w):
+        raise RuntimeError(f"{what}: slices / slices_mask must hold n x h x w elements")
+    if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
+        raise RuntimeError(f"{what}: one volume expected")
+    if tuple(j_map.shape) != (n, 2):
+        raise RuntimeError(f"{what}: j_map (n, 2) = ({n}, 2) expected, got {tuple(j_map.shape)}")
+    bins = int(bins)
+    if not 2 <= bins <= 64:
+        raise RuntimeError(f"{what}: 2 <= bins <= 64 expected, got {bins}")
+    psf = psf_args(n)
+    hist = torch.empty((n, K, bins, bins), dtype=torch.int64, device=vol.device)
+    lib = _lib.load()
+    nbytes = int(lib.nesvor_svr_joint_histogram_workspace_bytes(n, K, h, w, bins))  # (the bank twin's size does not differ)
+    workspace = _workspace(nbytes, vol.device)
+    with torch.cuda.device(vol.device):
+        err = getattr(lib, f"nesvor_{what}")(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), *psf, _lib.ptr(transforms), _lib.ptr(slices),
+                                             _lib.ptr(sm), n, K, h, w, float(res_slice), float(i_lo), float(i_scale), _lib.ptr(j_map),
+                                             bins, _lib.ptr(hist), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
+    _lib.check(err, what.replace("_", " "))
+    return hist
+
+
+def _svr_joint_histogram(vol, psf, transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins):
+    def psf_args(n):
+        _lib.require_device(psf, dtype=torch.float32, name="svr_joint_histogram psf")
+        if psf.ndim != 3:
+            raise RuntimeError("svr_joint_histogram: psf (d, h, w) expected")
+        return (_lib.ptr(psf), *(int(s) for s in psf.shape))
+
+    return _svr_histogram("svr_joint_histogram", vol, psf_args, transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins)
+
+
+def _svr_joint_histogram_bank(vol, psf_bank, psf_table, psf_id, transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins):
+    return _svr_histogram("svr_joint_histogram_bank", vol, lambda n: _bank("svr_joint_histogram_bank", psf_bank, psf_table, psf_id, n),
+                          transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins)
+
+
+def _fake_histogram(vol, tf, bins):
+    return vol.new_empty((tf.shape[0], tf.shape[1], bins, bins), dtype=torch.int64)
+
+
+_op("svr_joint_histogram(Tensor vol, Tensor psf, Tensor transforms, Tensor slices, Tensor? slices_mask, float res_slice, float i_lo, "
+    "float i_scale, Tensor j_map, int bins) -> Tensor", _svr_joint_histogram,
+    fake=lambda vol, psf, tf, s, sm, r, lo, sc, jm, bins: _fake_histogram(vol, tf, bins))
+_op("svr_joint_histogram_bank(Tensor vol, Tensor psf_bank, Tensor psf_table, Tensor psf_id, Tensor transforms, Tensor slices, "
+    "Tensor? slices_mask, float res_slice, float i_lo, float i_scale, Tensor j_map, int bins) -> Tensor", _svr_joint_histogram_bank,
+    fake=lambda vol, pb, pt, pi, tf, s, sm, r, lo, sc, jm, bins: _fake_histogram(vol, tf, bins))
+
+
+# =====================================================================================================================
 # grouped similarity sums (package registration, csrc/svr.hip): one correction per (group, pose), composed with every slice's
 # base pose in the kernel, sums per (group, pose) in CSR order.  The grouping arrives in HOST memory, is checked there and
 # uploaded: a bad index is a Python exception, never a device read, and no call reads the device back

@@ -41,6 +41,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from . import nmi as _nmi
 from .psf_bank import SAME_THICKNESS, PsfBank, bank_for
 from .slice_acquisition import bank_fused, slice_acquisition, slice_acquisition_bank
 from .transform import RigidTransform, mat_transform_points, mat_update_resolution
@@ -268,6 +269,7 @@ class _SliceLevel:
         self.volume, self.slices, self.mask, self.psf = volume, slices, mask, psf  # (D,H,W), (n,h,w), (n,h,w) bool, (d,h,w)
         self.res_slice, self.voxel = res_slice, voxel  # pixel size in voxels; voxel size in mm
         self.index: Optional[torch.Tensor] = None  # batch entry of the descent -> slice (the slices that take part in this level)
+        self.i_map, self.j_map = None, None  # nmi: the affine maps to bin coordinates, filled by the first evaluation
 
 
 class SVR(VVR):
@@ -285,10 +287,16 @@ class SVR(VVR):
     to ``res_s * 2^l``, the mask resampled and thresholded at 0.5; the PSF is that of a slice on the level's grid.  A slice
     with fewer than ``min_valid`` valid pixels at its pose when a level starts keeps its pose for that level (loss 0).
 
-    Two evaluation paths with one definition of the loss.  Fused (``torch.ops.nesvor.svr_similarity``, csrc/svr.hip): the 13
-    poses of a finite-difference gradient of all active slices in one call, the accept test a K = 1 call.  Composed: one
-    ``slice_acquisition`` per pose and fp64 torch sums - used for PSFs the kernel refuses (more than 1024 elements) and
-    forced with ``NESVOR_SVR=composed``."""
+    ``loss = {"name": "nmi", "bins": B}`` (2 <= B <= 64, default 32): normalised mutual information  1 - (H_I + H_J) / H_IJ  of a
+    joint histogram of (simulated, acquired) intensity per (slice, pose), for slices whose intensities are not linearly related to
+    the volume's (other contrast, other coil bias, saturation).  nesvor_amd/nmi.py states the definition; the simulated value is
+    binned on the range of the level's volume, the acquired value on the range of the slice's masked pixels at the level.
+
+    Two evaluation paths with one definition of the loss.  Fused (``torch.ops.nesvor.svr_similarity``, csrc/svr.hip; nmi:
+    ``svr_joint_histogram``, csrc/svr_nmi.hip): the 13 poses of a finite-difference gradient of all active slices in one call, the
+    accept test a K = 1 call.  Composed: one ``slice_acquisition`` per pose and fp64 torch sums (nmi: the torch integer ops of
+    ``nmi.joint_histogram``, bit-equal to the kernel) - used for PSFs the kernel refuses (more than 1024 elements) and forced with
+    ``NESVOR_SVR=composed``."""
 
     def __init__(self, num_levels: int, num_steps: int, step_size: float, max_iter: int, optimizer: Dict, loss: Dict,
                  min_valid: int = 32) -> None:
@@ -298,9 +306,12 @@ class SVR(VVR):
         if optimizer.get("name") != "gd":
             raise Exception("unknown optimizer")
         self.momentum = float(optimizer.get("momentum", 0))
-        if not isinstance(loss, dict) or loss.get("name") not in ("ncc", "mse") or not set(loss) <= {"name", "eps"}:
+        if not isinstance(loss, dict) or loss.get("name") not in ("ncc", "mse", "nmi"):
+            raise Exception("unknown loss")
+        if not set(loss) <= ({"name", "bins"} if loss["name"] == "nmi" else {"name", "eps"}):
             raise Exception("unknown loss")
         self._kind, self._eps = loss["name"], float(loss.get("eps", 1e-6))
+        self._bins = _nmi.check_bins(loss.get("bins", _nmi.DEFAULT_BINS), "loss bins") if self._kind == "nmi" else None
         self.min_valid = min_valid
         self.trans_first = True
 
@@ -340,6 +351,8 @@ class SVR(VVR):
         slices = lv.slices if ids is None else lv.slices[ids]
         mask = lv.mask if ids is None else lv.mask[ids]
         bank = isinstance(lv.psf, PsfBank)
+        if self._kind == "nmi":
+            return self._histograms_at(mats, lv, ids, self._fused_path(lv))
         if self._fused_path(lv):
             if bank:  # (the subset's ids on the device; members without a slice in it do no harm)
                 return torch.ops.nesvor.svr_similarity_bank(lv.volume, lv.psf.flat, lv.psf.table, lv.psf.ids if ids is None else
@@ -357,8 +370,49 @@ class SVR(VVR):
             out[:, k] = torch.stack([t.sum((1, 2)) for t in (valid, Ik, Ik * Ik, Ik * Jk, Jk, Jk * Jk)], -1)
         return out
 
+    # ---- nmi: the statistic is a joint histogram (nesvor_amd/nmi.py), (m,K,B,B) int64 in the place of the six sums ----
+    def _axis_maps(self, lv: _SliceLevel) -> Tuple[Tuple[float, float], torch.Tensor]:
+        """The level's affine maps to bin coordinates: (lo, scale) of the simulated value from the volume's range, and
+        ``j_map`` (n,2) fp32 of the acquired value from every slice's masked range (``GroupSVR._prepare`` pools it per group)."""
+        if lv.i_map is None:
+            lv.i_map = tuple(_nmi.axis_map(lv.volume.min(), lv.volume.max(), self._bins).tolist())
+        if lv.j_map is None:
+            lv.j_map = _nmi.axis_map(*_nmi.masked_range(lv.slices, lv.mask), self._bins).contiguous()
+        return lv.i_map, lv.j_map
+
+    def _histograms_at(self, mats: torch.Tensor, lv: _SliceLevel, ids: Optional[torch.Tensor], fused: bool) -> torch.Tensor:
+        """Joint histograms of slices ``ids`` (None: all) at mats (m,K,3,4) -> (m,K,B,B) int64; ``fused``: the kernel, else the same
+        definition with torch integer ops on the acquisition operator's output."""
+        m, K = mats.shape[:2]
+        i_map, j_map = self._axis_maps(lv)
+        slices = lv.slices if ids is None else lv.slices[ids]
+        mask = lv.mask if ids is None else lv.mask[ids]
+        j_map = j_map if ids is None else j_map[ids].contiguous()
+        bank = isinstance(lv.psf, PsfBank)
+        if fused:
+            if bank:
+                return torch.ops.nesvor.svr_joint_histogram_bank(lv.volume, lv.psf.flat, lv.psf.table, lv.psf.ids if ids is None else
+                                                                 lv.psf.ids[ids].contiguous(), mats, slices, mask, lv.res_slice, *i_map,
+                                                                 j_map, self._bins)
+            return torch.ops.nesvor.svr_joint_histogram(lv.volume, lv.psf, mats, slices, mask, lv.res_slice, *i_map, j_map, self._bins)
+        out = torch.empty((m, K, self._bins, self._bins), dtype=torch.int64, device=mats.device)
+        psf = lv.psf.subset(ids) if bank and ids is not None else lv.psf
+        acquire = slice_acquisition_bank if bank else slice_acquisition
+        for k in range(K):
+            sim, weight = acquire(mats[:, k], lv.volume[None, None], None, mask[:, None], psf, slices.shape[-2:], lv.res_slice, True,
+                                  False)
+            valid = mask & (weight[:, 0] > 0)
+            out[:, k] = _nmi.joint_histogram(sim[:, 0].flatten(1), slices.flatten(1), valid.flatten(1), i_map, j_map, self._bins)
+        return out
+
+    def _count_of(self, sums: torch.Tensor) -> torch.Tensor:
+        """The valid pixels behind the statistics of ``_sums`` (``min_valid`` is held against it)."""
+        return _nmi.valid_count(sums) if self._kind == "nmi" else sums[..., 0]
+
     def _loss_of(self, sums: torch.Tensor) -> torch.Tensor:
-        """(..., 6) moment sums -> loss; an entry without a valid pixel has loss 0."""
+        """(..., 6) moment sums (nmi: (..., B, B) histograms) -> loss; an entry without a valid pixel has loss 0."""
+        if self._kind == "nmi":
+            return _nmi.nmi_loss(sums).float()
         cnt = sums[..., 0]
         ok = cnt > 0
         sI, sII, sIJ, sJ, sJJ = ((sums[..., j] / torch.where(ok, cnt, torch.ones_like(cnt))) for j in range(1, 6))
@@ -406,7 +460,7 @@ class SVR(VVR):
         for level in range(self.num_levels - 1, -1, -1):
             self.current_level = level
             lv = self._level(level, slices, slices_mask, volume, params)
-            count = self._sums(cur[:, None], lv, None)[:, 0, 0]
+            count = self._count_of(self._sums(cur[:, None], lv, None)[:, 0])
             lv.index = torch.nonzero(count >= self.min_valid).flatten()
             loss = torch.zeros(n, dtype=theta.dtype, device=theta.device)
             if lv.index.numel() == 0:
@@ -516,7 +570,9 @@ class GroupSVR(SVR):
     level, (G,) each - the accept test keeps the end at or below the start.
 
     Two evaluation paths with one definition.  Fused (``torch.ops.nesvor.svr_similarity_groups``, csrc/svr.hip): the corrections
-    go to the kernel, which composes them with every slice's pose and adds a group's sums in CSR order.  Composed: the same
+    go to the kernel, which composes them with every slice's pose and adds a group's sums in CSR order (nmi: no grouped kernel -
+    the per-slice histograms of ``svr_joint_histogram`` at the matrices ``compose_mats`` gives, added per group in integers; every
+    slice of a group bins its acquired value on the group's pooled range, ``NESVOR_PACKAGES=composed`` takes the torch definition).  Composed: the same
     composition in float64 here (``compose_mats``), rounded to fp32, then ``SVR``'s per-slice sums (fused or composed themselves:
     ``NESVOR_SVR`` keeps its meaning) added per group in CSR order - taken for PSFs the kernel refuses and forced with
     ``NESVOR_PACKAGES=composed``."""
@@ -530,6 +586,15 @@ class GroupSVR(SVR):
         centroid = lv.centroid if gids is None else lv.centroid[gids]
         corr = centroid_corrections(x, centroid[:, None], lv.voxel).float().contiguous()
         m, K = corr.shape[:2]
+        if self._kind == "nmi":  # no grouped kernel: the per-slice histograms at the composed matrices, added per group in integers
+            out = torch.zeros((m, K, self._bins, self._bins), dtype=torch.int64, device=corr.device)
+            if listed.numel() == 0:
+                return out
+            sizes = (offsets[1:] - offsets[:-1]).long()
+            entry_group = torch.repeat_interleave(torch.arange(m), sizes).to(corr.device)
+            ids = listed.long().to(corr.device)
+            mats = compose_mats(corr[entry_group], lv.base[ids][:, None]).float().contiguous()  # (E,K,3,4)
+            return out.index_add_(0, entry_group, self._histograms_at(mats, lv, ids, self._packages_fused(lv)))
         if self._packages_fused(lv):
             if isinstance(lv.psf, PsfBank):
                 return torch.ops.nesvor.svr_similarity_groups_bank(lv.volume, lv.psf.flat, lv.psf.table, lv.psf.ids, corr, lv.base,
@@ -591,6 +656,17 @@ class GroupSVR(SVR):
         lv.base = mat_update_resolution(base_mm, 1, lv.voxel).contiguous()  # (n,3,4) fp32, the level's voxels
         lv.centroid = centroid_mm / lv.voxel
         lv.groups = groups
+        if self._kind == "nmi":  # every slice of a group bins J on the group's pooled range; a slice listed nowhere keeps its own
+            lo, hi = _nmi.masked_range(lv.slices, lv.mask)
+            offsets, listed = groups
+            if listed.numel() > 0:
+                G = offsets.numel() - 1
+                entry_group = torch.repeat_interleave(torch.arange(G), (offsets[1:] - offsets[:-1]).long()).to(lo.device)
+                ids = listed.long().to(lo.device)
+                g_lo = torch.full((G,), float("inf"), dtype=lo.dtype, device=lo.device).scatter_reduce_(0, entry_group, lo[ids], "amin")
+                g_hi = torch.full((G,), float("-inf"), dtype=hi.dtype, device=hi.device).scatter_reduce_(0, entry_group, hi[ids], "amax")
+                lo, hi = lo.index_copy(0, ids, g_lo[entry_group]), hi.index_copy(0, ids, g_hi[entry_group])
+            lv.j_map = _nmi.axis_map(lo, hi, self._bins).contiguous()
 
     @torch.no_grad()
     def evaluate(self, theta: torch.Tensor, groups, slices: torch.Tensor, slices_mask: torch.Tensor, volume: torch.Tensor,
@@ -617,7 +693,8 @@ class GroupSVR(SVR):
             self._prepare(lv, base_mm, centroid_mm, groups)
             sums = self._group_sums(cur[:, None], lv, None)[:, 0]
             start = self._loss_of(sums)
-            lv.index = torch.nonzero(sums[:, 0] >= self.min_valid).flatten()
+            enough = self._count_of(sums) >= self.min_valid
+            lv.index = torch.nonzero(enough).flatten()
             loss = torch.zeros(G, dtype=theta.dtype, device=theta.device)
             if lv.index.numel() > 0:
                 sub = cur[lv.index]
@@ -628,7 +705,7 @@ class GroupSVR(SVR):
                     step /= 2
                 cur[lv.index] = sub
                 loss[lv.index] = self._loss_of(self._group_sums(cur[:, None], lv, None))[lv.index, 0]
-            self.history.append((level, start, torch.where(sums[:, 0] >= self.min_valid, loss, start)))
+            self.history.append((level, start, torch.where(enough, loss, start)))
         self.corrections = cur
         # fold: every listed slice's pose becomes correction_g o pose, in float64 (mm), then back to the input's form
         offsets, listed = groups
@@ -796,7 +873,8 @@ def _cover_shape(poses: RigidTransform, mask: torch.Tensor, res_s: float, s_thic
 
 
 def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = None, n_outer: int = 3, template: int = 0,
-                    per_stack_thickness: bool = False, packages: Optional[Sequence[int]] = None, package_rounds: int = 2) -> List:
+                    per_stack_thickness: bool = False, packages: Optional[Sequence[int]] = None, package_rounds: int = 2,
+                    similarity: str = "ncc", nmi_bins: int = _nmi.DEFAULT_BINS) -> List:
     """``--registration svr``: stack registration (``register_stacks``, to the stack ``template``), then ``n_outer`` rounds of
     reconstruct a volume from all slices at their current poses  /  register every non-empty slice rigidly to it (``SVR``,
     global NCC); the per-slice poses are written back into the stacks.  ``res_r``: voxel size of the intermediate volume
@@ -806,7 +884,15 @@ def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = 
     ``packages`` (``--packages``; one count per stack, or one for all): between the stack registration and the slice rounds,
     ``package_rounds`` rounds of reconstruct a volume from all slices  /  register every interleaved package rigidly to it
     (``GroupSVR``).  Slice k of stack s belongs to package ``k mod P_s``, counted in file order before the empty slices are
-    dropped; ``P_s = 1`` registers the whole stack against the joint volume.  ``None``: no package stage, as before."""
+    dropped; ``P_s = 1`` registers the whole stack against the joint volume.  ``None``: no package stage, as before.
+
+    ``similarity`` (``--svr-similarity``): the metric of the package and the slice stage, ``"ncc"`` (global NCC, as before) or
+    ``"nmi"`` - normalised mutual information on a joint histogram of ``nmi_bins`` bins per axis (``--nmi-bins``; nesvor_amd/nmi.py),
+    for stacks whose intensities are not linearly related.  The stack registration in front keeps its NCC."""
+    if similarity not in ("ncc", "nmi"):
+        raise ValueError(f"similarity: 'ncc' or 'nmi' expected, got {similarity!r}")
+    loss_spec = {"name": "ncc"} if similarity == "ncc" else {"name": "nmi", "bins": _nmi.check_bins(nmi_bins, "nmi_bins")}
+    metric = similarity.upper()
     if packages is not None:  # (refusals before any work)
         package_groups([s.slices.shape[0] for s in dataset], packages)
     dataset = register_stacks(dataset, res_s, template, per_stack_thickness)
@@ -822,18 +908,18 @@ def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = 
         per_slice = [float(s.thickness) for s in dataset for _ in range(s.slices.shape[0])]
         s_thick = [per_slice[k] for k in keep.tolist()]
     theta = poses.axisangle()[keep].clone()
-    svr = SVR(num_levels=3, num_steps=4, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1}, loss={"name": "ncc"})
+    svr = SVR(num_levels=3, num_steps=4, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1}, loss=loss_spec)
     params = {"res_s": res_s, "s_thick": s_thick, "res_r": res_r}
     if packages is not None:
         groups = package_groups([s.slices.shape[0] for s in dataset], packages, keep.tolist())
         gsvr = GroupSVR(num_levels=3, num_steps=4, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1},
-                        loss={"name": "ncc"})
+                        loss=loss_spec)
         for it in range(package_rounds):
             current = RigidTransform(theta)
             shape = _cover_shape(current, mask, res_s, s_thick, res_r)
             volume = reconstruct_from_slices(mat_update_resolution(current.matrix(), 1, res_r), slices, res_s, s_thick, res_r, shape)
             theta, loss = gsvr(theta, groups, slices, mask, volume, params, True)
-            logging.debug("package registration round %d: volume %s, mean NCC %f", it, shape, -float(loss.mean()))
+            logging.debug("package registration round %d: volume %s, mean %s %f", it, shape, metric, -float(loss.mean()))
             if logging.getLogger().isEnabledFor(logging.DEBUG):
                 for g, c in enumerate(gsvr.corrections.tolist()):
                     logging.debug("  package %d: rotation (%.3f, %.3f, %.3f) deg, translation (%.3f, %.3f, %.3f) mm", g, *c)
@@ -842,7 +928,7 @@ def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = 
         shape = _cover_shape(current, mask, res_s, s_thick, res_r)
         volume = reconstruct_from_slices(mat_update_resolution(current.matrix(), 1, res_r), slices, res_s, s_thick, res_r, shape)
         theta, loss = svr(theta, slices, mask, volume, params, True)
-        logging.debug("slice registration round %d: volume %s, mean NCC %f", it, shape, -float(loss.mean()))
+        logging.debug("slice registration round %d: volume %s, mean %s %f", it, shape, metric, -float(loss.mean()))
     full = poses.axisangle().clone()
     full[keep] = theta
     start = 0

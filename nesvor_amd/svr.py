@@ -275,6 +275,7 @@ def svr_command(args: Namespace) -> Dict:
             logging.warning("Since <input-slices> is provided, <input-stacks>, <stack_masks> and <thicknesses> would be ignored.")
         cli.warn_template_ignored(args, "--input-slices")
         cli.warn_packages_ignored(args, "--input-slices")
+        cli.warn_similarity_ignored(args, "--input-slices")
         cli.warn_masking_ignored(args, "--input-slices")
         cli.warn_denoise_ignored(args, "--input-slices")
         loaded = load_slices(args.input_slices, args.device)
