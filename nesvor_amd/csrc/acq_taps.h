@@ -1,5 +1,6 @@
 // The PSF-tap core of the slice-acquisition operators: the kernels of slice_acq.hip (A, A^T and both backwards, linear and
-// interp_psf modes) and svr_similarity_kernel (svr.hip), which simulates A<float> under several poses per pixel.  Two kernels of
+// interp_psf modes) and the svr statistics (svr.hip, svr_nmi.hip), which simulate A<float> under several poses per pixel through
+// simulate_pixel, the one statement of that pixel outside slice_acq_fwd.  Two kernels of
 // slice_acq.hip keep their tap loops written out for speed: slice_acq_adjoint_gather (the parent's test: it indexes nothing by a
 // tap's position; under a non-finite pose A^T hands the NaN on into vol and vol_weight) and slice_acq_adjoint_bwd (this
 // header's order spelled out, its NaN rule in the hoisted form: pose_is_bounded).
@@ -20,6 +21,7 @@
 //     (reduce_pose_grad: wave_sum, then the four waves as (0 + 1) + (2 + 3)) in one order.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include "common.h"
 
 // (unnamed: every translation unit gets a copy of its own, as slice_sums.h's)
@@ -91,6 +93,35 @@ inline bool make_bank(const T* data, const int* table, int P, const int* ids, in
     if (e > max_elements) max_elements = e;
   }
   return true;
+}
+
+// The tap-list prologue of a workgroup that serves slice k: thread 0 compacts the slice's PSF into `taps` and publishes the count -
+// 0, with nothing indexed by k, for a workgroup that is not `live`.  Every thread calls; the caller places the barrier.
+template <typename T, typename PSF>
+__device__ __forceinline__ void workgroup_taps(const PSF& psfs, bool live, int k, Tap<T>* taps, int& n_taps) {
+  if (threadIdx.x == 0) {
+    int cnt = 0;
+    if (live) {
+      const PsfView<T> pk = psfs.at(k);
+      cnt = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
+    }
+    n_taps = cnt;
+  }
+}
+
+// The host's side of a kernel with an LDS tap list: its PSF source as the kernel argument, behind the checks every such entry point
+// makes - every PSF fits the list (kMaxTaps elements, ANY bank member) and the volume's voxel indices fit an int.  false: refused.
+// The two forms of an entry point differ in when they ask: the one-PSF form returns its no-op (nothing to do: 0) BEFORE it looks at
+// the PSF, the bank form checks the bank and the volume first and a bad bank is refused even where nothing would be launched.
+template <typename T> inline bool lds_one_psf(const T* psf, int d_p, int h_p, int w_p, int D, int H, int W, OnePsf<T>& out) {
+  if (d_p < 1 || h_p < 1 || w_p < 1 || (int64_t)d_p * h_p * w_p > kMaxTaps || (int64_t)D * H * W > INT_MAX) return false;
+  out = OnePsf<T>{psf, d_p, h_p, w_p};
+  return true;
+}
+template <typename T>
+inline bool lds_bank_psf(const T* data, const int* table, int P, const int* ids, int n, int D, int H, int W, BankPsf<T>& out) {
+  int64_t max_elements;
+  return make_bank(data, table, P, ids, n, out, max_elements) && max_elements <= kMaxTaps && (int64_t)D * H * W <= INT_MAX;
 }
 
 template <typename T> struct PixelGeom { T qx, qy, qz, xc, yc, zc; };
@@ -187,6 +218,23 @@ __device__ __forceinline__ void linear_tap(const T* __restrict__ vol, const uint
       wsum += pw;
     }
   }
+}
+
+// The pixel (ix, iy) of A<T> under pose t from an LDS tap list, linear mode, no volume mask: the value I = val / wsum and true iff
+// the PSF weight wsum > 0 (I untouched otherwise).  The functions, the order and the division are those of slice_acq_fwd<T, false,
+// true> (slice_acq.hip, which keeps its own statement: it carries the volume mask and the dense walk), so value and valid set are
+// that operator's bit for bit; every svr statistic takes its pixel from here.
+template <typename T>
+__device__ __forceinline__ bool simulate_pixel(const T* __restrict__ vol, int D, int H, int W, const T* t, int ix, int iy, int h, int w,
+                                               T res_slice, const Tap<T>* taps, int nt, T& I) {
+  const PixelGeom<T> g = pixel_geom(t, ix, iy, h, w, res_slice, D, H, W);
+  T val = 0, wsum = 0;
+  for_lds_taps(t, g, taps, nt, D, H, W, [&](T, T, T, T pv, T x, T y, T z) {
+    linear_tap(vol, (const uint8_t*)nullptr, trilinear_cell(x, y, z, H, W), pv, val, wsum);
+  });
+  if (!(wsum > 0)) return false;
+  I = val / wsum;
+  return true;
 }
 
 // Corner k = 0 .. 7 of a cell by bits (x lowest): its voxel index and per-axis weights; add_corner_gradient adds the corner's share

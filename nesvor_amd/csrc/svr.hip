@@ -8,9 +8,8 @@
 //   { count, sum I, sum I^2, sum I J, sum J, sum J^2 },   I = simulated, J = acquired,
 // from which NCC and MSE follow.
 //
-// A pixel's value under a pose comes from the functions slice_acq_fwd<float, false, true> calls (acq_taps.h: pixel_geom, the LDS
-// tap list, the inside test, linear_tap without a volume mask) and the same val / wsum, so value and valid set are that
-// operator's bit for bit.
+// A pixel's value under a pose is acq_taps.h's simulate_pixel: the functions slice_acq_fwd<float, false, true> calls and the same
+// val / wsum, so value and valid set are that operator's bit for bit.
 //
 // The sums are added in the reproducible order of slice_sums.h.  A workgroup serves all poses of its 256 pixels, so it parks
 // the wave sums per pose inside the pose loop and combines them after one barrier at the end, in that header's order.
@@ -19,6 +18,7 @@
 // pose) and a CSR grouping, composes the correction with each slice's base pose once per workgroup and runs the same pixel loop
 // (similarity_pixels); svr_groups_reduce_kernel adds a group's per-slice sums in CSR order.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "acq_taps.h"
 #include "slice_sums.h"
 #include "../../include/nesvor_hip.h"
@@ -51,13 +51,7 @@ __device__ __forceinline__ void similarity_pixels(const float* __restrict__ vol,
     float I = 0.f;
     bool valid = false;
     if (on) {  // (a wave without a masked-in pixel branches over its tap loops: its exec mask is empty)
-      const float* t = pose_of(k);  // wave-uniform
-      const PixelGeom<float> g = pixel_geom(t, ix, iy, h, w, res_slice, D, H, W);
-      float val = 0.f, wsum = 0.f;
-      for_lds_taps(t, g, taps, nt, D, H, W, [&](float, float, float, float pv, float x, float y, float z) {
-        linear_tap(vol, (const uint8_t*)nullptr, trilinear_cell(x, y, z, H, W), pv, val, wsum);
-      });
-      if (wsum > 0) { I = val / wsum; valid = true; }
+      valid = simulate_pixel(vol, D, H, W, pose_of(k) /* wave-uniform */, ix, iy, h, w, res_slice, taps, nt, I);
     }
     // this pose's six values leave the registers at once: wave sums, parked in LDS per (wave, pose)
     const float Jv = valid ? J : 0.f;
@@ -88,10 +82,7 @@ __global__ __launch_bounds__(256) void svr_similarity_kernel(const float* __rest
   __shared__ int n_taps;
   __shared__ float red[4][KT][kSums];
   const int in = blockIdx.x / wgs, wg = blockIdx.x - in * wgs;
-  if (threadIdx.x == 0) {
-    const PsfView<float> pk = psfs.at(in);
-    n_taps = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
-  }
+  workgroup_taps(psfs, true, in, taps, n_taps);
   __syncthreads();
   similarity_pixels<KT>(vol, D, H, W, taps, n_taps, red,
                         [&](int k) { return transforms + ((size_t)in * K + k0 + k) * 12; },  // the scalar path
@@ -138,14 +129,7 @@ __global__ __launch_bounds__(256) void svr_similarity_groups_kernel(const float*
   const int listed = group_slices[e];
   const bool live = listed >= 0 && listed < n;
   const int in = live ? listed : 0;
-  if (threadIdx.x == 0) {
-    int cnt = 0;
-    if (live) {
-      const PsfView<float> pk = psfs.at(in);
-      cnt = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
-    }
-    n_taps = cnt;
-  }
+  workgroup_taps(psfs, live, in, taps, n_taps);
   if (live && threadIdx.x < KT * 12) {
     const int k = threadIdx.x / 12, j = threadIdx.x - k * 12;
     const int g = group_of_entry(group_offsets, G, e);
@@ -182,6 +166,20 @@ extern "C" int64_t nesvor_svr_similarity_workspace_bytes(int n, int K, int h, in
 }
 
 namespace {
+// The K poses of a call in passes: 13 poses per pass (one finite-difference gradient), single poses otherwise.
+// pass(std::integral_constant<int, KT>, k0) launches poses k0 .. k0 + KT - 1.
+template <typename Pass> void for_pose_passes(int K, Pass pass) {
+  for (int k = 0; k < K;) {
+    if (K - k >= 13) {
+      pass(std::integral_constant<int, 13>{}, k);
+      k += 13;
+    } else {
+      pass(std::integral_constant<int, 1>{}, k);
+      k += 1;
+    }
+  }
+}
+
 // The launches of both entry points, behind their checks of the PSF source.
 template <typename PSF>
 int svr_similarity_launch(const float* vol, int D, int H, int W, const PSF& psfs, const float* transforms, const float* slices,
@@ -196,18 +194,10 @@ int svr_similarity_launch(const float* vol, int D, int H, int W, const PSF& psfs
   double* partial = (double*)workspace;
   const int64_t wgs = plan.wgs;
   const dim3 grid((unsigned)(wgs * n)), block(256);
-  int k = 0;
-  while (k < K) {  // 13 poses per pass (one finite-difference gradient), single poses otherwise
-    if (K - k >= 13) {
-      hipLaunchKernelGGL((svr_similarity_kernel<13, PSF>), grid, block, 0, st, vol, D, H, W, psfs, transforms, slices, slices_mask, K,
-                         k, h, w, (int)wgs, res_slice, partial);
-      k += 13;
-    } else {
-      hipLaunchKernelGGL((svr_similarity_kernel<1, PSF>), grid, block, 0, st, vol, D, H, W, psfs, transforms, slices, slices_mask, K,
-                         k, h, w, (int)wgs, res_slice, partial);
-      k += 1;
-    }
-  }
+  for_pose_passes(K, [&](auto kt, int k0) {
+    hipLaunchKernelGGL((svr_similarity_kernel<decltype(kt)::value, PSF>), grid, block, 0, st, vol, D, H, W, psfs, transforms, slices,
+                       slices_mask, K, k0, h, w, (int)wgs, res_slice, partial);
+  });
   plan.reduce(workspace, sums, st);
   return (int)hipGetLastError();
 }
@@ -218,9 +208,10 @@ extern "C" int nesvor_svr_similarity(const float* vol, int D, int H, int W, cons
                                      int h, int w, float res_slice, double* sums, void* workspace, size_t workspace_bytes,
                                      void* stream) {
   if (K <= 0 || n == 0) return 0;
-  if (d_p < 1 || h_p < 1 || w_p < 1 || (int64_t)d_p * h_p * w_p > kMaxTaps) return (int)hipErrorInvalidValue;
-  return svr_similarity_launch(vol, D, H, W, OnePsf<float>{psf, d_p, h_p, w_p}, transforms, slices, slices_mask, n, K, h, w, res_slice,
-                               sums, workspace, workspace_bytes, stream);
+  OnePsf<float> one;
+  if (!lds_one_psf(psf, d_p, h_p, w_p, D, H, W, one)) return (int)hipErrorInvalidValue;
+  return svr_similarity_launch(vol, D, H, W, one, transforms, slices, slices_mask, n, K, h, w, res_slice, sums, workspace,
+                               workspace_bytes, stream);
 }
 
 // The same sums with a PSF bank: slice i is simulated with PSF psf_id[i].  Refused if ANY member has more than kMaxTaps elements.
@@ -229,9 +220,7 @@ extern "C" int nesvor_svr_similarity_bank(const float* vol, int D, int H, int W,
                                           const uint8_t* slices_mask, int n, int K, int h, int w, float res_slice, double* sums,
                                           void* workspace, size_t workspace_bytes, void* stream) {
   BankPsf<float> bank;
-  int64_t max_elements;
-  if (!make_bank(psf_bank, psf_table, P, psf_id, n, bank, max_elements) || max_elements > kMaxTaps) return (int)hipErrorInvalidValue;
-  if ((int64_t)D * H * W > INT_MAX) return (int)hipErrorInvalidValue;
+  if (!lds_bank_psf(psf_bank, psf_table, P, psf_id, n, D, H, W, bank)) return (int)hipErrorInvalidValue;
   if (K <= 0 || n == 0) return 0;
   return svr_similarity_launch(vol, D, H, W, bank, transforms, slices, slices_mask, n, K, h, w, res_slice, sums, workspace,
                                workspace_bytes, stream);
@@ -239,8 +228,7 @@ extern "C" int nesvor_svr_similarity_bank(const float* vol, int D, int H, int W,
 
 // ---- grouped sums (package registration): the same pixels, poses composed in the kernel, sums per (group, pose) ----
 extern "C" int64_t nesvor_svr_similarity_groups_workspace_bytes(int E, int K, int h, int w) {
-  if (E < 1 || K < 1 || h < 1 || w < 1) return 0;
-  return slice_sums::Plan<kSums>{(int64_t)E * K, slice_sums::pixel_workgroups(h, w)}.workspace_bytes();
+  return nesvor_svr_similarity_workspace_bytes(E, K, h, w);  // (an entry in the place of a slice)
 }
 
 namespace {
@@ -262,18 +250,10 @@ int svr_similarity_groups_launch(const float* vol, int D, int H, int W, const PS
   double* partial = (double*)workspace;
   const int wgs = (int)plan.wgs;
   const dim3 grid((unsigned)(plan.wgs * E)), block(256);  // over the entries: a subset costs what it holds
-  int k = 0;
-  while (k < K) {  // 13 poses per pass (one finite-difference gradient), single poses otherwise: nesvor_svr_similarity's split
-    if (K - k >= 13) {
-      hipLaunchKernelGGL((svr_similarity_groups_kernel<13, PSF>), grid, block, 0, st, vol, D, H, W, psfs, base, corrections, group_offsets,
-                         G, group_slices, slices, slices_mask, n, K, k, h, w, wgs, res_slice, partial);
-      k += 13;
-    } else {
-      hipLaunchKernelGGL((svr_similarity_groups_kernel<1, PSF>), grid, block, 0, st, vol, D, H, W, psfs, base, corrections, group_offsets,
-                         G, group_slices, slices, slices_mask, n, K, k, h, w, wgs, res_slice, partial);
-      k += 1;
-    }
-  }
+  for_pose_passes(K, [&](auto kt, int k0) {
+    hipLaunchKernelGGL((svr_similarity_groups_kernel<decltype(kt)::value, PSF>), grid, block, 0, st, vol, D, H, W, psfs, base, corrections,
+                       group_offsets, G, group_slices, slices, slices_mask, n, K, k0, h, w, wgs, res_slice, partial);
+  });
   const int64_t total = (int64_t)G * K * kSums;
   hipLaunchKernelGGL(svr_groups_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)partial,
                      group_offsets, G, K, wgs, sums);
@@ -288,9 +268,10 @@ extern "C" int nesvor_svr_similarity_groups(const float* vol, int D, int H, int 
                                             void* workspace, size_t workspace_bytes, void* stream) {
   if (!grouping_accepted(group_offsets, group_slices, G, E)) return (int)hipErrorInvalidValue;
   if (K <= 0 || E == 0) return 0;
-  if (d_p < 1 || h_p < 1 || w_p < 1 || (int64_t)d_p * h_p * w_p > kMaxTaps) return (int)hipErrorInvalidValue;
-  return svr_similarity_groups_launch(vol, D, H, W, OnePsf<float>{psf, d_p, h_p, w_p}, base, corrections, group_offsets, group_slices, G,
-                                      E, slices, slices_mask, n, K, h, w, res_slice, sums, workspace, workspace_bytes, stream);
+  OnePsf<float> one;
+  if (!lds_one_psf(psf, d_p, h_p, w_p, D, H, W, one)) return (int)hipErrorInvalidValue;
+  return svr_similarity_groups_launch(vol, D, H, W, one, base, corrections, group_offsets, group_slices, G, E, slices, slices_mask, n, K,
+                                      h, w, res_slice, sums, workspace, workspace_bytes, stream);
 }
 
 extern "C" int nesvor_svr_similarity_groups_bank(const float* vol, int D, int H, int W, const float* psf_bank,
@@ -301,9 +282,7 @@ extern "C" int nesvor_svr_similarity_groups_bank(const float* vol, int D, int H,
                                                  void* stream) {
   if (!grouping_accepted(group_offsets, group_slices, G, E)) return (int)hipErrorInvalidValue;
   BankPsf<float> bank;
-  int64_t max_elements;
-  if (!make_bank(psf_bank, psf_table, P, psf_id, n, bank, max_elements) || max_elements > kMaxTaps) return (int)hipErrorInvalidValue;
-  if ((int64_t)D * H * W > INT_MAX) return (int)hipErrorInvalidValue;
+  if (!lds_bank_psf(psf_bank, psf_table, P, psf_id, n, D, H, W, bank)) return (int)hipErrorInvalidValue;
   if (K <= 0 || E == 0) return 0;
   return svr_similarity_groups_launch(vol, D, H, W, bank, base, corrections, group_offsets, group_slices, G, E, slices, slices_mask, n, K,
                                       h, w, res_slice, sums, workspace, workspace_bytes, stream);

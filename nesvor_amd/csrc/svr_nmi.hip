@@ -9,9 +9,8 @@
 // and its J weights to the cells (bI, bJ), 65536 units in all, zero products skipped.  Integer adds: the histogram does not depend
 // on the order of addition, so LDS atomics are reproducible here and no float atomic is used.
 //
-// A pixel's value under a pose comes from the functions slice_acq_fwd<float, false, true> and svr_similarity_kernel call (acq_taps.h:
-// pixel_geom, the LDS tap list, the inside test, linear_tap without a volume mask) and the same val / wsum, so I and the valid set
-// are that operator's bit for bit.
+// A pixel's value under a pose is acq_taps.h's simulate_pixel, as svr_similarity_kernel's: the functions slice_acq_fwd<float, false,
+// true> calls and the same val / wsum, so I and the valid set are that operator's bit for bit.
 //
 // Shape.  A slice's pixels are cut into segments; one workgroup serves one (slice, pose, segment): it keeps the histogram in LDS
 // (B B 32-bit cells, at most 16 KB, next to the 16 KB tap list), walks its pixels 256 at a time, adds with integer LDS atomics and
@@ -61,10 +60,7 @@ __global__ __launch_bounds__(256) void svr_joint_histogram_kernel(const float* _
   const int in = e / K;
   const int cells = B * B;
   for (int c = threadIdx.x; c < cells; c += 256) hist[c] = 0u;
-  if (threadIdx.x == 0) {
-    const PsfView<float> pk = psfs.at(in);
-    n_taps = compact_taps(pk.psf, pk.d, pk.h, pk.w, taps);
-  }
+  workgroup_taps(psfs, true, in, taps, n_taps);
   __syncthreads();
   const float* t = transforms + (size_t)e * 12;  // wave-uniform: the scalar path
   const float j_lo = j_map[2 * in], j_scale = j_map[2 * in + 1];
@@ -74,13 +70,9 @@ __global__ __launch_bounds__(256) void svr_joint_histogram_kernel(const float* _
   for (int pix = first + (int)threadIdx.x; pix < last; pix += 256) {
     const size_t idx = (size_t)in * h * w + pix;
     if (slices_mask != nullptr && !slices_mask[idx]) continue;
-    const PixelGeom<float> g = pixel_geom(t, pix % w, pix / w, h, w, res_slice, D, H, W);
-    float val = 0.f, wsum = 0.f;
-    for_lds_taps(t, g, taps, nt, D, H, W, [&](float, float, float, float pv, float x, float y, float z) {
-      linear_tap(vol, (const uint8_t*)nullptr, trilinear_cell(x, y, z, H, W), pv, val, wsum);
-    });
-    if (!(wsum > 0)) continue;
-    const AxisPlace a = axis_place(val / wsum, i_lo, i_scale, B), b = axis_place(slices[idx], j_lo, j_scale, B);
+    float I;
+    if (!simulate_pixel(vol, D, H, W, t, pix % w, pix / w, h, w, res_slice, taps, nt, I)) continue;
+    const AxisPlace a = axis_place(I, i_lo, i_scale, B), b = axis_place(slices[idx], j_lo, j_scale, B);
     const int c00 = a.b0 * B + b.b0;  // at most (B - 2) B + B - 2: the four cells stay below B B
     const uint32_t ai[2] = {(uint32_t)(256 - a.q), (uint32_t)a.q}, bj[2] = {(uint32_t)(256 - b.q), (uint32_t)b.q};
 #pragma unroll
@@ -153,9 +145,10 @@ extern "C" int nesvor_svr_joint_histogram(const float* vol, int D, int H, int W,
                                           int h, int w, float res_slice, float i_lo, float i_scale, const float* j_map, int bins,
                                           int64_t* hist, void* workspace, size_t workspace_bytes, void* stream) {
   if (K <= 0 || n == 0) return 0;
-  if (d_p < 1 || h_p < 1 || w_p < 1 || (int64_t)d_p * h_p * w_p > kMaxTaps) return (int)hipErrorInvalidValue;
-  return svr_joint_histogram_launch(vol, D, H, W, OnePsf<float>{psf, d_p, h_p, w_p}, transforms, slices, slices_mask, n, K, h, w,
-                                    res_slice, i_lo, i_scale, j_map, bins, hist, workspace, workspace_bytes, stream);
+  OnePsf<float> one;
+  if (!lds_one_psf(psf, d_p, h_p, w_p, D, H, W, one)) return (int)hipErrorInvalidValue;
+  return svr_joint_histogram_launch(vol, D, H, W, one, transforms, slices, slices_mask, n, K, h, w, res_slice, i_lo, i_scale, j_map,
+                                    bins, hist, workspace, workspace_bytes, stream);
 }
 
 // The same histograms with a PSF bank: slice i is simulated with PSF psf_id[i].  Refused if ANY member has more than kMaxTaps elements.
@@ -165,9 +158,7 @@ extern "C" int nesvor_svr_joint_histogram_bank(const float* vol, int D, int H, i
                                                float i_scale, const float* j_map, int bins, int64_t* hist, void* workspace,
                                                size_t workspace_bytes, void* stream) {
   BankPsf<float> bank;
-  int64_t max_elements;
-  if (!make_bank(psf_bank, psf_table, P, psf_id, n, bank, max_elements) || max_elements > kMaxTaps) return (int)hipErrorInvalidValue;
-  if ((int64_t)D * H * W > INT_MAX) return (int)hipErrorInvalidValue;
+  if (!lds_bank_psf(psf_bank, psf_table, P, psf_id, n, D, H, W, bank)) return (int)hipErrorInvalidValue;
   if (K <= 0 || n == 0) return 0;
   return svr_joint_histogram_launch(vol, D, H, W, bank, transforms, slices, slices_mask, n, K, h, w, res_slice, i_lo, i_scale, j_map,
                                     bins, hist, workspace, workspace_bytes, stream);

@@ -61,11 +61,12 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
 
 
-def _launch(name: str, device, sizes, *args) -> None:
-    """``nesvor_<name>(*args, workspace, nbytes, stream)`` on ``device`` with the scratch ``nesvor_<name>_workspace_bytes(*sizes)``
-    asks for.  A size of 0 (a shape the library refuses) still reaches the library: the refusal is its own."""
+def _launch(name: str, device, sizes, *args, query: Optional[str] = None) -> None:
+    """``nesvor_<name>(*args, workspace, nbytes, stream)`` on ``device`` with the scratch ``nesvor_<query>_workspace_bytes(*sizes)``
+    asks for (``query``: ``name`` unless given - a ``_bank`` twin has no size query of its own and names its sibling's).  A size
+    of 0 (a shape the library refuses) still reaches the library: the refusal is its own."""
     lib = _lib.load()
-    nbytes = int(getattr(lib, f"nesvor_{name}_workspace_bytes")(*sizes))
+    nbytes = int(getattr(lib, f"nesvor_{query or name}_workspace_bytes")(*sizes))
     workspace = _workspace(nbytes, device)
     with torch.cuda.device(device):
         err = getattr(lib, f"nesvor_{name}")(*args, _lib.ptr(workspace), nbytes, _lib.stream_ptr())
@@ -338,22 +339,51 @@ _op("slice_acq_adjoint_forward(Tensor transforms, Tensor psf, Tensor slices, Ten
 SVR_MAX_PSF_ELEMENTS = 1024  # larger PSFs are refused by the kernel (its LDS tap list); compose from slice_acq_forward
 
 
-def _svr_similarity(vol, psf, transforms, slices, slices_mask, res_slice):
-    _lib.require_device(vol, psf, transforms, slices, dtype=torch.float32, name="svr_similarity vol/psf/transforms/slices")
+def _svr_stack(what, ok, expected, vol, slices, slices_mask, n):
+    """What every svr statistic checks about the inputs they share: the shapes (``ok``: those of the op's own inputs, named in
+    ``expected``), vol (..., D, H, W) holding one volume, slices and the mask holding n x h x w elements
+    -> (mask or None, h, w, the volume's arguments (pointer, D, H, W))."""
     sm = _mask(slices_mask)
-    if vol.ndim < 3 or psf.ndim != 3 or transforms.ndim != 4 or tuple(transforms.shape[2:]) != (3, 4) or slices.ndim < 3:
-        raise RuntimeError("svr_similarity: vol (..., D, H, W), psf (d, h, w), transforms (n, K, 3, 4), slices (n, ..., h, w)")
-    n, K = int(transforms.shape[0]), int(transforms.shape[1])
+    if not ok or vol.ndim < 3 or slices.ndim < 3:
+        raise RuntimeError(f"{what}: vol (..., D, H, W), {expected}, slices (n, ..., h, w)")
     h, w = int(slices.shape[-2]), int(slices.shape[-1])
     if slices.numel() != n * h * w or (sm is not None and sm.numel() != n * h * w):
-        raise RuntimeError("svr_similarity: slices / slices_mask must hold n x h x w elements")
-    if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
-        raise RuntimeError("svr_similarity: one volume expected")
+        raise RuntimeError(f"{what}: slices / slices_mask must hold n x h x w elements")
+    D, H, W = (int(s) for s in vol.shape[-3:])
+    if vol.numel() != D * H * W:
+        raise RuntimeError(f"{what}: one volume expected")
+    return sm, h, w, (_lib.ptr(vol), D, H, W)
+
+
+def _svr_poses(what, vol, transforms, slices, slices_mask):
+    """The inputs of the statistics per (slice, pose): ``_svr_stack`` with transforms (n, K, 3, 4) -> (n, K, mask or None, h, w,
+    the volume's arguments)."""
+    ok = transforms.ndim == 4 and tuple(transforms.shape[2:]) == (3, 4)
+    n, K = (int(transforms.shape[0]), int(transforms.shape[1])) if ok else (-1, -1)
+    return (n, K, *_svr_stack(what, ok, "transforms (n, K, 3, 4)", vol, slices, slices_mask, n))
+
+
+def _one_psf(what, psf):
+    """One PSF for every slice, as the entry points of the family take it: (pointer, d_p, h_p, w_p)."""
+    _lib.require_device(psf, dtype=torch.float32, name=f"{what} psf")
+    if psf.ndim != 3:
+        raise RuntimeError(f"{what}: psf (d, h, w) expected")
+    return (_lib.ptr(psf), *(int(s) for s in psf.shape))
+
+
+def _svr_sums(what, vol, psf_args, transforms, slices, slices_mask, res_slice):
+    """``psf_args(n)``: the entry point's PSF arguments (``_one_psf``, or ``_bank`` for a ``_bank`` twin) - here and below."""
+    _lib.require_device(vol, transforms, slices, dtype=torch.float32, name=f"{what} vol/transforms/slices")
+    n, K, sm, h, w, volume = _svr_poses(what, vol, transforms, slices, slices_mask)
+    psf = psf_args(n)
     sums = torch.empty((n, K, 6), dtype=torch.float64, device=vol.device)
-    _launch("svr_similarity", vol.device, (n, K, h, w), _lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), _lib.ptr(psf),
-            *(int(s) for s in psf.shape), _lib.ptr(transforms), _lib.ptr(slices), _lib.ptr(sm), n, K, h, w, float(res_slice),
-            _lib.ptr(sums))
+    _launch(what, vol.device, (n, K, h, w), *volume, *psf, _lib.ptr(transforms), _lib.ptr(slices), _lib.ptr(sm), n, K, h, w,
+            float(res_slice), _lib.ptr(sums), query="svr_similarity")
     return sums
+
+
+def _svr_similarity(vol, psf, transforms, slices, slices_mask, res_slice):
+    return _svr_sums("svr_similarity", vol, lambda n: _one_psf("svr_similarity", psf), transforms, slices, slices_mask, res_slice)
 
 
 _op("svr_similarity(Tensor vol, Tensor psf, Tensor transforms, Tensor slices, Tensor? slices_mask, float res_slice) -> Tensor",
@@ -411,27 +441,8 @@ def _sa_adjoint_forward_bank(transforms, psf_bank, psf_table, psf_id, slices, sl
 
 
 def _svr_similarity_bank(vol, psf_bank, psf_table, psf_id, transforms, slices, slices_mask, res_slice):
-    _lib.require_device(vol, transforms, slices, dtype=torch.float32, name="svr_similarity_bank vol/transforms/slices")
-    sm = _mask(slices_mask)
-    if vol.ndim < 3 or transforms.ndim != 4 or tuple(transforms.shape[2:]) != (3, 4) or slices.ndim < 3:
-        raise RuntimeError("svr_similarity_bank: vol (..., D, H, W), transforms (n, K, 3, 4), slices (n, ..., h, w)")
-    n, K = int(transforms.shape[0]), int(transforms.shape[1])
-    h, w = int(slices.shape[-2]), int(slices.shape[-1])
-    if slices.numel() != n * h * w or (sm is not None and sm.numel() != n * h * w):
-        raise RuntimeError("svr_similarity_bank: slices / slices_mask must hold n x h x w elements")
-    if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
-        raise RuntimeError("svr_similarity_bank: one volume expected")
-    bank = _bank("svr_similarity_bank", psf_bank, psf_table, psf_id, n)
-    sums = torch.empty((n, K, 6), dtype=torch.float64, device=vol.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_svr_similarity_workspace_bytes(n, K, h, w))  # (the one-PSF twin's: the size does not differ)
-    workspace = _workspace(nbytes, vol.device)
-    with torch.cuda.device(vol.device):
-        err = lib.nesvor_svr_similarity_bank(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), *bank, _lib.ptr(transforms),
-                                             _lib.ptr(slices), _lib.ptr(sm), n, K, h, w, float(res_slice), _lib.ptr(sums),
-                                             _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, "svr similarity bank")
-    return sums
+    return _svr_sums("svr_similarity_bank", vol, lambda n: _bank("svr_similarity_bank", psf_bank, psf_table, psf_id, n), transforms,
+                     slices, slices_mask, res_slice)
 
 
 _op("slice_acq_forward_bank(Tensor transforms, Tensor vol, Tensor vol_mask, Tensor slices_mask, Tensor psf_bank, Tensor psf_table, "
@@ -452,15 +463,7 @@ _op("svr_similarity_bank(Tensor vol, Tensor psf_bank, Tensor psf_table, Tensor p
 # =====================================================================================================================
 def _svr_histogram(what, vol, psf_args, transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins):
     _lib.require_device(vol, transforms, slices, j_map, dtype=torch.float32, name=f"{what} vol/transforms/slices/j_map")
-    sm = _mask(slices_mask)
-    if vol.ndim < 3 or transforms.ndim != 4 or tuple(transforms.shape[2:]) != (3, 4) or slices.ndim < 3:
-        raise RuntimeError(f"{what}: vol (..., D, H, W), transforms (n, K, 3, 4), slices (n, ..., h, w)")
-    n, K = int(transforms.shape[0]), int(transforms.shape[1])
-    h, w = int(slices.shape[-2]), int(slices.shape[-1])
-    if slices.numel() != n * h * w or (sm is not None and sm.numel() != n * h * w):
-        raise RuntimeError(f"{what}: slices / slices_mask must hold n x h x w elements")
-    if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
-        raise RuntimeError(f"{what}: one volume expected")
+    n, K, sm, h, w, volume = _svr_poses(what, vol, transforms, slices, slices_mask)
     if tuple(j_map.shape) != (n, 2):
         raise RuntimeError(f"{what}: j_map (n, 2) = ({n}, 2) expected, got {tuple(j_map.shape)}")
     bins = int(bins)
@@ -468,25 +471,14 @@ def _svr_histogram(what, vol, psf_args, transforms, slices, slices_mask, res_sli
         raise RuntimeError(f"{what}: 2 <= bins <= 64 expected, got {bins}")
     psf = psf_args(n)
     hist = torch.empty((n, K, bins, bins), dtype=torch.int64, device=vol.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_svr_joint_histogram_workspace_bytes(n, K, h, w, bins))  # (the bank twin's size does not differ)
-    workspace = _workspace(nbytes, vol.device)
-    with torch.cuda.device(vol.device):
-        err = getattr(lib, f"nesvor_{what}")(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), *psf, _lib.ptr(transforms), _lib.ptr(slices),
-                                             _lib.ptr(sm), n, K, h, w, float(res_slice), float(i_lo), float(i_scale), _lib.ptr(j_map),
-                                             bins, _lib.ptr(hist), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, what.replace("_", " "))
+    _launch(what, vol.device, (n, K, h, w, bins), *volume, *psf, _lib.ptr(transforms), _lib.ptr(slices), _lib.ptr(sm), n, K, h, w,
+            float(res_slice), float(i_lo), float(i_scale), _lib.ptr(j_map), bins, _lib.ptr(hist), query="svr_joint_histogram")
     return hist
 
 
 def _svr_joint_histogram(vol, psf, transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins):
-    def psf_args(n):
-        _lib.require_device(psf, dtype=torch.float32, name="svr_joint_histogram psf")
-        if psf.ndim != 3:
-            raise RuntimeError("svr_joint_histogram: psf (d, h, w) expected")
-        return (_lib.ptr(psf), *(int(s) for s in psf.shape))
-
-    return _svr_histogram("svr_joint_histogram", vol, psf_args, transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins)
+    return _svr_histogram("svr_joint_histogram", vol, lambda n: _one_psf("svr_joint_histogram", psf), transforms, slices, slices_mask,
+                          res_slice, i_lo, i_scale, j_map, bins)
 
 
 def _svr_joint_histogram_bank(vol, psf_bank, psf_table, psf_id, transforms, slices, slices_mask, res_slice, i_lo, i_scale, j_map, bins):
@@ -533,42 +525,23 @@ def _svr_groups(what, vol, psf_args, corrections, base, group_offsets, group_sli
     n = int(base.shape[0]) if base.ndim == 3 else -1
     offsets, listed, G, E = check_grouping(what, group_offsets, group_slices, n)  # first: nothing is launched on a bad grouping
     _lib.require_device(vol, corrections, base, slices, dtype=torch.float32, name=f"{what} vol/corrections/base/slices")
-    sm = _mask(slices_mask)
-    if (vol.ndim < 3 or corrections.ndim != 4 or tuple(corrections.shape[2:]) != (3, 4) or base.ndim != 3
-            or tuple(base.shape[1:]) != (3, 4) or slices.ndim < 3 or int(corrections.shape[0]) != G):
-        raise RuntimeError(f"{what}: vol (..., D, H, W), corrections (G, K, 3, 4), base (n, 3, 4), slices (n, ..., h, w), "
-                           "group_offsets (G + 1)")
+    ok = (corrections.ndim == 4 and tuple(corrections.shape[2:]) == (3, 4) and base.ndim == 3 and tuple(base.shape[1:]) == (3, 4)
+          and int(corrections.shape[0]) == G)
+    sm, h, w, volume = _svr_stack(what, ok, "corrections (G, K, 3, 4), base (n, 3, 4), group_offsets (G + 1)", vol, slices, slices_mask, n)
     K = int(corrections.shape[1])
-    h, w = int(slices.shape[-2]), int(slices.shape[-1])
-    if slices.numel() != n * h * w or (sm is not None and sm.numel() != n * h * w):
-        raise RuntimeError(f"{what}: slices / slices_mask must hold n x h x w elements")
-    if vol.numel() != int(vol.shape[-3]) * int(vol.shape[-2]) * int(vol.shape[-1]):
-        raise RuntimeError(f"{what}: one volume expected")
     psf = psf_args(n)
     if E == 0 or K == 0:  # (the library returns without a launch and without writing)
         return torch.zeros((G, K, 6), dtype=torch.float64, device=vol.device)
     sums = torch.empty((G, K, 6), dtype=torch.float64, device=vol.device)
     offsets, listed = offsets.to(vol.device), listed.to(vol.device)
-    lib = _lib.load()
-    nbytes = int(lib.nesvor_svr_similarity_groups_workspace_bytes(E, K, h, w))
-    workspace = _workspace(nbytes, vol.device)
-    with torch.cuda.device(vol.device):
-        err = getattr(lib, f"nesvor_{what}")(_lib.ptr(vol), *(int(s) for s in vol.shape[-3:]), *psf, _lib.ptr(base), _lib.ptr(corrections),
-                                             _lib.ptr(offsets), _lib.ptr(listed), G, E, _lib.ptr(slices), _lib.ptr(sm), n, K, h, w,
-                                             float(res_slice), _lib.ptr(sums), _lib.ptr(workspace), nbytes, _lib.stream_ptr())
-    _lib.check(err, what.replace("_", " "))
+    _launch(what, vol.device, (E, K, h, w), *volume, *psf, _lib.ptr(base), _lib.ptr(corrections), _lib.ptr(offsets), _lib.ptr(listed),
+            G, E, _lib.ptr(slices), _lib.ptr(sm), n, K, h, w, float(res_slice), _lib.ptr(sums), query="svr_similarity_groups")
     return sums
 
 
 def _svr_similarity_groups(vol, psf, corrections, base, group_offsets, group_slices, slices, slices_mask, res_slice):
-    def psf_args(n):
-        _lib.require_device(psf, dtype=torch.float32, name="svr_similarity_groups psf")
-        if psf.ndim != 3:
-            raise RuntimeError("svr_similarity_groups: psf (d, h, w) expected")
-        return _lib.ptr(psf), *(int(s) for s in psf.shape)
-
-    return _svr_groups("svr_similarity_groups", vol, psf_args, corrections, base, group_offsets, group_slices, slices, slices_mask,
-                       res_slice)
+    return _svr_groups("svr_similarity_groups", vol, lambda n: _one_psf("svr_similarity_groups", psf), corrections, base, group_offsets,
+                       group_slices, slices, slices_mask, res_slice)
 
 
 def _svr_similarity_groups_bank(vol, psf_bank, psf_table, psf_id, corrections, base, group_offsets, group_slices, slices,

@@ -64,6 +64,14 @@ class PsfBank:
             if idx:
                 yield g, p, torch.tensor(idx, dtype=torch.int64, device=self.device)
 
+    def op_args(self, idx=None):
+        """``(psf_bank, psf_table, psf_id)`` as the ``_bank`` ops take them, for all slices or for ``slices[idx]`` (an index tensor
+        or sequence): the subset's ids, int32 and contiguous on the bank's device.  The members stay as they are - one without a
+        slice in the subset does no harm (``subset`` drops them, at the price of a new bank)."""
+        if idx is None:
+            return self.flat, self.table, self.ids
+        return self.flat, self.table, self.ids[torch.as_tensor(idx, dtype=torch.int64, device=self.device)].contiguous()
+
     def subset(self, idx) -> "PsfBank":
         """The bank of ``slices[idx]``: ids remapped, members no slice uses dropped (order of first appearance kept)."""
         idx = [int(i) for i in (idx.tolist() if torch.is_tensor(idx) else idx)]

@@ -272,6 +272,38 @@ class _SliceLevel:
         self.i_map, self.j_map = None, None  # nmi: the affine maps to bin coordinates, filled by the first evaluation
 
 
+def _psf_op(name: str, psf, ids: Optional[torch.Tensor] = None):
+    """The fused op of a statistic and what it takes in the place of the PSF: ``torch.ops.nesvor.<name>`` and ``(psf,)`` for a plain
+    PSF, the ``_bank`` twin and the bank's ``op_args(ids)`` (``ids``: the slices of the call, None for all) for a ``PsfBank``."""
+    if isinstance(psf, PsfBank):
+        return getattr(torch.ops.nesvor, name + "_bank"), psf.op_args(ids)
+    return getattr(torch.ops.nesvor, name), (psf,)
+
+
+def _composed_pixels(mats: torch.Tensor, lv: _SliceLevel, ids: Optional[torch.Tensor]):
+    """The composed path's pixels: for every pose k of mats (m,K,3,4), (simulated (m,h,w), valid (m,h,w) bool) of slices ``ids``
+    (None: all) from the acquisition operator - valid: mask set and PSF weight > 0, the fused kernels' valid set."""
+    mask = lv.mask if ids is None else lv.mask[ids]
+    bank = isinstance(lv.psf, PsfBank)
+    psf = lv.psf.subset(ids) if bank and ids is not None else lv.psf
+    acquire = slice_acquisition_bank if bank else slice_acquisition
+    for k in range(mats.shape[1]):
+        sim, weight = acquire(mats[:, k], lv.volume[None, None], None, mask[:, None], psf, mask.shape[-2:], lv.res_slice, True, False)
+        yield sim[:, 0], mask & (weight[:, 0] > 0)
+
+
+def _stencil_gradient(cur: torch.Tensor, step: float, losses: Callable) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One finite-difference gradient at cur (m,6): ``losses`` maps the 13-pose stencil (m,13,6) - row 0 the pose, rows 1 + 2 j and
+    2 + 2 j the pose with +step and -step on axis j - to (m,13) -> (the loss at the pose (m,), the central differences (m,6), not
+    divided by the step)."""
+    e = torch.zeros((13, 6), dtype=cur.dtype, device=cur.device)
+    j = torch.arange(6, device=cur.device)
+    e[1 + 2 * j, j] = step
+    e[2 + 2 * j, j] = -step
+    l = losses(cur[:, None] + e[None])
+    return l[:, 0], l[:, 1::2] - l[:, 2::2]
+
+
 class SVR(VVR):
     """``SVR(num_levels, num_steps, step_size, max_iter, optimizer, loss, min_valid=32)`` then
     ``theta_out, loss = svr(theta, slices, slices_mask, volume, params, trans_first)``: every slice registered rigidly to
@@ -347,26 +379,17 @@ class SVR(VVR):
 
     def _sums_at(self, mats: torch.Tensor, lv: _SliceLevel, ids: Optional[torch.Tensor]) -> torch.Tensor:
         """The same sums at given matrices: mats (m,K,3,4) fp32 in the level's voxels, row j the poses of slice ``ids[j]``."""
-        m, K = mats.shape[:2]
-        slices = lv.slices if ids is None else lv.slices[ids]
-        mask = lv.mask if ids is None else lv.mask[ids]
-        bank = isinstance(lv.psf, PsfBank)
         if self._kind == "nmi":
             return self._histograms_at(mats, lv, ids, self._fused_path(lv))
+        slices = lv.slices if ids is None else lv.slices[ids]
         if self._fused_path(lv):
-            if bank:  # (the subset's ids on the device; members without a slice in it do no harm)
-                return torch.ops.nesvor.svr_similarity_bank(lv.volume, lv.psf.flat, lv.psf.table, lv.psf.ids if ids is None else
-                                                            lv.psf.ids[ids].contiguous(), mats, slices, mask, lv.res_slice)
-            return torch.ops.nesvor.svr_similarity(lv.volume, lv.psf, mats, slices, mask, lv.res_slice)
-        out = torch.empty((m, K, 6), dtype=torch.float64, device=mats.device)
+            op, psf = _psf_op("svr_similarity", lv.psf, ids)
+            return op(lv.volume, *psf, mats, slices, lv.mask if ids is None else lv.mask[ids], lv.res_slice)
+        out = torch.empty((*mats.shape[:2], 6), dtype=torch.float64, device=mats.device)
         J = slices.double()
-        psf = lv.psf.subset(ids) if bank and ids is not None else lv.psf
-        acquire = slice_acquisition_bank if bank else slice_acquisition
-        for k in range(K):
-            sim, weight = acquire(mats[:, k], lv.volume[None, None], None, mask[:, None], psf, slices.shape[-2:],
-                                  lv.res_slice, True, False)
-            valid = (mask & (weight[:, 0] > 0)).double()
-            Ik, Jk = sim[:, 0].double() * valid, J * valid
+        for k, (sim, valid) in enumerate(_composed_pixels(mats, lv, ids)):
+            valid = valid.double()
+            Ik, Jk = sim.double() * valid, J * valid
             out[:, k] = torch.stack([t.sum((1, 2)) for t in (valid, Ik, Ik * Ik, Ik * Jk, Jk, Jk * Jk)], -1)
         return out
 
@@ -383,26 +406,15 @@ class SVR(VVR):
     def _histograms_at(self, mats: torch.Tensor, lv: _SliceLevel, ids: Optional[torch.Tensor], fused: bool) -> torch.Tensor:
         """Joint histograms of slices ``ids`` (None: all) at mats (m,K,3,4) -> (m,K,B,B) int64; ``fused``: the kernel, else the same
         definition with torch integer ops on the acquisition operator's output."""
-        m, K = mats.shape[:2]
         i_map, j_map = self._axis_maps(lv)
         slices = lv.slices if ids is None else lv.slices[ids]
-        mask = lv.mask if ids is None else lv.mask[ids]
         j_map = j_map if ids is None else j_map[ids].contiguous()
-        bank = isinstance(lv.psf, PsfBank)
         if fused:
-            if bank:
-                return torch.ops.nesvor.svr_joint_histogram_bank(lv.volume, lv.psf.flat, lv.psf.table, lv.psf.ids if ids is None else
-                                                                 lv.psf.ids[ids].contiguous(), mats, slices, mask, lv.res_slice, *i_map,
-                                                                 j_map, self._bins)
-            return torch.ops.nesvor.svr_joint_histogram(lv.volume, lv.psf, mats, slices, mask, lv.res_slice, *i_map, j_map, self._bins)
-        out = torch.empty((m, K, self._bins, self._bins), dtype=torch.int64, device=mats.device)
-        psf = lv.psf.subset(ids) if bank and ids is not None else lv.psf
-        acquire = slice_acquisition_bank if bank else slice_acquisition
-        for k in range(K):
-            sim, weight = acquire(mats[:, k], lv.volume[None, None], None, mask[:, None], psf, slices.shape[-2:], lv.res_slice, True,
-                                  False)
-            valid = mask & (weight[:, 0] > 0)
-            out[:, k] = _nmi.joint_histogram(sim[:, 0].flatten(1), slices.flatten(1), valid.flatten(1), i_map, j_map, self._bins)
+            op, psf = _psf_op("svr_joint_histogram", lv.psf, ids)
+            return op(lv.volume, *psf, mats, slices, lv.mask if ids is None else lv.mask[ids], lv.res_slice, *i_map, j_map, self._bins)
+        out = torch.empty((*mats.shape[:2], self._bins, self._bins), dtype=torch.int64, device=mats.device)
+        for k, (sim, valid) in enumerate(_composed_pixels(mats, lv, ids)):
+            out[:, k] = _nmi.joint_histogram(sim.flatten(1), slices.flatten(1), valid.flatten(1), i_map, j_map, self._bins)
         return out
 
     def _count_of(self, sums: torch.Tensor) -> torch.Tensor:
@@ -433,12 +445,7 @@ class SVR(VVR):
         return self._loss_of(self._sums(theta[:, None], lv, self._ids(idx, lv)))[:, 0]
 
     def _gradient_at(self, idx: torch.Tensor, cur: torch.Tensor, lv: _SliceLevel, step: float) -> Tuple[torch.Tensor, torch.Tensor]:
-        e = torch.zeros((13, 6), dtype=cur.dtype, device=cur.device)  # the pose and its 12 perturbations
-        j = torch.arange(6, device=cur.device)
-        e[1 + 2 * j, j] = step
-        e[2 + 2 * j, j] = -step
-        l = self._loss_of(self._sums(cur[:, None] + e[None], lv, self._ids(idx, lv)))
-        return l[:, 0], l[:, 1::2] - l[:, 2::2]
+        return _stencil_gradient(cur, step, lambda thetas: self._loss_of(self._sums(thetas, lv, self._ids(idx, lv))))
 
     @torch.no_grad()
     def evaluate(self, theta: torch.Tensor, slices: torch.Tensor, slices_mask: torch.Tensor, volume: torch.Tensor,
@@ -586,28 +593,20 @@ class GroupSVR(SVR):
         centroid = lv.centroid if gids is None else lv.centroid[gids]
         corr = centroid_corrections(x, centroid[:, None], lv.voxel).float().contiguous()
         m, K = corr.shape[:2]
-        if self._kind == "nmi":  # no grouped kernel: the per-slice histograms at the composed matrices, added per group in integers
-            out = torch.zeros((m, K, self._bins, self._bins), dtype=torch.int64, device=corr.device)
-            if listed.numel() == 0:
-                return out
-            sizes = (offsets[1:] - offsets[:-1]).long()
-            entry_group = torch.repeat_interleave(torch.arange(m), sizes).to(corr.device)
-            ids = listed.long().to(corr.device)
-            mats = compose_mats(corr[entry_group], lv.base[ids][:, None]).float().contiguous()  # (E,K,3,4)
-            return out.index_add_(0, entry_group, self._histograms_at(mats, lv, ids, self._packages_fused(lv)))
-        if self._packages_fused(lv):
-            if isinstance(lv.psf, PsfBank):
-                return torch.ops.nesvor.svr_similarity_groups_bank(lv.volume, lv.psf.flat, lv.psf.table, lv.psf.ids, corr, lv.base,
-                                                                   offsets, listed, lv.slices, lv.mask, lv.res_slice)
-            return torch.ops.nesvor.svr_similarity_groups(lv.volume, lv.psf, corr, lv.base, offsets, listed, lv.slices, lv.mask,
-                                                          lv.res_slice)
-        out = torch.zeros((m, K, 6), dtype=torch.float64, device=corr.device)
+        nmi = self._kind == "nmi"  # (no grouped kernel: the per-slice histograms at the composed matrices)
+        if not nmi and self._packages_fused(lv):
+            op, psf = _psf_op("svr_similarity_groups", lv.psf)
+            return op(lv.volume, *psf, corr, lv.base, offsets, listed, lv.slices, lv.mask, lv.res_slice)
+        out = (torch.zeros((m, K, self._bins, self._bins), dtype=torch.int64, device=corr.device) if nmi else
+               torch.zeros((m, K, 6), dtype=torch.float64, device=corr.device))
         if listed.numel() == 0:
             return out
         sizes = (offsets[1:] - offsets[:-1]).long()
         entry_group = torch.repeat_interleave(torch.arange(m), sizes).to(corr.device)
         ids = listed.long().to(corr.device)
         mats = compose_mats(corr[entry_group], lv.base[ids][:, None]).float().contiguous()  # (E,K,3,4)
+        if nmi:  # added per group in integers: no order to keep
+            return out.index_add_(0, entry_group, self._histograms_at(mats, lv, ids, self._packages_fused(lv)))
         per_entry = self._sums_at(mats, lv, ids)
         for j in range(int(sizes.max())):  # a group's entries one after the other from 0, in CSR order
             has = torch.nonzero(sizes > j).flatten()
@@ -624,12 +623,7 @@ class GroupSVR(SVR):
         return self._loss_of(self._group_sums(theta[:, None], lv, self._gids(idx, lv)))[:, 0]
 
     def _gradient_at(self, idx: torch.Tensor, cur: torch.Tensor, lv: _SliceLevel, step: float) -> Tuple[torch.Tensor, torch.Tensor]:
-        e = torch.zeros((13, 6), dtype=cur.dtype, device=cur.device)  # the correction and its 12 perturbations
-        j = torch.arange(6, device=cur.device)
-        e[1 + 2 * j, j] = step
-        e[2 + 2 * j, j] = -step
-        l = self._loss_of(self._group_sums(cur[:, None] + e[None], lv, self._gids(idx, lv)))
-        return l[:, 0], l[:, 1::2] - l[:, 2::2]
+        return _stencil_gradient(cur, step, lambda x: self._loss_of(self._group_sums(x, lv, self._gids(idx, lv))))
 
     @staticmethod
     def group_centroids(base_mm: torch.Tensor, slices_mask: torch.Tensor, res_s: float, groups) -> torch.Tensor:

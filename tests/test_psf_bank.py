@@ -53,6 +53,21 @@ def test_subset_remaps_ids_and_drops_unused_members():
     assert [g for g, _, _ in bank.members()] == [0, 1, 2] and [idx.tolist() for _, _, idx in bank.members()] == [[0, 2], [1, 4], [3, 5]]
 
 
+def test_op_args_are_the_bank_and_the_ids_of_all_slices_or_of_a_subset():
+    from nesvor_amd.psf_bank import PsfBank
+
+    bank = PsfBank([torch.full((1, 1, 1), 1.0), torch.full((2, 1, 1), 0.5), torch.full((3, 1, 1), 1 / 3)], [0, 1, 0, 2, 1, 2])
+    flat, table, ids = bank.op_args()
+    assert flat is bank.flat and table is bank.table and ids is bank.ids  # all slices: the bank's own tensors
+    for idx, want in ((torch.tensor([3, 5, 0]), [2, 2, 0]), ([4, 4], [1, 1]), (torch.tensor([], dtype=torch.int64), []), ([], []),
+                      (torch.arange(6)[::2], [0, 0, 1])):
+        flat, table, ids = bank.op_args(idx)
+        assert flat is bank.flat and table is bank.table  # the members stay: no new bank for a subset
+        assert ids.tolist() == want and tuple(ids.shape) == (len(want),)
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.device == bank.device
+    assert bank.ids.tolist() == [0, 1, 0, 2, 1, 2]  # (the bank's ids are not written)
+
+
 def test_ids_outside_the_bank_are_refused_on_the_host():
     from nesvor_amd.psf_bank import MAX_MEMBERS, PsfBank
 

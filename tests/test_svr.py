@@ -56,6 +56,48 @@ def test_svr_refuses_other_losses():
             SVR(2, 2, 2, 5, {"name": "gd", "momentum": 0.1}, loss)
 
 
+def test_a_plain_psf_selects_the_plain_op_and_a_bank_its_twin():
+    from nesvor_amd import ops  # noqa: F401  (defines torch.ops.nesvor.*)
+    from nesvor_amd.psf_bank import PsfBank
+    from nesvor_amd.registration import _psf_op
+
+    psf = torch.ones(3, 3, 3) / 27
+    bank = PsfBank([torch.ones(3, 3, 3) / 27, torch.ones(5, 3, 3) / 45], [0, 1, 1, 0, 1])
+    for name in ("svr_similarity", "svr_joint_histogram", "svr_similarity_groups"):
+        op, args = _psf_op(name, psf)
+        assert op is getattr(torch.ops.nesvor, name) and len(args) == 1 and args[0] is psf
+        assert _psf_op(name, psf, torch.tensor([2, 0]))[1][0] is psf  # (a subset takes the same PSF)
+        op, args = _psf_op(name, bank)
+        assert op is getattr(torch.ops.nesvor, name + "_bank")
+        assert len(args) == 3 and all(a is b for a, b in zip(args, bank.op_args()))
+        op, args = _psf_op(name, bank, torch.tensor([4, 0, 2]))
+        assert op is getattr(torch.ops.nesvor, name + "_bank")
+        assert args[0] is bank.flat and args[1] is bank.table and args[2].tolist() == [1, 0, 1] and args[2].dtype == torch.int32
+
+
+def test_the_gradient_stencil_is_the_pose_and_both_steps_on_each_axis():
+    from nesvor_amd.registration import _stencil_gradient
+
+    cur = torch.tensor([[1.0, 2.0, 3.0, 4.0, 5.0, 6.0], [-6.0, -5.0, -4.0, -3.0, -2.0, -1.0]], dtype=torch.float64)
+    step, seen = 0.25, []
+
+    def losses(thetas):
+        seen.append(thetas)
+        return (thetas * torch.tensor([1.0, 2.0, 4.0, 8.0, 16.0, 32.0], dtype=thetas.dtype)).sum(-1) + 100.0  # (exact in float64)
+
+    loss, grad = _stencil_gradient(cur, step, losses)
+    (thetas,) = seen
+    assert tuple(thetas.shape) == (2, 13, 6) and thetas.dtype == cur.dtype
+    assert torch.equal(thetas[:, 0], cur)  # row 0: the pose itself
+    for j in range(6):  # rows 1 + 2 j and 2 + 2 j: + step and - step on axis j, nothing else moved
+        e = torch.zeros(6, dtype=cur.dtype)
+        e[j] = step
+        assert torch.equal(thetas[:, 1 + 2 * j], cur + e) and torch.equal(thetas[:, 2 + 2 * j], cur - e)
+    # the read-out: the loss at the pose, and loss(+ step) - loss(- step) per axis, not divided by the step
+    assert torch.equal(loss, losses(cur[:, None])[:, 0])
+    assert torch.equal(grad, (2 * step * torch.tensor([1.0, 2.0, 4.0, 8.0, 16.0, 32.0], dtype=torch.float64)).expand(2, 6))
+
+
 def test_common_frame_keeps_every_pixel_in_place_and_round_trips_the_poses():
     """Stacks of odd and even sizes padded to one square frame: where the padding is uneven the frame's centre sits half a
     pixel off the slice's, and the frame's pose makes up for it - a pixel's world position is the same before and after,
