@@ -819,6 +819,37 @@ int nesvor_vvr_similarity(const float* source, int D, int H, int W, const float*
                           double* target_sums, void* stream);
 
 /* ----------------------------------------------------------------------
+ * Joint histograms of the stack registration (the statistic of its mutual-information similarity) and the samples behind them.
+ * source, points, target, mats, to_unit_xyz (HOST), M, K and the sample I of a (point, pose) are nesvor_vvr_similarity's - one
+ * device function serves the three kernels, so I is the same bit for bit; J = target.  EVERY point counts: one that leaves the
+ * source has I = 0.
+ *   i_lo, i_scale, j_lo, j_scale   the affine maps of I and of J to bin coordinates, one pair each for the call
+ *   bins    B, 2 <= B <= 64
+ * A value's position on its axis and what a point adds are nesvor_svr_joint_histogram's (below; nesvor_amd/nmi.py): weights
+ * 256 - q and q on bins b0 and b0 + 1 of either axis, the four integer products added to cells (bI, bJ), 65536 units per point.
+ *   hist[k][bI][bJ]   int64, (K,B,B), row = I bin; fully written (no memset needed); its total is 65536 * M.  Integer adds only: the
+ * result does not depend on the order of addition and is the same from run to run.  The point list is cut into segments of 1024
+ * to 16384 points (long ones for the 13 poses of a gradient, enough of them to reach about 1024 workgroups for a single pose); a
+ * (pose, segment) builds its histogram in LDS in 32-bit cells (16384 points of 65536 units stay below 2^32) and stores it to the
+ * workspace, and a second launch adds the segments in 64 bits: no cell overflows at any M.  No float atomic, no global atomic.
+ * workspace: device memory of at least nesvor_vvr_joint_histogram_workspace_bytes(M, K, bins) bytes (0 for sizes the call refuses
+ * or treats as a no-op).
+ * K <= 0 or M <= 0: no-op, returns 0 (hist is not touched).  hipErrorInvalidValue, without a launch: D, H or W below 1, bins
+ * outside [2, 64], M above INT_MAX, K times the number of segments above INT_MAX, a workspace that is NULL or too small.
+ * nesvor_vvr_sample: out[k][i] = I of point i under pose k, (K,M) fp32, fully written - what nesvor_amd/nmi.py's joint_histogram
+ * bins to the very histogram above (the composed path), and the sampling alone for timings.  K <= 0 or M <= 0: no-op;
+ * hipErrorInvalidValue: D, H or W below 1, K ceil(M / 256) above INT_MAX.
+ * (Added without a change of nesvor_hip_abi_version(): nothing that existed changed; resolve the symbols to find out.)
+ * ---------------------------------------------------------------------- */
+int nesvor_vvr_joint_histogram(const float* source, int D, int H, int W, const float* points, const float* target,
+                               const float* mats, const float* to_unit_xyz, int64_t M, int K, float i_lo, float i_scale,
+                               float j_lo, float j_scale, int bins, int64_t* hist, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int64_t nesvor_vvr_joint_histogram_workspace_bytes(int64_t M, int K, int bins);
+int nesvor_vvr_sample(const float* source, int D, int H, int W, const float* points, const float* mats,
+                      const float* to_unit_xyz, int64_t M, int K, float* out, void* stream);
+
+/* ----------------------------------------------------------------------
  * Similarity sums of the slice-to-volume registration: the acquisition operator A (nesvor_slice_acq_forward with
  * interp_psf = 0 and no volume mask) applied to every slice under K poses, reduced at once.  vol (D,H,W) fp32,
  * psf (d_p,h_p,w_p), transforms (n,K,3,4) in A's convention (voxel units), slices (n,h,w) acquired values,

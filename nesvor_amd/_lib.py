@@ -226,6 +226,11 @@ _SIGNATURES = {
     "nesvor_step_timing_read": ([_P, _P], c_int),
     "nesvor_step_run": ([_P, _P, _P, _P, c_uint64, c_uint64, _P, c_int, c_int, POINTER(AdamwT), _P], c_int),
     "nesvor_vvr_similarity": ([_P, c_int, c_int, c_int, _P, _P, _P, _P, c_int64, c_int, _P, _P, _P], c_int),
+    # the stack registration's joint histograms: (i_lo, i_scale, j_lo, j_scale, bins) behind K, int64 cells in the place of the sums
+    "nesvor_vvr_joint_histogram": ([_P, c_int, c_int, c_int, _P, _P, _P, _P, c_int64, c_int, c_float, c_float, c_float, c_float, c_int, _P,
+                                    _P, c_size_t, _P], c_int),
+    "nesvor_vvr_joint_histogram_workspace_bytes": ([c_int64, c_int, c_int], c_int64),
+    "nesvor_vvr_sample": ([_P, c_int, c_int, c_int, _P, _P, _P, c_int64, c_int, _P, _P], c_int),
     "nesvor_svr_similarity": ([_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P,
                                c_size_t, _P], c_int),
     "nesvor_svr_similarity_workspace_bytes": ([c_int, c_int, c_int, c_int], c_int64),

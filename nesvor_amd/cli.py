@@ -70,6 +70,13 @@ NCC of a slice and its simulation, or their normalised mutual information on a j
 the linear intensity relation NCC assumes fails.  With another registration, or with ``--input-slices``, the flags are ignored
 with a warning; a ``B`` outside [2, 64] ends the command.
 
+Also not in the reference: ``--stack-similarity ncc|nmi`` (default ``ncc``) on ``svr``, ``register`` and ``reconstruct`` chooses the
+metric of the stage in front of those: the stack registration of ``--registration stack``, which is also the first stage of
+``--registration svr``.  ``nmi`` registers every stack to the template on the normalised mutual information of a joint histogram of
+``--nmi-bins`` bins per axis over the template's points (the same definition, nesvor_amd/nmi.py; csrc/vvr_nmi.hip), so that
+stacks of another contrast reach the slice stage from a stack pose NCC would have got wrong.  ``--nmi-bins`` serves both flags and
+is checked when either asks for ``nmi``.  With ``--registration none`` or ``--input-slices`` the flag is ignored with a warning.
+
 Also not in the reference: ``--per-stack-thickness`` on ``svr``, ``register`` and ``reconstruct`` (there for the registration stage
 only) lets stacks of unequal slice thickness keep their own (``--thicknesses``, or the files' z spacing): ``--registration stack``
 registers every stack on the template's slice spacing and spaces its slices by its own gap, and ``svr`` / ``--registration svr``
@@ -299,7 +306,11 @@ def _package_flags(g) -> None:
     g.add_argument("--svr-similarity", choices=["ncc", "nmi"], default="ncc",
                    help="(not in the reference) the metric of --registration svr's package and slice stages: global NCC, or normalised "
                         "mutual information on a joint histogram (nesvor_amd/nmi.py) for stacks whose intensities are not linearly related")
-    g.add_argument("--nmi-bins", type=int, default=32, metavar="B", help="bins per axis of --svr-similarity nmi, 2 <= B <= 64")
+    g.add_argument("--nmi-bins", type=int, default=32, metavar="B",
+                   help="bins per axis of --svr-similarity nmi and --stack-similarity nmi, 2 <= B <= 64")
+    g.add_argument("--stack-similarity", choices=["ncc", "nmi"], default="ncc",
+                   help="(not in the reference) the metric of --registration stack and of the stack stage of --registration svr: global "
+                        "NCC, or normalised mutual information on a joint histogram (nesvor_amd/nmi.py, csrc/vvr_nmi.hip)")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -654,7 +665,7 @@ def register(args: Namespace, stacks: List) -> List:
         from .registration import register_stacks
 
         t1 = time.time()
-        stacks = register_stacks(stacks, template=template, per_stack_thickness=per_stack)
+        stacks = register_stacks(stacks, template=template, per_stack_thickness=per_stack, **similarity)
         logging.info("Stack registration finished in %.1f s", time.time() - t1)
     elif args.registration == "svr":
         from .registration import register_slices
@@ -682,23 +693,45 @@ def warn_packages_ignored(args: Namespace, why: str) -> None:
 
 
 def warn_similarity_ignored(args: Namespace, why: str) -> None:
-    """``--svr-similarity`` / ``--nmi-bins`` only act in the package and slice stages of ``--registration svr``."""
+    """``--svr-similarity`` / ``--nmi-bins`` only act in the package and slice stages of ``--registration svr``, ``--stack-similarity``
+    where stacks are registered."""
     if getattr(args, "svr_similarity", "ncc") != "ncc" or getattr(args, "nmi_bins", 32) != 32:
         logging.warning("--svr-similarity / --nmi-bins are ignored with %s: the metric is that of --registration svr only", why)
+    if getattr(args, "stack_similarity", "ncc") != "ncc":
+        logging.warning("--stack-similarity is ignored with %s: no stack is registered", why)
 
 
-def similarity_options(args: Namespace) -> Dict:
-    """``--svr-similarity`` / ``--nmi-bins`` as keyword arguments of ``register_slices`` (none for the default, NCC).  With a
-    registration other than ``svr`` the flags are ignored with a warning; ``--nmi-bins`` outside [2, 64] ends the command."""
-    if getattr(args, "registration", "none") != "svr":
-        warn_similarity_ignored(args, f"--registration {getattr(args, 'registration', 'none')}")
-        return {}
+def _nmi_bins(args: Namespace) -> int:
     bins = getattr(args, "nmi_bins", 32)
     if not 2 <= int(bins) <= 64:
         raise SystemExit(f"--nmi-bins: a number of bins in [2, 64] expected, got {bins}")
-    if getattr(args, "svr_similarity", "ncc") == "ncc":
+    return int(bins)
+
+
+def similarity_options(args: Namespace) -> Dict:
+    """``--svr-similarity`` / ``--stack-similarity`` / ``--nmi-bins`` as keyword arguments of the registration the command runs (none
+    for the defaults, NCC): of ``register_slices`` with ``--registration svr`` (``similarity``, ``stack_similarity``, ``nmi_bins``), of
+    ``register_stacks`` with ``--registration stack --stack-similarity nmi`` (``similarity``, ``nmi_bins``).  Flags that do not act
+    are ignored with a warning; ``--nmi-bins`` outside [2, 64] ends the command."""
+    registration = getattr(args, "registration", "none")
+    stack_nmi = getattr(args, "stack_similarity", "ncc") == "nmi"
+    if registration == "stack" and stack_nmi:
+        if getattr(args, "svr_similarity", "ncc") != "ncc":
+            logging.warning("--svr-similarity is ignored with --registration stack: it is the metric of --registration svr's package "
+                            "and slice stages")
+        return {"similarity": "nmi", "nmi_bins": _nmi_bins(args)}
+    if registration != "svr":
+        warn_similarity_ignored(args, f"--registration {registration}")  # (stack: --stack-similarity is at its default here)
         return {}
-    return {"similarity": "nmi", "nmi_bins": int(bins)}
+    bins = _nmi_bins(args)
+    out: Dict = {}
+    if getattr(args, "svr_similarity", "ncc") == "nmi":
+        out["similarity"] = "nmi"
+    if stack_nmi:
+        out["stack_similarity"] = "nmi"
+    if out:
+        out["nmi_bins"] = bins
+    return out
 
 
 def package_options(args: Namespace, n_stacks: int) -> Optional[List[int]]:

@@ -9,6 +9,9 @@
 // and its J weights to the cells (bI, bJ), 65536 units in all, zero products skipped.  Integer adds: the histogram does not depend
 // on the order of addition, so LDS atomics are reproducible here and no float atomic is used.
 //
+// nmi_hist.h holds what this file shares with the stack registration's histograms (vvr_nmi.hip): axis_place, the four adds of a
+// sample, the segment rule and the 64-bit reduction of the segments.
+//
 // A pixel's value under a pose is acq_taps.h's simulate_pixel, as svr_similarity_kernel's: the functions slice_acq_fwd<float, false,
 // true> calls and the same val / wsum, so I and the valid set are that operator's bit for bit.
 //
@@ -24,26 +27,12 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include "acq_taps.h"
+#include "nmi_hist.h"
 #include "../../include/nesvor_hip.h"
 
 namespace {
 using namespace acq;
-
-constexpr int kMaxNmiBins = 64;
-constexpr int kMinSegmentPixels = 1024, kMaxSegmentPixels = 16384;  // multiples of the workgroup's 256 pixels
-constexpr int kTargetWorkgroups = 1024;                             // four per CU: what a launch is cut for
-static_assert(kMinSegmentPixels % 256 == 0 && kMaxSegmentPixels % 256 == 0 && kMaxSegmentPixels <= 65535,
-              "a 32-bit cell holds at most 65535 pixels of 65536 units");
-
-// A value's place on an axis: the lower bin and the weight (of 256) of the upper one.
-struct AxisPlace { int b0, q; };
-
-__device__ __forceinline__ AxisPlace axis_place(float v, float lo, float scale, int B) {
-  const float u = fminf(fmaxf((v - lo) * scale, 0.f), (float)(B - 1));  // (a NaN becomes 0: nothing is indexed by it)
-  const int b0 = min((int)u, B - 2);
-  const float f = u - (float)b0;
-  return AxisPlace{b0, (int)(f * 256.f + 0.5f)};
-}
+using namespace nmi_hist;
 
 // grid: n K S workgroups, S = ceil(h w / seg) segments of `seg` pixels per (slice, pose); block e S + s serves segment s of entry
 // e = slice K + pose.  partial: (n K, S, B, B) 32-bit cells, row = I bin.
@@ -73,44 +62,15 @@ __global__ __launch_bounds__(256) void svr_joint_histogram_kernel(const float* _
     float I;
     if (!simulate_pixel(vol, D, H, W, t, pix % w, pix / w, h, w, res_slice, taps, nt, I)) continue;
     const AxisPlace a = axis_place(I, i_lo, i_scale, B), b = axis_place(slices[idx], j_lo, j_scale, B);
-    const int c00 = a.b0 * B + b.b0;  // at most (B - 2) B + B - 2: the four cells stay below B B
-    const uint32_t ai[2] = {(uint32_t)(256 - a.q), (uint32_t)a.q}, bj[2] = {(uint32_t)(256 - b.q), (uint32_t)b.q};
-#pragma unroll
-    for (int di = 0; di < 2; ++di)
-#pragma unroll
-      for (int dj = 0; dj < 2; ++dj) {
-        const uint32_t p = ai[di] * bj[dj];
-        if (p != 0u) atomicAdd(&hist[c00 + di * B + dj], p);
-      }
+    add_sample(a, b, B, [&](int cell, uint32_t p) { atomicAdd(&hist[cell], p); });
   }
   __syncthreads();
   uint32_t* row = partial + (size_t)blockIdx.x * cells;
   for (int c = threadIdx.x; c < cells; c += 256) row[c] = hist[c];
 }
 
-// out[e][c] = the S segments of entry e added in 64 bits; one thread per (entry, cell), total = entries * cells.
-__global__ __launch_bounds__(256) void svr_joint_histogram_reduce_kernel(const uint32_t* __restrict__ partial, int64_t total, int cells, int S,
-                                                                         int64_t* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int64_t e = t / cells;
-  const int c = (int)(t - e * cells);
-  int64_t sum = 0;
-  for (int s = 0; s < S; ++s) sum += (int64_t)partial[((size_t)e * S + s) * cells + c];
-  out[t] = sum;
-}
-
-// The segment length of a launch of `entries` (slice, pose) pairs of h w pixels: the slice cut into as many segments as it takes to
-// reach kTargetWorkgroups workgroups, in whole trips of 256 pixels, between kMinSegmentPixels and kMaxSegmentPixels.
-inline int segment_pixels(int64_t entries, int64_t hw) {
-  const int64_t want = (kTargetWorkgroups + entries - 1) / entries;
-  const int64_t seg = ((hw + want - 1) / want + 255) / 256 * 256;
-  return (int)(seg < kMinSegmentPixels ? kMinSegmentPixels : seg > kMaxSegmentPixels ? kMaxSegmentPixels : seg);
-}
-inline int64_t segments(int64_t entries, int h, int w) {
-  const int64_t hw = (int64_t)h * w, seg = segment_pixels(entries, hw);
-  return (hw + seg - 1) / seg;
-}
+// The segments a slice of h w pixels is cut into in a launch of `entries` (slice, pose) pairs (nmi_hist.h has the rule).
+inline int64_t segments(int64_t entries, int h, int w) { return nmi_hist::segments(entries, (int64_t)h * w); }
 
 // The launches of both entry points, behind their checks of the PSF source.
 template <typename PSF>
@@ -129,7 +89,7 @@ int svr_joint_histogram_launch(const float* vol, int D, int H, int W, const PSF&
   hipLaunchKernelGGL((svr_joint_histogram_kernel<PSF>), dim3((unsigned)(entries * S)), dim3(256), 0, st, vol, D, H, W, psfs, transforms,
                      slices, slices_mask, K, h, w, (int)S, segment_pixels(entries, (int64_t)h * w), res_slice, i_lo, i_scale, j_map, bins, partial);
   const int64_t total = entries * cells;
-  hipLaunchKernelGGL(svr_joint_histogram_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint32_t*)partial,
+  hipLaunchKernelGGL(joint_histogram_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint32_t*)partial,
                      total, (int)cells, (int)S, hist);
   return (int)hipGetLastError();
 }

@@ -7,18 +7,19 @@
 // sums per pose from which NCC or MSE follow.
 //
 // Sampling = F.grid_sample(mode="bilinear", padding_mode="zeros", align_corners=True): normalised coordinate g in
-// [-1, 1] -> index (g + 1) / 2 * (size - 1); corners outside the volume contribute 0.
+// [-1, 1] -> index (g + 1) / 2 * (size - 1); corners outside the volume contribute 0.  The per-point sampling below is, operation for
+// operation, vvr_sample.h's sample_point, which the kernels of vvr_nmi.hip call; it stays written out here because calling the
+// function changes this kernel's code ("Mutual-information stack registration").  Change both or neither.
 // Gather-bound (8 reads per point and pose, the source volume is L2-resident); sums leave the chip as
 // one fp64 atomic per workgroup and moment.
 #include <hip/hip_runtime.h>
 #include "common.h"
+#include "vvr_sample.h"
 #include "../../include/nesvor_hip.h"
 
 namespace {
 
-__device__ __forceinline__ float fetch(const float* __restrict__ v, int x, int y, int z, int W, int H, int D) {
-  return (x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) ? v[((size_t)z * H + y) * W + x] : 0.f;
-}
+using namespace vvr;  // fetch
 
 template <int KT>
 __global__ __launch_bounds__(256) void vvr_similarity_kernel(const float* __restrict__ src, int D, int H, int W,

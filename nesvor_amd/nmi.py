@@ -17,7 +17,14 @@ needs.
 
 Loss (``nmi_loss``), in float64:  N = sum H, p = H / N, entropies with 0 log 0 = 0,  ``loss = 1 - (H_I + H_J) / H_IJ``  in [-1, 0];
 0 where N == 0 or H_IJ <= 0 ("no valid pixel" is the worst loss, as the descent assumes); the valid count is N / 65536.  A group's
-histogram is the integer sum of its members'."""
+histogram is the integer sum of its members'.
+
+The stack registration (``VVR`` with ``loss = {"name": "nmi"}``; csrc/vvr_nmi.hip, ``torch.ops.nesvor.vvr_joint_histogram``) uses the
+same statement per (pyramid level, pose) over ALL ``M`` points of the level's point list - there is no mask: I is the source sampled
+at the moved point (trilinear, zero padding, so a point that leaves the source has I = 0 and still counts, as it does for NCC), J
+the target's value at the point; I's map is ``axis_map`` of the min / max of the level's source, J's of the min / max of the point
+list's values ((0, 0) for an empty list), both computed once per level.  A histogram's total is ``UNITS * M``; an empty list gives
+zeros and loss 0."""
 from typing import Tuple
 
 import torch

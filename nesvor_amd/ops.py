@@ -499,6 +499,57 @@ _op("svr_joint_histogram_bank(Tensor vol, Tensor psf_bank, Tensor psf_table, Ten
 
 
 # =====================================================================================================================
+# joint histograms of the stack registration (csrc/vvr_nmi.hip; the definition: nesvor_amd/nmi.py) and the samples they bin: what
+# nesvor_vvr_similarity sums into moments - source (..., D, H, W), points (M, 3), target (M), mats (K, 3, 4), to_unit three floats
+# =====================================================================================================================
+def _vvr_cloud(what, source, points, mats, to_unit, target=None):
+    """The checks of a stack registration's call -> (D, H, W, M, K, to_unit as the library reads it)."""
+    names = "source/points/mats" + ("" if target is None else "/target")
+    _lib.require_device(source, points, mats, target, dtype=torch.float32, name=f"{what} {names}")
+    if source.ndim < 3 or source.numel() != source.shape[-3] * source.shape[-2] * source.shape[-1]:
+        raise RuntimeError(f"{what}: source must hold one (D, H, W) volume, got {tuple(source.shape)}")
+    if points.ndim != 2 or points.shape[1] != 3 or mats.ndim != 3 or tuple(mats.shape[1:]) != (3, 4) or len(to_unit) != 3:
+        raise RuntimeError(f"{what}: points (M, 3), mats (K, 3, 4) and three to_unit factors expected")
+    if target is not None and target.numel() != points.shape[0]:
+        raise RuntimeError(f"{what}: target must hold one value per point ({points.shape[0]}), got {target.numel()}")
+    if any(t.device != source.device for t in (points, mats) + (() if target is None else (target,))):
+        raise RuntimeError(f"{what}: {names} must be on one device")
+    D, H, W = (int(s) for s in source.shape[-3:])
+    return D, H, W, int(points.shape[0]), int(mats.shape[0]), (ctypes.c_float * 3)(*(float(u) for u in to_unit))
+
+
+def _vvr_joint_histogram(source, points, target, mats, to_unit, i_lo, i_scale, j_lo, j_scale, bins):
+    what = "vvr_joint_histogram"
+    D, H, W, M, K, unit = _vvr_cloud(what, source, points, mats, to_unit, target)
+    bins = int(bins)
+    if not 2 <= bins <= 64:
+        raise RuntimeError(f"{what}: 2 <= bins <= 64 expected, got {bins}")
+    if M == 0 or K == 0:  # (a no-op of the library: an empty point list has an empty histogram)
+        return torch.zeros((K, bins, bins), dtype=torch.int64, device=source.device)
+    hist = torch.empty((K, bins, bins), dtype=torch.int64, device=source.device)
+    _launch(what, source.device, (M, K, bins), _lib.ptr(source), D, H, W, _lib.ptr(points), _lib.ptr(target), _lib.ptr(mats), unit, M, K,
+            float(i_lo), float(i_scale), float(j_lo), float(j_scale), bins, _lib.ptr(hist))
+    return hist
+
+
+def _vvr_sample(source, points, mats, to_unit):
+    D, H, W, M, K, unit = _vvr_cloud("vvr_sample", source, points, mats, to_unit)
+    out = torch.empty((K, M), dtype=torch.float32, device=source.device)
+    with torch.cuda.device(source.device):
+        err = _lib.load().nesvor_vvr_sample(_lib.ptr(source), D, H, W, _lib.ptr(points), _lib.ptr(mats), unit, M, K, _lib.ptr(out),
+                                            _lib.stream_ptr())
+    _lib.check(err, "vvr sample")
+    return out
+
+
+_op("vvr_joint_histogram(Tensor source, Tensor points, Tensor target, Tensor mats, float[] to_unit, float i_lo, float i_scale, "
+    "float j_lo, float j_scale, int bins) -> Tensor", _vvr_joint_histogram,
+    fake=lambda src, pts, tgt, mats, u, ilo, isc, jlo, jsc, bins: src.new_empty((mats.shape[0], bins, bins), dtype=torch.int64))
+_op("vvr_sample(Tensor source, Tensor points, Tensor mats, float[] to_unit) -> Tensor", _vvr_sample,
+    fake=lambda src, pts, mats, u: src.new_empty((mats.shape[0], pts.shape[0])))
+
+
+# =====================================================================================================================
 # grouped similarity sums (package registration, csrc/svr.hip): one correction per (group, pose), composed with every slice's
 # base pose in the kernel, sums per (group, pose) in CSR order.  The grouping arrives in HOST memory, is checked there and
 # uploaded: a bad index is a Python exception, never a device read, and no call reads the device back

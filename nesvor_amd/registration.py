@@ -23,6 +23,15 @@ finite-difference gradient needs 13 of them.  Fused (HIP, ``nesvor_vvr_similarit
 (global NCC or MSE) and the gradient is by finite differences, ONE launch samples the source under all 13 poses and
 returns the moment sums the loss is a function of (fp64); ``stack_registration`` uses it.
 
+``loss = {"name": "nmi", "bins": B}`` (not in the reference; ``--stack-similarity nmi``): normalised mutual information of the
+sampled source and the target over ALL points of the level (nesvor_amd/nmi.py has the definition; I is binned on the range of the
+level's source, J on the range of the level's point list), for stacks whose intensities are not linearly related.  Three
+evaluation paths with that one definition: fused (``torch.ops.nesvor.vvr_joint_histogram``, csrc/vvr_nmi.hip: the 13 poses of a
+gradient in one call, the accept test a K = 1 call) under the conditions of the fused path above; composed (the kernel's own
+samples, ``torch.ops.nesvor.vvr_sample``, binned by ``nmi.joint_histogram`` - bit-equal to the fused one), forced with
+``NESVOR_VVR_NMI=composed``; generic (``grid_sample`` + ``nmi.joint_histogram``) for batches and devices without the kernels.  The
+histogram is integer, so the gradient is by finite differences only.
+
 Slice-to-volume registration (``SVR``, ``register_slices`` = ``--registration svr``; no counterpart in the reference, whose
 slice-level choices need the pretrained SVoRT transformer): the same descent with one pose per slice, the objective being
 the similarity of the acquired slice and the slice simulated from the volume by the acquisition operator.
@@ -79,6 +88,7 @@ class _Level:
         self.to_unit = torch.tensor(unit, dtype=source.dtype, device=source.device)
         self.to_unit_host = (ctypes.c_float * 3)(*unit)
         self.target_sums = None  # (sum J, sum J^2) of the fused path, filled by its first call
+        self.i_map, self.j_map = None, None  # nmi: the affine maps to bin coordinates, filled by the first evaluation
 
 
 class VVR:
@@ -88,7 +98,8 @@ class VVR:
     theta (B,6) axis-angle [rad | mm] of the source in the ``trans_first`` convention, source / target volumes
     (1,1,D,H,W), ``params = {"res_s": in-plane, "s_thick": through-plane}`` voxel sizes, ``transform_t`` the target's
     pose.  ``optimizer = {"name": "gd", "momentum": m}``; ``loss`` = {"name": "mse" | "ncc", ...} or a callable
-    ``loss(self, warped, target) -> per-element or per-batch loss``.
+    ``loss(self, warped, target) -> per-element or per-batch loss``, or ``{"name": "nmi", "bins": B}`` (2 <= B <= 64, default
+    32; no other key; ``auto_grad=True`` raises): the module docstring has its paths.
     """
 
     def __init__(self, num_levels: int, num_steps: int, step_size: float, max_iter: int, optimizer: Dict,
@@ -110,6 +121,13 @@ class VVR:
                 self._loss = lambda x, y: ncc_loss(x, y, reduction="none", level=self.current_level, **kw)
                 if kw.get("win", 9) is None and set(kw) <= {"win", "eps"}:  # global NCC: a function of five moment sums
                     self._fused_kind, self._eps = "ncc", float(kw.get("eps", 1e-6))
+            elif name == "nmi":  # a statistic of the whole point list, not a loss per element: `_objective` takes its own way
+                if set(kw) - {"bins"}:
+                    raise Exception("unknown loss")
+                if auto_grad:
+                    raise ValueError("loss nmi: an integer histogram has no gradient; auto_grad=False (finite differences) expected")
+                self._bins = _nmi.check_bins(kw.get("bins", _nmi.DEFAULT_BINS), "loss bins")
+                self._loss, self._fused_kind = None, "nmi"
             else:
                 raise Exception("unknown loss")
         elif callable(loss):
@@ -147,6 +165,8 @@ class VVR:
 
     def _objective(self, theta_deg: torch.Tensor, lv: _Level) -> torch.Tensor:
         warped = self._warp(theta_deg, lv)
+        if self._fused_kind == "nmi":
+            return _nmi.nmi_loss(self._bin(warped, lv)).to(theta_deg.dtype)
         loss = self._loss(warped[:, None], lv.values.view(1, 1, -1).expand(warped.shape[0], -1, -1))
         return loss.reshape(loss.shape[0], -1).mean(1)
 
@@ -159,6 +179,8 @@ class VVR:
         K = thetas_deg.shape[0]
         pose = RigidTransform(thetas_deg * self._unit(thetas_deg), trans_first=self.trans_first)
         mats = pose.inv().compose(self.theta_t).matrix().contiguous()
+        if self._fused_kind == "nmi":
+            return _nmi.nmi_loss(self._level_histograms(mats, lv, os.environ.get("NESVOR_VVR_NMI", "") != "composed")).to(thetas_deg.dtype)
         dev = lv.source.device
         sums = torch.empty((K, 3), dtype=torch.float64, device=dev)
         first = lv.target_sums is None
@@ -178,6 +200,35 @@ class VVR:
             return (sII - 2 * sIJ + sJJ).float()
         cross = sIJ - sI * sJ
         return (-(cross * cross) / ((sII - sI * sI) * (sJJ - sJ * sJ) + self._eps)).float()
+
+    # ---- nmi: the statistic of a pose is a joint histogram (nesvor_amd/nmi.py) over ALL points of the level, (K,B,B) int64 ----
+    def _level_maps(self, lv: _Level) -> Tuple[Tuple[float, float], Tuple[float, float]]:
+        """The level's affine maps to bin coordinates, (lo, scale) each: of the sampled value from the source's range, of the
+        target's value from the range of the point list ((0, 0) for an empty one).  Computed once per level."""
+        if lv.i_map is None:
+            lv.i_map = tuple(_nmi.axis_map(lv.source.min(), lv.source.max(), self._bins).tolist())
+            empty = lv.values.numel() == 0
+            lv.j_map = (0.0, 0.0) if empty else tuple(_nmi.axis_map(lv.values.min(), lv.values.max(), self._bins).tolist())
+        return lv.i_map, lv.j_map
+
+    def _bin(self, samples: torch.Tensor, lv: _Level) -> torch.Tensor:
+        """Samples (K,M) of K poses binned against the level's values with the torch integer ops of the definition."""
+        i_map, j_map = self._level_maps(lv)
+        K = samples.shape[0]
+        J = lv.values.float().view(1, -1).expand(K, -1)
+        j_rows = torch.tensor(j_map, dtype=torch.float32, device=samples.device).view(1, 2).expand(K, 2)
+        return _nmi.joint_histogram(samples.float(), J, torch.ones_like(J, dtype=torch.bool), i_map, j_rows, self._bins)
+
+    def _level_histograms(self, mats: torch.Tensor, lv: _Level, fused: bool) -> torch.Tensor:
+        """Joint histograms at mats (K,3,4) on a HIP device: ``fused`` - one call of the kernel; else composed - the kernel's own
+        samples (``vvr_sample``) binned by ``nmi.joint_histogram``, bit-equal to it."""
+        from . import ops  # noqa: F401  (registers torch.ops.nesvor)
+
+        i_map, j_map = self._level_maps(lv)
+        src, unit = lv.source.contiguous(), list(lv.to_unit_host)
+        if fused:
+            return torch.ops.nesvor.vvr_joint_histogram(src, lv.points, lv.values, mats, unit, *i_map, *j_map, self._bins)
+        return self._bin(torch.ops.nesvor.vvr_sample(src, lv.points, mats, unit), lv)
 
     def _gradient(self, theta: torch.Tensor, lv: _Level, h: float) -> Tuple[torch.Tensor, torch.Tensor]:
         if self._fused(theta, lv):  # the pose and its 12 perturbations in one launch
@@ -726,20 +777,23 @@ def _mean_pose(t: RigidTransform) -> RigidTransform:
 
 def stack_registration(transforms_list: List[List[RigidTransform]], transform_target: RigidTransform,
                        stacks: List[torch.Tensor], res_s: float, s_thick: float,
-                       gaps: Optional[Sequence[float]] = None) -> List[RigidTransform]:
+                       gaps: Optional[Sequence[float]] = None, loss: Optional[Dict] = None) -> List[RigidTransform]:
     """Register every stack (as a volume of its slices) to stack 0 and return per-slice poses
     (svort/inference.py:308-367): stack j starts from each candidate in ``transforms_list`` (mean pose of its
     slices, expressed relative to the target's), the best final NCC wins; the output poses put the slices of stack
     j at  centre o registered_j o (0,0,(i - (n-1)/2) * s_thick).
+
+    ``loss``: the similarity ``VVR`` descends on, ``None`` = global NCC (``{"name": "ncc", "win": None}``, the reference's);
+    ``{"name": "nmi", "bins": B}`` = normalised mutual information, for stacks whose intensities are not linearly related.
 
     ``gaps`` (per-stack slice profiles), one slice spacing per stack: every other stack is resampled along z from its own gap to
     stack 0's before it is registered (``s_thick`` is then that gap), and the output poses of stack j are ``gaps[j]`` apart."""
     device = transform_target.device
     t_target = _mean_pose(transform_target)
     candidates = [[_mean_pose(t) for t in ts] for ts in transforms_list]
-    # global NCC given by name: on a HIP device VVR then evaluates a gradient's 13 poses in one launch
+    # the loss given by name (global NCC unless told otherwise): on a HIP device VVR then evaluates a gradient's 13 poses in one launch
     vvr = VVR(num_levels=3, num_steps=4, step_size=2, max_iter=20, optimizer={"name": "gd", "momentum": 0.1},
-              loss={"name": "ncc", "win": None}, auto_grad=False)
+              loss={"name": "ncc", "win": None} if loss is None else loss, auto_grad=False)
     trans_first = False
     registered = [t_target]
     target = stacks[0].squeeze(1)[None, None]
@@ -771,7 +825,15 @@ def _unequal(values: Sequence[float]) -> bool:
     return max(values) - min(values) > SAME_THICKNESS
 
 
-def register_stacks(dataset: List, res_s: float = 1.0, template: int = 0, per_stack_thickness: bool = False) -> List:
+def _stack_loss(similarity: str, nmi_bins, what: str = "similarity") -> Optional[Dict]:
+    """The ``loss`` of ``stack_registration`` behind a similarity's name (None: its default, global NCC); ValueError otherwise."""
+    if similarity not in ("ncc", "nmi"):
+        raise ValueError(f"{what}: 'ncc' or 'nmi' expected, got {similarity!r}")
+    return None if similarity == "ncc" else {"name": "nmi", "bins": _nmi.check_bins(nmi_bins, "nmi_bins")}
+
+
+def register_stacks(dataset: List, res_s: float = 1.0, template: int = 0, per_stack_thickness: bool = False,
+                    similarity: str = "ncc", nmi_bins: int = _nmi.DEFAULT_BINS) -> List:
     """``--registration stack``: in-plane resampling of the masked stacks to ``res_s`` mm (parse_data), stack
     registration to the first stack, new per-slice poses written into the stacks (run_svort with svort=False, vvr=True).
     As in the reference, the slice spacing of the output poses is the MEAN thickness of the input stacks.
@@ -782,12 +844,17 @@ def register_stacks(dataset: List, res_s: float = 1.0, template: int = 0, per_st
 
     ``per_stack_thickness`` (``--per-stack-thickness``) and stacks whose thicknesses or gaps differ by more than 1e-3 mm: every
     stack is registered on the template's slice spacing (resampled along z from its own gap) and its output poses are its own
-    gap apart.  Stacks that agree take the path above, bit for bit."""
+    gap apart.  Stacks that agree take the path above, bit for bit.
+
+    ``similarity`` (``--stack-similarity``): ``"ncc"`` (global NCC, the reference's, as before) or ``"nmi"`` - normalised mutual
+    information on a joint histogram of ``nmi_bins`` bins per axis over the template's points (nesvor_amd/nmi.py; ``VVR``), for
+    stacks whose intensities are not linearly related to the template's."""
+    loss = _stack_loss(similarity, nmi_bins)  # (refusals before any work)
     if template != 0:
         if not 0 <= template < len(dataset):
             raise ValueError(f"template stack {template} out of range: {len(dataset)} stacks")
         register_stacks([dataset[template]] + [s for j, s in enumerate(dataset) if j != template], res_s,
-                        per_stack_thickness=per_stack_thickness)
+                        per_stack_thickness=per_stack_thickness, similarity=similarity, nmi_bins=nmi_bins)
         return dataset
     t0 = time.time()
     stacks = [resample(s.slices * s.mask, (s.resolution_x, s.resolution_y), (res_s, res_s)) for s in dataset]
@@ -795,9 +862,9 @@ def register_stacks(dataset: List, res_s: float = 1.0, template: int = 0, per_st
     s_thick = float(sum(s.thickness for s in dataset) / len(dataset))
     gaps = [float(s.gap) for s in dataset]
     if per_stack_thickness and (_unequal(gaps) or _unequal([float(s.thickness) for s in dataset])):
-        out = stack_registration([transforms], transforms[0], stacks, res_s, gaps[0], gaps)
+        out = stack_registration([transforms], transforms[0], stacks, res_s, gaps[0], gaps, loss=loss)
     else:
-        out = stack_registration([transforms], transforms[0], stacks, res_s, s_thick)
+        out = stack_registration([transforms], transforms[0], stacks, res_s, s_thick, loss=loss)
     logging.debug("time for stack registration: %f s", time.time() - t0)
     for s, t in zip(dataset, out):
         s.transformation = t
@@ -868,7 +935,7 @@ def _cover_shape(poses: RigidTransform, mask: torch.Tensor, res_s: float, s_thic
 
 def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = None, n_outer: int = 3, template: int = 0,
                     per_stack_thickness: bool = False, packages: Optional[Sequence[int]] = None, package_rounds: int = 2,
-                    similarity: str = "ncc", nmi_bins: int = _nmi.DEFAULT_BINS) -> List:
+                    similarity: str = "ncc", nmi_bins: int = _nmi.DEFAULT_BINS, stack_similarity: str = "ncc") -> List:
     """``--registration svr``: stack registration (``register_stacks``, to the stack ``template``), then ``n_outer`` rounds of
     reconstruct a volume from all slices at their current poses  /  register every non-empty slice rigidly to it (``SVR``,
     global NCC); the per-slice poses are written back into the stacks.  ``res_r``: voxel size of the intermediate volume
@@ -882,14 +949,16 @@ def register_slices(dataset: List, res_s: float = 1.0, res_r: Optional[float] = 
 
     ``similarity`` (``--svr-similarity``): the metric of the package and the slice stage, ``"ncc"`` (global NCC, as before) or
     ``"nmi"`` - normalised mutual information on a joint histogram of ``nmi_bins`` bins per axis (``--nmi-bins``; nesvor_amd/nmi.py),
-    for stacks whose intensities are not linearly related.  The stack registration in front keeps its NCC."""
+    for stacks whose intensities are not linearly related.  ``stack_similarity`` (``--stack-similarity``): the same choice for the
+    stack registration in front (``register_stacks``), which keeps its NCC unless told otherwise; ``nmi_bins`` serves both."""
     if similarity not in ("ncc", "nmi"):
         raise ValueError(f"similarity: 'ncc' or 'nmi' expected, got {similarity!r}")
+    _stack_loss(stack_similarity, nmi_bins, "stack_similarity")  # (refusals before any work)
     loss_spec = {"name": "ncc"} if similarity == "ncc" else {"name": "nmi", "bins": _nmi.check_bins(nmi_bins, "nmi_bins")}
     metric = similarity.upper()
     if packages is not None:  # (refusals before any work)
         package_groups([s.slices.shape[0] for s in dataset], packages)
-    dataset = register_stacks(dataset, res_s, template, per_stack_thickness)
+    dataset = register_stacks(dataset, res_s, template, per_stack_thickness, similarity=stack_similarity, nmi_bins=nmi_bins)
     t0 = time.time()
     res_r = res_s if res_r is None else res_r
     s_thick = float(sum(s.thickness for s in dataset) / len(dataset))
